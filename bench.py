@@ -1,21 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- fused points/s of the GEM point-cloud -> elevation-grid hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N = 1 (the contract line).  A "step" is one pass of the hot path over one batch of synthetic input: one 64-beam LiDAR sweep
 (64 x 2048 = 131 072 XYZI points, BASELINE.json configs[1]) projected, binned and Kalman-fused into the robot-centric
 600 x 600 @ 0.05 m map with gem_add_device (inputs already resident in HBM).  Steps cycle through 8 distinct seeded sweeps
-(moving sensor).  W warm-up steps, then EXACTLY K steps are timed between synchronisations -- and, because K steps of ~10 us are a
-sub-millisecond sample, that K-step region is repeated until at least 50 ms have been measured; `ms_per_step` is the MEDIAN
-over the repetitions (`timed_repetitions` says how many).
+(moving sensor).  W warm-up steps, then EXACTLY K steps are timed between two synchronisations; `ms_per_step` is that time / K
+(K steps of ~10 us are a sub-millisecond sample: choose K for the precision wanted).
+--dump-outputs DIR: after the timed steps, what a caller of the timed path reads back -- the map's layers after the last timed step
+(C2: elevation / variance / intensity; C5: elevation / variance of the whole map, rank 0) -- as DIR/<layer>.npy (float32).  The
+inputs are seeded: the same arguments give the same inputs, so two builds can be compared output for output.
 What was timed is checked: (1) `parity_checked` -- the same code paths on a fresh map reproduce the committed golden digests
 (tests/golden/digests.json: the C2 stream, the C4 batch), no oracle involved; (2) `cpu_baseline.replay_matches_timed_map` -- the
 CPU oracle replays the very sequence of sweeps the timed map has seen and the two maps are compared bit for bit.
 `roofline` describes the dominant kernel (dispatch time stamps on the stream it runs on, second loop), `batched_c4` the
 bandwidth-regime configuration (BASELINE configs[3]), `cpu_baseline` the oracle on this box's host cores.
 
-N > 1 (one rank per GPU; launched by torch.distributed.run -- or by this script itself when WORLD_SIZE is not set: it re-executes
+N > 1 (one rank per GPU; launched by torch.distributed.run -- or by this script itself when WORLD_SIZE is not set: it starts itself
 under torch.distributed.run with N ranks, and exits non-zero when fewer than N devices are visible): BASELINE configs[4], STRONG
 scaling -- the same 10^7-point aggregated cloud -> 2400 x 2400 map on N ranks per step: every rank projects / bins / sorts its
 N-th of the points, the sorted records go to the tile-row strip owners (RCCL send / recv), the owners fuse, and the fused strips
@@ -44,7 +46,7 @@ sys.path.insert(0, str(ROOT))
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6300.0    # the same guide: 6.29 TB/s measured copy rate (SURVEY 8d asks for both fractions)
 N_DISTINCT = 8
-MIN_TIMED_S = 0.05
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
@@ -58,7 +60,22 @@ def parse():
     ap.add_argument("--workload", choices=["c2", "c5"], default=None,
                     help="default: c2 (the headline configuration) at --gpus 1, c5 at --gpus N > 1; `--workload c5 --gpus 1` times C5 through the "
                          "same sharded entry points on one rank -- the like-for-like N = 1 point of the scaling curve")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the layers the timed path left after its last step to DIR/<layer>.npy (float32)")
     return ap.parse_args()
+
+
+def dump_outputs(dirname: str, emap, names) -> None:
+    """The layers a caller of the timed path reads back, as DIR/<name>.npy in float32 (at most DUMP_LIMIT_BYTES in all)."""
+    arrays = {n: np.ascontiguousarray(emap.layer(n), np.float32) for n in names}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(d / f"{n}.npy", a)
+    print(f"[bench] --dump-outputs: {', '.join(arrays)} -> {d} ({total} bytes)", file=sys.stderr, flush=True)
 
 
 def sha(a: np.ndarray) -> str:
@@ -122,7 +139,7 @@ def cpu_baseline(wl, n_sweeps_timed_map: int, timed_layers, budget_s: float):
         out["value"] = n_sweeps_timed_map * n_per / dt
         ok = bool(np.array_equal(m.layer("elevation"), timed_layers[0]) and np.array_equal(m.layer("variance"), timed_layers[1]))
         out["replay_matches_timed_map"] = ok
-        out["sample"] = (f"the {n_sweeps_timed_map} sweeps x {n_per} pts the timed GPU map has fused (warm-up + timed repetitions), replayed by "
+        out["sample"] = (f"the {n_sweeps_timed_map} sweeps x {n_per} pts the timed GPU map has fused (warm-up + timed steps), replayed by "
                          f"oracle/gem_oracle_mt.c gemo_add_batch_mt on {nt} threads ({dt:.1f} s) and compared with it bit for bit")
     else:
         sweeps = max(N_DISTINCT, int(min(left, 15.0) * rate_est / n_per))
@@ -614,6 +631,8 @@ def run_c5_distributed(args, torch, dist, world, rank, local_rank, dev):
     for _ in range(args.warmup):
         step()
     elapsed = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, emap, ("elevation", "variance"))       # the whole map, after the all-gather of the last step
     # the same steps without the all-gather of the layers (what the exchange + walk pipeline does on its own)
     elapsed_nogather = timed(args.steps, gather=False)
     # what every rank holds after the all-gather is the whole map: check it against the committed digest of ONE pass
@@ -743,8 +762,9 @@ def self_launch(args) -> None:
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), str(Path(__file__).resolve()), *sys.argv[1:]]
-    print("[bench] re-executing under torch.distributed.run: " + " ".join(cmd), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    print("[bench] running under torch.distributed.run: " + " ".join(cmd), file=sys.stderr, flush=True)
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)          # a fresh child process: this one has already asked the runtime for its devices
 
 
 _REAL_STDOUT = None
@@ -764,7 +784,7 @@ def main():
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)                                    # does not return
+        self_launch(args)                                    # does not return (exits with the ranks' status)
     # Libraries underneath write to stdout on their own (RCCL prints a version banner at communicator creation, the compiled
     # reference printf's from its Init): everything but the JSON line goes to stderr.
     global _REAL_STDOUT
@@ -820,17 +840,16 @@ def main():
     for _ in range(args.warmup):
         step()
     sync()
-    # EXACTLY K steps between synchronisations, repeated until >= 50 ms have been timed; the median repetition counts
-    rep_s, total = [], 0.0
-    while total < MIN_TIMED_S and len(rep_s) < 2000:
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        sync()
-        rep_s.append(time.perf_counter() - t0); total += rep_s[-1]
-    elapsed = float(np.median(rep_s))
+    # EXACTLY K steps between two synchronisations
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    sync()
+    elapsed = time.perf_counter() - t0
     n_timed_map = done[0]
     timed_layers = (emap.layer("elevation"), emap.layer("variance"))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, emap, ("elevation", "variance", "intensity"))
     value = args.steps * n_per / elapsed
 
     # ---- roofline of the dominant kernel: dispatch time stamps of every kernel launch (recorded on the handle's stream by
@@ -889,8 +908,7 @@ def main():
         "value": value, "unit": "points/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "timed_repetitions": len(rep_s), "timed_total_ms": 1e3 * total,
-        "ms_per_step_min_max": [1e3 * min(rep_s) / args.steps, 1e3 * max(rep_s) / args.steps],
+        "timed_total_ms": 1e3 * elapsed,
         "config": {"workload": "C2: single 64-beam LiDAR sweep (64x2048 = 131072 XYZI pts) -> 600x600 @ 0.05 m grid, "
                                "per step; 8 distinct seeded sweeps cycled; reject filter off",
                    "points_per_step": n_per, "grid": "600x600@0.05m", "parallelism": "single",

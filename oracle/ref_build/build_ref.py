@@ -46,9 +46,17 @@ def rewrite_launches(text: str) -> tuple[str, int]:
     return "".join(out), n
 
 
+def _present(p: Path) -> bool:
+    """True when the reference file can be read here (an unreadable reference counts as absent)."""
+    try:
+        return p.is_file() and open(p, "rb").close() is None
+    except OSError:
+        return False
+
+
 def build(reference: Path = Path("/root/reference"), force: bool = False, verbose: bool = False) -> Path | None:
     src = reference / REL
-    if not src.exists():
+    if not _present(src):
         return OUT if OUT.exists() else None                # e.g. on the GPU box: use the prebuilt library
     deps = [src, HERE / "cuda_runtime.h", HERE / "ref_exports.inc", HERE / "Eigen" / "Core", Path(__file__)]
     if OUT.exists() and not force and all(OUT.stat().st_mtime >= d.stat().st_mtime for d in deps):
@@ -80,7 +88,7 @@ def build_motion(reference: Path = Path("/root/reference"), force: bool = False,
     against the stand-ins under motion/ for what is not installed here -- Eigen, kindr, ROS, and the one method of ElevationMap the
     class touches.  The Jacobians, the F matrix and the covariance products are the reference's text; nothing of it is copied."""
     src = reference / REL_MOTION
-    if not src.exists():
+    if not _present(src):
         return OUT_MOTION if OUT_MOTION.exists() else None
     m = HERE / "motion"
     deps = [src, reference / REL_INCLUDE / "elevation_mapping" / "RobotMotionMapUpdater.hpp", Path(__file__)] + [f for f in m.rglob("*") if f.is_file()]
@@ -113,7 +121,7 @@ def build_sensors(reference: Path = Path("/root/reference"), force: bool = False
     out in the reference, the laser model lives in gpu_process.cu -- libgem_ref.so.)  `private` / `protected` are lifted for the
     reference's files so that the harness can set the transformation members TF would have filled."""
     srcs = [reference / REL_SENSORS / f for f in SENSOR_FILES]
-    if not all(s.exists() for s in srcs):
+    if not all(_present(s) for s in srcs + [reference / REL_SENSORS / "SensorProcessorBase.cpp"]):
         return OUT_SENSORS if OUT_SENSORS.exists() else None
     m = HERE / "sensors"
     deps = srcs + [reference / REL_SENSORS / "SensorProcessorBase.cpp", Path(__file__)] + [f for f in m.rglob("*") if f.is_file()]

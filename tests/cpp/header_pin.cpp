@@ -3,7 +3,10 @@
 // SensorProcessorBase::readcomputerparam (SPB.cpp:270-290), compiled where they lie into oracle/_ref/libgem_ref_motion.so and
 // libgem_ref_sensors.so (oracle/ref_build/build_ref.py).  The Python twin of the header (gem_amd/api.py) has had this test since
 // round 4 (tests/test_motion_update.py); this one drives the header itself.  CPU only: nothing here touches a device.
-//     header_pin <libgem_ref_motion.so> <libgem_ref_sensors.so>
+//     header_pin <libgem_ref_motion.so> <libgem_ref_sensors.so> [--record FILE]
+//     header_pin --replay FILE
+// --record writes every answer of the two libraries (with a digest of the call's inputs) to FILE; --replay takes the answers from
+// FILE instead, where the libraries cannot be built (tests/golden/header_pin_ref.bin, tests/golden/make_ref_golden.py --tape).
 #include "gem/gem.hpp"
 
 #include <dlfcn.h>
@@ -11,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <random>
 
@@ -43,6 +47,34 @@ static long long ulps(float a, float b)                                // distan
     return ia > ib ? (long long)ia - ib : (long long)ib - ia;
 }
 
+static FILE* rec = nullptr;
+static FILE* play = nullptr;
+
+static std::uint64_t fnv(std::uint64_t h, const void* p, std::size_t n)    // FNV-1a over the bytes of a call's inputs
+{
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (std::size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+    return h;
+}
+
+// one answer of the reference: from the library (and into the recording) or from the recording
+template <class F>
+static int answer(std::uint64_t digest, float* out, int n_out, F live)
+{
+    int rc = 0;
+    if (play) {
+        std::uint64_t d = 0;
+        if (std::fread(&d, 8, 1, play) != 1 || d != digest || std::fread(&rc, 4, 1, play) != 1 || std::fread(out, 4, n_out, play) != (std::size_t)n_out) {
+            std::printf("replay: the inputs are not the recorded ones\n");
+            std::exit(2);
+        }
+        return rc;
+    }
+    rc = live();
+    if (rec) { std::fwrite(&digest, 8, 1, rec); std::fwrite(&rc, 4, 1, rec); std::fwrite(out, 4, n_out, rec); }
+    return rc;
+}
+
 typedef void* (*motion_create_t)(double);
 typedef void (*motion_destroy_t)(void*);
 typedef int (*motion_update_t)(void*, const double*, const double*, const double*, const double*, int, double, float*);
@@ -50,14 +82,22 @@ typedef int (*readparam_t)(const double*, const double*, const double*, const do
 
 int main(int argc, char** argv)
 {
-    if (argc < 3) { std::printf("usage: header_pin libgem_ref_motion.so libgem_ref_sensors.so\n"); return 2; }
-    void* lm = dlopen(argv[1], RTLD_NOW); void* ls = dlopen(argv[2], RTLD_NOW);
-    if (!lm || !ls) { std::printf("dlopen: %s\n", dlerror()); return 2; }
-    const motion_create_t m_create = (motion_create_t)dlsym(lm, "gemref_motion_create");
-    const motion_destroy_t m_destroy = (motion_destroy_t)dlsym(lm, "gemref_motion_destroy");
-    const motion_update_t m_update = (motion_update_t)dlsym(lm, "gemref_motion_update");
-    const readparam_t readparam = (readparam_t)dlsym(ls, "gemref_readcomputerparam");
-    if (!m_create || !m_destroy || !m_update || !readparam) { std::printf("dlsym failed\n"); return 2; }
+    if (argc == 3 && std::strcmp(argv[1], "--replay") == 0) {
+        if (!(play = std::fopen(argv[2], "rb"))) { std::printf("cannot read %s\n", argv[2]); return 2; }
+    } else if (argc != 3 && !(argc == 5 && std::strcmp(argv[3], "--record") == 0)) {
+        std::printf("usage: header_pin libgem_ref_motion.so libgem_ref_sensors.so [--record FILE] | header_pin --replay FILE\n"); return 2;
+    }
+    motion_create_t m_create = nullptr; motion_destroy_t m_destroy = nullptr; motion_update_t m_update = nullptr; readparam_t readparam = nullptr;
+    if (!play) {
+        void* lm = dlopen(argv[1], RTLD_NOW); void* ls = dlopen(argv[2], RTLD_NOW);
+        if (!lm || !ls) { std::printf("dlopen: %s\n", dlerror()); return 2; }
+        m_create = (motion_create_t)dlsym(lm, "gemref_motion_create");
+        m_destroy = (motion_destroy_t)dlsym(lm, "gemref_motion_destroy");
+        m_update = (motion_update_t)dlsym(lm, "gemref_motion_update");
+        readparam = (readparam_t)dlsym(ls, "gemref_readcomputerparam");
+        if (!m_create || !m_destroy || !m_update || !readparam) { std::printf("dlsym failed\n"); return 2; }
+        if (argc == 5 && !(rec = std::fopen(argv[4], "wb"))) { std::printf("cannot write %s\n", argv[4]); return 2; }
+    }
 
     // ---- gem::RobotMotionMapUpdater::compute (gem.hpp) vs RobotMotionMapUpdater::update (RMU.cpp:42-90), random trajectories:
     //      pitched and rolled robots, full covariances, a rotated map, several covariance scales (tests/test_motion_update.py's)
@@ -69,7 +109,7 @@ int main(int argc, char** argv)
         const double scales[4] = {1.0, 0.5, 2.5, 1.3};
         const double scale = scales[seed % 4];
         gem::RobotMotionMapUpdater mine(scale);
-        void* theirs = m_create(scale);
+        void* theirs = play ? nullptr : m_create(scale);
         gem::Mat3 mapR{1, 0, 0, 0, 1, 0, 0, 0, 1};
         if (seed % 3 == 0) mapR = rot_zyx(0.4 * N01(rng), 0.0, 0.0);
         double mq[4]; quat_of(mapR, mq);
@@ -84,7 +124,9 @@ int main(int argc, char** argv)
             const float a = mine.compute(pos, R, c, mapR);
             double q[4]; quat_of(R, q);
             float b = 0.f;
-            const int did = m_update(theirs, pos.data(), q, cov, mq, 600, 1.0 + k, &b);
+            std::uint64_t h = fnv(14695981039346656037ull, &scale, sizeof scale);
+            h = fnv(h, pos.data(), sizeof(double) * 3); h = fnv(h, q, sizeof q); h = fnv(h, cov, sizeof cov); h = fnv(h, mq, sizeof mq); h = fnv(h, &k, sizeof k);
+            const int did = answer(h, &b, 1, [&] { return m_update(theirs, pos.data(), q, cov, mq, 600, 1.0 + k, &b); });
             CHECK(did == 1);
             // The doubles' summation order differs between the two (Eigen's unrolled reductions vs plain loops) and the value is a
             // DIFFERENCE of covariances: one float ulp, or -- where the difference cancels -- 1e-12 absolute.
@@ -93,7 +135,7 @@ int main(int argc, char** argv)
             if (std::fabs((double)a - (double)b) > 1e-12) worst = d > worst ? d : worst;
             exact += d == 0; ++steps;
         }
-        m_destroy(theirs);
+        if (theirs) m_destroy(theirs);
     }
     std::printf("RobotMotionMapUpdater: %d steps, %d bit-equal, worst %lld float ulp(s)\n", steps, exact, worst);
 
@@ -117,7 +159,9 @@ int main(int argc, char** argv)
         sp.updateTransformations(I, baseFromSensor, mapFromBase);
         const gem_frame_params p = sp.frameParams();
         float ref[27];
-        CHECK(readparam(C_BM.data(), C_SB.data(), b, laser, ref) == 0);
+        std::uint64_t h = fnv(14695981039346656037ull, C_BM.data(), sizeof(double) * 9);
+        h = fnv(h, C_SB.data(), sizeof(double) * 9); h = fnv(h, b, sizeof b); h = fnv(h, laser, sizeof laser);
+        CHECK(answer(h, ref, 27, [&] { return readparam(C_BM.data(), C_SB.data(), b, laser, ref); }) == 0);
         // the casts: min_r / beam_a / beam_c reach the kernel as floats (SPB.cpp:286-288: float = double)
         CHECK((float)p.sensor_params[0] == ref[0]); CHECK((float)p.sensor_params[1] == ref[1]); CHECK((float)p.sensor_params[2] == ref[2]);
         long long w = 0;
@@ -129,6 +173,8 @@ int main(int argc, char** argv)
         ++cases;
     }
     std::printf("readcomputerparam: %d cases, worst %lld float ulp(s)\n", cases, worst_p);
+    if (rec) std::fclose(rec);
+    if (play) std::fclose(play);
     std::printf(fails ? "FAILED\n" : "ok\n");
     return fails ? 1 : 0;
 }

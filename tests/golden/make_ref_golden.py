@@ -12,6 +12,15 @@ ref_scene.npz is ONE scripted session of the reference's interface on an 80 x 80
   lowest after Raytracing.
 tests/test_golden.py replays the session on the oracle (CPU) and on libgem_hip (GPU) against these arrays, so the pin
 travels with the repository (the GPU box has no /root/reference).
+
+    python tests/golden/make_ref_golden.py --tape [--merge] [-- PYTEST ARGS]     # rewrites tests/golden/ref_tape.npz
+
+ref_tape.npz holds every result the compiled reference returns to the tests (oracle/ref.py), recorded while they run against
+the live libraries (default: the CPU tests), so that they run where the reference cannot be built: a map's answers as their
+SHA-1 and their difference from the oracle's answers to the same calls (mostly none), the rest in full.  --merge keeps the entries
+already recorded (e.g. to add those of the GPU tests, recorded on a GPU machine with the prebuilt oracle/_ref libraries).  The
+same run rewrites header_pin_ref.bin (the answers tests/cpp/header_pin.cpp gets from the motion / sensor libraries) and
+caller_symbols.json (the mangled names the reference's callers link against, tests/test_cabi.py).
 """
 import sys
 from pathlib import Path
@@ -78,5 +87,31 @@ def main():
           "accepted per frame:", [int((out[f"pp_index_{k}"] >= 0).sum()) for k in range(3)])
 
 
+def record_tape(merge: bool, pytest_args: list[str]) -> int:
+    import pytest
+    if ref.lib() is None or ref.motion_lib() is None or ref.sensor_lib() is None:
+        raise SystemExit("recording needs the compiled reference (the reference sources, or prebuilt oracle/_ref libraries)")
+    ref.start_recording()
+    if merge and ref.have_tape():
+        ref._recording.update(ref._load_recording())
+    before = len(ref._recording)
+    class Record:                   # the two C++-side recordings of tests/test_cabi.py
+        @staticmethod
+        def pytest_collection_finish(session):
+            for item in session.items:
+                for flag in ("HEADER_PIN_RECORD", "RECORD_CALLER_SYMBOLS"):
+                    if hasattr(item.module, flag):
+                        setattr(item.module, flag, True)
+    rc = pytest.main(["-q", "-p", "no:cacheprovider", str(ROOT / "tests")] + (pytest_args or ["-m", "not gpu"]), plugins=[Record()])
+    if rc != 0:
+        raise SystemExit(f"pytest failed ({rc}): nothing written")
+    n = ref.save_recording()
+    print(f"{ref.TAPE.name}: {n} arrays ({n - before} new), {ref.TAPE.stat().st_size} bytes")
+    return 0
+
+
 if __name__ == "__main__":
+    if "--tape" in sys.argv:
+        args = sys.argv[sys.argv.index("--") + 1:] if "--" in sys.argv else []
+        sys.exit(record_tape("--merge" in sys.argv[:sys.argv.index("--")] if "--" in sys.argv else "--merge" in sys.argv, args))
     main()

@@ -94,9 +94,9 @@ def test_against_the_references_own_code_over_random_trajectories(oracle_mod):
     ROS (oracle/ref_build/motion) -- against the oracle's restatement AND the product's host implementation: random walks with
     pitched and rolled robots, full covariances, a rotated map, several covariance scales."""
     import ref
-    if ref.motion_lib() is None:
+    if not ref.have_motion():
         import pytest
-        pytest.skip("no /root/reference to build from and no prebuilt oracle/_ref/libgem_ref_motion.so")
+        pytest.skip("no reference to build from, no prebuilt oracle/_ref/libgem_ref_motion.so and no tests/golden/ref_tape.npz")
     worst = 0.0
     for seed in range(12):
         rng = np.random.default_rng(100 + seed)

@@ -25,8 +25,8 @@ W = 640
 @pytest.fixture(scope="module")
 def sensors():
     import ref
-    if ref.sensor_lib() is None:
-        pytest.skip("no /root/reference to build from and no prebuilt oracle/_ref/libgem_ref_sensors.so")
+    if not ref.have_sensors():
+        pytest.skip("no reference to build from, no prebuilt oracle/_ref/libgem_ref_sensors.so and no tests/golden/ref_tape.npz")
     return ref
 
 
