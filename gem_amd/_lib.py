@@ -17,6 +17,7 @@ LAYER_ELEVATION, LAYER_VARIANCE, LAYER_INTENSITY, LAYER_TRAVER, LAYER_LOWEST, \
     LAYER_COLOR_R, LAYER_COLOR_G, LAYER_COLOR_B, LAYER_ROUGH, LAYER_SLOPE = range(10)
 LAYOUT_STORAGE_ROWMAJOR, LAYOUT_GRIDMAP_COLMAJOR_NAN = 0, 1
 MODEL_LASER, MODEL_STRUCTURED_LIGHT, MODEL_STEREO, MODEL_PERFECT = range(4)
+CLEAN_NONE, CLEAN_REMOVE_NAN, CLEAN_PASSTHROUGH_Z = range(3)
 
 
 class MapConfig(C.Structure):
@@ -38,6 +39,10 @@ class FrameParams(C.Structure):
 
 class Camera(C.Structure):
     _fields_ = [("lidar_to_image", c_double * 12), ("width", c_int), ("height", c_int)]
+
+
+class CleanParams(C.Structure):
+    _fields_ = [("mode", c_int), ("z_min", c_float), ("z_max", c_float)]
 
 
 class Stats(C.Structure):
@@ -92,6 +97,13 @@ SIGNATURES = {
                                       POINTER(c_uint32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
     "gem_shard_fuse_device": (c_int, [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), POINTER(c_void_p), POINTER(c_uint32),
                                       c_int, POINTER(c_float)]),
+    "gem_clean_params_for_model": (c_int, [c_int, c_double, c_double, POINTER(CleanParams)]),
+    "gem_clean_device": (c_int, [c_void_p, POINTER(CleanParams), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gem_add_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_void_p]),
+    "gem_add_raw_device": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_void_p]),
+    "gem_add_aos_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gem_process_points_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_void_p, c_void_p,
+                                       POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {

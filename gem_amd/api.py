@@ -76,14 +76,30 @@ class SensorModel:
     ignore_points_above: float = float("inf")               # SensorProcessorBase.cpp:61
     ignore_points_below: float = float("-inf")              # SensorProcessorBase.cpp:62
     original_width: int = 0
+    # structured light: sensor_processor/cutoff_min_depth | cutoff_max_depth (StructuredLightSensorProcessor.cpp:40-41); None = the
+    # reference's defaults numeric_limits<double>::min() / ::max().  Used by the raw-cloud entries only (clean_params()).
+    cutoff_min_depth: Optional[float] = None
+    cutoff_max_depth: Optional[float] = None
 
     @staticmethod
     def velodyne() -> "SensorModel":                         # velodyne.yaml:4-9
         return SensorModel(_lib.MODEL_LASER, (0.018, 0.0006, 0.0015), 0.8, -5.0)
 
     @staticmethod
-    def realsense_d435() -> "SensorModel":                   # realsense_d435.yaml:4-11
-        return SensorModel(_lib.MODEL_STRUCTURED_LIGHT, (0.000611, 0.003587, 0.3515, 0.0, 1.0, 0.01576))
+    def realsense_d435() -> "SensorModel":                   # realsense_d435.yaml:4-13
+        return SensorModel(_lib.MODEL_STRUCTURED_LIGHT, (0.000611, 0.003587, 0.3515, 0.0, 1.0, 0.01576),
+                           cutoff_min_depth=0.2, cutoff_max_depth=3.25)
+
+    def clean_params(self) -> "_lib.CleanParams":
+        """The cleanPointCloud step SensorProcessorBase::process runs for this model (gem_clean_params_for_model): REMOVE_NAN for
+        laser / stereo / perfect, PASSTHROUGH_Z on the float-rounded cutoffs for structured light."""
+        lo = sys.float_info.min if self.cutoff_min_depth is None else float(self.cutoff_min_depth)
+        hi = sys.float_info.max if self.cutoff_max_depth is None else float(self.cutoff_max_depth)
+        out = _lib.CleanParams()
+        rc = _lib.load().gem_clean_params_for_model(int(self.kind), lo, hi, C.byref(out))
+        if rc != _lib.GEM_OK:
+            raise GemError(f"gem_clean_params_for_model failed ({rc})")
+        return out
 
     @staticmethod
     def perfect() -> "SensorModel":
@@ -203,6 +219,11 @@ class SensorProcessor:
         """SensorProcessorBase::process -> Process_points (SPB.cpp:66-94, 208): returns the
         per-point arrays the reference hands to Fuse."""
         return elevation_map.process_points(self.frame(), x, y, z, orig_index)
+
+    def process_raw(self, elevation_map: "ElevationMap", x, y, z):
+        """SensorProcessorBase::process on a RAW cloud: cleanPointCloud (SPB.cpp:89) on the device, then Process_points on the kept
+        points; the per-point arrays cover the kept points, "orig" holds their raw positions (ElevationMap.process_points_raw)."""
+        return elevation_map.process_points_raw(self.frame(), x, y, z, self.model.clean_params())
 
 
 class PackedBatch:
@@ -355,6 +376,107 @@ class ElevationMap:
         p = frame.to_struct()
         self._check(self._lib.gem_add_aos(self._h, C.byref(p), n, a.ctypes.data_as(C.c_void_p), step, off_x, off_y, off_z,
                                           off_intensity, off_rgb), "gem_add_aos")
+
+    # -- raw clouds: cleanPointCloud (SensorProcessorBase.cpp:89) on the device -----------------------------------------------------
+    @staticmethod
+    def _device_words(t, n: int, like, what: str):
+        """an optional per-point 32-bit device array next to the device cloud `like`: contiguous, n elements of 4 bytes, same device"""
+        if t is None:
+            return None
+        if not _is_device_tensor(t) or t.device != like.device or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n:
+            raise ValueError(f"{what} must be a contiguous 32-bit device tensor of {n} elements on {like.device}")
+        return C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _clean(clean, frame: Optional[Frame] = None) -> "_lib.CleanParams":
+        if clean is None:
+            if frame is None:
+                raise ValueError("clean parameters needed")
+            return frame.model.clean_params()
+        if isinstance(clean, SensorModel):
+            return clean.clean_params()
+        if isinstance(clean, _lib.CleanParams):
+            return clean
+        raise TypeError("clean: a SensorModel, a CleanParams or None (the frame's model)")
+
+    def clean_device(self, clean, xyzi, rgb=None, sync: bool = True, out=None):
+        """gem_clean_device on a float32 [N, 4] device tensor (+ optional int32 / uint32 rgb [N]): returns (xyzi_out [N, 4],
+        rgb_out [N] or None, orig [N] int32, count [1] int32), device tensors whose first count rows hold the kept points in input
+        order -- new ones, or the four of `out` (a previous call's result, reused).  Enqueued on the handle's stream; with
+        sync=False the caller synchronises the handle before reading them."""
+        import torch
+        if not _is_device_tensor(xyzi) or not xyzi.is_contiguous() or xyzi.dtype != torch.float32 or xyzi.numel() != 4 * int(xyzi.shape[0]):
+            raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
+        n = int(xyzi.shape[0])
+        cp = self._clean(clean)
+        if out is not None:
+            out, rgb_out, orig, count = out
+            if out.shape != xyzi.shape or orig.numel() < n or count.numel() < 1 or (rgb is not None and (rgb_out is None or rgb_out.numel() < n)):
+                raise ValueError("clean_device: `out` does not fit this cloud")
+            rgb_out = rgb_out if rgb is not None else None
+        else:
+            out = torch.empty_like(xyzi)
+            orig = torch.empty(n, dtype=torch.int32, device=xyzi.device)
+            count = torch.zeros(1, dtype=torch.int32, device=xyzi.device)
+            rgb_out = torch.empty(n, dtype=torch.int32, device=xyzi.device) if rgb is not None else None
+        prgb = self._device_words(rgb, n, xyzi, "rgb")
+        dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(self._lib.gem_clean_device(self._h, C.byref(cp), n, dp(xyzi), prgb, dp(out), dp(rgb_out), dp(orig), dp(count)),
+                    "gem_clean_device")
+        self._hold(xyzi, rgb, out, rgb_out, orig, count)
+        if sync:
+            self.synchronize()
+        return out, rgb_out, orig, count
+
+    def add_raw(self, frame: Frame, xyzi, rgb=None, clean=None) -> None:
+        """add() of a RAW cloud (NaN holes, out-of-range depths): the cleanPointCloud step of the frame's model -- or `clean` --
+        is done on the device (gem_add_raw / gem_add_raw_device); the raw position is every point's orig index."""
+        p = frame.to_struct()
+        cp = self._clean(clean, frame)
+        if _is_device_tensor(xyzi):
+            n = int(xyzi.shape[0])
+            if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n:
+                raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
+            prgb = self._device_words(rgb, n, xyzi, "rgb")
+            self._check(self._lib.gem_add_raw_device(self._h, C.byref(p), C.byref(cp), n, C.c_void_p(xyzi.data_ptr()), prgb), "gem_add_raw_device")
+            self._hold(xyzi, rgb)
+            return
+        a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+        n = a.shape[0]
+        kr, pr = _host_ptr(rgb, np.uint32, n)
+        self._check(self._lib.gem_add_raw(self._h, C.byref(p), C.byref(cp), n, a.ctypes.data_as(C.c_void_p), pr), "gem_add_raw")
+
+    def add_aos_raw(self, frame: Frame, points: np.ndarray, off_x: int = 0, off_y: int = 4, off_z: int = 8, off_intensity: int = 24,
+                    off_rgb: int = 16, clean=None) -> None:
+        """add_aos() of a RAW cloud of point structs (gem_add_aos_raw)."""
+        a = np.ascontiguousarray(points)
+        n, step = a.shape[0], a.dtype.itemsize * (int(np.prod(a.shape[1:])) if a.ndim > 1 else 1)
+        p = frame.to_struct()
+        cp = self._clean(clean, frame)
+        self._check(self._lib.gem_add_aos_raw(self._h, C.byref(p), C.byref(cp), n, a.ctypes.data_as(C.c_void_p), step, off_x, off_y, off_z,
+                                              off_intensity, off_rgb), "gem_add_aos_raw")
+
+    def process_points_raw(self, frame: Frame, x, y, z, clean=None):
+        """process_points() of a RAW cloud (gem_process_points_raw): the arrays cover the kept points only, in order; "orig" holds
+        their raw positions and "n_kept" their number."""
+        n = int(np.asarray(x).size)
+        xa = np.ascontiguousarray(x, np.float32).reshape(-1); ya = np.ascontiguousarray(y, np.float32).reshape(-1)
+        za = np.ascontiguousarray(z, np.float32).reshape(-1)
+        if ya.size != n or za.size != n:
+            raise ValueError("x, y, z differ in length")
+        cp = self._clean(clean, frame)
+        out = {"orig": np.empty(n, np.int32), "index": np.empty(n, np.int32), "var": np.empty(n, np.float32),
+               "x_ts": np.empty(n, np.float32), "y_ts": np.empty(n, np.float32), "height": np.empty(n, np.float32)}
+        k = C.c_int()
+        p = frame.to_struct()
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.gem_process_points_raw(self._h, C.byref(p), C.byref(cp), n, vp(xa), vp(ya), vp(za), C.byref(k), vp(out["orig"]),
+                                                     vp(out["index"]), vp(out["var"]), vp(out["x_ts"]), vp(out["y_ts"]), vp(out["height"])),
+                    "gem_process_points_raw")
+        kept = int(k.value)
+        res = {key: v[:kept].copy() for key, v in out.items()}
+        res["n_kept"] = kept
+        return res
 
     @staticmethod
     def pack_batch(frames: Sequence[Frame], offsets, var_updates=None) -> "PackedBatch":

@@ -6,6 +6,7 @@
 // Here a handle owns persistent arenas that only ever grow, everything is enqueued on one HIP
 // stream, and nothing returns to the host unless the caller asks for it.
 #include "gem_capi_internal.hpp"
+#include "gem_clean.hpp"
 
 extern "C" {
 
@@ -105,7 +106,8 @@ void gem_destroy(gem_handle* h)
     if (h->layers.elevation) hipFree(h->layers.elevation);      // base of the single layer allocation
     if (h->d_counters) hipFree(h->d_counters);
     for (Arena* a : {&h->stage, &h->scratch, &h->dbg, &h->color, &h->ray, &h->sh_dev, &h->sh_recv_hv[0], &h->sh_recv_key[0], &h->sh_recv_rng[0],
-                     &h->sh_recv_hv[1], &h->sh_recv_key[1], &h->sh_recv_rng[1], &h->sh_ranges, &h->published[0], &h->published[1]}) if (a->p) hipFree(a->p);
+                     &h->sh_recv_hv[1], &h->sh_recv_key[1], &h->sh_recv_rng[1], &h->sh_ranges, &h->published[0], &h->published[1],
+                     &h->clean_cnt}) if (a->p) hipFree(a->p);
     if (h->sh_host) hipHostFree(h->sh_host);
     for (auto& b : h->pb) {
         for (Arena* a : {&b.rec, &b.srt, &b.seg, &b.flag, &b.gflag, &b.tables, &b.s_hv1, &b.s_hv2, &b.s_key1, &b.s_key2, &b.s_src1, &b.s_src2,
@@ -528,6 +530,8 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
     const long long blocks = 4ll * ((h->L + 31) / 32) * ((h->L + 31) / 32);
     // staging of host-pointer inputs (gem_add: XYZI + rgb + orig; gem_fuse: seven arrays; gem_process_points: nine)
     if ((rc = ensure(h, h->stage, ((size_t)max_points * 4 + 256) * 9))) return rc;
+    // (the raw-cloud entries, gem_capi_clean.cpp, work inside that staging arena; their compactions add a count per 1024 points)
+    if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
     {   // ... and its pinned counterpart for callers with host arrays (gem_process_points: nine arrays; gem_map_feature: nine layers),
         // where that is a modest amount: larger ones grow on first use
         constexpr size_t kReserveMax = 64u << 20;

@@ -239,6 +239,7 @@ struct gem_handle {
     Arena ray;          // gem_raytracing: the cells that walk, their number (two counters in turn), the snapshot of the lowest scan points
     unsigned ray_calls = 0;
     Arena color;        // gem_colorize: its own sort arrays and tables (never shared with a pass in flight on the binning stream)
+    Arena clean_cnt;    // the compactions' per-workgroup counts (gem_clean.hip; sized by gem_reserve)
     bool  dbg_on = false;
     bool  dbg_frame = false;            // debug knob: with the stamps on, a stream of single sweeps still runs as k_frame (its tiles AND its binning blocks are stamped)
     long long sort_fallbacks = 0;      // passes whose forced sorted form / pass count did not fit the map and took the other form (gem_debug_get)

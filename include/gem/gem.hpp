@@ -111,10 +111,28 @@ public:
     }
 
     // SensorProcessorBase::process (SensorProcessorBase.cpp:66-94): same out-arrays as the reference,
-    // caller-owned, length = cloud size.  The cloud is assumed NaN-free (cleanPointCloud, Laser.cpp:50-59).
+    // caller-owned, length = cloud size.  The cloud is assumed NaN-free (cleanPointCloud, Laser.cpp:50-59);
+    // a raw cloud goes to processRaw, which does that step on the device.
     bool process(ElevationMap& map, const PointXYZRGBICT* cloud, int n,
                  int* point_colorR, int* point_colorG, int* point_colorB, int* point_index,
                  float* point_intensity, float* point_height, float* point_var);
+
+    // ... on the RAW cloud as the driver publishes it (organised, NaN holes): cleanPointCloud (SensorProcessorBase.cpp:89, this
+    // processor's cleanParams()) on the device, then Process_points on the kept points.  `width` = cloud->width (the stereo
+    // processor's originalWidth_, StereoSensorProcessor.cpp:41).  The out-arrays (n elements each) hold the kept points in order,
+    // colours and intensity taken from them -- the arrays the reference hands to Fuse.  Returns the kept count, or -1 on an error.
+    int processRaw(ElevationMap& map, const PointXYZRGBICT* cloud, int n, int width,
+                   int* point_colorR, int* point_colorG, int* point_colorB, int* point_index,
+                   float* point_intensity, float* point_height, float* point_var);
+
+    // the cleanPointCloud step of this processor: removeNaNFromPointCloud (Laser.cpp:50-59, Perfect.cpp:41-49, Stereo.cpp:37-48);
+    // the structured-light processor overrides it with its PassThrough on z
+    virtual gem_clean_params cleanParams() const
+    {
+        gem_clean_params c{};
+        gem_clean_params_for_model(sensorModel(), std::numeric_limits<double>::min(), std::numeric_limits<double>::max(), &c);
+        return c;
+    }
 
     std::map<std::string, double>& sensorParameters() { return sensorParameters_; }
     void setOriginalWidth(int w) { originalWidth_ = w; }
@@ -143,6 +161,17 @@ protected:
     void fillSensorParams(double o[8]) const override { o[0] = param("min_radius"); o[1] = param("beam_angle"); o[2] = param("beam_constant"); }
 };
 class StructuredLightSensorProcessor : public SensorProcessorBase {   // StructuredLightSensorProcessor.cpp:36-50
+public:
+    // pcl::PassThrough on z with sensor_processor/cutoff_min_depth | cutoff_max_depth, read with the reference's defaults
+    // numeric_limits<double>::min() / ::max() (StructuredLightSensorProcessor.cpp:40-41, 51-66) -- not param()'s 0
+    gem_clean_params cleanParams() const override
+    {
+        auto get = [&](const char* k, double dflt) { auto it = sensorParameters_.find(k); return it == sensorParameters_.end() ? dflt : it->second; };
+        gem_clean_params c{};
+        gem_clean_params_for_model(GEM_MODEL_STRUCTURED_LIGHT, get("cutoff_min_depth", std::numeric_limits<double>::min()),
+                                   get("cutoff_max_depth", std::numeric_limits<double>::max()), &c);
+        return c;
+    }
 protected:
     int sensorModel() const override { return GEM_MODEL_STRUCTURED_LIGHT; }
     void fillSensorParams(double o[8]) const override
@@ -212,6 +241,11 @@ public:
     { check(gem_add(h_, &frame, n, xyzi, rgb, origIndex), "gem_add"); }
     void addDevice(const gem_frame_params& frame, const void* d_xyzi, int n, const void* d_rgb = nullptr, const void* d_origIndex = nullptr)
     { check(gem_add_device(h_, &frame, n, d_xyzi, d_rgb, d_origIndex), "gem_add_device"); }
+    // ... of a RAW cloud: the cleanPointCloud step (SensorProcessorBase::cleanParams()) on the device; raw positions are the orig indices
+    void addRaw(const gem_frame_params& frame, const gem_clean_params& clean, const float* xyzi, int n, const std::uint32_t* rgb = nullptr)
+    { check(gem_add_raw(h_, &frame, &clean, n, xyzi, rgb), "gem_add_raw"); }
+    void addRawDevice(const gem_frame_params& frame, const gem_clean_params& clean, const void* d_xyzi, int n, const void* d_rgb = nullptr)
+    { check(gem_add_raw_device(h_, &frame, &clean, n, d_xyzi, d_rgb), "gem_add_raw_device"); }
 
     // Fuse(length, point_num, index, R, G, B, intensity, height, var)  (ElevationMapping.cpp:280)
     void fuse(int n, const int* index, const int* R, const int* G, const int* B, const float* intensity, const float* height, const float* var)
@@ -333,6 +367,31 @@ inline bool SensorProcessorBase::process(ElevationMap& map, const PointXYZRGBICT
     const int rc = gem_process_points(map.handle(), &p, n, x.data(), y.data(), z.data(), nullptr, 0,
                                       point_index, point_var, nullptr, nullptr, point_height);     // SensorProcessorBase.cpp:208
     return rc == GEM_OK;
+}
+
+inline int SensorProcessorBase::processRaw(ElevationMap& map, const PointXYZRGBICT* cloud, int n, int width,
+                                           int* point_colorR, int* point_colorG, int* point_colorB, int* point_index,
+                                           float* point_intensity, float* point_height, float* point_var)
+{
+    if (n < 0 || (n > 0 && !cloud)) return -1;
+    originalWidth_ = width;                                                                  // StereoSensorProcessor.cpp:41
+    std::vector<float> x(n), y(n), z(n);
+    for (int i = 0; i < n; ++i) { x[i] = cloud[i].x; y[i] = cloud[i].y; z[i] = cloud[i].z; }
+    std::vector<int> orig(n > 0 ? n : 1);
+    const gem_frame_params p = frameParams();
+    const gem_clean_params c = cleanParams();
+    int kept = 0;
+    const int rc = gem_process_points_raw(map.handle(), &p, &c, n, x.data(), y.data(), z.data(), &kept, orig.data(),
+                                          point_index, point_var, nullptr, nullptr, point_height);
+    if (rc != GEM_OK) return -1;
+    for (int k = 0; k < kept; ++k) {                                                         // the kept points' fields (SPB.cpp:160-169)
+        const PointXYZRGBICT& q = cloud[orig[k]];
+        if (point_colorR) point_colorR[k] = q.r;
+        if (point_colorG) point_colorG[k] = q.g;
+        if (point_colorB) point_colorB[k] = q.b;
+        if (point_intensity) point_intensity[k] = q.intensity;
+    }
+    return kept;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -165,6 +165,53 @@ int  gem_add_device(gem_handle* h, const gem_frame_params* p, int n, const void*
 int  gem_add_aos(gem_handle* h, const gem_frame_params* p, int n, const void* points_host, int point_step,
                  int off_x, int off_y, int off_z, int off_intensity, int off_rgb);
 
+/* ---- cleanPointCloud (SPB.cpp:89, the first step of SensorProcessorBase::process) on the device: a raw cloud as the sensor
+ *      driver publishes it -- an organised depth image with its NaN holes -- goes to the GPU with nothing done on the host.
+ *        GEM_CLEAN_REMOVE_NAN      keep point i iff x, y and z are all finite, in input order: pcl::removeNaNFromPointCloud on a cloud
+ *                                  with is_dense == false (Laser LaserSensorProcessor.cpp:50-59, Perfect PerfectSensorProcessor.cpp:41-49,
+ *                                  Stereo StereoSensorProcessor.cpp:37-48, which also keeps each kept point's position in the organised
+ *                                  cloud -- indices_ -- for getI / getJ, StereoSensorProcessor.cpp:108-116).  An is_dense cloud is kept
+ *                                  whole by the reference: pass GEM_CLEAN_NONE for it.
+ *        GEM_CLEAN_PASSTHROUGH_Z   ... and z_min <= z <= z_max, compared in FLOAT: pcl::PassThrough<PointT> on "z" with cutoff_min_depth /
+ *                                  cutoff_max_depth (StructuredLightSensorProcessor.cpp:40-41, 51-66), whose limits PCL stores as float.
+ *      Every compaction here is stable: kept points keep their order, orig[k] = input position of the k-th kept point.
+ *      The fuse entries (gem_add_raw*, gem_add_aos_raw) compact nothing.  The pipelines already reject a point with a non-finite
+ *      coordinate in projection: h = T[8] x + T[9] y + T[10] z + T[11] is then NaN or +-inf (0 * inf is NaN), and the height window
+ *      h > lower && h < upper is false for NaN, for +inf (inf < upper fails even for upper = +inf) and for -inf (-inf > lower fails
+ *      even for lower = -inf) -- in project_point and project_bin_laser_fast alike.  So REMOVE_NAN costs no pass at all, and
+ *      PASSTHROUGH_Z one copy of the cloud in which every dropped point has x = y = z = NaN.  The orig index a stereo frame derives its
+ *      pixel from stays the RAW position (no orig array = "first + i"), which is what the reference's indices_ hold: fusing a raw
+ *      cloud gives the map of fusing the cleaned cloud, of the cleaned count, with its indices (the reference's intended behaviour;
+ *      not its hazard of Fuse'ing point_num = the RAW count over arrays whose tail is uninitialised, EMg.cpp:259,280).
+ *      gem_stats.points_in counts the RAW points of a gem_add_raw* call.                                                        */
+enum { GEM_CLEAN_NONE = 0, GEM_CLEAN_REMOVE_NAN = 1, GEM_CLEAN_PASSTHROUGH_Z = 2 };
+typedef struct gem_clean_params {
+    int   mode;                    /* GEM_CLEAN_* */
+    float z_min, z_max;            /* GEM_CLEAN_PASSTHROUGH_Z: inclusive float limits */
+} gem_clean_params;
+/*      What SensorProcessorBase::process runs for a sensor model: laser / stereo / perfect -> REMOVE_NAN; structured light ->
+ *      PASSTHROUGH_Z with the cutoffs rounded to float (round to nearest).  The reference's defaults numeric_limits<double>::min() /
+ *      ::max() become +0.0f (so z = -0.0 is kept) and +inf.  Pure host function: needs no device.                            */
+int  gem_clean_params_for_model(int sensor_model, double cutoff_min_depth, double cutoff_max_depth, gem_clean_params* out);
+/*      The compaction itself, device pointers, enqueued on the handle's stream (behind gem_wait_event's events; the host is never
+ *      synchronised): n XYZI points (+ packed rgb, may be NULL) -> the kept points in order in d_xyzi_out / d_rgb_out, their input
+ *      positions in d_orig_out (int), their number in *d_count_out (an int in DEVICE memory).  Outputs other than d_count_out may be
+ *      NULL; each holds n elements.  Any n >= 0.                                                                                 */
+int  gem_clean_device(gem_handle* h, const gem_clean_params* clean, int n, const void* d_xyzi, const void* d_rgb,
+                      void* d_xyzi_out, void* d_rgb_out, void* d_orig_out, void* d_count_out);
+/*      gem_add / gem_add_device / gem_add_aos on a RAW cloud (staging, arenas and gem_reserve rules as theirs; no orig array: the raw
+ *      position is every point's orig index).  Same map as the plain entry on the cleaned cloud with the kept indices.          */
+int  gem_add_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n, const float* xyzi, const uint32_t* rgb);
+int  gem_add_raw_device(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n, const void* d_xyzi, const void* d_rgb);
+int  gem_add_aos_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n, const void* points_host, int point_step,
+                     int off_x, int off_y, int off_z, int off_intensity, int off_rgb);
+/*      SensorProcessorBase::process on a raw cloud (SPB.cpp:66-94): clean, then Process_points on the kept points.  The per-point
+ *      outputs (each may be NULL; each holds n elements) cover the *n_kept kept points in order; orig_out = their raw positions.
+ *      Host arrays: the kept count is read back.                                                                                 */
+int  gem_process_points_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n,
+                            const float* x, const float* y, const float* z, int* n_kept, int* orig_out,
+                            int* map_index, float* var, float* x_ts, float* y_ts, float* height);
+
 /* ---- batched sweeps (BASELINE config 4): for s in 0..n_sweeps-1:
  *        Mapvar_update(var_updates[s]) ; add(params[s], cloud s)
  *      with the map pose fixed for the batch.  Clouds are device-resident, concatenated:
