@@ -104,6 +104,13 @@ SIGNATURES = {
     "gem_add_aos_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gem_process_points_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_void_p, c_void_p,
                                        POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gem_local_enable": (c_int, [c_void_p, c_longlong]),
+    "gem_local_capture": (c_int, [c_void_p, c_double, c_double, POINTER(c_double)]),
+    "gem_local_keep_previous": (c_int, [c_void_p]),
+    "gem_local_grid_cloud": (c_int, [c_void_p, c_void_p, POINTER(c_int)]),
+    "gem_local_spill": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "gem_local_export": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_longlong), c_int]),
+    "gem_local_size": (c_int, [c_void_p, POINTER(c_longlong)]),
 }
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {

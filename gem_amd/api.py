@@ -31,6 +31,10 @@ LAYER_BY_NAME = {
 }
 _INT_LAYERS = {_lib.LAYER_COLOR_R, _lib.LAYER_COLOR_G, _lib.LAYER_COLOR_B}
 
+# PointXYZRGBICT (include/gem/gem.hpp; the reference's Anypoint): the records of the local map (ElevationMap.local_*)
+POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("pad", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1"),
+                        ("covariance", "<f4"), ("intensity", "<f4"), ("travers", "<f4")])
+
 
 class GemError(RuntimeError):
     pass
@@ -570,6 +574,51 @@ class ElevationMap:
         self._check(self._lib.gem_show(self._h, float(map_length), float(resolution), pos, vp(visual), vp(xyz), vp(rgb), C.byref(n), vp(img)), "gem_show")
         k = int(n.value)
         return {"visual": visual.reshape(9, L, L), "points_xyz": xyz[:k].copy(), "points_rgb": rgb[:k].copy(), "image_bgr": img, "count": k}
+
+    # -- the rolling-window local map (updateLocalMap, EMg.cpp:609-767; visualPointMap, :520-530) ---------------
+    def local_enable(self, capacity: int = 1 << 16) -> None:
+        """Switch the device local map on, empty, with room for `capacity` entries (it grows on demand); 0 switches it off and
+        frees its memory (gem_local_enable)."""
+        self._check(self._lib.gem_local_enable(self._h, int(capacity)), "gem_local_enable")
+
+    def local_capture(self, map_length: float = 0.0, resolution: float = 0.0, position=None) -> None:
+        """What show() leaves in visualMap_, with its geometry (gem_show's rules).  Between map_feature() and raytracing()."""
+        pos = None if position is None else (C.c_double * 2)(float(position[0]), float(position[1]))
+        self._check(self._lib.gem_local_capture(self._h, float(map_length), float(resolution), pos), "gem_local_capture")
+
+    def local_keep_previous(self) -> None:
+        """prevMap_ = visualMap_ (EMg.cpp:422): the last capture becomes the previous one."""
+        self._check(self._lib.gem_local_keep_previous(self._h), "gem_local_keep_previous")
+
+    def local_grid_cloud(self) -> np.ndarray:
+        """gridMaptoPointCloud of the last capture (EMg.cpp:1198-1224): POINT_DTYPE records in iteration order."""
+        out = np.empty(self.length * self.length, POINT_DTYPE)
+        n = C.c_int()
+        self._check(self._lib.gem_local_grid_cloud(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)), "gem_local_grid_cloud")
+        return out[:n.value].copy()
+
+    def local_spill(self, current_position, position_shift):
+        """The "Local mapping" block of updateLocalMap (EMg.cpp:715-764) without its gate, on the previous capture: returns
+        (records spilled in iteration order, replaced = the reference's `count`).  Positions and shifts are taken as float."""
+        cp = (C.c_float * 2)(*[float(np.float32(v)) for v in current_position[:2]])
+        ps = (C.c_float * 2)(*[float(np.float32(v)) for v in position_shift[:2]])
+        out = np.empty(self.length * self.length, POINT_DTYPE)
+        n, rep = C.c_int(), C.c_int()
+        self._check(self._lib.gem_local_spill(self._h, cp, ps, out.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(rep)), "gem_local_spill")
+        return out[:n.value].copy(), int(rep.value)
+
+    def local_export(self, clear: bool = False) -> np.ndarray:
+        """localHashtoPointCloud (EMg.cpp:1124-1140) in last-write order; clear=True empties the local map afterwards."""
+        out = np.empty(max(self.local_size(), 1), POINT_DTYPE)
+        n = C.c_longlong()
+        self._check(self._lib.gem_local_export(self._h, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n), int(bool(clear))),
+                    "gem_local_export")
+        return out[:n.value].copy()
+
+    def local_size(self) -> int:
+        n = C.c_longlong()
+        self._check(self._lib.gem_local_size(self._h, C.byref(n)), "gem_local_size")
+        return int(n.value)
 
     # -- the step in front of the path: input colourisation (EMg.cpp:349-381) -------------------------------
     @staticmethod

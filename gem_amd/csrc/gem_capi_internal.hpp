@@ -240,6 +240,18 @@ struct gem_handle {
     unsigned ray_calls = 0;
     Arena color;        // gem_colorize: its own sort arrays and tables (never shared with a pass in flight on the binning stream)
     Arena clean_cnt;    // the compactions' per-workgroup counts (gem_clean.hip; sized by gem_reserve)
+    // the rolling-window local map (gem_local_*, gem_capi_local.cpp; kernels in gem_local.hip)
+    struct Local {
+        bool enabled = false;
+        struct Capture { Arena rec, lin; double off = 0, res = 0, px = 0, py = 0; int sx = 0, sy = 0; } slot[2];
+        int cur = -1, prev = -1;        // the slot the last capture wrote / the slot keep_previous kept (-1: none)
+        Arena log[2];                   // the log of upserts and its compaction target, in turn (`act` is the log)
+        int act = 0;
+        Arena keys, vals;               // the open-addressing table: key -> log position
+        Arena spill_cnt, exp_cnt;       // per-workgroup counts of the spill / capture and of the export compactions
+        Arena small;                    // device words: capture counts [2] | spill total | export total | new keys
+        long long log_cap = 0, log_len = 0, table_cap = 0, live = 0;
+    } local;
     bool  dbg_on = false;
     bool  dbg_frame = false;            // debug knob: with the stamps on, a stream of single sweeps still runs as k_frame (its tiles AND its binning blocks are stamped)
     long long sort_fallbacks = 0;      // passes whose forced sorted form / pass count did not fit the map and took the other form (gem_debug_get)
@@ -311,6 +323,7 @@ int flush_deferred(gem_handle* h);
 int flush_walk(gem_handle* h);
 int flush_local(gem_handle* h);
 int wait_gather(gem_handle* h);
+void local_free(gem_handle* h);                 // gem_capi_local.cpp: the local map's arenas (gem_destroy, gem_local_enable(0))
 int settle(gem_handle* h);
 int flush_pending(gem_handle* h, bool with_floor);
 int index_to_range(int index, int L);          // gpu_process.cu:914-919

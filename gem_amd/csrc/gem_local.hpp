@@ -1,0 +1,69 @@
+// gem_local.hpp -- the rolling-window local map on the device (internal header): argument blocks and host launchers of gem_local.hip.
+//   capture  stable compaction of the cells ElevationMap::show keeps (EM.cpp:101) into 32-byte records + their linear indices
+//   spill    the L-shaped band of the previous capture that left the window (EMg.cpp:715-764), appended to the local map's log
+//   insert   upsert of log entries into the open-addressing table (key -> log position, the larger position wins)
+//   export   stable compaction of the live log entries (an entry is live while the table points at it)
+// Every compaction is three launches (count per workgroup -> one-workgroup scan -> scatter), as in gem_clean.hip.
+#pragma once
+
+#include "gem_kernels.hpp"
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace gem {
+
+constexpr int kLocalThreads = 256;                          // one workgroup = 4 waves
+constexpr int kLocalItems = 4;                              // items per thread
+constexpr int kLocalTile = kLocalThreads * kLocalItems;     // items per workgroup (1024)
+constexpr unsigned long long kLocalEmpty = ~0ull;           // empty table slot: the bits of the key (NaN, NaN), never a finite position
+
+// PointXYZRGBICT (include/gem/gem.hpp): x, y, z, pad | b, g, r, a | covariance, intensity, travers
+struct LocalRecord {
+    float x, y, z, pad;
+    uint32_t bgra;
+    float covariance, intensity, travers;
+};
+static_assert(sizeof(LocalRecord) == 32, "PointXYZRGBICT is 32 bytes");
+
+// grid_map's getPositionFromIndex for a capture: (px + off) - res * unwrapped index, off = 0.5 * map_length - 0.5 * resolution
+struct LocalGeom {
+    double off, res, px, py;
+    int L, sx, sy;
+};
+
+struct LocalCaptureArgs {
+    LayerPtrs m; LocalGeom g;
+    LocalRecord* rec; int* lin;         // [L^2] the kept cells in iteration order, their linear (column-major buffer) index
+};
+
+struct LocalSpillArgs {
+    const LocalRecord* rec; const int* lin; const uint32_t* count;   // the previous capture
+    LocalGeom g;
+    double lo_x, hi_x, lo_y, hi_y;      // current_{x,y} -/+ length * resolution / 2 (double)
+    float dx, dy;                       // position_shift (float compares)
+    LocalRecord* out;                   // the log, at its current length
+};
+
+struct LocalTable {
+    unsigned long long* keys;           // [cap] (x bits | y bits << 32), -0 stored as +0; kLocalEmpty when free
+    int* vals;                          // [cap] log position, -1 when free
+    unsigned long long mask;            // cap - 1 (cap a power of two)
+};
+
+struct LocalExportArgs {
+    const LocalRecord* log; long long n;
+    LocalTable t;
+    LocalRecord* out;
+};
+
+inline unsigned local_blocks(long long n) { return n > 0 ? (unsigned)((n + kLocalTile - 1) / kLocalTile) : 0u; }
+
+// block_cnt: [local_blocks(n)] scratch; *total: kept items (device)
+hipError_t launch_local_capture(hipStream_t st, const LocalCaptureArgs& a, uint32_t* block_cnt, uint32_t* total);
+hipError_t launch_local_spill(hipStream_t st, const LocalSpillArgs& a, long long bound, uint32_t* block_cnt, uint32_t* total, bool scatter);
+hipError_t launch_local_export(hipStream_t st, const LocalExportArgs& a, uint32_t* block_cnt, uint32_t* total);
+// log[p0, p0 + n) into the table; *new_keys (may be NULL) += keys that were not present
+hipError_t launch_local_insert(hipStream_t st, const LocalRecord* log, long long p0, long long n, LocalTable t, uint32_t* new_keys);
+
+} // namespace gem

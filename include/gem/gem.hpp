@@ -12,6 +12,7 @@
 //   RobotMotionMapUpdater::update (+ computeReducedCovariance / computeRelativeCovariance)
 //       src/RobotMotionMapUpdater.cpp:42-90, 92-109, 111-145
 //   ElevationMap layer names                                      src/ElevationMap.cpp:43-44
+//   ElevationMapping::updateLocalMap / visualPointMap (LocalMap)   src/ElevationMapping.cpp:609-767, 520-530
 #pragma once
 
 #include "../gem_hip.h"
@@ -350,6 +351,68 @@ private:
     gem_handle* h_ = nullptr;
     int length_ = 0;
     float resolution_ = 0.f;
+};
+
+// ---------------------------------------------------------------------------------------------
+// The rolling-window local map of ElevationMapping::updateLocalMap (ElevationMapping.cpp:609-767) and the grid cloud of
+// visualPointMap (:520-530), on the device (gem_local_*).  The flags and the gate of the node stay with the caller, see
+// INTEGRATION.md.  Records: PointXYZRGBICT with pad = 1 and a = 0; exported entries carry their intensity (the reference's
+// localHashtoPointCloud leaves it unset).
+// ---------------------------------------------------------------------------------------------
+class LocalMap {
+public:
+    // capacity: initial entries (grows on demand)
+    explicit LocalMap(ElevationMap& map, long long capacity = 1 << 16) : map_(map)
+    { map_.check(gem_local_enable(map_.handle(), capacity), "gem_local_enable"); }
+    ~LocalMap() { gem_local_enable(map_.handle(), 0); }
+    LocalMap(const LocalMap&) = delete;
+    LocalMap& operator=(const LocalMap&) = delete;
+
+    // map_.show()'s visualMap_ with its geometry (0 / 0 / nullptr: as ElevationMap::show).  Between mapFeature and raytracing.
+    void capture(double mapLength = 0.0, double resolution = 0.0, const double position[2] = nullptr)
+    { map_.check(gem_local_capture(map_.handle(), mapLength, resolution, position), "gem_local_capture"); }
+    // prevMap_ = map_.visualMap_
+    void keepPrevious() { map_.check(gem_local_keep_previous(map_.handle()), "gem_local_keep_previous"); }
+    // gridMaptoPointCloud(map_.visualMap_, ...)
+    std::vector<PointXYZRGBICT> gridCloud()
+    {
+        std::vector<PointXYZRGBICT> v(cells());
+        int n = 0;
+        map_.check(gem_local_grid_cloud(map_.handle(), v.data(), &n), "gem_local_grid_cloud");
+        v.resize(static_cast<size_t>(n));
+        return v;
+    }
+    // the "Local mapping" block's body (ElevationMapping.cpp:715-764): the cells it pushes to visualCloud_, in order; *replaced
+    // (optional) = its `count`
+    std::vector<PointXYZRGBICT> spill(const float currentPosition[2], const float positionShift[2], int* replaced = nullptr)
+    {
+        std::vector<PointXYZRGBICT> v(cells());
+        int n = 0, r = 0;
+        map_.check(gem_local_spill(map_.handle(), currentPosition, positionShift, v.data(), &n, &r), "gem_local_spill");
+        v.resize(static_cast<size_t>(n));
+        if (replaced) *replaced = r;
+        return v;
+    }
+    // localHashtoPointCloud(localMap_, ...), in last-write order; clear: then localMap_.swap(tmp)
+    std::vector<PointXYZRGBICT> exportCloud(bool clear = false)
+    {
+        std::vector<PointXYZRGBICT> v(static_cast<size_t>(size()));
+        long long n = 0;
+        map_.check(gem_local_export(map_.handle(), v.empty() ? nullptr : v.data(), static_cast<long long>(v.size()), &n, clear ? 1 : 0),
+                   "gem_local_export");
+        v.resize(static_cast<size_t>(n));
+        return v;
+    }
+    long long size() const
+    {
+        long long n = 0;
+        map_.check(gem_local_size(map_.handle(), &n), "gem_local_size");
+        return n;
+    }
+
+private:
+    size_t cells() const { const size_t L = static_cast<size_t>(map_.length()); return L * L; }
+    ElevationMap& map_;
 };
 
 inline bool SensorProcessorBase::process(ElevationMap& map, const PointXYZRGBICT* cloud, int n,

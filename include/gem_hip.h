@@ -362,6 +362,45 @@ int  gem_shard_sort_device(gem_handle* h, int n_local_sweeps, const gem_frame_pa
 int  gem_shard_fuse_device(gem_handle* h, int n_src, const void* const* d_hv, const void* const* d_key, const uint32_t* counts,
                            const void* const* d_ranges, const uint32_t* bases, int n_global_sweeps, const float* var_updates_global);
 
+
+/* ---- the rolling-window local map (ElevationMapping::updateLocalMap, EMg.cpp:609-767; visualPointMap, :520-530) -----------------
+ *   gem_local_enable           capacity > 0: switch the local map on, empty, with room for `capacity` entries (it grows on demand);
+ *                              on an enabled handle it starts over (empty map, no capture).  0: switch it off and free its memory.
+ *   gem_local_capture          what map_.show() leaves in visualMap_ (EM.cpp:89-111): the cells with elevation != -10, traver != -10
+ *                              and traver not NaN, in grid_map's iteration order, with the geometry (gem_show's rules: map_length <= 0
+ *                              -> L * resolution, resolution <= 0 -> the map's, position NULL -> the map's centre) and the start
+ *                              index at the time of the call.  Take it between gem_map_feature and gem_raytracing: prevMap_ is a copy
+ *                              of the show output, so cells raytracing deletes afterwards are still in it (EMg.cpp:413-422).
+ *   gem_local_keep_previous    prevMap_ = map_.visualMap_ (EMg.cpp:422, :621, :1025): the last capture becomes the previous one.
+ *   gem_local_grid_cloud       gridMaptoPointCloud (EMg.cpp:1198-1224) of the last capture: every kept cell, in iteration order.
+ *   gem_local_spill            the body of the "Local mapping" block (EMg.cpp:715-764) without its gate: every cell of the PREVIOUS
+ *                              capture with traver >= 0.0 (double; NaN fails) whose position -- grid_map's getPositionFromIndex in
+ *                              double from that capture's geometry -- passes the eight-way predicate of :726-733 against
+ *                              current_position (float, promoted) -/+ length * resolution / 2 (double; the previous capture's
+ *                              resolution) with float compares of position_shift's signs.  In iteration order, each is written to
+ *                              points and upserted under ((float) x, (float) y): a present key is removed and inserted again, so it
+ *                              moves to the end of the order.  out_replaced = the reference's `count`: selected cells whose key was
+ *                              present, an earlier cell of the same call included (far from the origin distinct cells can round to
+ *                              one key: the later one wins).  Keys compare as float pairs, so -0 equals +0.  The caller keeps the
+ *                              gate, verbatim:  if (std::abs(dx) >= res || (std::abs(dy) >= res && initFlag == 0 && JumpFlag == 0)).
+ *   gem_local_export           localHashtoPointCloud (EMg.cpp:1124-1140), in last-write order (a dict with del d[k]; d[k] = v); with
+ *                              clear != 0 the local map is emptied afterwards (localMap_.swap(tmp)).  points may be NULL: only the
+ *                              count is returned.
+ *   gem_local_size             entries of the local map.
+ * Records are PointXYZRGBICT (32 bytes): x, y the float positions, z elevation, pad = 1.0f, b g r from the colour layers through int,
+ * a = 0, covariance = variance, intensity, travers = traver.  The reference leaves pad and a uninitialised and its
+ * localHashtoPointCloud never sets intensity: the device writes the stored intensity there.  points arrays: L * L records (spill,
+ * grid_cloud) or max_points (export); they may be NULL.  GEM_ERR_INVALID: not enabled, spill / keep_previous before any capture,
+ * spill before any keep_previous, a handle with a communicator, max_points below the entry count.  Positions are assumed finite. */
+int  gem_local_enable(gem_handle* h, long long capacity);
+int  gem_local_capture(gem_handle* h, double map_length, double resolution, const double position[2]);
+int  gem_local_keep_previous(gem_handle* h);
+int  gem_local_grid_cloud(gem_handle* h, void* points, int* out_count);
+int  gem_local_spill(gem_handle* h, const float current_position[2], const float position_shift[2],
+                     void* points, int* out_count, int* out_replaced);
+int  gem_local_export(gem_handle* h, void* points, long long max_points, long long* out_count, int clear);
+int  gem_local_size(gem_handle* h, long long* out_count);
+
 #ifdef __cplusplus
 }
 #endif
