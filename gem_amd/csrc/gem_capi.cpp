@@ -621,6 +621,8 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
                 GEM_HIP(h, hipMemsetAsync(pb.gflag.p, 0, pb.gflag.cap, h->stream));
                 pb.epoch = 0;
             }
+            // a stream of single sweeps (k_frame): any one of them up to the bound -- clouds beyond kSweepPoints are cut into a batch
+            if (ts == 4 && (r = ensure_frame_buckets(h, pb, (int)T, (int)units_of(std::min(points, kSweepPoints))))) return r;
         }
         return GEM_OK;
     };

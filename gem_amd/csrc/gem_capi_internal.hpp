@@ -69,6 +69,7 @@ struct gem_handle {
     // pass p runs on `stream` (binning does not depend on the map, only on the cloud and the pose).
     struct PassBuffers {
         Arena rec, srt, seg, flag, gflag;   // records, descriptor table, touched stamps per (tile, sweep) and per (sweep, tile, 32 units)
+        Arena bkt, bcnt, spill, fctl;       // k_frame's per-tile buckets, their counts (all-zero between passes), the spill slots (all free), its two form words
         Arena s_hv1, s_hv2, s_key1, s_key2, s_src1, s_src2, s_cnt1, s_cnt2, s_misc;   // the sorted pipeline of big passes (gem_sort.hip)
         bool blkcnt_dirty = false;     // k_sort_project has been asked to count into s_blkcnt and k_block_prefix has not cleared it yet
         Arena s_blkcnt;                // [4 T] records per block, zero between passes (k_sort_project adds, k_block_prefix reads and clears)
@@ -287,6 +288,7 @@ int step_abort(gem_handle* h, int rc);
 
 int ensure(gem_handle* h, Arena& a, size_t bytes);
 int ensure_zeroed(gem_handle* h, Arena& a, size_t bytes);
+int ensure_frame_buckets(gem_handle* h, gem_handle::PassBuffers& pb, int T, int B);   // k_frame's record arenas for T tiles and B units
 
 struct HostXfer { void* host; void* dev; size_t bytes; };
 

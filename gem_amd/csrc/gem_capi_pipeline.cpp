@@ -592,9 +592,15 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     }
 
     if (defer) {
+        // k_frame bins into per-tile buckets: the point index rides in 22 bits of a record (a single sweep has at most kSweepPoints)
+        static_assert(kSweepPoints <= (1ll << 22), "k_frame's record format");
+        if ((rc = ensure_frame_buckets(h, pb, T, B))) return rc;
+        ba.bkt = static_cast<uint32_t*>(pb.bkt.p); ba.bcount = static_cast<uint32_t*>(pb.bcnt.p); ba.spill = static_cast<uint4*>(pb.spill.p);
+        ba.ctl = static_cast<uint32_t*>(pb.fctl.p);
+        fa.bkt = ba.bkt; fa.bcount = ba.bcount; fa.spill = ba.spill; fa.ctl = ba.ctl;
         if (h->deferred.valid && h->deferred.attr != attr) { const int rcd = flush_deferred(h); if (rcd) return rcd; }   // (cannot happen: toggling the tracking flushes)
         if (h->deferred.valid) { Timed t(h, 2); GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, ba, attr, t.events())); }
-        else                   { Timed t(h, 0); GEM_HIP(h, launch_bin(h->stream, ba, in.src, ts, t.events())); }
+        else                   { Timed t(h, 0); GEM_HIP(h, launch_frame(h->stream, FuseArgs{}, ba, attr, t.events())); }   // (no tile blocks: binning only)
         h->deferred.fa = fa; h->deferred.ts = ts; h->deferred.attr = attr; h->deferred.valid = true;
         h->n_pending = 0;
         h->floor_dirty = false;

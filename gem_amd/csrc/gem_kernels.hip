@@ -69,15 +69,20 @@ template <int W> __device__ __forceinline__ uint32_t rec_load_cell(const uint4* 
     return reinterpret_cast<const uint32_t*>(rec)[(size_t)i * W + 2];
 }
 
-// one unit = 64 consecutive points, binned by one wave
-template <int SRC, int TS, bool BATCH>
+// one unit = 64 consecutive points, binned by one wave.
+// BUCKET (k_frame, one sweep, no colours): no descriptor words and no touched stamps.  The leader of each tile group reserves a range
+// of the tile's bucket with ONE returning atomic on bcount[tile] and the group's lanes store their records there, the point index
+// above the cell in the third word ({h, var, cell | index << 8}; a sweep holds at most 2^17 points).  A record whose position lies
+// past the bucket's kFrameBucket slots goes to spill[point index] = {h, var, cell | index << 8, tile} instead (frame_tile's slow path).
+template <int SRC, int TS, bool BATCH, bool BUCKET = false>
 __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
 {
     constexpr int TE = 1 << TS;
     constexpr int U = 64;
+    static_assert(!BUCKET || (SRC == 0 && TS == 4 && !BATCH), "bucket form: single sweeps of XYZI on 16x16 tiles");
     const int lane = lane_id();
     if (unit >= a.B) return;                               // whole wave leaves together
-    if (unit == 0 && lane == 0) *a.srt_top = 0u;            // bump pointer of the sorted arena (dense tiles of k_fuse_list, same pass)
+    if (!BUCKET && unit == 0 && lane == 0) *a.srt_top = 0u; // bump pointer of the sorted arena (dense tiles of k_fuse_list, same pass)
 
     int sweep = 0, unit_first = 0, orig0 = 0;
     long long base, sweep_begin = 0, sweep_end = a.n;
@@ -139,6 +144,17 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
     const uint32_t rank = (uint32_t)__popcll(peers & lt);
     const uint32_t cnt = (uint32_t)__popcll(peers);
     const bool leader = valid && rank == 0;
+    if constexpr (BUCKET) {
+        uint32_t old = 0;
+        if (leader) old = atomicAdd(&a.bcount[tile], cnt);
+        old = (uint32_t)__shfl((int)old, valid ? (__ffsll((unsigned long long)peers) - 1) : lane, 64);
+        if (valid) {
+            const uint32_t pos = old + rank, z = cl | (src << 8);
+            if (pos < (uint32_t)kFrameBucket) rec_store3(reinterpret_cast<uint4*>(a.bkt), (size_t)tile * kFrameBucket + pos, __float_as_uint(hh), __float_as_uint(vv), z);
+            else a.spill[src] = make_uint4(__float_as_uint(hh), __float_as_uint(vv), z, tile);
+        }
+        return;
+    }
     const uint32_t x = leader ? cnt : 0u;
     const uint32_t start_leader = wave_inclusive_scan(x) - x;       // groups laid out in order of first appearance
     const int my_leader = valid ? (__ffsll((unsigned long long)peers) - 1) : lane;
@@ -177,11 +193,11 @@ __device__ __forceinline__ void bin_stamp_end(const BinArgs& a, int block)
     }
 }
 
-template <int SRC, int TS, bool BATCH>
+template <int SRC, int TS, bool BATCH, bool BUCKET = false>
 __device__ __forceinline__ void bin_wave_body(const BinArgs& a, int block)
 {
     bin_stamp_begin(a, block);
-    bin_unit<SRC, TS, BATCH>(a, (int)(block * 4 + (threadIdx.x >> 6)));
+    bin_unit<SRC, TS, BATCH, BUCKET>(a, (int)(block * 4 + (threadIdx.x >> 6)));
     bin_stamp_end(a, block);
 }
 
@@ -368,10 +384,37 @@ __device__ __forceinline__ DenseResult dense_tile(const uint4* __restrict__ rec,
 // kernel keep the dense path's registers (and spills) out of the code every LiDAR tile runs.
 template <int CPT> struct TileState { float e[CPT], s[CPT], lw[CPT]; uint32_t tmask, acc_nd, acc_P; int sweep; };
 
+constexpr int kFrameRunBits = 3;                    // runs of 2^kFrameRunBits neighbouring tiles per XCD (runs of 2 / 4 / 8: FETCH_SIZE 4.9 / 4.35 / 4.03 MB per C2 frame, 8.56 / 8.41 / 8.40 us per step)
+constexpr int kFrameGridUnit = 8 << kFrameRunBits;  // ... the tile blocks come in multiples of this
+constexpr int kFramePB = kFrameBucket;              // records per tile the fast path holds in LDS
+constexpr int kFrameSpec = 256;                     // records requested before the count is known: one per thread
+constexpr int kFrameWG = 6;                         // workgroups per CU the register budget is set for
+// LDS: rank rows [256] x 8 u16 | generic lists head / tail [256][4] u16 (aliased), cell of a slot [PB] u16, next [PB] u16, stage [PB] x 16 B, misc
+constexpr size_t kFrameLds = 256 * 16 + kFramePB * 2 * 2 + kFramePB * 16 + 16;
+
+// block -> tile: centre-first in dispatch order (the heaviest tiles of a robot-centric map start first), and XCD-AWARE --
+// workgroup b runs on XCD b % 8, each XCD has its own L2, and four tiles that follow each other in a tile row share their
+// 128-byte lines of the layers: runs of 2^kFrameRunBits consecutive ranks go to ONE XCD (with plain rank = block the neighbours
+// sat on eight different XCDs and every shared line was fetched twice: FETCH_SIZE 5.6 MB per frame instead of 3.6,
+// profiles/r05_c2_bench.txt).  Rows c, c-1, c+1, ...; columns in runs of neighbours on alternating sides: 0 1 2 3 | -1 -2 -3 -4 | 4 5 6 7 | ...
+__device__ __forceinline__ bool frame_tile_of(const FuseArgs& a, int block, int& tr, int& tc)
+{
+    const int tpr = a.tiles_per_row;
+    const int x = block & 7, i = block >> 3;
+    const int rnk = ((((i >> kFrameRunBits) << 3) + x) << kFrameRunBits) + (i & ((1 << kFrameRunBits) - 1));
+    if (rnk >= a.T) return false;
+    const int bi = rnk / tpr, bj = rnk - bi * tpr;
+    const int oi = (bi & 1) ? -((bi + 1) >> 1) : (bi >> 1);
+    const int cj = bj >> kFrameRunBits, t = bj & ((1 << kFrameRunBits) - 1);
+    const int oj = (cj & 1) ? -(((cj - 1) >> 1) << kFrameRunBits) - 1 - t : ((cj >> 1) << kFrameRunBits) + t;
+    tr = a.center_tr + oi; tr = tr < 0 ? tr + tpr : (tr >= tpr ? tr - tpr : tr);
+    tc = a.center_tc + oj; tc = tc < 0 ? tc + tpr : (tc >= tpr ? tc - tpr : tc);
+    return true;
+}
+
 // FLAGS: bits 0-1 = ATTR (0 none, 1 colours from the cloud, 2 colours from gem_fuse's arrays), bit 2 = LOWEST (also maintain the
 // map_lowest layer, GPU:432-439, for gem_raytracing)
-constexpr int kFrameRunBits = 3;                    // k_frame: runs of 2^kFrameRunBits neighbouring tiles per XCD (fuse_list_body, RANKED; runs of 2 / 4 / 8: FETCH_SIZE 4.9 / 4.35 / 4.03 MB per C2 frame, 8.56 / 8.41 / 8.40 us per step)
-constexpr int kFrameGridUnit = 8 << kFrameRunBits;  // ... its tile blocks come in multiples of this
+// RANKED: k_frame's descriptor form (frame_tile_of maps blocks to tiles)
 template <int TS, int NT, int PB, int FLAGS, bool BATCH, int MODE, bool RANKED = false>
 __device__ __forceinline__ bool fuse_list_body(const FuseArgs& a, int tile, unsigned char* lds_raw, TileState<(1 << (2 * TS)) / NT>& st)
 {
@@ -431,23 +474,18 @@ __device__ __forceinline__ bool fuse_list_body(const FuseArgs& a, int tile, unsi
     const int block_in = (int)blockIdx.x;                                  // (profiling aid: stamp row word 15)
     int tr, tc;
     if constexpr (!BATCH) {
-        const int q4 = (a.T + 3) >> 2;
-        // RANKED (k_frame, whose tiles are all resident at once): centre-first in dispatch order, and XCD-AWARE -- workgroup b runs on
-        // XCD b % 8, each XCD has its own L2, and four tiles that follow each other in a tile row share their 128-byte lines of the
-        // layers: runs of 2^kFrameRunBits consecutive ranks go to ONE XCD (with plain rank = block the neighbours sat on eight different XCDs
-        // and every shared line was fetched twice: FETCH_SIZE 5.6 MB per frame instead of 3.6, profiles/r05_c2_bench.txt)
-        int rnk;
-        if (RANKED) { const int x = tile & 7, i = tile >> 3; rnk = ((((i >> kFrameRunBits) << 3) + x) << kFrameRunBits) + (i & ((1 << kFrameRunBits) - 1)); }
-        else rnk = (tile & 3) * q4 + (tile >> 2);
-        if (rnk >= a.T) return false;
-        const int bi = rnk / tpr, bj = rnk - bi * tpr;
-        const int oi = (bi & 1) ? -((bi + 1) >> 1) : (bi >> 1);
-        // columns: plain alternation c, c-1, c+1, ... or (RANKED) runs of neighbours on alternating sides: 0 1 2 3 | -1 -2 -3 -4 | 4 5 6 7 | ...
-        int oj;
-        if (RANKED) { const int cj = bj >> kFrameRunBits, t = bj & ((1 << kFrameRunBits) - 1); oj = (cj & 1) ? -(((cj - 1) >> 1) << kFrameRunBits) - 1 - t : ((cj >> 1) << kFrameRunBits) + t; }
-        else oj = (bj & 1) ? -((bj + 1) >> 1) : (bj >> 1);
-        tr = a.center_tr + oi; tr = tr < 0 ? tr + tpr : (tr >= tpr ? tr - tpr : tr);
-        tc = a.center_tc + oj; tc = tc < 0 ? tc + tpr : (tc >= tpr ? tc - tpr : tc);
+        if constexpr (RANKED) {
+            if (!frame_tile_of(a, tile, tr, tc)) return false;
+        } else {
+            const int q4 = (a.T + 3) >> 2;
+            const int rnk = (tile & 3) * q4 + (tile >> 2);
+            if (rnk >= a.T) return false;
+            const int bi = rnk / tpr, bj = rnk - bi * tpr;
+            const int oi = (bi & 1) ? -((bi + 1) >> 1) : (bi >> 1);
+            const int oj = (bj & 1) ? -((bj + 1) >> 1) : (bj >> 1);      // columns: plain alternation c, c-1, c+1, ...
+            tr = a.center_tr + oi; tr = tr < 0 ? tr + tpr : (tr >= tpr ? tr - tpr : tr);
+            tc = a.center_tc + oj; tc = tc < 0 ? tc + tpr : (tc >= tpr ? tc - tpr : tc);
+        }
         tile = tr * tpr + tc;
     } else {
         if (tile >= a.T) return false;
@@ -1114,25 +1152,285 @@ __global__ __launch_bounds__(NT, fuse_list_waves(TS, NT, PB, ATTR, BATCH)) void 
 // ------------------------------------------------------------------------------------------
 // FLAGS: 0, or 4 = the fusion also maintains map_lowest (GPU:432-439; the adapter of the unmodified node turns it on for Raytracing).
 // Round 5, from the launch's own time line (tools/frame_phases.py, profiles/r05_c2_frame_phases.txt: every workgroup's start and
-// end on the chip-wide 100 MHz clock): the chip starts about 850 workgroups of this kernel per microsecond, a tile lives 3.5 us
-// whatever it holds (three dependent memory round trips, five barrier-separated phases), and with 85 VGPRs / 31 KB of LDS five
-// workgroups fit a CU -- 1280 of the launch's 1956, so the rest waited for the first tiles to END and the launch took two tile
-// lifetimes.  Now: rounds of kFramePB = 768 records (24 KB) and at most 80 VGPRs -- six workgroups per CU, 1536 slots: every tile
-// is resident from the start, the binning blocks follow as the light tiles leave -- and the tiles in plain centre-first order
-// (the heaviest are dispatched first; the round-1 interleave by quarters spread them over the whole 1.5 us ramp): 9.1 -> 7.9 us.
-// Measured and dropped: the binning blocks first (+0.9 us: every tile starts later), two or eight units per binning wave
+// end on the chip-wide 100 MHz clock): the chip starts about 850 workgroups of this kernel per microsecond, and at most 80 VGPRs
+// give six workgroups per CU -- 1536 slots: every tile is resident from the start, the binning blocks follow as the light tiles
+// leave.  Measured and dropped: the binning blocks first (+0.9 us: every tile starts later), two or eight units per binning wave
 // (+0.7 / +6 us: a unit is ~3 k cycles of a wave's issue, the blocks became the launch's tail), rounds of 512 records with
 // 64 VGPRs and eight workgroups per CU (+3.5 us: the fuse body spills).
-constexpr int kFramePB = 768;        // records per LDS round of k_frame's fuse half (k_fuse_list alone keeps 1024)
-constexpr int kFrameWG = 6;          // workgroups per CU the register budget is set for
+// The records are binned into per-tile buckets (bin_unit, BUCKET): a tile issues the load of its count, the first kFrameSpec
+// records of its bucket (LDS DMA, speculative: the slots past the count hold stale records and are ignored) and its own cells
+// together -- ONE dependent memory round trip before the records are in LDS, where the unit-indexed descriptor table took three
+// (touched stamps, descriptor words, records).  A bucket holds records in the order the binning waves reserved them, so the
+// owner of a cell sorts its <= kRankMax records by point index (key = index << 10 | slot) instead of by slot.
+// One 16x16 tile of a single sweep, 256 threads, one cell per thread.
+//   FAST PATH (at most kFramePB records in the tile and kRankMax per cell -- every tile of a C2 sweep): the records are in LDS
+//     after the first round trip (after a second one for tiles of more than kFrameSpec records), ranked per cell by an LDS atomic,
+//     and the owner sorts its <= 7 keys and runs the reference's recurrence (GPU:480-531) from registers;
+//   SLOW PATH (anything else: a fuller bucket, its spill, more records in a cell): rounds over windows of kFramePB consecutive point
+//     indices.  A record of the window goes to slot (index - window start), so slot order IS input order, and the per-wave in-order
+//     linked lists of k_fuse_list's generic path give every cell its records in that order.  Each round re-reads the bucket (and
+//     scans the whole spill arena when the bucket overflowed); the next window starts at the smallest index left.
+template <int FLAGS>
+__device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigned char* lds_raw)
+{
+    constexpr bool LOWEST = (FLAGS & 4) != 0;
+    constexpr int TS = 4, TE = 16, CELLS = 256, NT = 256, NW = 4, PB = kFramePB;
+    constexpr uint32_t NIL = 0xffffu;
+    static_assert(PB % 64 == 0 && PB % NT == 0 && kFrameSpec == NT && PB <= 1024, "geometry");
+    uint16_t* rowp  = reinterpret_cast<uint16_t*>(lds_raw);                // fast path: rows[CELLS] of 8 u16 {slot 0..6, count}
+    uint16_t* head  = rowp;                                                // slow path: head / tail [CELLS][NW]
+    uint16_t* tail  = head + CELLS * NW;
+    uint16_t* scell = reinterpret_cast<uint16_t*>(lds_raw + CELLS * 16);   // [PB] slow path: cell of a slot, NIL = no record
+    uint16_t* nxt   = scell + PB;                                          // [PB]
+    uint4*    stage = reinterpret_cast<uint4*>(nxt + PB);                  // [PB] {h, var, cell | index << 8, -}
+    uint32_t* misc  = reinterpret_cast<uint32_t*>(stage + PB);             // [0] fast-path overflow, [1] next window
+
+    const int tid = (int)threadIdx.x, lane = lane_id();
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);              // (uniform: the LDS base of a DMA goes to M0)
+    int tr, tc;
+    if (!frame_tile_of(a, block, tr, tc)) return;
+    const int tile = tr * a.tiles_per_row + tc;
+    const int row_base = tr << TS, col_base = tc << TS;
+    const int L = a.L;
+    int dbg_k = 0;
+#define GEM_STAMP() do { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + dbg_k++] = (unsigned long long)__builtin_readcyclecounter(); } while (0)
+    GEM_STAMP();                                                         // 0: start
+    if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + 12] = (unsigned long long)__builtin_amdgcn_s_memrealtime();   // (100 MHz, one clock for the chip)
+
+    // ---- one round trip: the count, the first kFrameSpec records of the bucket and the tile ------------------
+    const uint32_t nrec = a.bcount[tile];                                // block-uniform
+    const uint32_t* const bkt = a.bkt + (size_t)tile * kFrameBucket * 3;
+    auto dma = [&](uint32_t k0) {                                        // records [k0, k0 + 64) -> stage[k0 ..]: lane l's 12 bytes land at 16 l
+        const auto* gsrc = (const __attribute__((address_space(1))) void*)(bkt + (size_t)(k0 + (uint32_t)lane) * 3);
+        auto* ldst = (__attribute__((address_space(3))) void*)(stage + k0);
+        __builtin_amdgcn_global_load_lds(gsrc, ldst, 12, 0, 0);
+    };
+    dma((uint32_t)w * 64u);                                              // (inside the bucket whatever the count: kFrameSpec <= kFrameBucket)
+
+    const int c = tid;
+    const int row = row_base + (c >> TS), col = col_base + (c & (TE - 1));
+    const bool owned = row < a.row1 && row >= a.row0 && col < L;
+    float ce, cs, lw = 0.0f;
+    {   // unconditional loads (clamped address): cells outside the map or the strip read cell 0 and are never written back
+        const size_t g = owned ? (size_t)row * L + col : 0;
+        ce = a.elevation[g]; cs = a.variance[g];
+        if constexpr (LOWEST) {
+            // map_lowest is indexed by the GEOGRAPHIC cell (GPU:430 PointsToIndex), not by the circular-buffer cell
+            int gr = row - a.start0, gc = col - a.start1;
+            gr += gr < 0 ? L : 0; gc += gc < 0 ? L : 0;
+            lw = a.lowest[owned ? (size_t)gr * L + gc : 0];
+        }
+    }
+    const float ce0 = ce, cs0 = cs;                                      // as loaded: only cells that changed are written back
+    reinterpret_cast<uint4*>(rowp)[tid] = make_uint4(0, 0, 0, 0);        // rank rows start with count 0
+    if (tid == 0) misc[0] = 0u;
+    GEM_STAMP();                                                         // 1: loads issued
+    if (nrec == 0 && !a.dense) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }    // (no LDS DMA outlives the workgroup)
+    const bool fits = nrec <= (uint32_t)PB;
+    if (fits && nrec > (uint32_t)kFrameSpec)                             // block-uniform: the rest of a heavy tile (a second round trip)
+        for (uint32_t k0 = (uint32_t)kFrameSpec + (uint32_t)w * 64u; k0 < nrec; k0 += NW * 64u) dma(k0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    GEM_STAMP();                                                         // 2: records and tile arrived
+    // consumed: the count is zero again for the pass after next (behind the barrier: every wave has its copy of the count)
+    if (tid == 0 && nrec != 0) a.bcount[tile] = 0u;
+
+    // queued Mapvar_update increments (GPU:540-547), before the first record
+    for (int k = 0; k < a.n_pending; ++k) if (cs != kInitVariance) cs += a.pending[k];
+
+    bool slow = !fits;
+    if (fits) {
+        // ---- ranks: PB / NT slots per thread, all cell reads, then all rank atomics, then all row writes in flight together
+        constexpr int RK = PB / NT;
+        uint32_t rcell[RK], rold[RK];
+#pragma unroll
+        for (int r = 0; r < RK; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rcell[r] = k < nrec ? (stage[k].z & 0xffu) : 0u; }
+#pragma unroll
+        for (int r = 0; r < RK; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rold[r] = 0; if (k < nrec) rold[r] = atomicAdd(reinterpret_cast<uint32_t*>(rowp) + rcell[r] * 4 + 3, 0x10000u); }
+#pragma unroll
+        for (int r = 0; r < RK; ++r) {
+            const uint32_t k = (uint32_t)(tid + r * NT);
+            if (k < nrec) { const uint32_t rk = rold[r] >> 16; if (rk < (uint32_t)kRankMax) rowp[rcell[r] * 8 + rk] = (uint16_t)k; else misc[0] = 1u; }
+        }
+        __syncthreads();
+        GEM_STAMP();                                                     // 3: ranked
+        slow = misc[0] != 0;                                             // block-uniform
+    }
+    if (!slow) {
+        // ---- owner: sort <= 7 keys (point index << 10 | slot), run the chain from registers
+        const uint4 rw = *reinterpret_cast<const uint4*>(rowp + tid * 8);
+        const uint32_t n = rw.w >> 16;
+        const uint32_t p[kRankMax] = {rw.x & 0xffffu, rw.x >> 16, rw.y & 0xffffu, rw.y >> 16, rw.z & 0xffffu, rw.z >> 16, rw.w & 0xffffu};
+        uint32_t k[8];                                                   // ~0 = no record: sorted behind the live keys
+#pragma unroll
+        for (int i = 0; i < 8; ++i) k[i] = 0xffffffffu;
+#pragma unroll
+        for (int i = 0; i < kRankMax; ++i) {
+            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
+            const uint32_t sl = (uint32_t)i < n ? p[i] : 0u;             // slot 0 is always a valid address
+            if ((uint32_t)i < n) k[i] = ((stage[sl].z >> 8) << 10) | sl;
+        }
+        GEM_CSWAP(k[0], k[1]); GEM_CSWAP(k[2], k[3]); GEM_CSWAP(k[4], k[5]); GEM_CSWAP(k[6], k[7]);
+        GEM_CSWAP(k[0], k[2]); GEM_CSWAP(k[1], k[3]); GEM_CSWAP(k[4], k[6]); GEM_CSWAP(k[5], k[7]);
+        GEM_CSWAP(k[1], k[2]); GEM_CSWAP(k[5], k[6]); GEM_CSWAP(k[0], k[4]); GEM_CSWAP(k[3], k[7]);
+        GEM_CSWAP(k[1], k[5]); GEM_CSWAP(k[2], k[6]);
+        GEM_CSWAP(k[1], k[4]); GEM_CSWAP(k[3], k[6]);
+        GEM_CSWAP(k[2], k[4]); GEM_CSWAP(k[3], k[5]);
+        GEM_CSWAP(k[3], k[4]);
+        float hh[kRankMax], vv[kRankMax];
+#pragma unroll
+        for (int i = 0; i < kRankMax; ++i) {
+            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
+            const uint32_t sl = (uint32_t)i < n ? (k[i] & 1023u) : 0u;
+            hh[i] = __uint_as_float(stage[sl].x); vv[i] = __uint_as_float(stage[sl].y);
+        }
+#pragma unroll
+        for (int i = 0; i < kRankMax; ++i) {
+            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
+            float e2 = ce, s2 = cs;
+            (void)fuse_step(e2, s2, hh[i], vv[i], a.mahal, a.var_floor);
+            const bool live = (uint32_t)i < n;
+            const bool fl = live && (!LOWEST || hh[i] != -1.0f);         // GPU:482 (only LOWEST passes carry such records)
+            ce = fl ? e2 : ce; cs = fl ? s2 : cs;
+            if constexpr (LOWEST) { const float l2 = lowest_step(lw, hh[i], vv[i]); lw = live ? l2 : lw; }
+        }
+    } else {
+        // ---- slow path: windows [lo, lo + PB) of point indices, in order.  It re-reads the tile's records per window (and the
+        //      whole spill arena when the bucket overflowed): the pass buffer set is switched to the descriptor form for good
+        //      (frame_form), so a stream pays this once per buffer set
+        if (tid == 0) a.ctl[0] = 1u;
+        const uint32_t nb = min(nrec, (uint32_t)kFrameBucket);
+        const uint32_t nspill = fits ? 0u : (uint32_t)a.B_total * (uint32_t)a.U;
+        const uint64_t lt = lanemask_lt();
+        uint32_t lo = 0;
+        for (;;) {                                                       // block-uniform
+            const uint32_t hi = lo + (uint32_t)PB;
+            reinterpret_cast<uint4*>(head)[tid] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);   // head + tail: 4 KB
+            for (int k = tid; k < PB; k += NT) scell[k] = (uint16_t)NIL;
+            if (tid == 0) misc[1] = 0xffffffffu;
+            __syncthreads();
+            uint32_t next = 0xffffffffu;
+            auto take = [&](uint32_t x, uint32_t y, uint32_t z) -> bool {
+                const uint32_t idx = z >> 8;
+                if (idx >= lo && idx < hi) { stage[idx - lo] = make_uint4(x, y, z, 0u); scell[idx - lo] = (uint16_t)(z & 0xffu); return true; }
+                if (idx >= hi) next = min(next, idx);
+                return false;
+            };
+            for (uint32_t k = (uint32_t)tid; k < nb; k += NT) (void)take(bkt[k * 3], bkt[k * 3 + 1], bkt[k * 3 + 2]);
+            for (uint32_t j = (uint32_t)tid; j < nspill; j += NT) {
+                const uint4 r = a.spill[j];
+                if (r.w == (uint32_t)tile && take(r.x, r.y, r.z)) a.spill[j].w = kSpillFree;   // taken: the slot is free for the pass after next
+            }
+            if (next != 0xffffffffu) atomicMin(&misc[1], next);
+            __syncthreads();
+            {   // wave w appends slots [w PB / NW, (w + 1) PB / NW) to its own list of each cell, 64 consecutive slots per step
+                constexpr uint32_t per = PB / NW;
+                for (uint32_t kc = (uint32_t)w * per; kc < (uint32_t)(w + 1) * per; kc += 64) {
+                    const uint32_t sl = kc + (uint32_t)lane;
+                    const uint32_t cell = scell[sl];
+                    const bool on = cell != NIL;
+                    const uint64_t peers = wave_peers(on, cell, 2 * TS);
+                    const uint64_t above = lane == 63 ? 0ull : (peers & (~0ull << (lane + 1)));
+                    if (on) {
+                        nxt[sl] = above ? (uint16_t)(sl + (uint32_t)(__ffsll((unsigned long long)above) - 1 - lane)) : (uint16_t)NIL;
+                        const uint32_t hx = cell * NW + (uint32_t)w;
+                        if ((peers & lt) == 0) {                         // first of its group: link behind the wave's list of this cell
+                            if (head[hx] == NIL) head[hx] = (uint16_t)sl;
+                            else nxt[tail[hx]] = (uint16_t)sl;
+                        }
+                        if (above == 0) tail[hx] = (uint16_t)sl;
+                    }
+                }
+            }
+            __syncthreads();
+            {   // walk list(wave 0), list(wave 1), ... of this thread's cell
+                const uint2 hv = *reinterpret_cast<const uint2*>(head + c * NW);
+                const uint32_t hd[NW] = {hv.x & 0xffffu, hv.x >> 16, hv.y & 0xffffu, hv.y >> 16};
+                uint32_t ww = 0, cur = NIL;
+#pragma unroll
+                for (int x = NW - 1; x >= 0; --x) if (hd[x] != NIL) { cur = hd[x]; ww = (uint32_t)x; }
+                while (__ballot(cur != NIL) != 0) {                      // wave-uniform
+                    const bool live = cur != NIL;
+                    const uint32_t sl = live ? cur : 0u;
+                    const float h = __uint_as_float(stage[sl].x), v = __uint_as_float(stage[sl].y);
+                    uint32_t nx = nxt[sl];
+                    if (live && nx == NIL) {                             // end of this wave's list: the next non-empty one
+                        uint32_t nw_ = NW;
+#pragma unroll
+                        for (int x = NW - 1; x >= 0; --x) if ((uint32_t)x > ww && hd[x] != NIL) { nx = hd[x]; nw_ = (uint32_t)x; }
+                        ww = nw_;
+                    }
+                    float e2 = ce, s2 = cs;
+                    (void)fuse_step(e2, s2, h, v, a.mahal, a.var_floor);
+                    const bool fl = live && (!LOWEST || h != -1.0f);     // GPU:482
+                    ce = fl ? e2 : ce; cs = fl ? s2 : cs;
+                    if constexpr (LOWEST) { const float l2 = lowest_step(lw, h, v); lw = live ? l2 : lw; }
+                    cur = live ? nx : NIL;
+                }
+            }
+            const uint32_t nlo = misc[1];
+            __syncthreads();                                             // every thread has read misc[1] and left the lists
+            if (nlo == 0xffffffffu) break;
+            lo = nlo;
+        }
+    }
+    GEM_STAMP();                                                         // 4: chains done
+
+    // ---- variance floor at the end of every Fuse (GPU:533-534), then the single write-back of the tile
+    if (cs < a.var_floor) cs = a.var_floor;
+    if (owned) {
+        // (recomputed here: the address of the tile's read, kept alive across the body, costs registers of the 80-VGPR budget)
+        int cc = tid;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(cc));
+#endif
+        const size_t g = (size_t)(row_base + (cc >> TS)) * L + col_base + (cc & (TE - 1));
+        if (__float_as_uint(ce) != __float_as_uint(ce0)) a.elevation[g] = ce;
+        if (__float_as_uint(cs) != __float_as_uint(cs0)) a.variance[g] = cs;
+        if constexpr (LOWEST) {
+            int gr = row_base + (cc >> TS) - a.start0, gc = col_base + (cc & (TE - 1)) - a.start1;
+            gr += gr < 0 ? L : 0; gc += gc < 0 ? L : 0;
+            a.lowest[(size_t)gr * L + gc] = lw;
+        }
+    }
+    GEM_STAMP();                                                         // 5: stores issued
+    if (a.dbg && tid == 0) {
+        a.dbg[(size_t)tile * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
+        a.dbg[(size_t)tile * 16 + 15] = (unsigned long long)block + 1ull;
+        a.dbg[(size_t)tile * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID: the XCD's clock is its own
+    }
+#undef GEM_STAMP
+}
+
+// Two forms of a pass, chosen per pass buffer set on the device (ctl words, no host round trip):
+//   bucket form (above) while no tile of the set has needed frame_tile's slow path;
+//   descriptor form -- k_bin_wave's records, descriptor words and stamps, fused by k_fuse_list's body -- once one has: its rounds
+//   of kFramePB records read every record once however heavy the tile, which is what maps at 0.1-0.2 m (tiles of thousands of
+//   records, tens per cell) need.  ctl[0] (sticky) is set by the fuse of a pass and read by the binning of the set's next pass,
+//   two launches later; ctl[1] = the form the binning chose, read by the fuse of the same pass one launch later.
+__device__ __forceinline__ void bin_frame_body(const BinArgs& ba, int block)
+{
+    const bool desc = ba.ctl[0] != 0u;                                   // uniform: written two launches ago
+    if (block == 0 && threadIdx.x == 0) ba.ctl[1] = desc ? 1u : 0u;
+    if (desc) bin_wave_body<0, 4, false, false>(ba, block);
+    else      bin_wave_body<0, 4, false, true>(ba, block);
+}
+
 template <int FLAGS>
 __global__ __launch_bounds__(256, kFrameWG) void k_frame(FuseArgs fa, BinArgs ba)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
-    const int nf = (fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1);     // fuse blocks (see the block -> tile mapping)
-    if ((int)blockIdx.x < nf) { TileState<1> st; fuse_list_body<4, 256, kFramePB, FLAGS, false, 0, true>(fa, (int)blockIdx.x, lds_dyn, st); }
-    else bin_wave_body<0, 4, false>(ba, (int)blockIdx.x - nf);
+    const int nf = (fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1);     // fuse blocks (see frame_tile_of)
+    if ((int)blockIdx.x < nf) {
+        if (fa.ctl[1] != 0u) { TileState<1> st; fuse_list_body<4, 256, kFramePB, FLAGS, false, 0, true>(fa, (int)blockIdx.x, lds_dyn, st); }
+        else frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
+    } else {
+        bin_frame_body(ba, (int)blockIdx.x - nf);
+    }
 }
+
+// the binning of the first frame of a stream, with nothing to fuse beside it (no LDS, the occupancy of k_bin_wave)
+__global__ __launch_bounds__(256) void k_bin_frame(BinArgs ba) { bin_frame_body(ba, (int)blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------
 // dense / state kernels
@@ -1625,13 +1923,18 @@ hipError_t launch_fuse(hipStream_t st, const FuseArgs& a, int ts, int attr, int 
     return launch_fuse_list<5, 512, 2048>(st, a, attr, ev);
 }
 
-// fuse of the previous frame + bin of this one (single sweeps on 16x16 tiles, no attributes)
+// fuse of the previous frame + bin of this one (single sweeps on 16x16 tiles, no attributes); fa.T == 0: binning only (k_bin_frame), ba.B == 0: fuse only
 hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, int attr, LaunchEvents ev)
 {
+    if (attr != 0 && attr != 4) return hipErrorInvalidValue;
+    if (fa.T == 0) {                                                     // binning only
+        if (ba.B > 0) GEM_LAUNCH((k_bin_frame), dim3((ba.B + 3) / 4), dim3(256), 0, st, ev, ba);
+        return hipGetLastError();
+    }
     const dim3 grid(((fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1)) + (ba.B + 3) / 4), block(256);
-    if (attr == 4)      GEM_LAUNCH((k_frame<4>), grid, block, fuse_list_lds(256, 4, kFramePB, 0), st, ev, fa, ba);
-    else if (attr == 0) GEM_LAUNCH((k_frame<0>), grid, block, fuse_list_lds(256, 4, kFramePB, 0), st, ev, fa, ba);
-    else return hipErrorInvalidValue;
+    const size_t lds = std::max(kFrameLds, fuse_list_lds(256, 4, kFramePB, 0));      // (either form of the fuse half)
+    if (attr == 4) GEM_LAUNCH((k_frame<4>), grid, block, lds, st, ev, fa, ba);
+    else           GEM_LAUNCH((k_frame<0>), grid, block, lds, st, ev, fa, ba);
     return hipGetLastError();
 }
 

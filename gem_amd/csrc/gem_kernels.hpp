@@ -20,6 +20,11 @@ struct LayerPtrs {
     float *rough, *slope;           // outputs of the traversability stage (not touched by init / clear, like the reference's scratch arrays)
 };
 
+// k_frame's records (a stream of single sweeps): one bucket of kFrameBucket 12-byte records per tile, filled through a per-tile count;
+// what does not fit goes to a spill arena indexed by point (gem_kernels.hip: bin_unit, frame_tile)
+constexpr int      kFrameBucket   = 768;
+constexpr uint32_t kSpillFree     = 0xffffffffu;      // tile word of a spill slot that holds no record (the arena's state between passes)
+
 // A "unit" is 64 consecutive points of one sweep, binned by one wave.  Unit u owns record slots
 // [64 u, 64 (u + 1)) of the arena and one word per tile in its sweep's block of the descriptor table.
 struct BinArgs {
@@ -55,6 +60,11 @@ struct BinArgs {
     uint32_t*         srt_top;         // bump pointer of the sorted arena (reset here, used by the fuse of the same pass)
     int               keep_sentinel;   // keep records with h == -1 (GPU:482) for the LOWEST fuse variants
     unsigned long long* dbg;           // optional: [blocks][16] cycle stamps of the binning blocks (word 0 start, 1 end, 15 = block index + 1; profiling aid)
+    // k_frame's binning half only (instead of rec / seg / flag / gflag)
+    uint32_t* bkt;                     // [T][kFrameBucket][3] records {h, var, cell | point index << 8}
+    uint32_t* bcount;                  // [T] records reserved in each bucket (all-zero between passes: the fuse zeroes what it reads)
+    uint4*    spill;                   // [B * U] by point index: {h, var, cell | index << 8, tile} past a full bucket, else tile == kSpillFree
+    uint32_t* ctl;                     // [2] of the pass buffer set: [0] != 0 -> bin in the descriptor form (rec / seg / flag / gflag); [1] := the form chosen
 };
 
 struct FuseArgs {
@@ -89,6 +99,11 @@ struct FuseArgs {
     uint32_t          dense_min;       // a (tile, sweep) with more records than this takes the dense path (16x16 tiles only)
     int   count_per_pass;              // the sweeps are one cloud cut into pieces: count a cell once
     unsigned long long* dbg;           // optional: [T][16] cycle-counter stamps of thread 0 (profiling aid)
+    // k_frame's fuse half only (the records of BinArgs' bucket form; B_total * U spill slots are scanned when a bucket overflowed)
+    const uint32_t* bkt;
+    uint32_t* bcount;                  // zeroed as read
+    uint4*    spill;                   // slots taken are set back to kSpillFree
+    uint32_t* ctl;                     // [1] = the form the binning of this pass chose; [0] := 1 when a tile takes the bucket form's slow path
 };
 
 // ---- the sorted pipelines of big passes (gem_sort.hip) -----------------------------------------------------------------------

@@ -23,7 +23,7 @@ for k in range(n_sw - 2):
 m.synchronize()
 assert lib.gem_debug_set(m._h, b"dbg_frame", 1) == 0
 lib.gem_debug_fuse_stamps(m._h, 1, None, 0)
-m.add(wl.frames[n_sw - 2], d[n_sw - 2])          # k_bin_wave alone (the synchronisation above flushed the deferred fuse)
+m.add(wl.frames[n_sw - 2], d[n_sw - 2])          # binning alone (the synchronisation above flushed the deferred fuse)
 m.add(wl.frames[n_sw - 1], d[n_sw - 1])          # k_frame: fuse of sweep n-2 + binning of sweep n-1  <- the launch whose stamps are read
 ROWS = 8192
 buf = np.zeros((ROWS, 16), np.uint64)
@@ -48,11 +48,15 @@ print("window (us)     tiles starting  tiles ending  bin blocks starting  bin bl
 for a_, b_ in zip(edges[:-1], edges[1:]):
     print(f"  [{a_:4.1f},{b_:4.1f})   {((ts >= a_) & (ts < b_)).sum():8d}      {((te >= a_) & (te < b_)).sum():8d}      {((bs >= a_) & (bs < b_)).sum():8d}           {((be >= a_) & (be < b_)).sum():8d}")
 dur = tiles[np.arange(len(tiles)), nst - 1] - tiles[:, 0]                        # cycles (the workgroup's own counter)
-full = nst == 7
+NS = int(nst.max())                                                              # stamps of a tile that took the fast path
+full = nst == NS
 
-names = ["flags (round trip 1)", "descriptor words (round trip 2)", "scan + list", "records in LDS + ranks (round trip 3)", "chains", "stores"]
+if NS == 7:     # libraries before the per-tile buckets: the unit-indexed descriptor table
+    names = ["flags (round trip 1)", "descriptor words (round trip 2)", "scan + list", "records in LDS + ranks (round trip 3)", "chains", "stores"]
+else:           # per-tile buckets (frame_tile)
+    names = ["loads issued", "count + records + tile (round trip)", "ranks", "sort + chains", "stores"]
 if full.any():
-    dd = np.diff(tiles[full, :7], axis=1)
+    dd = np.diff(tiles[full, :NS], axis=1)
     print("tiles with records:", int(full.sum()), "| mean cycles per phase:", dict(zip(names, dd.mean(0).astype(int).tolist())))
     order = np.argsort(-dur)
     for i in order[:5]:
@@ -60,6 +64,6 @@ if full.any():
     late = np.argsort(-te)[:5]
     for i in late:
         print(f"  last to end: block {blk_t[i]:5d} start {ts[i]:6.2f} us end {te[i]:6.2f} us total {dur[i]:6d} cycles ({dur[i] / max(1e-9, (te[i] - ts[i])) / 1000:.2f} GHz)")
-print("tiles that left early (no record):", int((nst < 7).sum()), "mean life", int(dur[nst < 7].mean()) if (nst < 7).any() else 0)
+print("tiles that left early (no record) or took another path:", int((nst < NS).sum()), "mean life", int(dur[nst < NS].mean()) if (nst < NS).any() else 0)
 if len(bins):
     print(f"binning blocks: mean life {(be - bs).mean():.2f} us, max {(be - bs).max():.2f} | first start {bs.min():.2f} us, last start {bs.max():.2f} us")
