@@ -18,12 +18,19 @@ LAYER_ELEVATION, LAYER_VARIANCE, LAYER_INTENSITY, LAYER_TRAVER, LAYER_LOWEST, \
 LAYOUT_STORAGE_ROWMAJOR, LAYOUT_GRIDMAP_COLMAJOR_NAN = 0, 1
 MODEL_LASER, MODEL_STRUCTURED_LIGHT, MODEL_STEREO, MODEL_PERFECT = range(4)
 CLEAN_NONE, CLEAN_REMOVE_NAN, CLEAN_PASSTHROUGH_Z = range(3)
+VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTENSITY = range(5)
 
 
 class MapConfig(C.Structure):
     _fields_ = [("length", c_int), ("resolution", c_float), ("mahalanobis_threshold", c_float),
                 ("variance_floor", c_float), ("obstacle_threshold", c_float),
                 ("strip_row0", c_int), ("strip_rows", c_int), ("device", c_int)]
+
+
+class VoxelParams(C.Structure):
+    """gem_voxel_params: one pcl::VoxelGrid stage."""
+    _fields_ = [("leaf", c_float * 3), ("field", c_int), ("limit_min", c_double), ("limit_max", c_double),
+                ("limit_negative", c_int), ("reserved", c_int)]
 
 
 class RejectFilter(C.Structure):
@@ -104,6 +111,9 @@ SIGNATURES = {
     "gem_add_aos_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
     "gem_process_points_raw": (c_int, [c_void_p, POINTER(FrameParams), POINTER(CleanParams), c_int, c_void_p, c_void_p, c_void_p,
                                        POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gem_voxel_device": (c_int, [c_void_p, POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gem_add_voxel": (c_int, [c_void_p, POINTER(FrameParams), POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p]),
+    "gem_add_voxel_device": (c_int, [c_void_p, POINTER(FrameParams), POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p]),
     "gem_local_enable": (c_int, [c_void_p, c_longlong]),
     "gem_local_capture": (c_int, [c_void_p, c_double, c_double, POINTER(c_double)]),
     "gem_local_keep_previous": (c_int, [c_void_p]),

@@ -125,6 +125,54 @@ class RejectFilter:
 
 
 @dataclass
+class VoxelStage:
+    """One pcl::VoxelGrid<pcl::PCLPointCloud2> stage as pcl_ros's nodelet runs it (gem_voxel_params; the contract is in
+    include/gem_hip.h).  field: None, "x", "y", "z" or "intensity"; PCL's defaults elsewhere."""
+    leaf_size: float = 0.01
+    field: Optional[str] = None
+    limit_min: float = -3.4028234663852886e38
+    limit_max: float = 3.4028234663852886e38
+    limit_negative: bool = False
+
+    FIELDS = {None: _lib.VOXEL_FIELD_NONE, "": _lib.VOXEL_FIELD_NONE, "x": _lib.VOXEL_FIELD_X, "y": _lib.VOXEL_FIELD_Y,
+              "z": _lib.VOXEL_FIELD_Z, "intensity": _lib.VOXEL_FIELD_INTENSITY}
+
+    def to_struct(self) -> "_lib.VoxelParams":
+        if self.field not in self.FIELDS:
+            raise ValueError(f"voxel filter field {self.field!r}: none, x, y, z or intensity")
+        leaf = self.leaf_size if np.ndim(self.leaf_size) else (self.leaf_size,) * 3
+        v = _lib.VoxelParams()
+        for k in range(3):
+            v.leaf[k] = float(np.float32(leaf[k]))                       # the nodelet's double leaf_size, cast to float
+        v.field = self.FIELDS[self.field]
+        v.limit_min, v.limit_max = float(self.limit_min), float(self.limit_max)
+        v.limit_negative = int(bool(self.limit_negative))
+        return v
+
+    @staticmethod
+    def filter_launch() -> "list[VoxelStage]":
+        """filter.launch: one stage, x in [-10, 10], leaf 0.1."""
+        return [VoxelStage(0.1, "x", -10.0, 10.0)]
+
+    @staticmethod
+    def filter_kitti_launch() -> "list[VoxelStage]":
+        """filter_kitti.launch: x in [-40, 40], then z in [-25, 25], then y in [-40, 40], leaf 0.2 each."""
+        return [VoxelStage(0.2, "x", -40.0, 40.0), VoxelStage(0.2, "z", -25.0, 25.0), VoxelStage(0.2, "y", -40.0, 40.0)]
+
+
+def _voxel_stages(stages) -> "C.Array":
+    if isinstance(stages, (VoxelStage, _lib.VoxelParams)):
+        stages = [stages]
+    stages = list(stages)
+    if not 1 <= len(stages) <= 4:
+        raise ValueError("1 to 4 voxel stages")
+    arr = (_lib.VoxelParams * len(stages))()
+    for i, st in enumerate(stages):
+        arr[i] = st if isinstance(st, _lib.VoxelParams) else st.to_struct()
+    return arr
+
+
+@dataclass
 class Frame:
     """Per-frame constants as plain numpy data (what GPUPointCloudprocess derives, SPB.cpp:171-208)."""
     T: np.ndarray                                            # 4x4 float32, sensor -> map
@@ -449,6 +497,54 @@ class ElevationMap:
         n = a.shape[0]
         kr, pr = _host_ptr(rgb, np.uint32, n)
         self._check(self._lib.gem_add_raw(self._h, C.byref(p), C.byref(cp), n, a.ctypes.data_as(C.c_void_p), pr), "gem_add_raw")
+
+    # -- the VoxelGrid pre-filter of the launch files (pcl/VoxelGrid nodelets) on the device ------------------------------------------
+    def voxel_device(self, stages, xyzi, rgb=None, sync: bool = True, out=None):
+        """gem_voxel_device on a float32 [N, 4] device tensor (+ optional 32-bit rgb [N]): returns (xyzi_out [N, 4], rgb_out [N] or
+        None, count [1] int32), device tensors whose first count rows hold the centroids in voxel order and whose tail has NaN x, y, z
+        -- new ones, or the three of `out` (a previous call's result, reused).  Enqueued on the handle's stream; with sync=False the
+        caller synchronises the handle before reading them."""
+        import torch
+        if not _is_device_tensor(xyzi) or not xyzi.is_contiguous() or xyzi.dtype != torch.float32 or xyzi.numel() != 4 * int(xyzi.shape[0]):
+            raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
+        n = int(xyzi.shape[0])
+        arr = _voxel_stages(stages)
+        if out is not None:
+            out, rgb_out, count = out
+            if out.shape != xyzi.shape or count.numel() < 1 or (rgb is not None and (rgb_out is None or rgb_out.numel() < n)):
+                raise ValueError("voxel_device: `out` does not fit this cloud")
+            rgb_out = rgb_out if rgb is not None else None
+        else:
+            out = torch.empty_like(xyzi)
+            count = torch.zeros(1, dtype=torch.int32, device=xyzi.device)
+            rgb_out = torch.empty(n, dtype=torch.int32, device=xyzi.device) if rgb is not None else None
+        prgb = self._device_words(rgb, n, xyzi, "rgb")
+        dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(self._lib.gem_voxel_device(self._h, arr, len(arr), n, dp(xyzi), prgb, dp(out), dp(rgb_out), dp(count)),
+                    "gem_voxel_device")
+        self._hold(xyzi, rgb, out, rgb_out, count)
+        if sync:
+            self.synchronize()
+        return out, rgb_out, count
+
+    def add_voxel(self, frame: Frame, stages, xyzi, rgb=None) -> None:
+        """add() behind the VoxelGrid stages (gem_add_voxel / gem_add_voxel_device): the map of add() on the centroids, orig index =
+        position in the filtered cloud."""
+        p = frame.to_struct()
+        arr = _voxel_stages(stages)
+        if _is_device_tensor(xyzi):
+            n = int(xyzi.shape[0])
+            if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n:
+                raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
+            prgb = self._device_words(rgb, n, xyzi, "rgb")
+            self._check(self._lib.gem_add_voxel_device(self._h, C.byref(p), arr, len(arr), n, C.c_void_p(xyzi.data_ptr()), prgb),
+                        "gem_add_voxel_device")
+            self._hold(xyzi, rgb)
+            return
+        a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+        n = a.shape[0]
+        kr, pr = _host_ptr(rgb, np.uint32, n)
+        self._check(self._lib.gem_add_voxel(self._h, C.byref(p), arr, len(arr), n, a.ctypes.data_as(C.c_void_p), pr), "gem_add_voxel")
 
     def add_aos_raw(self, frame: Frame, points: np.ndarray, off_x: int = 0, off_y: int = 4, off_z: int = 8, off_intensity: int = 24,
                     off_rgb: int = 16, clean=None) -> None:

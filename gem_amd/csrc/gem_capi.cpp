@@ -108,7 +108,7 @@ void gem_destroy(gem_handle* h)
     if (h->d_counters) hipFree(h->d_counters);
     for (Arena* a : {&h->stage, &h->scratch, &h->dbg, &h->color, &h->ray, &h->sh_dev, &h->sh_recv_hv[0], &h->sh_recv_key[0], &h->sh_recv_rng[0],
                      &h->sh_recv_hv[1], &h->sh_recv_key[1], &h->sh_recv_rng[1], &h->sh_ranges, &h->published[0], &h->published[1],
-                     &h->clean_cnt}) if (a->p) hipFree(a->p);
+                     &h->clean_cnt, &h->vox_state, &h->vox_hist, &h->vox_rec, &h->vox_tmp, &h->vox_out[0], &h->vox_out[1]}) if (a->p) hipFree(a->p);
     if (h->sh_host) hipHostFree(h->sh_host);
     for (auto& b : h->pb) {
         for (Arena* a : {&b.rec, &b.srt, &b.seg, &b.flag, &b.gflag, &b.tables, &b.s_hv1, &b.s_hv2, &b.s_key1, &b.s_key2, &b.s_src1, &b.s_src2,
@@ -533,6 +533,7 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
     if ((rc = ensure(h, h->stage, ((size_t)max_points * 4 + 256) * 9))) return rc;
     // (the raw-cloud entries, gem_capi_clean.cpp, work inside that staging arena; their compactions add a count per 1024 points)
     if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
+    if ((rc = voxel_reserve(h, max_points))) return rc;        // (the VoxelGrid entries, gem_capi_voxel.cpp)
     {   // ... and its pinned counterpart for callers with host arrays (gem_process_points: nine arrays; gem_map_feature: nine layers),
         // where that is a modest amount: larger ones grow on first use
         constexpr size_t kReserveMax = 64u << 20;

@@ -241,6 +241,11 @@ struct gem_handle {
     unsigned ray_calls = 0;
     Arena color;        // gem_colorize: its own sort arrays and tables (never shared with a pass in flight on the binning stream)
     Arena clean_cnt;    // the compactions' per-workgroup counts (gem_clean.hip; sized by gem_reserve)
+    // the VoxelGrid pre-filter (gem_voxel_*, gem_capi_voxel.cpp; kernels in gem_voxel.hip), all sized by gem_reserve
+    Arena vox_state, vox_hist;          // VoxState and the two digit histograms: all-zero between stages (zeroed when allocated)
+    Arena vox_rec, vox_tmp;             // the records of the sort passes | a chain's two intermediate clouds
+    Arena vox_out[2];                   // gem_add_voxel*: the filtered cloud, the two in turn (vox_flip)
+    unsigned vox_flip = 0;
     // the rolling-window local map (gem_local_*, gem_capi_local.cpp; kernels in gem_local.hip)
     struct Local {
         bool enabled = false;
@@ -326,6 +331,7 @@ int flush_walk(gem_handle* h);
 int flush_local(gem_handle* h);
 int wait_gather(gem_handle* h);
 void local_free(gem_handle* h);                 // gem_capi_local.cpp: the local map's arenas (gem_destroy, gem_local_enable(0))
+int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);
 int flush_pending(gem_handle* h, bool with_floor);
 int index_to_range(int index, int L);          // gpu_process.cu:914-919

@@ -13,6 +13,7 @@
 //       src/RobotMotionMapUpdater.cpp:42-90, 92-109, 111-145
 //   ElevationMap layer names                                      src/ElevationMap.cpp:43-44
 //   ElevationMapping::updateLocalMap / visualPointMap (LocalMap)   src/ElevationMapping.cpp:609-767, 520-530
+//   pcl::VoxelGrid of the launch files' nodelets (VoxelGrid)       filter.launch, filter_kitti.launch
 #pragma once
 
 #include "../gem_hip.h"
@@ -413,6 +414,84 @@ public:
 private:
     size_t cells() const { const size_t L = static_cast<size_t>(map_.length()); return L * L; }
     ElevationMap& map_;
+};
+
+// ---------------------------------------------------------------------------------------------
+// The pcl/VoxelGrid nodelets of the launch files (filter.launch, filter_kitti.launch) on the device (gem_voxel_*): the setters
+// of pcl::VoxelGrid; each addStage() appends the current settings as one more stage of the chain (at most four).  The contract
+// is in gem_hip.h (gem_voxel_device).
+// ---------------------------------------------------------------------------------------------
+class VoxelGrid {
+public:
+    VoxelGrid() { reset(); }
+    void setLeafSize(float lx, float ly, float lz) { cur_.leaf[0] = lx; cur_.leaf[1] = ly; cur_.leaf[2] = lz; }
+    // "" (none), "x", "y", "z" or "intensity"
+    void setFilterFieldName(const std::string& name)
+    {
+        static const std::map<std::string, int> fields = {{"", GEM_VOXEL_FIELD_NONE}, {"x", GEM_VOXEL_FIELD_X}, {"y", GEM_VOXEL_FIELD_Y},
+                                                          {"z", GEM_VOXEL_FIELD_Z}, {"intensity", GEM_VOXEL_FIELD_INTENSITY}};
+        const auto it = fields.find(name);
+        if (it == fields.end()) throw Error(GEM_ERR_INVALID, "VoxelGrid: filter field " + name + " (none, x, y, z or intensity)");
+        cur_.field = it->second;
+    }
+    void setFilterLimits(double limitMin, double limitMax) { cur_.limit_min = limitMin; cur_.limit_max = limitMax; }
+    void setFilterLimitsNegative(bool negative) { cur_.limit_negative = negative ? 1 : 0; }
+    // the current settings become the next stage; the setters then start from PCL's defaults again
+    VoxelGrid& addStage()
+    {
+        if (stages_.size() >= 4) throw Error(GEM_ERR_INVALID, "VoxelGrid: at most four stages");
+        stages_.push_back(cur_);
+        reset();
+        return *this;
+    }
+    const std::vector<gem_voxel_params>& stages() const { return stages_; }
+    // n XYZI points on the device -> d_xyzi_out (n points: the m centroids, then the NaN tail), m in *d_count (device int);
+    // enqueued on the map's stream.  Without addStage() the current settings are the one stage.
+    void filterDevice(ElevationMap& map, const void* d_xyzi, int n, void* d_xyzi_out, void* d_count, const void* d_rgb = nullptr,
+                      void* d_rgb_out = nullptr) const
+    {
+        const std::vector<gem_voxel_params> s = chain();
+        map.check(gem_voxel_device(map.handle(), s.data(), static_cast<int>(s.size()), n, d_xyzi, d_rgb, d_xyzi_out, d_rgb_out, d_count),
+                  "gem_voxel_device");
+    }
+    // ElevationMap::add behind the filter: host XYZI (gem_add_voxel) or device XYZI (addToDevice, gem_add_voxel_device)
+    void addTo(ElevationMap& map, const gem_frame_params& frame, const float* xyzi, int n, const uint32_t* rgb = nullptr) const
+    {
+        const std::vector<gem_voxel_params> s = chain();
+        map.check(gem_add_voxel(map.handle(), &frame, s.data(), static_cast<int>(s.size()), n, xyzi, rgb), "gem_add_voxel");
+    }
+    void addToDevice(ElevationMap& map, const gem_frame_params& frame, const void* d_xyzi, int n, const void* d_rgb = nullptr) const
+    {
+        const std::vector<gem_voxel_params> s = chain();
+        map.check(gem_add_voxel_device(map.handle(), &frame, s.data(), static_cast<int>(s.size()), n, d_xyzi, d_rgb), "gem_add_voxel_device");
+    }
+    static VoxelGrid filterLaunch()                  // filter.launch
+    {
+        VoxelGrid v;
+        v.setLeafSize(0.1f, 0.1f, 0.1f); v.setFilterFieldName("x"); v.setFilterLimits(-10.0, 10.0);
+        return v.addStage();
+    }
+    static VoxelGrid filterKittiLaunch()             // filter_kitti.launch
+    {
+        VoxelGrid v;
+        const char* f[3] = {"x", "z", "y"};
+        const double lim[3] = {40.0, 25.0, 40.0};
+        for (int i = 0; i < 3; ++i) { v.setLeafSize(0.2f, 0.2f, 0.2f); v.setFilterFieldName(f[i]); v.setFilterLimits(-lim[i], lim[i]); v.addStage(); }
+        return v;
+    }
+
+private:
+    void reset()
+    {
+        cur_ = gem_voxel_params{};
+        cur_.leaf[0] = cur_.leaf[1] = cur_.leaf[2] = 0.01f;                  // (pcl::VoxelGrid's default leaf is 0: set one)
+        cur_.field = GEM_VOXEL_FIELD_NONE;
+        cur_.limit_min = -static_cast<double>(std::numeric_limits<float>::max());
+        cur_.limit_max = static_cast<double>(std::numeric_limits<float>::max());
+    }
+    std::vector<gem_voxel_params> chain() const { return stages_.empty() ? std::vector<gem_voxel_params>{cur_} : stages_; }
+    gem_voxel_params cur_{};
+    std::vector<gem_voxel_params> stages_;
 };
 
 inline bool SensorProcessorBase::process(ElevationMap& map, const PointXYZRGBICT* cloud, int n,

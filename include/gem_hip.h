@@ -212,6 +212,47 @@ int  gem_process_points_raw(gem_handle* h, const gem_frame_params* p, const gem_
                             const float* x, const float* y, const float* z, int* n_kept, int* orig_out,
                             int* map_index, float* var, float* x_ts, float* y_ts, float* height);
 
+/* ---- the VoxelGrid pre-filter of the launch files (filter.launch: one stage; filter_kitti.launch: three) on the device: one
+ *      pcl::VoxelGrid<pcl::PCLPointCloud2> stage as pcl_ros's nodelet runs it (PCL 1.7 / 1.8, downsample_all_data, no minimum
+ *      points per voxel), up to four stages per call.  One stage on n XYZI points, inv[k] = 1.0f / leaf[k] in float:
+ *        1. bounds (getMinMax3D): over the points with finite x, y, z whose field value passes the limit test against the limits
+ *           CAST TO FLOAT -- normal: skip if v > max || v < min; negative: skip if v < max && v > min (a NaN value is kept) --
+ *           the float min_p / max_p per coordinate.  No such point: the output is empty.
+ *        2. point test: the same test against the DOUBLE limits (v promoted), and x, y, z finite.  (At a limit float cannot hold,
+ *           say 0.1, a point may shape the bounds and not be output.)  GEM_VOXEL_FIELD_NONE: finite x, y, z only.
+ *        3. overflow: d_k = (int64)((max_p[k] - min_p[k]) * inv[k]) + 1 in float; d0 * d1 * d2 > INT32_MAX: the stage's output
+ *           is its input unchanged, all n points in order (PCL's output = *input_).
+ *        4. voxel: min_b = (int)floorf(min_p * inv), div = (int)floorf(max_p * inv) - min_b + 1, mul = (1, div0, div0 * div1);
+ *           ijk_k = (int)floorf(p_k * inv_k) - min_b_k, idx = ijk . mul in wrapping int32, taken as uint32.  (int) of a float
+ *           outside the int range is INT_MIN, as x86 converts it.
+ *        5. order: ascending idx; inside a voxel, input order.  (PCL's std::sort is not stable: PCL itself may sum a voxel of
+ *           three or more points in another order, last-bit differences there.)
+ *        6. centroid: x, y, z, intensity summed sequentially in float from +0.0f, divided by (float)count; with rgb, r, g, b
+ *           summed as floats, divided, truncated to int, repacked (r << 16) | (g << 8) | b.
+ *      The output holds n points: the m centroids, then x = y = z = NaN, intensity 0 (rgb 0), which the pipelines reject in
+ *      projection (above) and gem_colorize_device gives pixel -1.  Stage s + 1 reads stage s's m points.                     */
+enum { GEM_VOXEL_FIELD_NONE = 0, GEM_VOXEL_FIELD_X = 1, GEM_VOXEL_FIELD_Y = 2, GEM_VOXEL_FIELD_Z = 3, GEM_VOXEL_FIELD_INTENSITY = 4 };
+typedef struct gem_voxel_params {
+    float  leaf[3];                /* leaf size (the nodelet's double leaf_size cast to float); finite, > 0 */
+    int    field;                  /* GEM_VOXEL_FIELD_* */
+    double limit_min, limit_max;   /* filter limits (PCL's defaults: -FLT_MAX, FLT_MAX) */
+    int    limit_negative;         /* keep the points OUTSIDE the limits */
+    int    reserved;               /* 0 */
+} gem_voxel_params;
+/*      n_stages (1..4) stages on n XYZI points (+ packed rgb, may be NULL), device pointers, enqueued on the handle's stream (the
+ *      host is never synchronised): the result in d_xyzi_out / d_rgb_out (n elements each; d_rgb_out may be NULL; neither may
+ *      overlap an input), m in *d_count_out (an int in DEVICE memory).  Any n >= 0.  GEM_ERR_INVALID for a leaf that is not
+ *      finite or not > 0, n_stages outside 1..4, a field outside the enum, and on a handle that joined a communicator.        */
+int  gem_voxel_device(gem_handle* h, const gem_voxel_params* stages, int n_stages, int n, const void* d_xyzi, const void* d_rgb,
+                      void* d_xyzi_out, void* d_rgb_out, void* d_count_out);
+/*      gem_add (host XYZI, staged as gem_add stages it) / gem_add_device behind the filter: the same map as gem_add on the m
+ *      centroids with orig index = output position.  The filtered cloud lives in the handle's arenas (gem_reserve sizes them);
+ *      the rules of those entries hold otherwise.                                                                               */
+int  gem_add_voxel(gem_handle* h, const gem_frame_params* p, const gem_voxel_params* stages, int n_stages, int n, const float* xyzi,
+                   const uint32_t* rgb);
+int  gem_add_voxel_device(gem_handle* h, const gem_frame_params* p, const gem_voxel_params* stages, int n_stages, int n,
+                          const void* d_xyzi, const void* d_rgb);
+
 /* ---- batched sweeps (BASELINE config 4): for s in 0..n_sweeps-1:
  *        Mapvar_update(var_updates[s]) ; add(params[s], cloud s)
  *      with the map pose fixed for the batch.  Clouds are device-resident, concatenated:

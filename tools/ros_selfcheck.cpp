@@ -1,19 +1,25 @@
-// tools/ros_selfcheck.cpp -- the closing procedure for the two rows of SURVEY 8f whose oracle restates UN-VENDORED third-party code
-// ("missing" #3):
+// tools/ros_selfcheck.cpp -- the closing procedure for the rows whose oracle restates UN-VENDORED third-party code
+// ("missing" #3; the third row came with the VoxelGrid pre-filter):
 //
 //   f2  gem_show     restates grid_map's iteration order (GridMapIterator over the circular buffer), getPosition and the
 //                    grid_map::Matrix layout that ElevationMap::show fills (reference: elevation_mapping/src/ElevationMap.cpp:85-149)
 //   f4  gem_colorize restates OpenCV's cv::circle(img, p, 1, colour) as "the four edge neighbours of p", drawn into the image the later
 //                    points sample (reference: elevation_mapping/src/ElevationMapping.cpp:349-381)
+//   vox gem_voxel_device restates pcl::VoxelGrid<pcl::PCLPointCloud2> as pcl_ros's nodelet runs it (the launch files' filter stages);
+//                    tests/voxel_ref.py restates the same contract in numpy
 //
-// Neither library exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
+// None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
 // MI355X with libgem_hip.so): it drives the real libraries through the same loops the reference runs and compares every output of the
-// HIP path bit for bit.  Exit code 0 = both rows pinned on the real third-party code; non-zero = first difference printed.
+// HIP path bit for bit.  Exit code 0 = every row pinned on the real third-party code; non-zero = first difference printed.
+// The voxel row is bit for bit in the output order, the count and every voxel of one or two points; in voxels of three or more points
+// it allows a few ulps, because PCL's std::sort is not stable and may sum such a voxel in another order than input order.
 //
-//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4) \
-//       -Lgem_amd/lib -lgem_hip -Wl,-rpath,$PWD/gem_amd/lib -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4) \
-//       -o ros_selfcheck && ./ros_selfcheck [seed]
+//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8) \
+//       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Lgem_amd/lib -lgem_hip -Wl,-rpath,$PWD/gem_amd/lib -L/opt/rocm/lib -lamdhip64 \
+//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
+//
+// It cannot be compiled where the test suite runs (no ROS, grid_map, OpenCV or PCL there).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 #include <algorithm>
@@ -21,6 +27,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
+#include <cfloat>
 #include <cstring>
 #include <random>
 #include <vector>
@@ -30,6 +37,14 @@
 #include <grid_map_core/iterators/GridMapIterator.hpp>
 #include <opencv2/core.hpp>
 #include <opencv2/imgproc.hpp>
+#include <hip/hip_runtime_api.h>
+#include <pcl/PCLPointCloud2.h>
+#include <pcl/conversions.h>
+#include <pcl/filters/voxel_grid.h>
+#include <pcl/point_types.h>
+
+#include <limits>
+#include <map>
 
 #include "gem_hip.h"
 
@@ -211,6 +226,113 @@ int check_colorize(uint32_t seed)
     return 0;
 }
 
+// ---- vox -----------------------------------------------------------------------------------------------------------------------
+// Seeded clouds with NaN points and crowded voxels through the real pcl::VoxelGrid<pcl::PCLPointCloud2> (setLeafSize, setFilterFieldName,
+// setFilterLimits, setFilterLimitsNegative as the nodelet sets them), against gem_voxel_device with the same stage.
+int check_voxel_stage(gem_handle* h, std::mt19937& rng, float leaf, const char* field, int field_id, double lo, double hi, bool negative)
+{
+    const int N = 200000;
+    std::normal_distribution<float> xy(0.0f, 12.0f), z(0.0f, 1.0f);
+    std::uniform_real_distribution<float> u01(0.0f, 1.0f);
+    pcl::PointCloud<pcl::PointXYZI> cloud;
+    cloud.resize(N);
+    cloud.is_dense = false;
+    for (int i = 0; i < N; ++i) {
+        pcl::PointXYZI& p = cloud.points[i];
+        p.x = xy(rng); p.y = xy(rng); p.z = z(rng); p.intensity = 255.0f * u01(rng);
+        if (u01(rng) < 0.2f) { p.x = std::round(p.x * 2.0f) / 2.0f; p.y = std::round(p.y * 2.0f) / 2.0f; }   // crowded voxels
+        if (u01(rng) < 0.02f) p.y = std::numeric_limits<float>::quiet_NaN();
+    }
+    pcl::PCLPointCloud2::Ptr in(new pcl::PCLPointCloud2), out(new pcl::PCLPointCloud2);
+    pcl::toPCLPointCloud2(cloud, *in);
+    pcl::VoxelGrid<pcl::PCLPointCloud2> vg;
+    vg.setInputCloud(in);
+    vg.setLeafSize(leaf, leaf, leaf);
+    vg.setFilterFieldName(field);
+    if (field[0]) { vg.setFilterLimits(lo, hi); vg.setFilterLimitsNegative(negative); }
+    vg.filter(*out);
+    pcl::PointCloud<pcl::PointXYZI> want;
+    pcl::fromPCLPointCloud2(*out, want);
+
+    std::vector<float> xyzi(4 * (size_t)N);
+    for (int i = 0; i < N; ++i) {
+        const pcl::PointXYZI& p = cloud.points[i];
+        xyzi[4 * i] = p.x; xyzi[4 * i + 1] = p.y; xyzi[4 * i + 2] = p.z; xyzi[4 * i + 3] = p.intensity;
+    }
+    gem_voxel_params vp{};
+    vp.leaf[0] = vp.leaf[1] = vp.leaf[2] = leaf;
+    vp.field = field_id; vp.limit_min = lo; vp.limit_max = hi; vp.limit_negative = negative ? 1 : 0;
+    if (!field[0]) { vp.limit_min = -FLT_MAX; vp.limit_max = FLT_MAX; }
+    void *d_in = nullptr, *d_out = nullptr, *d_cnt = nullptr;
+    if (hipMalloc(&d_in, xyzi.size() * 4) != hipSuccess || hipMalloc(&d_out, xyzi.size() * 4) != hipSuccess || hipMalloc(&d_cnt, 4) != hipSuccess) return 2;
+    if (hipMemcpy(d_in, xyzi.data(), xyzi.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return 2;
+    CHECK_GEM(gem_voxel_device(h, &vp, 1, N, d_in, nullptr, d_out, nullptr, d_cnt));
+    CHECK_GEM(gem_synchronize(h));
+    int m = 0;
+    std::vector<float> got(xyzi.size());
+    if (hipMemcpy(&m, d_cnt, 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(got.data(), d_out, got.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return 2;
+    (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_cnt);
+
+    // points per voxel, by the contract's key (gem_hip.h), to know which voxels may differ in the last bits
+    const int before = g_failures;
+    if (m != (int)want.size()) report("voxel: centroid count", -1, m, (double)want.size());
+    const int k = std::min(m, (int)want.size());
+    auto ulps = [](float a, float b) { int32_t x, y; std::memcpy(&x, &a, 4); std::memcpy(&y, &b, 4); return std::abs((long long)x - (long long)y); };
+    std::map<uint32_t, int> count;
+    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    const float inv = 1.0f / leaf;
+    auto passes = [&](const float* p, bool dbl) {
+        if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) return false;
+        if (!field[0]) return true;
+        const float v = p[field_id - 1];
+        if (dbl) return negative ? !((double)v < hi && (double)v > lo) : !((double)v > hi || (double)v < lo);
+        return negative ? !(v < (float)hi && v > (float)lo) : !(v > (float)hi || v < (float)lo);
+    };
+    for (int i = 0; i < N; ++i)
+        if (passes(&xyzi[4 * i], false))
+            for (int c = 0; c < 3; ++c) { mn[c] = std::min(mn[c], xyzi[4 * i + c]); mx[c] = std::max(mx[c], xyzi[4 * i + c]); }
+    int mb[3], div[3];
+    for (int c = 0; c < 3; ++c) { mb[c] = (int)std::floor(mn[c] * inv); div[c] = (int)std::floor(mx[c] * inv) - mb[c] + 1; }
+    std::vector<uint32_t> keys;
+    for (int i = 0; i < N; ++i) {
+        if (!passes(&xyzi[4 * i], true)) continue;
+        uint32_t key = 0, mul = 1;
+        for (int c = 0; c < 3; ++c) { key += (uint32_t)((int)std::floor(xyzi[4 * i + c] * inv) - mb[c]) * mul; mul *= (uint32_t)div[c]; }
+        ++count[key];
+    }
+    std::vector<int> voxel_size;
+    for (const auto& kv : count) voxel_size.push_back(kv.second);      // ascending key = output order
+    int relaxed = 0;
+    for (int i = 0; i < k; ++i) {
+        const float w[4] = {want.points[i].x, want.points[i].y, want.points[i].z, want.points[i].intensity};
+        const bool crowded = i < (int)voxel_size.size() && voxel_size[i] >= 3;
+        for (int c = 0; c < 4; ++c) {
+            if (same_bits(got[4 * i + c], w[c])) continue;
+            if (crowded && ulps(got[4 * i + c], w[c]) <= 4) { ++relaxed; continue; }
+            report("voxel: centroid component", 4ll * i + c, got[4 * i + c], w[c]);
+        }
+    }
+    std::printf("vox gem_voxel_device vs pcl::VoxelGrid<PCLPointCloud2> (leaf %g, field '%s' [%g, %g]%s): %d centroids: %s (%d components "
+                "within 4 ulps in voxels of >= 3 points)\n", leaf, field, lo, hi, negative ? " negative" : "", m,
+                g_failures == before ? "IDENTICAL" : "DIFFERENT", relaxed);
+    return 0;
+}
+
+int check_voxel(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 64; cfg.resolution = 0.1f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    std::mt19937 rng(seed);
+    int rc = check_voxel_stage(h, rng, 0.1f, "x", GEM_VOXEL_FIELD_X, -10.0, 10.0, false);          // filter.launch
+    if (!rc) rc = check_voxel_stage(h, rng, 0.2f, "z", GEM_VOXEL_FIELD_Z, -25.0, 25.0, false);      // a filter_kitti.launch stage
+    if (!rc) rc = check_voxel_stage(h, rng, 0.25f, "y", GEM_VOXEL_FIELD_Y, -3.0, 0.1, true);
+    if (!rc) rc = check_voxel_stage(h, rng, 0.3f, "", GEM_VOXEL_FIELD_NONE, 0.0, 0.0, false);
+    gem_destroy(h);
+    return rc;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -218,8 +340,9 @@ int main(int argc, char** argv)
     const uint32_t seed = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 20260101u;
     int rc = check_show(seed);
     if (rc == 0) rc = check_colorize(seed + 1u);
+    if (rc == 0) rc = check_voxel(seed + 2u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the oracle's restatement of grid_map / cv::circle does NOT match this installation\n", g_failures); return 1; }
-    std::printf("both rows pinned on the installed grid_map_core and OpenCV (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the oracle's restatement of grid_map / cv::circle / pcl::VoxelGrid does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all three rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
     return 0;
 }
