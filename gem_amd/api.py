@@ -67,6 +67,33 @@ def _host_ptr(a: Optional[np.ndarray], dtype, n: Optional[int] = None):
     return arr, arr.ctypes.data_as(C.c_void_p)
 
 
+_XYZI_DEVICE = "xyzi must be a contiguous float32 [N,4] device tensor"
+
+
+def _cloud(xyzi, rgb=None, orig=None, device_only: bool = False):
+    """The cloud of add / add_raw / add_voxel, host arrays or device tensors (device_only: float32 device tensors, clean_device /
+    voxel_device) -> (on_device, n, (xyzi, rgb, orig) void*s, the host copies the call must keep alive).  Device rgb / orig: at
+    least n contiguous 32-bit words on the cloud's device; host ones: n words."""
+    if _is_device_tensor(xyzi):
+        n = int(xyzi.shape[0])
+        if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n or (device_only and not xyzi.is_floating_point()):
+            raise ValueError(_XYZI_DEVICE)
+        ptrs = [C.c_void_p(xyzi.data_ptr())]
+        for t, what in ((rgb, "rgb"), (orig, "orig_index")):
+            if t is not None and (not _is_device_tensor(t) or t.device != xyzi.device or not t.is_contiguous() or t.element_size() != 4
+                                  or t.numel() < n):
+                raise ValueError(f"{what} must be a contiguous 32-bit device tensor of at least {n} elements on {xyzi.device}")
+            ptrs.append(None if t is None else C.c_void_p(t.data_ptr()))
+        return True, n, ptrs, None
+    if device_only:
+        raise ValueError(_XYZI_DEVICE)
+    a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+    n = a.shape[0]
+    kr, pr = _host_ptr(rgb, np.uint32, n)
+    ko, po = _host_ptr(orig, np.int32, n)
+    return False, n, [a.ctypes.data_as(C.c_void_p), pr, po], (a, kr, ko)
+
+
 def skew(v) -> np.ndarray:
     """kindr::getSkewMatrixFromVector (same matrix as gpu_process.cu:302-307)."""
     return np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]], dtype=np.float64)
@@ -406,18 +433,12 @@ class ElevationMap:
     # -- the fused path: process + Fuse in one call (ElevationMapping::processpoints, EMg.cpp:254-283) --
     def add(self, frame: Frame, xyzi, rgb=None, orig_index=None) -> None:
         p = frame.to_struct()
-        if _is_device_tensor(xyzi):
-            n = int(xyzi.shape[0])
-            if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n:
-                raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
-            dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            self._check(self._lib.gem_add_device(self._h, C.byref(p), n, dp(xyzi), dp(rgb), dp(orig_index)), "gem_add_device")
+        dev, n, (px, pr, po), keep = _cloud(xyzi, rgb, orig_index)
+        if dev:
+            self._check(self._lib.gem_add_device(self._h, C.byref(p), n, px, pr, po), "gem_add_device")
             self._hold(xyzi, rgb, orig_index)
-            return
-        a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
-        n = a.shape[0]
-        kr, pr = _host_ptr(rgb, np.uint32, n); ko, po = _host_ptr(orig_index, np.int32, n)
-        self._check(self._lib.gem_add(self._h, C.byref(p), n, a.ctypes.data_as(C.c_void_p), pr, po), "gem_add")
+        else:
+            self._check(self._lib.gem_add(self._h, C.byref(p), n, px, pr, po), "gem_add")
 
     def add_aos(self, frame: Frame, points: np.ndarray, off_x: int = 0, off_y: int = 4, off_z: int = 8, off_intensity: int = 24,
                 off_rgb: int = 16) -> None:
@@ -430,15 +451,6 @@ class ElevationMap:
                                           off_intensity, off_rgb), "gem_add_aos")
 
     # -- raw clouds: cleanPointCloud (SensorProcessorBase.cpp:89) on the device -----------------------------------------------------
-    @staticmethod
-    def _device_words(t, n: int, like, what: str):
-        """an optional per-point 32-bit device array next to the device cloud `like`: contiguous, n elements of 4 bytes, same device"""
-        if t is None:
-            return None
-        if not _is_device_tensor(t) or t.device != like.device or not t.is_contiguous() or t.element_size() != 4 or t.numel() != n:
-            raise ValueError(f"{what} must be a contiguous 32-bit device tensor of {n} elements on {like.device}")
-        return C.c_void_p(t.data_ptr())
-
     @staticmethod
     def _clean(clean, frame: Optional[Frame] = None) -> "_lib.CleanParams":
         if clean is None:
@@ -457,9 +469,7 @@ class ElevationMap:
         order -- new ones, or the four of `out` (a previous call's result, reused).  Enqueued on the handle's stream; with
         sync=False the caller synchronises the handle before reading them."""
         import torch
-        if not _is_device_tensor(xyzi) or not xyzi.is_contiguous() or xyzi.dtype != torch.float32 or xyzi.numel() != 4 * int(xyzi.shape[0]):
-            raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
-        n = int(xyzi.shape[0])
+        _, n, (px, prgb, _), _ = _cloud(xyzi, rgb, device_only=True)
         cp = self._clean(clean)
         if out is not None:
             out, rgb_out, orig, count = out
@@ -471,9 +481,8 @@ class ElevationMap:
             orig = torch.empty(n, dtype=torch.int32, device=xyzi.device)
             count = torch.zeros(1, dtype=torch.int32, device=xyzi.device)
             rgb_out = torch.empty(n, dtype=torch.int32, device=xyzi.device) if rgb is not None else None
-        prgb = self._device_words(rgb, n, xyzi, "rgb")
         dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(self._lib.gem_clean_device(self._h, C.byref(cp), n, dp(xyzi), prgb, dp(out), dp(rgb_out), dp(orig), dp(count)),
+        self._check(self._lib.gem_clean_device(self._h, C.byref(cp), n, px, prgb, dp(out), dp(rgb_out), dp(orig), dp(count)),
                     "gem_clean_device")
         self._hold(xyzi, rgb, out, rgb_out, orig, count)
         if sync:
@@ -485,18 +494,12 @@ class ElevationMap:
         is done on the device (gem_add_raw / gem_add_raw_device); the raw position is every point's orig index."""
         p = frame.to_struct()
         cp = self._clean(clean, frame)
-        if _is_device_tensor(xyzi):
-            n = int(xyzi.shape[0])
-            if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n:
-                raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
-            prgb = self._device_words(rgb, n, xyzi, "rgb")
-            self._check(self._lib.gem_add_raw_device(self._h, C.byref(p), C.byref(cp), n, C.c_void_p(xyzi.data_ptr()), prgb), "gem_add_raw_device")
+        dev, n, (px, pr, _), keep = _cloud(xyzi, rgb)
+        if dev:
+            self._check(self._lib.gem_add_raw_device(self._h, C.byref(p), C.byref(cp), n, px, pr), "gem_add_raw_device")
             self._hold(xyzi, rgb)
-            return
-        a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
-        n = a.shape[0]
-        kr, pr = _host_ptr(rgb, np.uint32, n)
-        self._check(self._lib.gem_add_raw(self._h, C.byref(p), C.byref(cp), n, a.ctypes.data_as(C.c_void_p), pr), "gem_add_raw")
+        else:
+            self._check(self._lib.gem_add_raw(self._h, C.byref(p), C.byref(cp), n, px, pr), "gem_add_raw")
 
     # -- the VoxelGrid pre-filter of the launch files (pcl/VoxelGrid nodelets) on the device ------------------------------------------
     def voxel_device(self, stages, xyzi, rgb=None, sync: bool = True, out=None):
@@ -505,9 +508,7 @@ class ElevationMap:
         -- new ones, or the three of `out` (a previous call's result, reused).  Enqueued on the handle's stream; with sync=False the
         caller synchronises the handle before reading them."""
         import torch
-        if not _is_device_tensor(xyzi) or not xyzi.is_contiguous() or xyzi.dtype != torch.float32 or xyzi.numel() != 4 * int(xyzi.shape[0]):
-            raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
-        n = int(xyzi.shape[0])
+        _, n, (px, prgb, _), _ = _cloud(xyzi, rgb, device_only=True)
         arr = _voxel_stages(stages)
         if out is not None:
             out, rgb_out, count = out
@@ -518,9 +519,8 @@ class ElevationMap:
             out = torch.empty_like(xyzi)
             count = torch.zeros(1, dtype=torch.int32, device=xyzi.device)
             rgb_out = torch.empty(n, dtype=torch.int32, device=xyzi.device) if rgb is not None else None
-        prgb = self._device_words(rgb, n, xyzi, "rgb")
         dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self._check(self._lib.gem_voxel_device(self._h, arr, len(arr), n, dp(xyzi), prgb, dp(out), dp(rgb_out), dp(count)),
+        self._check(self._lib.gem_voxel_device(self._h, arr, len(arr), n, px, prgb, dp(out), dp(rgb_out), dp(count)),
                     "gem_voxel_device")
         self._hold(xyzi, rgb, out, rgb_out, count)
         if sync:
@@ -532,19 +532,12 @@ class ElevationMap:
         position in the filtered cloud."""
         p = frame.to_struct()
         arr = _voxel_stages(stages)
-        if _is_device_tensor(xyzi):
-            n = int(xyzi.shape[0])
-            if not xyzi.is_contiguous() or xyzi.element_size() != 4 or xyzi.numel() != 4 * n:
-                raise ValueError("xyzi must be a contiguous float32 [N,4] device tensor")
-            prgb = self._device_words(rgb, n, xyzi, "rgb")
-            self._check(self._lib.gem_add_voxel_device(self._h, C.byref(p), arr, len(arr), n, C.c_void_p(xyzi.data_ptr()), prgb),
-                        "gem_add_voxel_device")
+        dev, n, (px, pr, _), keep = _cloud(xyzi, rgb)
+        if dev:
+            self._check(self._lib.gem_add_voxel_device(self._h, C.byref(p), arr, len(arr), n, px, pr), "gem_add_voxel_device")
             self._hold(xyzi, rgb)
-            return
-        a = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
-        n = a.shape[0]
-        kr, pr = _host_ptr(rgb, np.uint32, n)
-        self._check(self._lib.gem_add_voxel(self._h, C.byref(p), arr, len(arr), n, a.ctypes.data_as(C.c_void_p), pr), "gem_add_voxel")
+        else:
+            self._check(self._lib.gem_add_voxel(self._h, C.byref(p), arr, len(arr), n, px, pr), "gem_add_voxel")
 
     def add_aos_raw(self, frame: Frame, points: np.ndarray, off_x: int = 0, off_y: int = 4, off_z: int = 8, off_intensity: int = 24,
                     off_rgb: int = 16, clean=None) -> None:

@@ -8,6 +8,79 @@
 #include "gem_capi_internal.hpp"
 #include "gem_clean.hpp"
 
+namespace gemi {
+
+bool aos_fields_ok(int point_step, int off_x, int off_y, int off_z, int off_intensity, int off_rgb)
+{
+    auto field_ok = [&](int o, bool optional) { return (optional && o < 0) || (o >= 0 && (o & 3) == 0 && o + 4 <= point_step); };
+    return point_step >= 12 && !(point_step & 3) && field_ok(off_x, false) && field_ok(off_y, false) && field_ok(off_z, false) &&
+           field_ok(off_intensity, true) && field_ok(off_rgb, true);
+}
+
+// One add pass.  The cloud is read where the caller has it (device buffers), from the half of the pinned staging buffer it was
+// copied into, or from the staging arena (host arrays, stage_cloud; the point structs, unpacked there by k_unpack_aos); a front end
+// on h->stream turns it into the pass's input in handle-owned memory: the clean mask writes the arena's XYZI slot (in place on the
+// arena copy of a host cloud or on the unpacked structs, into h->stage for a device cloud; rgb is read from the source unmasked), the
+// VoxelGrid writes vox_out (voxel_front).  Such a pass is never one that leaves its walk to the next call (caller_device): every
+// reader of that memory is ordered before the next call's writer.  A held staging half is handed back behind the pass, whatever failed.
+int add_cloud(gem_handle* h, const gem_frame_params* p, const AddCloud& c, const AddFront& fe)
+{
+    hipSetDevice(h->device);
+    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
+    PassInput in; in.src = 0; in.n = c.n; in.params = p;
+    // (a host cloud is in the handle's own memory when the kernels run: like a device-resident one, it may take the one-launch-per-frame
+    //  path whose deferred fuse reads the binned records only)
+    in.device_input = c.source != AddSource::aos;
+    in.caller_device = c.source == AddSource::device && fe.kind == FrontEnd::none;
+    if (c.source == AddSource::device) {
+        in.xyzi = static_cast<const float4*>(c.xyzi); in.rgb = static_cast<const uint32_t*>(c.rgb); in.orig = static_cast<const int*>(c.orig);
+    }
+    int half = -1;
+    if (c.n > 0) {
+        float4* slot = nullptr;                     // the handle-owned XYZI the clean mask writes
+        int rc;
+        switch (c.source) {
+        case AddSource::host: {
+            StagedCloud s;
+            rc = stage_cloud(h, c.n, static_cast<const float*>(c.xyzi), static_cast<const uint32_t*>(c.rgb), static_cast<const int*>(c.orig), s);
+            if (rc) return rc;
+            in.xyzi = s.xyzi; in.rgb = s.rgb; in.orig = s.orig;
+            slot = s.arena_xyzi; half = s.half;
+            break;
+        }
+        case AddSource::device:
+            if (fe.kind == FrontEnd::clean) {
+                if ((rc = ensure(h, h->stage, cloud_layout(c.n, false, false).bytes))) return rc;
+                slot = static_cast<float4*>(h->stage.p);
+            }
+            break;
+        case AddSource::aos: {
+            const size_t raw = ((size_t)c.n * c.point_step + 15) & ~(size_t)15, S = (size_t)c.n * 4;
+            if ((rc = ensure(h, h->stage, raw + S * 5))) return rc;
+            unsigned char* d = static_cast<unsigned char*>(h->stage.p);
+            HostXfer up{const_cast<void*>(c.xyzi), d, (size_t)c.n * c.point_step};
+            if ((rc = upload_arrays(h, &up, 1))) return rc;              // (returns once the caller's buffer has been read)
+            slot = reinterpret_cast<float4*>(d + raw);
+            uint32_t* rgb = c.off_rgb >= 0 ? reinterpret_cast<uint32_t*>(d + raw + S * 4) : nullptr;
+            GEM_HIP(h, launch_unpack_aos(h->stream, d, c.n, c.point_step, c.off_x, c.off_y, c.off_z, c.off_intensity, c.off_rgb, slot, rgb));
+            in.xyzi = slot; in.rgb = rgb;
+            break;
+        }
+        }
+        if (fe.kind == FrontEnd::clean) {
+            const hipError_t e = launch_clean_mask(h->stream, in.xyzi, slot, c.n, fe.clean->mode, fe.clean->z_min, fe.clean->z_max);
+            if (e != hipSuccess) return release_half(h, half, fail(h, GEM_ERR_HIP, "launch_clean_mask", e));
+            in.xyzi = slot;
+        }
+        if (fe.kind == FrontEnd::voxel && (rc = voxel_front(h, fe.stages, fe.n_stages, c.n, in.xyzi, in.rgb, &in.xyzi, &in.rgb)))
+            return release_half(h, half, rc);
+        if (c.source == AddSource::aos || fe.kind != FrontEnd::none) h->main_reads_pb = true;     // (binning streams wait for them)
+    }
+    return release_half(h, half, run_pipeline(h, in));
+}
+
+} // namespace gemi
+
 extern "C" {
 
 int gem_abi_version(void) { return GEM_ABI_VERSION; }
@@ -324,6 +397,7 @@ int gem_fuse(gem_handle* h, int n, const int* index, const int* R, const int* G,
     const bool attr = R && G && B && intensity;
     const size_t S = (size_t)n * 4;
     PassInput in; in.src = 1; in.n = n;
+    int half = -1;
     if (n > 0) {
         int rc;
         const size_t P = (S + 255) & ~(size_t)255;                  // the arrays' stride on the device = in the staging buffer (upload_arrays)
@@ -335,7 +409,7 @@ int gem_fuse(gem_handle* h, int n, const int* index, const int* R, const int* G,
         // the caller's arrays are only valid for the call (they are stack VLAs in the reference, EMg.cpp:260-267): read before it returns
         // -- into a half of the staging buffer, where the pass's kernels read them over the link (zero copy, see upload_arrays), or,
         // when the staging buffer does not take them, into the arena by the runtime's copies
-        unsigned char* region = nullptr; int half = -1;
+        unsigned char* region = nullptr;
         if ((rc = upload_arrays(h, up, attr ? 7 : 3, true, &region, &half))) return rc;
         if (region) d = region;
         in.f_index = reinterpret_cast<const int*>(d); in.f_height = reinterpret_cast<const float*>(d + P);
@@ -344,15 +418,8 @@ int gem_fuse(gem_handle* h, int n, const int* index, const int* R, const int* G,
             in.f_R = reinterpret_cast<const int*>(d + 3 * P); in.f_G = reinterpret_cast<const int*>(d + 4 * P);
             in.f_B = reinterpret_cast<const int*>(d + 5 * P); in.f_I = reinterpret_cast<const float*>(d + 6 * P);
         }
-        if (region) {
-            rc = run_pipeline(h, in);
-            const hipError_t e = hipEventRecord(h->ev_half[half], h->stream);       // (the half is free when the pass's kernels have read it)
-            if (e != hipSuccess && rc == GEM_OK) rc = fail(h, GEM_ERR_HIP, "hipEventRecord(staging half)", e);
-            h->half_pending[half] = true;
-            return rc;
-        }
     }
-    return run_pipeline(h, in);
+    return release_half(h, half, run_pipeline(h, in));
 }
 
 int gem_add_device(gem_handle* h, const gem_frame_params* p, int n, const void* d_xyzi, const void* d_rgb, const void* d_orig_index)
@@ -360,11 +427,7 @@ int gem_add_device(gem_handle* h, const gem_frame_params* p, int n, const void* 
     ApiRange api_range(h, "gem_add_device");
     if (!h || !p || n < 0 || (n > 0 && !d_xyzi)) return h ? fail(h, GEM_ERR_INVALID, "gem_add_device: bad argument") : GEM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p; in.device_input = true; in.caller_device = true;
-    in.xyzi = static_cast<const float4*>(d_xyzi); in.rgb = static_cast<const uint32_t*>(d_rgb); in.orig = static_cast<const int*>(d_orig_index);
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::device, n, d_xyzi, d_rgb, d_orig_index}, {});
 }
 
 int gem_add(gem_handle* h, const gem_frame_params* p, int n, const float* xyzi, const uint32_t* rgb, const int* orig_index)
@@ -372,42 +435,7 @@ int gem_add(gem_handle* h, const gem_frame_params* p, int n, const float* xyzi, 
     ApiRange api_range(h, "gem_add");
     if (!h || !p || n < 0 || (n > 0 && !xyzi)) return h ? fail(h, GEM_ERR_INVALID, "gem_add: bad argument") : GEM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p;
-    if (n > 0) {
-        const size_t S = (size_t)n * 4;
-        int rc;
-        const size_t P4 = (S * 4 + 255) & ~(size_t)255, P = (S + 255) & ~(size_t)255;      // strides as in the staging buffer (upload_arrays)
-        if ((rc = ensure(h, h->stage, P4 + 2 * P))) return rc;
-        unsigned char* d = static_cast<unsigned char*>(h->stage.p);
-        HostXfer up[3] = {{const_cast<float*>(xyzi), d, S * 4}, {nullptr, nullptr, 0}, {nullptr, nullptr, 0}};
-        int nu = 1;
-        in.xyzi = reinterpret_cast<const float4*>(d);
-        unsigned char* next = d + P4;
-        if (rgb) { up[nu++] = {const_cast<uint32_t*>(rgb), next, S}; in.rgb = reinterpret_cast<const uint32_t*>(next); next += P; }
-        if (orig_index) { up[nu++] = {const_cast<int*>(orig_index), next, S}; in.orig = reinterpret_cast<const int*>(next); }
-        // (the cloud is in the handle's own memory when the kernels run: like a device-resident one, it may take the one-launch-per-frame
-        //  path whose deferred fuse reads the binned records only)
-        unsigned char* region = nullptr; int half = -1;
-        if ((rc = upload_arrays(h, up, nu, true, &region, &half))) return rc;
-        in.device_input = true;
-        if (region) {
-            // the kernels read the staging half itself (upload_arrays): same strides as the arena's
-            in.xyzi = reinterpret_cast<const float4*>(region);
-            unsigned char* nxt = region + P4;
-            if (rgb) { in.rgb = reinterpret_cast<const uint32_t*>(nxt); nxt += P; }
-            if (orig_index) in.orig = reinterpret_cast<const int*>(nxt);
-            rc = run_pipeline(h, in);
-            // the half is free again when everything enqueued so far has run (the pass's kernels read it; a deferred fuse does not)
-            // (a pass that put its binning on another stream: that stream's work is ordered before the walk / fuse on h->stream)
-            const hipError_t e = hipEventRecord(h->ev_half[half], h->stream);
-            if (e != hipSuccess && rc == GEM_OK) rc = fail(h, GEM_ERR_HIP, "hipEventRecord(staging half)", e);
-            h->half_pending[half] = true;
-            return rc;
-        }
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::host, n, xyzi, rgb, orig_index}, {});
 }
 
 // BASELINE config 4 from HOST memory (gem_add_batch): sweep s = clouds[s][0 .. counts[s]) XYZI points, frames and
@@ -464,27 +492,10 @@ int gem_add_aos(gem_handle* h, const gem_frame_params* p, int n, const void* poi
 {
     ApiRange api_range(h, "gem_add_aos");
     if (!h || !p || n < 0 || (n > 0 && !points)) return h ? fail(h, GEM_ERR_INVALID, "gem_add_aos: bad argument") : GEM_ERR_INVALID;
-    auto field_ok = [&](int o, bool optional) { return (optional && o < 0) || (o >= 0 && (o & 3) == 0 && o + 4 <= point_step); };
-    if (point_step < 12 || (point_step & 3) || !field_ok(off_x, false) || !field_ok(off_y, false) || !field_ok(off_z, false) ||
-        !field_ok(off_intensity, true) || !field_ok(off_rgb, true))
+    if (!aos_fields_ok(point_step, off_x, off_y, off_z, off_intensity, off_rgb))
         return fail(h, GEM_ERR_INVALID, "gem_add_aos: fields must be 4-byte aligned inside point_step");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p;
-    if (n > 0) {
-        const size_t raw = ((size_t)n * point_step + 15) & ~(size_t)15, S = (size_t)n * 4;
-        int rc;
-        if ((rc = ensure(h, h->stage, raw + S * 5))) return rc;
-        unsigned char* d = static_cast<unsigned char*>(h->stage.p);
-        HostXfer up{const_cast<void*>(points), d, (size_t)n * point_step};
-        if ((rc = upload_arrays(h, &up, 1))) return rc;              // (returns once the caller's buffer has been read)
-        float4* xyzi = reinterpret_cast<float4*>(d + raw);
-        uint32_t* rgb = off_rgb >= 0 ? reinterpret_cast<uint32_t*>(d + raw + S * 4) : nullptr;
-        GEM_HIP(h, launch_unpack_aos(h->stream, d, n, point_step, off_x, off_y, off_z, off_intensity, off_rgb, xyzi, rgb));
-        in.xyzi = xyzi; in.rgb = rgb;
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::aos, n, points, nullptr, nullptr, point_step, off_x, off_y, off_z, off_intensity, off_rgb}, {});
 }
 
 int gem_add_batch_device(gem_handle* h, int n_sweeps, const gem_frame_params* params, const void* d_xyzi,
@@ -529,9 +540,11 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
     if (max_points == 0) return GEM_OK;
     int rc;
     const long long blocks = 4ll * ((h->L + 31) / 32) * ((h->L + 31) / 32);
-    // staging of host-pointer inputs (gem_add: XYZI + rgb + orig; gem_fuse: seven arrays; gem_process_points: nine)
-    if ((rc = ensure(h, h->stage, ((size_t)max_points * 4 + 256) * 9))) return rc;
-    // (the raw-cloud entries, gem_capi_clean.cpp, work inside that staging arena; their compactions add a count per 1024 points)
+    // staging of host-pointer inputs: a host cloud of the add entries (cloud_layout, where the clean mask also writes), gem_fuse's
+    // seven arrays, gem_process_points' nine
+    const size_t stage = std::max(cloud_layout(max_points, true, true).bytes, ((size_t)max_points * 4 + 256) * 9);
+    if ((rc = ensure(h, h->stage, stage))) return rc;
+    // (the raw-cloud compactions, gem_capi_clean.cpp, add a count per 1024 points)
     if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
     if ((rc = voxel_reserve(h, max_points))) return rc;        // (the VoxelGrid entries, gem_capi_voxel.cpp)
     {   // ... and its pinned counterpart for callers with host arrays (gem_process_points: nine arrays; gem_map_feature: nine layers),

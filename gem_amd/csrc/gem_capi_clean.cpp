@@ -2,30 +2,16 @@
 // device (gem_clean_device, gem_process_points_raw) and the raw-cloud forms of the fuse entries (gem_add_raw*, gem_add_aos_raw).
 // The kernels are in gem_clean.hip.  A REMOVE_NAN / NONE fuse takes the plain entry as it is (projection rejects non-finite points,
 // see gem_hip.h); a PASSTHROUGH_Z fuse reads a copy of the cloud with the dropped points' x, y, z set to NaN, written into the
-// handle's staging arena on its stream -- the arena gem_add's own host path uploads into, sized by gem_reserve (so a stream of raw
-// clouds inside the reserved bounds allocates nothing).  Every reader of that copy is ordered before the next call's writer: the copy
-// is written on h->stream, main_reads_pb puts the binning streams behind it, the pass's walk / fuse on h->stream waits for its
-// binning, and the pass is never one that leaves its walk to the next call (that needs caller_device).
+// handle's staging arena on its stream (add_cloud, gem_capi.cpp) -- the arena gem_add's own host path uploads into, sized by
+// gem_reserve (so a stream of raw clouds inside the reserved bounds allocates nothing).
 #include "gem_capi_internal.hpp"
 #include "gem_clean.hpp"
-
-#include <cfloat>
 
 namespace {
 
 bool clean_ok(const gem_clean_params* c)
 {
     return c && c->mode >= GEM_CLEAN_NONE && c->mode <= GEM_CLEAN_PASSTHROUGH_Z;
-}
-
-// double -> float, round to nearest even, defined for every double (a plain cast of a value beyond FLT_MAX is undefined in C++):
-// beyond FLT_MAX + half an ulp (2^103) the nearest is +-inf, and the tie itself rounds to inf (FLT_MAX's significand is odd)
-float to_float_rn(double v)
-{
-    const double lim = (double)FLT_MAX + std::ldexp(1.0, 103);
-    if (v >= lim) return INFINITY;
-    if (v <= -lim) return -INFINITY;
-    return static_cast<float>(v);
 }
 
 } // namespace
@@ -75,36 +61,7 @@ int gem_add_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params
     ApiRange api_range(h, "gem_add_raw");
     if (!p || n < 0 || (n > 0 && !xyzi)) return fail(h, GEM_ERR_INVALID, "gem_add_raw: bad argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p;
-    if (n > 0) {
-        // gem_add's staging (deferred upload, the kernels reading the staging half where it takes the arrays), then the mask
-        const size_t S = (size_t)n * 4;
-        const size_t P4 = (S * 4 + 255) & ~(size_t)255;
-        int rc;
-        if ((rc = ensure(h, h->stage, P4 + S + 256))) return rc;
-        unsigned char* d = static_cast<unsigned char*>(h->stage.p);
-        HostXfer up[2] = {{const_cast<float*>(xyzi), d, S * 4}, {const_cast<uint32_t*>(rgb), d + P4, rgb ? S : 0}};
-        unsigned char* region = nullptr; int half = -1;
-        if ((rc = upload_arrays(h, up, rgb ? 2 : 1, true, &region, &half))) return rc;
-        // the cloud is in the staging half (zero copy) or already in the arena at d: the mask writes the arena's copy (in place then)
-        const unsigned char* src = region ? region : d;
-        float4* masked = reinterpret_cast<float4*>(d);
-        GEM_HIP(h, launch_clean_mask(h->stream, reinterpret_cast<const float4*>(src), masked, n, clean->mode, clean->z_min, clean->z_max));
-        h->main_reads_pb = true;                                  // (binning streams wait for the mask)
-        in.device_input = true;
-        in.xyzi = masked;
-        if (rgb) in.rgb = reinterpret_cast<const uint32_t*>(src + P4);
-        if (region) {
-            rc = run_pipeline(h, in);
-            const hipError_t e = hipEventRecord(h->ev_half[half], h->stream);       // (as gem_add: the half is free behind the pass)
-            if (e != hipSuccess && rc == GEM_OK) rc = fail(h, GEM_ERR_HIP, "hipEventRecord(staging half)", e);
-            h->half_pending[half] = true;
-            return rc;
-        }
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::host, n, xyzi, rgb}, {FrontEnd::clean, clean});
 }
 
 int gem_add_raw_device(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n, const void* d_xyzi, const void* d_rgb)
@@ -114,19 +71,7 @@ int gem_add_raw_device(gem_handle* h, const gem_frame_params* p, const gem_clean
     ApiRange api_range(h, "gem_add_raw_device");
     if (!p || n < 0 || (n > 0 && !d_xyzi)) return fail(h, GEM_ERR_INVALID, "gem_add_raw_device: bad argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p; in.device_input = true;
-    if (n > 0) {
-        int rc;
-        if ((rc = ensure(h, h->stage, (size_t)n * 16))) return rc;
-        float4* masked = static_cast<float4*>(h->stage.p);
-        GEM_HIP(h, launch_clean_mask(h->stream, static_cast<const float4*>(d_xyzi), masked, n, clean->mode, clean->z_min, clean->z_max));
-        h->main_reads_pb = true;
-        in.xyzi = masked;
-        in.rgb = static_cast<const uint32_t*>(d_rgb);
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::device, n, d_xyzi, d_rgb}, {FrontEnd::clean, clean});
 }
 
 int gem_add_aos_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n, const void* points, int point_step,
@@ -136,30 +81,11 @@ int gem_add_aos_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_pa
     if (clean->mode != GEM_CLEAN_PASSTHROUGH_Z) return gem_add_aos(h, p, n, points, point_step, off_x, off_y, off_z, off_intensity, off_rgb);
     ApiRange api_range(h, "gem_add_aos_raw");
     if (!p || n < 0 || (n > 0 && !points)) return fail(h, GEM_ERR_INVALID, "gem_add_aos_raw: bad argument");
-    auto field_ok = [&](int o, bool optional) { return (optional && o < 0) || (o >= 0 && (o & 3) == 0 && o + 4 <= point_step); };
-    if (point_step < 12 || (point_step & 3) || !field_ok(off_x, false) || !field_ok(off_y, false) || !field_ok(off_z, false) ||
-        !field_ok(off_intensity, true) || !field_ok(off_rgb, true))
+    if (!aos_fields_ok(point_step, off_x, off_y, off_z, off_intensity, off_rgb))
         return fail(h, GEM_ERR_INVALID, "gem_add_aos_raw: fields must be 4-byte aligned inside point_step");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p;
-    if (n > 0) {
-        const size_t raw = ((size_t)n * point_step + 15) & ~(size_t)15, S = (size_t)n * 4;
-        int rc;
-        if ((rc = ensure(h, h->stage, raw + S * 5))) return rc;
-        unsigned char* d = static_cast<unsigned char*>(h->stage.p);
-        HostXfer up{const_cast<void*>(points), d, (size_t)n * point_step};
-        if ((rc = upload_arrays(h, &up, 1))) return rc;              // (returns once the caller's buffer has been read)
-        float4* xyzi = reinterpret_cast<float4*>(d + raw);
-        uint32_t* rgb = off_rgb >= 0 ? reinterpret_cast<uint32_t*>(d + raw + S * 4) : nullptr;
-        // gem_add_aos's own unpack (k_unpack_aos, one definition of the field layout), then the mask in place on its output
-        GEM_HIP(h, launch_unpack_aos(h->stream, d, n, point_step, off_x, off_y, off_z, off_intensity, off_rgb, xyzi, rgb));
-        GEM_HIP(h, launch_clean_mask(h->stream, xyzi, xyzi, n, clean->mode, clean->z_min, clean->z_max));
-        h->main_reads_pb = true;
-        in.xyzi = xyzi; in.rgb = rgb;
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::aos, n, points, nullptr, nullptr, point_step, off_x, off_y, off_z, off_intensity, off_rgb},
+                     {FrontEnd::clean, clean});
 }
 
 int gem_process_points_raw(gem_handle* h, const gem_frame_params* p, const gem_clean_params* clean, int n,

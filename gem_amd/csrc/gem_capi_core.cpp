@@ -7,6 +7,7 @@
 // stream, and nothing returns to the host unless the caller asks for it.
 #include "gem_capi_internal.hpp"
 
+#include <cfloat>
 #include <dlfcn.h>
 
 namespace gemi {
@@ -221,6 +222,61 @@ int upload_arrays(gem_handle* h, const HostXfer* x, int n, bool defer_ok, unsign
     GEM_HIP(h, hipEventSynchronize(h->stage_read));
     h->stage_read_pending = false;
     return GEM_OK;
+}
+
+CloudLayout cloud_layout(long long n, bool rgb, bool orig)
+{
+    const size_t S = (size_t)n * 4, P = (S + 255) & ~(size_t)255, P4 = (S * 4 + 255) & ~(size_t)255;
+    CloudLayout l;
+    l.rgb = P4;
+    l.orig = P4 + (rgb ? P : 0);
+    l.bytes = l.orig + (orig ? P : 0);
+    return l;
+}
+
+// The caller's arrays are only valid for the call: read before it returns -- into a half of the staging buffer, where the pass's
+// kernels read them over the link (zero copy, see upload_arrays), or, when the staging buffer does not take them, into the arena
+int stage_cloud(gem_handle* h, long long n, const float* xyzi, const uint32_t* rgb, const int* orig, StagedCloud& out)
+{
+    const CloudLayout l = cloud_layout(n, rgb, orig);
+    int rc;
+    if ((rc = ensure(h, h->stage, l.bytes))) return rc;
+    unsigned char* d = static_cast<unsigned char*>(h->stage.p);
+    const size_t S = (size_t)n * 4;
+    HostXfer up[3] = {{const_cast<float*>(xyzi), d, S * 4}};
+    int nu = 1;
+    if (rgb) up[nu++] = {const_cast<uint32_t*>(rgb), d + l.rgb, S};
+    if (orig) up[nu++] = {const_cast<int*>(orig), d + l.orig, S};
+    unsigned char* region = nullptr;
+    out.half = -1;
+    if ((rc = upload_arrays(h, up, nu, true, &region, &out.half))) return rc;
+    const unsigned char* src = region ? region : d;            // (the half has the arena's strides)
+    out.xyzi = reinterpret_cast<const float4*>(src);
+    out.rgb = rgb ? reinterpret_cast<const uint32_t*>(src + l.rgb) : nullptr;
+    out.orig = orig ? reinterpret_cast<const int*>(src + l.orig) : nullptr;
+    out.arena_xyzi = reinterpret_cast<float4*>(d);
+    return GEM_OK;
+}
+
+// The half is free again when everything enqueued so far has run: the pass's kernels read it, a deferred fuse does not (a pass that
+// put its binning on another stream: that stream's work is ordered before the walk / fuse on h->stream)
+int release_half(gem_handle* h, int half, int rc)
+{
+    if (half < 0) return rc;
+    const hipError_t e = hipEventRecord(h->ev_half[half], h->stream);
+    if (e != hipSuccess && rc == GEM_OK) rc = fail(h, GEM_ERR_HIP, "hipEventRecord(staging half)", e);
+    h->half_pending[half] = true;
+    return rc;
+}
+
+// double -> float, round to nearest even, defined for every double (a plain cast of a value beyond FLT_MAX is undefined in C++):
+// beyond FLT_MAX + half an ulp (2^103) the nearest is +-inf, and the tie itself rounds to inf (FLT_MAX's significand is odd)
+float to_float_rn(double v)
+{
+    const double lim = (double)FLT_MAX + std::ldexp(1.0, 103);
+    if (v >= lim) return INFINITY;
+    if (v <= -lim) return -INFINITY;
+    return static_cast<float>(v);
 }
 
 // Device -> host arrays, after everything enqueued on h->stream so far.  Returns when the caller's arrays hold the data (and

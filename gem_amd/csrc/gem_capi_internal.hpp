@@ -306,6 +306,24 @@ unsigned char* host_stage(gem_handle* h, size_t bytes);
 int drain_staging(gem_handle* h);
 int upload_arrays(gem_handle* h, const HostXfer* x, int n, bool defer_ok = false, unsigned char** zero_copy_region = nullptr, int* zero_copy_half = nullptr);
 int download_arrays(gem_handle* h, const HostXfer* x, int n, size_t stage_off);
+
+// A host cloud of the add entries in h->stage, at the stride upload_arrays gives a half of the staging buffer: XYZI at 0, then rgb,
+// then orig, each present array 256-byte aligned behind the one before; `bytes` covers them all
+struct CloudLayout { size_t rgb, orig, bytes; };
+CloudLayout cloud_layout(long long n, bool rgb, bool orig);
+// ... staged by a deferred upload: what the kernels read (the zero-copy half of the pinned staging buffer or the arena), the arena's
+// own XYZI slot (where a mask or a filter may write) and the half it holds (-1: none, release_half then does nothing)
+struct StagedCloud {
+    const float4* xyzi = nullptr; const uint32_t* rgb = nullptr; const int* orig = nullptr;
+    float4* arena_xyzi = nullptr;
+    int half = -1;
+};
+int stage_cloud(gem_handle* h, long long n, const float* xyzi, const uint32_t* rgb, const int* orig, StagedCloud& out);
+// a held half is handed back behind everything enqueued on h->stream, the pass that read it included -- whether or not the call
+// failed: returns rc, or the record's failure if rc is GEM_OK
+int release_half(gem_handle* h, int half, int rc);
+float to_float_rn(double v);                   // double -> float, round to nearest even, +-inf beyond FLT_MAX (defined for every double)
+
 void fill_frame(const gem_handle* h, const gem_frame_params* p, FrameConst& f);
 hipEvent_t get_event(gem_handle* h);
 
@@ -380,6 +398,27 @@ struct ShardOpts { int sweep_id0; int nstrips; const int* strip_rows; bool bound
 
 int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGeometry& geo, const ShardOpts* shard = nullptr);
 int run_pipeline(gem_handle* h, const PassInput& in0);
+
+// The add entries (gem_add*, gem_add_raw*, gem_add_voxel*, gem_add_aos*) as one body (gem_capi.cpp): a cloud from one of three
+// sources, one of three front ends between it and the pass
+enum class AddSource { host, device, aos };     // XYZI (+ rgb, + orig) in host arrays | in device buffers | host point structs
+enum class FrontEnd { none, clean, voxel };     // the pass reads the cloud | a copy with the dropped points' x, y, z NaN | the centroids
+struct AddCloud {
+    AddSource source;
+    int n;
+    const void* xyzi; const void* rgb = nullptr; const void* orig = nullptr;                  // aos: xyzi = the point structs
+    int point_step = 0, off_x = 0, off_y = 0, off_z = 0, off_intensity = -1, off_rgb = -1;   // aos
+};
+struct AddFront {
+    FrontEnd kind = FrontEnd::none;
+    const gem_clean_params* clean = nullptr;                        // clean: PASSTHROUGH_Z
+    const gem_voxel_params* stages = nullptr; int n_stages = 0;     // voxel
+};
+int add_cloud(gem_handle* h, const gem_frame_params* p, const AddCloud& c, const AddFront& fe);     // (arguments checked, h->mu held)
+bool aos_fields_ok(int point_step, int off_x, int off_y, int off_z, int off_intensity, int off_rgb);
+// gem_capi_voxel.cpp: the stages of a gem_add_voxel* call into vox_out[vox_flip], which flips: the n filtered points (NaN tail)
+int voxel_front(gem_handle* h, const gem_voxel_params* stages, int ns, int n, const float4* xyzi, const uint32_t* rgb,
+                const float4** out, const uint32_t** rgb_out);
 
 // gem_capi_comm.cpp
 int shard_finish_locked(gem_handle* h);       // the second half of a pending gem_add_sharded_device step

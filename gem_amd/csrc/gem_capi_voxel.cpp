@@ -5,24 +5,14 @@
 // them so); the records, a chain's two intermediates and the fused path's filtered clouds are plain arenas.  gem_reserve sizes all
 // of them (voxel_reserve), so a stream of voxel frames inside the reserved bounds allocates nothing.
 // The fused path writes the filtered cloud into vox_out[vox_flip] and flips: a pass that leaves work to the next call (k_frame's
-// deferred fuse, which reads the binned records only) never has its input rewritten by the next call's filter, and a host cloud is
-// read from gem_add's staging half, which is handed back behind the pass (the discipline of gem_add / gem_add_raw).
+// deferred fuse, which reads the binned records only) never has its input rewritten by the next call's filter (voxel_front; the rest
+// of the add path is add_cloud, gem_capi.cpp).
 #include "gem_capi_internal.hpp"
 #include "gem_voxel.hpp"
 
-#include <cfloat>
 #include <cstddef>
 
 namespace {
-
-// double -> float, round to nearest even, defined for every double (beyond FLT_MAX + half an ulp the nearest is +-inf)
-float to_float_rn(double v)
-{
-    const double lim = (double)FLT_MAX + std::ldexp(1.0, 103);
-    if (v >= lim) return INFINITY;
-    if (v <= -lim) return -INFINITY;
-    return static_cast<float>(v);
-}
 
 bool stages_ok(const gem_voxel_params* s, int ns)
 {
@@ -85,9 +75,12 @@ int enqueue(gem_handle* h, const gem_voxel_params* stages, int ns, long long n, 
     return GEM_OK;
 }
 
-// gem_add_voxel*: filter into vox_out[vox_flip], then one pass over the n filtered points (the NaN tail is rejected in projection)
-int filter_and_add(gem_handle* h, const gem_frame_params* p, const gem_voxel_params* stages, int ns, int n, const float4* xyzi,
-                   const uint32_t* rgb, PassInput& in)
+} // namespace
+
+namespace gemi {
+
+int voxel_front(gem_handle* h, const gem_voxel_params* stages, int ns, int n, const float4* xyzi, const uint32_t* rgb,
+                const float4** out, const uint32_t** rgb_out)
 {
     int rc;
     if ((rc = arenas(h, n, ns))) return rc;
@@ -96,18 +89,12 @@ int filter_and_add(gem_handle* h, const gem_frame_params* p, const gem_voxel_par
     h->vox_flip ^= 1u;
     unsigned char* d = static_cast<unsigned char*>(o.p);
     float4* fx = reinterpret_cast<float4*>(d);
-    uint32_t* fc = reinterpret_cast<uint32_t*>(d + (size_t)n * 16 + 256);
+    uint32_t* fc = rgb ? reinterpret_cast<uint32_t*>(d + (size_t)n * 16 + 256) : nullptr;
     int* cnt = reinterpret_cast<int*>(d + (size_t)n * 20 + 512);
-    if ((rc = enqueue(h, stages, ns, n, xyzi, rgb, fx, rgb ? fc : nullptr, cnt))) return rc;
-    h->main_reads_pb = true;                                   // (binning streams wait for the filter)
-    in.src = 0; in.n = n; in.params = p; in.device_input = true;
-    in.xyzi = fx; in.rgb = rgb ? fc : nullptr;
+    if ((rc = enqueue(h, stages, ns, n, xyzi, rgb, fx, fc, cnt))) return rc;
+    *out = fx; *rgb_out = fc;
     return GEM_OK;
 }
-
-} // namespace
-
-namespace gemi {
 
 int voxel_reserve(gem_handle* h, long long max_points)
 {
@@ -146,14 +133,7 @@ int gem_add_voxel_device(gem_handle* h, const gem_frame_params* p, const gem_vox
         return h ? fail(h, GEM_ERR_INVALID, "gem_add_voxel_device: bad argument") : GEM_ERR_INVALID;
     if (h->tp_x) return fail(h, GEM_ERR_INVALID, "gem_add_voxel_device: not on a handle with a communicator");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p; in.device_input = true;
-    if (n > 0) {
-        const int rc = filter_and_add(h, p, stages, n_stages, n, static_cast<const float4*>(d_xyzi), static_cast<const uint32_t*>(d_rgb), in);
-        if (rc) return rc;
-    }
-    return run_pipeline(h, in);
+    return add_cloud(h, p, {AddSource::device, n, d_xyzi, d_rgb}, {FrontEnd::voxel, nullptr, stages, n_stages});
 }
 
 int gem_add_voxel(gem_handle* h, const gem_frame_params* p, const gem_voxel_params* stages, int n_stages, int n, const float* xyzi,
@@ -164,28 +144,7 @@ int gem_add_voxel(gem_handle* h, const gem_frame_params* p, const gem_voxel_para
         return h ? fail(h, GEM_ERR_INVALID, "gem_add_voxel: bad argument") : GEM_ERR_INVALID;
     if (h->tp_x) return fail(h, GEM_ERR_INVALID, "gem_add_voxel: not on a handle with a communicator");
     std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
-    PassInput in; in.src = 0; in.n = n; in.params = p;
-    if (n == 0) return run_pipeline(h, in);
-    // gem_add's staging (deferred upload; the filter reads the staging half where it takes the arrays)
-    const size_t S = (size_t)n * 4;
-    const size_t P4 = (S * 4 + 255) & ~(size_t)255;
-    int rc;
-    if ((rc = ensure(h, h->stage, P4 + S + 256))) return rc;
-    unsigned char* d = static_cast<unsigned char*>(h->stage.p);
-    HostXfer up[2] = {{const_cast<float*>(xyzi), d, S * 4}, {const_cast<uint32_t*>(rgb), d + P4, rgb ? S : 0}};
-    unsigned char* region = nullptr; int half = -1;
-    if ((rc = upload_arrays(h, up, rgb ? 2 : 1, true, &region, &half))) return rc;
-    const unsigned char* src = region ? region : d;
-    rc = filter_and_add(h, p, stages, n_stages, n, reinterpret_cast<const float4*>(src), rgb ? reinterpret_cast<const uint32_t*>(src + P4) : nullptr, in);
-    if (rc == GEM_OK) rc = run_pipeline(h, in);
-    if (region) {
-        const hipError_t e = hipEventRecord(h->ev_half[half], h->stream);       // (as gem_add: the half is free behind the filter)
-        if (e != hipSuccess && rc == GEM_OK) rc = fail(h, GEM_ERR_HIP, "hipEventRecord(staging half)", e);
-        h->half_pending[half] = true;
-    }
-    return rc;
+    return add_cloud(h, p, {AddSource::host, n, xyzi, rgb}, {FrontEnd::voxel, nullptr, stages, n_stages});
 }
 
 } // extern "C"

@@ -6,7 +6,9 @@
   3. gem_add_raw / gem_add_raw_device / gem_add_aos_raw over a sequence of frames with moves in between: the map of fusing the
      cleaned cloud with its indices, on every pipeline;
   4. REMOVE_NAN fuses with no pass of its own (gem_hip.h): a cloud full of non-finite values, filter on and off, window at +-inf;
-  5. the C++ processors' processRaw (tests/cpp/clean_facade_check.cpp) as a child process."""
+  5. gem_add_raw / gem_add_voxel from host arrays with rgb through both staging branches (the pinned buffer and the arena), = the
+     device calls and the oracle; the Python twin's checks of device rgb / orig_index;
+  6. the C++ processors' processRaw (tests/cpp/clean_facade_check.cpp) as a child process."""
 import subprocess
 import sys
 from pathlib import Path
@@ -286,7 +288,85 @@ def test_remove_nan_fuse_needs_no_pass(oracle_mod, filter_on):
     host.close(); dev.close()
 
 
-# ---- 5. the C++ processors ------------------------------------------------------------------------------------------------------
+# ---- 5. the host entries' two staging branches ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("copy_threads", [0, 4])
+def test_host_raw_and_voxel_through_staging_and_arena(oracle_mod, copy_threads):
+    """gem_add_raw (d435 cut-offs, PASSTHROUGH_Z) and gem_add_voxel (filter_launch) from host arrays with rgb, on clouds of at least
+    128 KB (with copy threads: read in place from a half of the pinned staging buffer) and of less (copied into the arena), and one
+    n = 0 call behind a variance update: every layer bit for bit the map of the same calls from device tensors and the oracle's."""
+    import torch
+    from gem_amd import VoxelStage
+    import voxel_ref as vr
+    raw, T, _, L, res, pos = raw_workload("structured_light", seed=19)
+    d435, laser = SensorModel.realsense_d435(), SensorModel.velodyne()
+    cp = d435.clean_params()
+    wl = synth.config_c2()
+    sweep, stages = wl.clouds[0], VoxelStage.filter_launch()
+    rng = np.random.default_rng(29)
+    raw_host, raw_dev = ElevationMap(L, res), ElevationMap(L, res)
+    vox_host, vox_dev = ElevationMap(wl.length, wl.resolution), ElevationMap(wl.length, wl.resolution)
+    raw_ref, vox_ref = oracle_mod.OracleMap(L, res), oracle_mod.OracleMap(wl.length, wl.resolution)
+    gpus = (raw_host, raw_dev, vox_host, vox_dev)
+    for m in gpus:
+        m.debug_set("copy_threads", copy_threads)
+    for m in (raw_host, raw_dev, raw_ref):
+        m.move(pos)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def colours(n):
+        rgb = (rng.integers(0, 3, (n, 3)) * 100).astype(np.uint32)
+        return (rgb[:, 0] << 16) | (rgb[:, 1] << 8) | rgb[:, 2]
+
+    # XYZI + rgb: 20 bytes a point, 60 000 and the 131 072 of the sweep above 128 KB, 3 000 below
+    for step, (n_raw, n_vox) in enumerate(((60_000, sweep.shape[0]), (3_000, 3_000), (0, 0), (60_000, sweep.shape[0]), (3_000, 3_000))):
+        if step:
+            for m in gpus + (raw_ref, vox_ref):
+                m.mapvar_update(1e-5)
+        part, c_raw = raw[rng.permutation(raw.shape[0])[:n_raw]], colours(n_raw)
+        cloud, c_vox = sweep[rng.permutation(sweep.shape[0])[:n_vox]], colours(n_vox)
+        f_raw, f_vox = frame_at(T, laser, step), frame_at(wl.frames[0].T.astype(np.float64), wl.frames[0].model, step)
+        raw_host.add_raw(f_raw, part, rgb=c_raw, clean=d435)
+        raw_dev.add_raw(f_raw, dev(part), rgb=dev(c_raw.view(np.int32)), clean=d435)
+        kx, kc, kept = clean_ref.clean(part, c_raw, cp.mode, cp.z_min, cp.z_max)
+        raw_ref.add(f_raw, kx, rgb=kc, orig_index=kept)
+        vox_host.add_voxel(f_vox, stages, cloud, rgb=c_vox)
+        vox_dev.add_voxel(f_vox, stages, dev(cloud), rgb=dev(c_vox.view(np.int32)))
+        fx, fc, k = vr.voxel(cloud, c_vox, stages)
+        vox_ref.add(f_vox, fx[:k], rgb=fc[:k])
+        for who, m, ref in (("add_raw host", raw_host, raw_ref), ("add_raw device", raw_dev, raw_ref),
+                            ("add_voxel host", vox_host, vox_ref), ("add_voxel device", vox_dev, vox_ref)):
+            for name in ("elevation", "variance", "intensity", "color_r", "color_g", "color_b"):
+                bad = np.flatnonzero(bits(m.layer(name)) != bits(ref.layer(name)))
+                assert bad.size == 0, f"{who} step {step} {name}: {bad.size} cells differ from the oracle"
+    assert (raw_ref.layer("elevation") != -10).sum() > 1000 and (vox_ref.layer("elevation") != -10).sum() > 1000
+    for m in gpus:
+        m.close()
+
+
+@pytest.mark.one_pipeline
+def test_device_colours_and_indices_must_cover_the_cloud():
+    """add / add_raw / add_voxel of a device cloud: an rgb or orig_index tensor shorter than the cloud or not on its device is a
+    ValueError before anything is enqueued (the kernels would read past its end); longer ones are read up to n"""
+    import torch
+    from gem_amd import VoxelStage
+    m = ElevationMap(64, 0.1)
+    f = synth._frame_for(np.eye(4), SensorModel.velodyne())
+    d = torch.from_numpy(synth.random_cloud(3, 100, 2.0)).cuda()
+    short, on_host = torch.zeros(99, dtype=torch.int32, device=d.device), torch.zeros(100, dtype=torch.int32)
+    for bad in (short, on_host):
+        for call in (lambda: m.add(f, d, rgb=bad), lambda: m.add(f, d, orig_index=bad), lambda: m.add_raw(f, d, rgb=bad),
+                     lambda: m.add_voxel(f, [VoxelStage(0.1)], d, rgb=bad)):
+            with pytest.raises(ValueError):
+                call()
+    assert m.stats()["points_in"] == 0
+    longer = torch.zeros(101, dtype=torch.int32, device=d.device)
+    m.add(f, d, rgb=longer, orig_index=longer)
+    m.synchronize()
+    assert m.stats()["points_in"] == 100
+    m.close()
+
+
+# ---- 6. the C++ processors ------------------------------------------------------------------------------------------------------
 @pytest.mark.one_pipeline            # (a C++ child process: the fixture's knobs never reach it)
 def test_cpp_process_raw_on_gpu(tmp_path):
     from test_clean_cpu import build_clean_facade_check
