@@ -121,6 +121,12 @@ SIGNATURES = {
     "gem_local_spill": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_void_p, POINTER(c_int), POINTER(c_int)]),
     "gem_local_export": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_longlong), c_int]),
     "gem_local_size": (c_int, [c_void_p, POINTER(c_longlong)]),
+    "gem_global_enable": (c_int, [c_void_p, c_longlong]),
+    "gem_global_push_local": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "gem_global_push": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_int)]),
+    "gem_global_loop_closure": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float), c_float, c_double, POINTER(c_longlong)]),
+    "gem_global_export": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_longlong)]),
+    "gem_global_count": (c_int, [c_void_p, POINTER(c_int)]),
 }
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {

@@ -709,6 +709,56 @@ class ElevationMap:
         self._check(self._lib.gem_local_size(self._h, C.byref(n)), "gem_local_size")
         return int(n.value)
 
+    # -- the submap stack (globalMap_: updateLocalMap's new-keyframe branch, EMg.cpp:630-687; updateGlobalMap, :773-905) ----------
+    def global_enable(self, capacity: int = 1 << 20) -> None:
+        """Switch the device submap stack on, empty, with room for `capacity` records (it grows on demand); 0 switches it off and
+        frees its memory (gem_global_enable)."""
+        self._check(self._lib.gem_global_enable(self._h, int(capacity)), "gem_global_enable")
+
+    def global_push_local(self, clear_local: bool = True) -> int:
+        """globalMap_.push_back(*out_pc + *grid_pc) on the device: the local map's export followed by the last capture's grid cloud.
+        clear_local=True empties the local map afterwards.  Returns the new submap's index."""
+        i = C.c_int()
+        self._check(self._lib.gem_global_push_local(self._h, int(bool(clear_local)), C.byref(i)), "gem_global_push_local")
+        return int(i.value)
+
+    def global_push(self, points) -> int:
+        """A POINT_DTYPE cloud (host) as a new submap; returns its index."""
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        i = C.c_int()
+        self._check(self._lib.gem_global_push(self._h, pts.ctypes.data_as(C.c_void_p) if pts.size else None, pts.shape[0], C.byref(i)),
+                    "gem_global_push")
+        return int(i.value)
+
+    def global_loop_closure(self, transforms, centres, radius: float = 25.0, resolution: float = 0.0) -> int:
+        """updateGlobalMap's body (gem_global_loop_closure): transforms = n_opt 4x4 matrices M[row][col] (laid out column-major for the
+        library, as Eigen::Matrix4f::data()), centres = n_opt (x, y) pairs; resolution <= 0 takes the map's.  Returns the fused count."""
+        t = np.asarray(transforms, np.float32).reshape(-1, 4, 4)
+        c = np.ascontiguousarray(np.asarray(centres, np.float32).reshape(-1, 2))
+        n = t.shape[0]
+        if c.shape[0] != n:
+            raise ValueError("global_loop_closure: one centre per transform")
+        tc = np.ascontiguousarray(t.transpose(0, 2, 1))                  # column-major per matrix
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a.size else None
+        fused = C.c_longlong()
+        self._check(self._lib.gem_global_loop_closure(self._h, n, fp(tc), fp(c), float(np.float32(radius)), float(resolution),
+                                                      C.byref(fused)), "gem_global_loop_closure")
+        return int(fused.value)
+
+    def global_export(self, index: int = -1) -> np.ndarray:
+        """Submap `index` (-1: all, in stack order) as POINT_DTYPE records."""
+        n = C.c_longlong()
+        self._check(self._lib.gem_global_export(self._h, int(index), None, 0, C.byref(n)), "gem_global_export")
+        out = np.empty(max(n.value, 1), POINT_DTYPE)
+        self._check(self._lib.gem_global_export(self._h, int(index), out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)),
+                    "gem_global_export")
+        return out[:n.value].copy()
+
+    def global_count(self) -> int:
+        n = C.c_int()
+        self._check(self._lib.gem_global_count(self._h, C.byref(n)), "gem_global_count")
+        return int(n.value)
+
     # -- the step in front of the path: input colourisation (EMg.cpp:349-381) -------------------------------
     @staticmethod
     def lidar_to_image(tcamera, tlidar) -> np.ndarray:

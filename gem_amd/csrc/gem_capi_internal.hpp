@@ -258,6 +258,17 @@ struct gem_handle {
         Arena small;                    // device words: capture counts [2] | spill total | export total | new keys
         long long log_cap = 0, log_len = 0, table_cap = 0, live = 0;
     } local;
+    // the submap stack of updateGlobalMap (gem_global_*, gem_capi_global.cpp; kernels in gem_global.hip)
+    struct Global {
+        bool enabled = false;
+        Arena stack[2];                 // the records of every submap, one arena in use (`act`), the other the target when it grows
+        int act = 0;
+        long long cap = 0, used = 0;    // records the active arena holds / records up to the end of the last submap's room
+        std::vector<long long> off, room, cnt;      // per submap: first record, records it may hold, records it holds
+        Arena cnts;                     // per submap record counts on the device, read by a loop closure's kernels
+        Arena out[2], keys[2], tkeys[2], tvals[2], blk[2];  // a pair step's sides (0 = old, 1 = new): output, keys, table, counts
+        Arena small;                    // device words: the sides' totals [2] | fused keys | the local map's export total
+    } global;
     bool  dbg_on = false;
     bool  dbg_frame = false;            // debug knob: with the stamps on, a stream of single sweeps still runs as k_frame (its tiles AND its binning blocks are stamped)
     long long sort_fallbacks = 0;      // passes whose forced sorted form / pass count did not fit the map and took the other form (gem_debug_get)
@@ -349,6 +360,11 @@ int flush_walk(gem_handle* h);
 int flush_local(gem_handle* h);
 int wait_gather(gem_handle* h);
 void local_free(gem_handle* h);                 // gem_capi_local.cpp: the local map's arenas (gem_destroy, gem_local_enable(0))
+// gem_capi_local.cpp, for gem_global_push_local: the record count of the last capture (downloaded; GEM_ERR_INVALID without one), and
+// the local map's export followed by that capture's grid cloud written to dst (device), the map emptied afterwards with clear
+int local_grid_count(gem_handle* h, uint32_t* n);
+int local_export_to(gem_handle* h, void* dst, uint32_t n_grid, bool clear);
+void global_free(gem_handle* h);                // gem_capi_global.cpp: the submap stack's arenas (gem_destroy, gem_global_enable(0))
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);
 int flush_pending(gem_handle* h, bool with_floor);

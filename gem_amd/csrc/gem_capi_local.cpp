@@ -91,6 +91,41 @@ void local_free(gem_handle* h)
     lc = gem_handle::Local{};
 }
 
+int local_grid_count(gem_handle* h, uint32_t* n)
+{
+    auto& lc = h->local;
+    if (!lc.enabled || lc.cur < 0) return fail(h, GEM_ERR_INVALID, "the local map is not enabled or has no capture");
+    int rc;
+    HostXfer c{n, small_word(h, kWordCapture + lc.cur), 4};
+    if ((rc = download_arrays(h, &c, 1, 0))) return rc;
+    if (*n > (uint32_t)h->cells) return fail(h, GEM_ERR_HIP, "local_grid_count: capture count out of range");
+    return GEM_OK;
+}
+
+// gem_local_export's compaction straight into dst, then the capture's records behind it; the live count is checked on the host
+int local_export_to(gem_handle* h, void* dst, uint32_t n_grid, bool clear)
+{
+    auto& lc = h->local;
+    int rc;
+    LocalRecord* out = static_cast<LocalRecord*>(dst);
+    uint32_t n = 0;
+    if (lc.live > 0) {
+        LocalExportArgs e{log_at(h, lc.act), lc.log_len, table_of(h), out};
+        GEM_HIP(h, launch_local_export(h->stream, e, static_cast<uint32_t*>(lc.exp_cnt.p), small_word(h, kWordExport)));
+    }
+    if (n_grid) GEM_HIP(h, hipMemcpyAsync(out + lc.live, lc.slot[lc.cur].rec.p, (size_t)n_grid * kRec, hipMemcpyDeviceToDevice, h->stream));
+    if (lc.live > 0) {
+        HostXfer c{&n, small_word(h, kWordExport), 4};
+        if ((rc = download_arrays(h, &c, 1, 0))) return rc;
+        if ((long long)n != lc.live) return fail(h, GEM_ERR_HIP, "local_export_to: live entry count mismatch");
+    }
+    if (clear) {                                                   // localMap_.swap(tmp)
+        if ((rc = clear_table(h))) return rc;
+        lc.log_len = lc.live = 0;
+    }
+    return GEM_OK;
+}
+
 } // namespace gemi
 
 extern "C" {

@@ -28,20 +28,6 @@ __device__ __forceinline__ void local_position(const LocalGeom& g, size_t lin, d
     y = (g.py + g.off) + g.res * (double)(-uy);
 }
 
-__device__ __forceinline__ unsigned long long local_key(float x, float y)
-{
-    x = x == 0.0f ? 0.0f : x;                                               // -0 == +0 (GridPointEqual compares floats)
-    y = y == 0.0f ? 0.0f : y;
-    return (unsigned long long)__float_as_uint(x) | ((unsigned long long)__float_as_uint(y) << 32);
-}
-
-__device__ __forceinline__ unsigned long long local_hash(unsigned long long k)      // murmur3's 64-bit finaliser
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
-}
-
 struct CaptureSrc {
     LocalCaptureArgs a;
     __device__ size_t size() const { return (size_t)a.g.L * a.g.L; }
@@ -87,17 +73,6 @@ struct SpillSrc {
     }
     __device__ void emit(size_t i, size_t o) const { a.out[o] = a.rec[i]; }
 };
-
-__device__ __forceinline__ unsigned long long local_find(const LocalTable& t, unsigned long long key)
-{
-    unsigned long long s = local_hash(key) & t.mask;
-    for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
-        const unsigned long long k = t.keys[s];
-        if (k == key || k == kLocalEmpty) return s;
-        s = (s + 1) & t.mask;
-    }
-    return s;
-}
 
 struct ExportSrc {
     LocalExportArgs a;
@@ -188,18 +163,7 @@ __global__ __launch_bounds__(256) void k_local_insert(const LocalRecord* __restr
     bool added = false;
     if (j < n) {
         const long long p = p0 + j;
-        const unsigned long long key = local_key(log[p].x, log[p].y);
-        unsigned long long s = local_hash(key) & t.mask;
-        for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
-            unsigned long long prev = kLocalEmpty;
-            if (__hip_atomic_compare_exchange_strong(t.keys + s, &prev, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                added = true;
-                break;
-            }
-            if (prev == key) break;
-            s = (s + 1) & t.mask;
-        }
-        __hip_atomic_fetch_max(t.vals + s, (int)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        added = local_upsert<LocalWins::Last>(t, local_key(log[p].x, log[p].y), (int)p);
     }
     if (new_keys) {
         const uint64_t m = __ballot(added);

@@ -59,6 +59,55 @@ struct LocalExportArgs {
 
 inline unsigned local_blocks(long long n) { return n > 0 ? (unsigned)((n + kLocalTile - 1) / kLocalTile) : 0u; }
 
+// The table's device side, shared by the local map (gem_local.hip) and the submap stack (gem_global.hip).
+__device__ __forceinline__ unsigned long long local_key(float x, float y)
+{
+    x = x == 0.0f ? 0.0f : x;                                               // -0 == +0 (GridPointEqual compares floats)
+    y = y == 0.0f ? 0.0f : y;
+    return (unsigned long long)__float_as_uint(x) | ((unsigned long long)__float_as_uint(y) << 32);
+}
+
+__device__ __forceinline__ unsigned long long local_hash(unsigned long long k)      // murmur3's 64-bit finaliser
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
+    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}
+
+__device__ __forceinline__ unsigned long long local_find(const LocalTable& t, unsigned long long key)
+{
+    unsigned long long s = local_hash(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
+        const unsigned long long k = t.keys[s];
+        if (k == key || k == kLocalEmpty) return s;
+        s = (s + 1) & t.mask;
+    }
+    return s;
+}
+
+// Which position a key keeps when several entries carry it: the last (atomicMax; free slots hold -1) or the first (atomicMin; free
+// slots hold INT_MAX).  The key's slot is claimed by CAS from empty with linear probing; returns whether this call added the key.
+enum class LocalWins { Last, First };
+
+template <LocalWins W>
+__device__ __forceinline__ bool local_upsert(const LocalTable& t, unsigned long long key, int pos)
+{
+    bool added = false;
+    unsigned long long s = local_hash(key) & t.mask;
+    for (unsigned long long probe = 0; probe <= t.mask; ++probe) {
+        unsigned long long prev = kLocalEmpty;
+        if (__hip_atomic_compare_exchange_strong(t.keys + s, &prev, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+            added = true;
+            break;
+        }
+        if (prev == key) break;
+        s = (s + 1) & t.mask;
+    }
+    if (W == LocalWins::Last) __hip_atomic_fetch_max(t.vals + s, pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_fetch_min(t.vals + s, pos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return added;
+}
+
 // block_cnt: [local_blocks(n)] scratch; *total: kept items (device)
 hipError_t launch_local_capture(hipStream_t st, const LocalCaptureArgs& a, uint32_t* block_cnt, uint32_t* total);
 hipError_t launch_local_spill(hipStream_t st, const LocalSpillArgs& a, long long bound, uint32_t* block_cnt, uint32_t* total, bool scatter);

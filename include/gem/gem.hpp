@@ -13,6 +13,7 @@
 //       src/RobotMotionMapUpdater.cpp:42-90, 92-109, 111-145
 //   ElevationMap layer names                                      src/ElevationMap.cpp:43-44
 //   ElevationMapping::updateLocalMap / visualPointMap (LocalMap)   src/ElevationMapping.cpp:609-767, 520-530
+//   ElevationMapping::updateGlobalMap and globalMap_ (GlobalMap)   src/ElevationMapping.cpp:630-687, 773-905
 //   pcl::VoxelGrid of the launch files' nodelets (VoxelGrid)       filter.launch, filter_kitti.launch
 #pragma once
 
@@ -413,6 +414,68 @@ public:
 
 private:
     size_t cells() const { const size_t L = static_cast<size_t>(map_.length()); return L * L; }
+    ElevationMap& map_;
+};
+
+// ---------------------------------------------------------------------------------------------
+// The submap stack globalMap_ of ElevationMapping (ElevationMapping.cpp:630-687 push, :773-905 updateGlobalMap) on the device
+// (gem_global_*).  The pose bookkeeping (trajectory_, localMapLoc_, optGlobalMapLoc_, the flags) stays with the caller, see
+// INTEGRATION.md; the handle's lock replaces GlobalMapMutex_.
+// ---------------------------------------------------------------------------------------------
+class GlobalMap {
+public:
+    // capacity: initial records (grows on demand)
+    explicit GlobalMap(ElevationMap& map, long long capacity = 1 << 20) : map_(map)
+    { map_.check(gem_global_enable(map_.handle(), capacity), "gem_global_enable"); }
+    ~GlobalMap() { gem_global_enable(map_.handle(), 0); }
+    GlobalMap(const GlobalMap&) = delete;
+    GlobalMap& operator=(const GlobalMap&) = delete;
+
+    // globalMap_.push_back(*out_pc + *grid_pc), device to device; clearLocal: then localMap_.swap(tmp).  Returns the submap's index.
+    int pushLocal(bool clearLocal = true)
+    {
+        int i = -1;
+        map_.check(gem_global_push_local(map_.handle(), clearLocal ? 1 : 0, &i), "gem_global_push_local");
+        return i;
+    }
+    // a cloud of the caller's (the denseSubmap branch: pointcloudinterpolation's output)
+    int push(const std::vector<PointXYZRGBICT>& cloud)
+    {
+        int i = -1;
+        map_.check(gem_global_push(map_.handle(), cloud.empty() ? nullptr : cloud.data(), static_cast<long long>(cloud.size()), &i),
+                   "gem_global_push");
+        return i;
+    }
+    // updateGlobalMap's body: transforms[i] = (optGlobalMapLoc_[i] * trajectory_[i].inverse()).matrix() as Matrix4f::data()
+    // (column-major), centres[i] = localMapLoc_[i]; one of each per optimised keyframe.  Returns the fused count.
+    long long loopClosure(const std::vector<std::array<float, 16>>& transforms, const std::vector<std::array<float, 2>>& centres,
+                          float radius = 25.f, double resolution = 0.0)
+    {
+        static_assert(sizeof(std::array<float, 16>) == 64 && sizeof(std::array<float, 2>) == 8, "packed matrices and centres");
+        if (transforms.size() != centres.size()) throw Error(GEM_ERR_INVALID, "GlobalMap::loopClosure: one centre per transform");
+        long long fused = 0;
+        map_.check(gem_global_loop_closure(map_.handle(), static_cast<int>(transforms.size()),
+                                           transforms.empty() ? nullptr : transforms[0].data(), centres.empty() ? nullptr : centres[0].data(),
+                                           radius, resolution, &fused), "gem_global_loop_closure");
+        return fused;
+    }
+    // submap `index`, or all of them in stack order (-1: visualCloud_, composingGlobalMap, savingMap)
+    std::vector<PointXYZRGBICT> exportCloud(int index = -1)
+    {
+        long long n = 0;
+        map_.check(gem_global_export(map_.handle(), index, nullptr, 0, &n), "gem_global_export");
+        std::vector<PointXYZRGBICT> v(static_cast<size_t>(n));
+        map_.check(gem_global_export(map_.handle(), index, v.empty() ? nullptr : v.data(), n, &n), "gem_global_export");
+        return v;
+    }
+    int size() const
+    {
+        int n = 0;
+        map_.check(gem_global_count(map_.handle(), &n), "gem_global_count");
+        return n;
+    }
+
+private:
     ElevationMap& map_;
 };
 

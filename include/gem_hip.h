@@ -442,6 +442,50 @@ int  gem_local_spill(gem_handle* h, const float current_position[2], const float
 int  gem_local_export(gem_handle* h, void* points, long long max_points, long long* out_count, int clear);
 int  gem_local_size(gem_handle* h, long long* out_count);
 
+/* ---- the submap stack (globalMap_: the new-keyframe branch of updateLocalMap, EMg.cpp:630-687; updateGlobalMap, :773-905) -------
+ *   gem_global_enable          capacity > 0: switch the stack on, empty, with room for `capacity` records (it grows on demand); on an
+ *                              enabled handle it starts over.  0: switch it off and free its memory.
+ *   gem_global_push_local      globalMap_.push_back(*out_pc + *grid_pc) on the device: the local map's export (gem_local_export's
+ *                              records, last-write order) followed by the last capture's grid cloud (gem_local_grid_cloud), as one new
+ *                              submap; with clear_local != 0 the local map is emptied afterwards (localMap_.swap(tmp)).
+ *   gem_global_push            a caller's PointXYZRGBICT cloud (host memory) as one new submap (the denseSubmap branch: the node's
+ *                              own pointcloudinterpolation output).
+ *   gem_global_loop_closure    the body of updateGlobalMap after the flag, restated:
+ *     1. n = min(n_opt, submaps) (optKeyframeNum clamped, :784-786); submaps >= n are untouched.
+ *     2. transforms: n_opt 4x4 float matrices, each column-major as Eigen::Matrix4f::data() -- the node's
+ *        (optGlobalMapLoc_[i] * trajectory_[i].inverse()).matrix().  Entry 0 is ignored.
+ *     3. for i in [1, n) every record of submap i, a non-finite one included, becomes x' = x*m00 + (y*m01 + (z*m02 + m03)), y', z' and
+ *        pad likewise from rows 1, 2, 3, each product and sum rounded in float (no FMA); the other fields are copied.  This restates
+ *        the SSE2 form of pcl::detail::Transformer<float>::se3 (PCL >= 1.10, x86-64).
+ *     4. the neighbours of submap i, i in [0, n): the j in [0, n) whose centre (centres: n_opt float pairs, localMapLoc_, not moved by
+ *        the transforms) has d2 = dx*dx + dy*dy (float; neighbour minus i) < (float)(radius * radius) (the square in double), in
+ *        ascending d2, ties by ascending j.  This restates KdTreeFLANN::radiusSearch with sorted results and FLANN's strict test.
+ *     5. a list of more than two entries (:844) runs the pair steps (i, k = list[p]) for p = 1, 2, ... in order; position 0 is skipped
+ *        even when it is not i (a coincident centre of lower index comes first, and then k == i).  A step hashes old = submap i and
+ *        new = submap k, both as they are before the step: each record gets the key ((float)(ceil((double)x / res) * res - res / 2.0),
+ *        the same for y), res = resolution (a double; <= 0: the map's resolution), and the first record of a key keeps it (keys compare
+ *        as float pairs; every record with a NaN key is kept and never matched).  For every key of new also in old whose old variance
+ *        ov satisfies 0 < ov < 1 (float compares), in double with nv, ne new's variance and elevation and oe old's elevation:
+ *          nv2 = nv*nv, ov2 = ov*ov, elevation = (float)(((nv2*oe) + ((ov2*ne) / ov2)) + nv2), variance = (float)(((ov2*nv2) / ov2) + nv2)
+ *        -- :862-863 as C++ precedence parses them -- with new's r, g, b, intensity and travers, into both maps; *out_fused counts these
+ *        keys over all steps.  Then submap k := export(new) and after it submap i := export(old), so for k == i old wins.  An export
+ *        writes per key x, y = the key, z = elevation, pad = 1, b g r, a = 0, covariance, intensity (the reference leaves it unset:
+ *        the stored one is written), travers, in the order of the key's first record in the cloud the map was built from (the
+ *        reference's order is std::unordered_map's; after one hash the keys are unique, so no value depends on it).
+ *   gem_global_export          submap `index` (-1: all, in stack order) into points (host); points NULL: only *out_count.
+ *   gem_global_count           the number of submaps.
+ * Records are PointXYZRGBICT (32 bytes) as in gem_local_*.  The pose bookkeeping (trajectory_, localMapLoc_, the flags) stays with the
+ * caller.  GEM_ERR_INVALID, the stack left as it was: not enabled, a handle with a communicator, push_local without an enabled local
+ * map or a capture, n_opt < 0, transforms or centres NULL with n_opt > 1, radius not finite or negative, an index out of range,
+ * max_points below the record count. */
+int  gem_global_enable(gem_handle* h, long long capacity);
+int  gem_global_push_local(gem_handle* h, int clear_local, int* out_index);
+int  gem_global_push(gem_handle* h, const void* points, long long n, int* out_index);
+int  gem_global_loop_closure(gem_handle* h, int n_opt, const float* transforms, const float* centres, float radius,
+                             double resolution, long long* out_fused);
+int  gem_global_export(gem_handle* h, int index, void* points, long long max_points, long long* out_count);
+int  gem_global_count(gem_handle* h, int* out_submaps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,10 @@
 //                    points sample (reference: elevation_mapping/src/ElevationMapping.cpp:349-381)
 //   vox gem_voxel_device restates pcl::VoxelGrid<pcl::PCLPointCloud2> as pcl_ros's nodelet runs it (the launch files' filter stages);
 //                    tests/voxel_ref.py restates the same contract in numpy
+//   glob gem_global_loop_closure restates pcl::transformPointCloud (x' = x*m00 + (y*m01 + (z*m02 + m03)) in float, no FMA: the SSE2
+//                    form of PCL >= 1.10 on x86-64) and KdTreeFLANN<PointXY>::radiusSearch (d2 < r2 strictly, sorted by d2, ties by
+//                    index) as updateGlobalMap calls them (reference: elevation_mapping/src/ElevationMapping.cpp:790-840);
+//                    tests/global_ref.py restates the same contract in numpy
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -15,9 +19,9 @@
 // The voxel row is bit for bit in the output order, the count and every voxel of one or two points; in voxels of three or more points
 // it allows a few ulps, because PCL's std::sort is not stable and may sum such a voxel in another order than input order.
 //
-//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8) \
+//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8 pcl_kdtree-1.8) \
 //       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Lgem_amd/lib -lgem_hip -Wl,-rpath,$PWD/gem_amd/lib -L/opt/rocm/lib -lamdhip64 \
-//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
+//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, OpenCV or PCL there).
 //
@@ -41,6 +45,8 @@
 #include <pcl/PCLPointCloud2.h>
 #include <pcl/conversions.h>
 #include <pcl/filters/voxel_grid.h>
+#include <pcl/common/transforms.h>
+#include <pcl/kdtree/kdtree_flann.h>
 #include <pcl/point_types.h>
 
 #include <limits>
@@ -333,6 +339,119 @@ int check_voxel(uint32_t seed)
     return rc;
 }
 
+// ---- glob ----------------------------------------------------------------------------------------------------------------------
+// (a) seeded records, non-finite ones included, through the real pcl::transformPointCloud with the node's Matrix4f, against submap 1
+//     of a loop closure whose centres are too far apart for any pair step (the transform alone);
+// (b) centre sets with a centre exactly at the radius, tied distances and coincident centres through the real KdTreeFLANN::radiusSearch,
+//     against the rule gem_global_loop_closure documents, and against the device: one record per submap, all on one key with variance
+//     0.5, so every pair step fuses exactly once and the fused count is the sum of (list length - 1) over the lists longer than two.
+std::vector<int> documented_list(const std::vector<float>& c, int n, int i, float radius)
+{
+    const float r2 = (float)((double)radius * (double)radius);
+    std::vector<std::pair<float, int>> hits;
+    for (int j = 0; j < n; ++j) {
+        const float dx = c[2 * j] - c[2 * i], dy = c[2 * j + 1] - c[2 * i + 1];
+        const float d2 = dx * dx + dy * dy;
+        if (d2 < r2) hits.emplace_back(d2, j);
+    }
+    std::sort(hits.begin(), hits.end());
+    std::vector<int> out;
+    for (const auto& p : hits) out.push_back(p.second);
+    return out;
+}
+
+struct Rec { float x, y, z, pad; uint8_t b, g, r, a; float covariance, intensity, travers; };
+static_assert(sizeof(Rec) == 32, "PointXYZRGBICT");
+
+int check_global(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 64; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<float> u(-30.0f, 30.0f), ang(-0.05f, 0.05f);
+    // (a)
+    const int N = 100000;
+    std::vector<Rec> cloud(N);
+    pcl::PointCloud<pcl::PointXYZ> in;
+    in.resize(N);
+    in.is_dense = true;
+    for (int i = 0; i < N; ++i) {
+        Rec r{};
+        r.x = u(rng); r.y = u(rng); r.z = u(rng) * 0.1f; r.pad = 1.0f; r.covariance = 2.0f;
+        if (i == 7) r.x = std::numeric_limits<float>::infinity();
+        if (i == 11) r.y = std::numeric_limits<float>::quiet_NaN();
+        cloud[i] = r;
+        in[i].x = r.x; in[i].y = r.y; in[i].z = r.z;
+    }
+    Eigen::Isometry3f opt = Eigen::Isometry3f::Identity(), traj = Eigen::Isometry3f::Identity();
+    opt.rotate(Eigen::AngleAxisf(ang(rng), Eigen::Vector3f::UnitZ())); opt.pretranslate(Eigen::Vector3f(u(rng), u(rng), 0.1f));
+    traj.rotate(Eigen::AngleAxisf(ang(rng), Eigen::Vector3f::UnitZ())); traj.pretranslate(Eigen::Vector3f(u(rng), u(rng), -0.2f));
+    const Eigen::Matrix4f M = (opt * traj.inverse()).matrix();
+    pcl::PointCloud<pcl::PointXYZ> out;
+    pcl::transformPointCloud(in, out, M);
+    CHECK_GEM(gem_global_enable(h, 2 * N));
+    int idx = 0;
+    CHECK_GEM(gem_global_push(h, cloud.data(), 1, &idx));
+    CHECK_GEM(gem_global_push(h, cloud.data(), N, &idx));
+    std::vector<float> T(32, 0.0f);
+    std::copy(M.data(), M.data() + 16, T.begin() + 16);
+    const float far[4] = {0.0f, 0.0f, 1e6f, 0.0f};
+    long long fused = 0, n = 0;
+    CHECK_GEM(gem_global_loop_closure(h, 2, T.data(), far, 25.0f, 0.05, &fused));
+    std::vector<Rec> got(N);
+    CHECK_GEM(gem_global_export(h, 1, got.data(), N, &n));
+    int bad = 0;
+    for (int i = 0; i < N && bad < 5; ++i) {
+        const float w[3] = {out[i].x, out[i].y, out[i].z}, g[3] = {got[i].x, got[i].y, got[i].z};
+        for (int c = 0; c < 3; ++c)
+            if (std::memcmp(&w[c], &g[c], 4) != 0 && !(std::isnan(w[c]) && std::isnan(g[c]))) {
+                std::fprintf(stderr, "glob: transformPointCloud record %d coord %d: pcl %a device %a\n", i, c, w[c], g[c]);
+                ++bad; ++g_failures;
+            }
+    }
+    // (b)
+    const std::vector<std::vector<float>> sets = {
+        {0, 0, 3, 4, 0, 1, 1, 0, 0, -1, -1, 0, 2.5f, 2.5f},               // (3, 4): exactly at radius 5; four ties at 1
+        {0, 0, 0, 0, 5, 0, 10, 0, 0, 0, -5, 0},                            // coincident centres
+    };
+    const float radii[2] = {5.0f, 7.0f};
+    for (size_t si = 0; si < sets.size(); ++si) {
+        const std::vector<float>& c = sets[si];
+        const int S = (int)c.size() / 2;
+        pcl::PointCloud<pcl::PointXY>::Ptr pts(new pcl::PointCloud<pcl::PointXY>());
+        for (int j = 0; j < S; ++j) { pcl::PointXY p; p.x = c[2 * j]; p.y = c[2 * j + 1]; pts->push_back(p); }
+        pcl::KdTreeFLANN<pcl::PointXY> kd;
+        kd.setInputCloud(pts);
+        long long want = 0;
+        for (int i = 0; i < S; ++i) {
+            std::vector<int> ids; std::vector<float> d2;
+            kd.radiusSearch((*pts)[i], radii[si], ids, d2);
+            const std::vector<int> doc = documented_list(c, S, i, radii[si]);
+            if (ids != doc) {
+                std::fprintf(stderr, "glob: set %zu centre %d: radiusSearch gives", si, i);
+                for (int j : ids) std::fprintf(stderr, " %d", j);
+                std::fprintf(stderr, ", the documented rule");
+                for (int j : doc) std::fprintf(stderr, " %d", j);
+                std::fprintf(stderr, "\n");
+                ++g_failures;
+            }
+            if (ids.size() > 2) want += (long long)ids.size() - 1;
+        }
+        CHECK_GEM(gem_global_enable(h, 64));
+        Rec one{};
+        one.x = 0.01f; one.y = 0.01f; one.z = 1.0f; one.pad = 1.0f; one.covariance = 0.5f;
+        for (int j = 0; j < S; ++j) CHECK_GEM(gem_global_push(h, &one, 1, &idx));
+        std::vector<float> eye(16 * S, 0.0f);
+        for (int j = 0; j < S; ++j) eye[16 * j] = eye[16 * j + 5] = eye[16 * j + 10] = eye[16 * j + 15] = 1.0f;
+        CHECK_GEM(gem_global_loop_closure(h, S, eye.data(), c.data(), radii[si], 0.05, &fused));
+        if (fused != want) { std::fprintf(stderr, "glob: set %zu: device fused %lld, radiusSearch's lists give %lld\n", si, fused, want); ++g_failures; }
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -341,8 +460,9 @@ int main(int argc, char** argv)
     int rc = check_show(seed);
     if (rc == 0) rc = check_colorize(seed + 1u);
     if (rc == 0) rc = check_voxel(seed + 2u);
+    if (rc == 0) rc = check_global(seed + 3u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the oracle's restatement of grid_map / cv::circle / pcl::VoxelGrid does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all three rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all four rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
     return 0;
 }
