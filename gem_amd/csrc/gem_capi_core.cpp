@@ -449,7 +449,8 @@ int flush_walk(gem_handle* h)
     // to a kernel launched afterwards on ANOTHER stream of this device -- bin_done carries no system-scope fence, so this rests on the
     // release at the end of the sort's last dispatch (L2 write-back of the device's own XCDs) and the acquire at the start of the
     // walk's, which is what ROCm 7.x does for every kernel boundary.  The "walk_always_wait" knob states the edge instead (5 us of
-    // the walk's stream, profiles/r05_ubench_handover.txt); the soak and tests/test_parity_gpu.py run both.
+    // the walk's stream, profiles/r05_ubench_handover.txt); the soaks (tools/fuzz_parity.py's KNOBS, tools/fuzz_node.py) and
+    // tests/test_parity_gpu.py / tests/test_local_global_scale_gpu.py run both.
     if (!h->walk_always_wait && hipEventQuery(pb.bin_done) == hipSuccess) ++h->walks_unwaited;
     else { (void)hipGetLastError(); GEM_HIP(h, hipStreamWaitEvent(h->stream, pb.bin_done, 0)); }
     {

@@ -3,7 +3,11 @@ EMg.cpp:630-687, and updateGlobalMap, :773-905), the semantics include/gem_hip.h
 
 The stack is a Python list of POINT arrays.  A hashed submap is a dict from the key -- a pair of Python floats, or ("nan", position)
 for a record whose key has a NaN, so that it never equals anything -- to (record, position of the key's first record); dicts keep
-insertion order, which is the device's export order: the first occurrence of each key."""
+insertion order, which is the device's export order: the first occurrence of each key.
+
+The dict forms are the definition.  hash_fast / pair_step_fast (loop_closure(..., fast=True)) are the same on arrays -- the first
+record of a key by a stable np.unique on the key's bits, NaN keys kept apart -- fast enough for submaps of a million records;
+tests/test_vectorised_refs_cpu.py pins the two forms to identical bytes."""
 import numpy as np
 
 import local_ref
@@ -101,8 +105,45 @@ def pair_step(stack: list, i: int, k: int, res: float) -> int:
     return fused
 
 
+def hash_fast(rec: np.ndarray, res: float):
+    """export(hash_cloud(rec, res)) on arrays, with the entries' keys (local_key's bits) and which of them are NaN keys"""
+    kx, ky = quantise(rec["x"], res), quantise(rec["y"], res)
+    nan = np.isnan(kx) | np.isnan(ky)
+    bits = local_ref.key_bits(kx, ky)
+    real = np.flatnonzero(~nan)
+    _, first = np.unique(bits[real], return_index=True)                   # stable: the first occurrence of every key
+    keep = np.sort(np.concatenate([real[first], np.flatnonzero(nan)]))
+    out = rec[keep].copy()
+    out["x"], out["y"], out["pad"], out["a"] = kx[keep], ky[keep], 1.0, 0
+    return out, bits[keep], nan[keep]
+
+
+def pair_step_fast(stack: list, i: int, k: int, res: float) -> int:
+    """pair_step on arrays"""
+    old, okey, onan = hash_fast(stack[i], res)
+    new, nkey, nnan = hash_fast(stack[k], res)
+    oreal, nreal = np.flatnonzero(~onan), np.flatnonzero(~nnan)
+    _, oi, ni = np.intersect1d(okey[oreal], nkey[nreal], assume_unique=True, return_indices=True)
+    oi, ni = oreal[oi], nreal[ni]
+    oc = old["covariance"][oi]
+    hit = (F32(0) < oc) & (oc < F32(1))
+    oi, ni = oi[hit], ni[hit]
+    nv, ne = new["covariance"][ni].astype(np.float64), new["z"][ni].astype(np.float64)
+    ov, oe = old["covariance"][oi].astype(np.float64), old["z"][oi].astype(np.float64)
+    f = new[ni].copy()
+    with np.errstate(all="ignore"):
+        nv2, ov2 = nv * nv, ov * ov
+        f["z"] = (((nv2 * oe) + ((ov2 * ne) / ov2)) + nv2).astype(F32)
+        f["covariance"] = (((ov2 * nv2) / ov2) + nv2).astype(F32)
+    new[ni] = f
+    old[oi] = f
+    stack[k] = new
+    stack[i] = old
+    return int(ni.size)
+
+
 def loop_closure(stack: list, n_opt: int, transforms, centres, radius: float = 25.0, resolution: float = 0.0,
-                 map_resolution: float = None) -> int:
+                 map_resolution: float = None, fast: bool = False) -> int:
     """updateGlobalMap's body; transforms M[row][col] per submap (entry 0 ignored).  Returns the fused count."""
     n = min(n_opt, len(stack))
     res = float(resolution) if resolution > 0 else float(F32(map_resolution))
@@ -113,7 +154,7 @@ def loop_closure(stack: list, n_opt: int, transforms, centres, radius: float = 2
         lst = neighbours(centres, n, i, radius)
         if len(lst) > 2:
             for k in lst[1:]:
-                fused += pair_step(stack, i, k, res)
+                fused += (pair_step_fast if fast else pair_step)(stack, i, k, res)
     return fused
 
 

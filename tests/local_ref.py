@@ -1,7 +1,14 @@
 """numpy / dict restatement of the rolling-window local map (ElevationMapping::updateLocalMap, EMg.cpp:609-767; visualPointMap,
 :520-530), the semantics include/gem_hip.h pins for gem_local_*.  Driven from OracleMap.show()'s `visual` output and its geometry;
 the local map is a Python dict keyed by the float pair ((float) x, (float) y): `del d[k]; d[k] = v` is the reference's erase +
-insert, and the dict's order is the device's export order (last write).  Python floats compare -0.0 == 0.0 and hash them alike."""
+insert, and the dict's order is the device's export order (last write).  Python floats compare -0.0 == 0.0 and hash them alike.
+
+The reference hashes GridPoint by its bit pattern, so under libstdc++ -0.0 and +0.0 would be two keys there; the device (local_key)
+and this restatement take them as one.  A capture's positions are never -0.0, so no result depends on it.
+
+spill() / export() over a dict are the definition.  LocalMap + spill_fast() are the same map on arrays (the key as its float bits,
+-0.0 as +0.0; the positions of a capture are finite), fast enough for node-sized maps; tests/test_vectorised_refs_cpu.py pins the two
+forms to identical bytes."""
 import numpy as np
 
 # PointXYZRGBICT (include/gem/gem.hpp:40)
@@ -82,3 +89,44 @@ def spill(prev: Capture, current_position, position_shift, local: dict):
 def export(local: dict) -> np.ndarray:
     """localHashtoPointCloud (EMg.cpp:1124-1140) in the device's order: last write."""
     return np.frombuffer(b"".join(local.values()), POINT).copy() if local else np.zeros(0, POINT)
+
+
+def key_bits(x, y) -> np.ndarray:
+    """the key of (x, y) as local_key builds it: x's float bits | y's << 32, -0.0 taken as +0.0"""
+    x = np.where(np.asarray(x, np.float32) == 0, np.float32(0), x).astype(np.float32)
+    y = np.where(np.asarray(y, np.float32) == 0, np.float32(0), y).astype(np.float32)
+    return x.view(np.uint32).astype(np.uint64) | (y.view(np.uint32).astype(np.uint64) << np.uint64(32))
+
+
+class LocalMap:
+    """The local map of spill() on arrays: the live records in last-write order and their keys."""
+
+    def __init__(self):
+        self.rec, self.key = np.zeros(0, POINT), np.zeros(0, np.uint64)
+
+    def __len__(self):
+        return int(self.key.size)
+
+    def clear(self):
+        self.__init__()
+
+
+def spill_fast(prev: Capture, current_position, position_shift, local: LocalMap):
+    """spill() on a LocalMap: the last record of a key within the spill is its write, every key the spill writes moves to the end in
+    the order of those last records, and the replaced count is the records minus the keys the map did not hold."""
+    out = prev.rec[spill_mask(prev, current_position, position_shift)].copy()
+    n = out.size
+    if n == 0:
+        return out, 0
+    k = key_bits(out["x"], out["y"])
+    uniq, first_rev = np.unique(k[::-1], return_index=True)               # first in reverse = last in order
+    last = np.sort(n - 1 - first_rev)
+    added = int(np.count_nonzero(~np.isin(uniq, local.key, assume_unique=True)))
+    stay = ~np.isin(local.key, uniq, assume_unique=True)
+    local.rec = np.concatenate([local.rec[stay], out[last]])
+    local.key = np.concatenate([local.key[stay], k[last]])
+    return out, n - added
+
+
+def export_fast(local: LocalMap) -> np.ndarray:
+    return local.rec.copy()

@@ -1091,16 +1091,17 @@ def test_stream_of_sorted_passes_whose_walks_the_next_call_launches(oracle_mod, 
     """Device clouds through the OVERLAPPED sorted pipeline call after call with nothing read in between: every call sorts, leaves its
     walk to its successor and launches its predecessor's -- clouds of different sizes, single clouds and batches, a variance increment,
     a small sweep that takes the tile pipeline, a move, and a host array (never deferred) in between; the map is compared at the end
-    and once in the middle.  The same with the deferral switched off must give the same map."""
+    and once in the middle.  The same with walk_always_wait (every walk left behind waits for its sort's event on the stream, even
+    when the host has seen the sort complete: flush_walk), and with the deferral switched off, must give the same map."""
     import torch
     wl = synth.config_c4(n_sweeps=8)
     knobs = dict(ElevationMap.base_debug or {}); knobs.update({"overlap_min_points": 1})
     if "sort_form" not in knobs:
         knobs.update({"sort_min_points": 20000, "sort_form": form})
     maps = []
-    for defer in (1, 0):
+    for defer, always_wait in ((1, 0), (1, 1), (0, 0)):
         gpu, ref = make_pair(oracle_mod, wl.length, wl.resolution)
-        for k, v in dict(knobs, defer_walk=defer).items():
+        for k, v in dict(knobs, defer_walk=defer, walk_always_wait=always_wait).items():
             gpu.debug_set(k, v)
         d = [torch.from_numpy(c).to("cuda:0") for c in wl.clouds]
         sizes = [131072, 60000, 131072, 25000, 131072, 9000, 131072, 100001]
@@ -1125,6 +1126,9 @@ def test_stream_of_sorted_passes_whose_walks_the_next_call_launches(oracle_mod, 
                 assert_maps_match(gpu, ref)
         assert_maps_match(gpu, ref)
         maps.append((gpu.layer("elevation"), gpu.layer("variance"), gpu.debug_get("walks_left")))
+        if always_wait:
+            assert gpu.debug_get("walks_unwaited") == 0
         gpu.close()
-    assert np.array_equal(maps[0][0], maps[1][0]) and np.array_equal(maps[0][1], maps[1][1])
-    assert maps[0][2] >= 4 and maps[1][2] == 0                           # (walks were left to later calls; switched off: none)
+    for m in maps[1:]:
+        assert np.array_equal(maps[0][0], m[0]) and np.array_equal(maps[0][1], m[1])
+    assert maps[0][2] >= 4 and maps[1][2] >= 4 and maps[2][2] == 0       # (walks were left to later calls; switched off: none)
