@@ -18,6 +18,7 @@ LAYER_ELEVATION, LAYER_VARIANCE, LAYER_INTENSITY, LAYER_TRAVER, LAYER_LOWEST, \
 LAYOUT_STORAGE_ROWMAJOR, LAYOUT_GRIDMAP_COLMAJOR_NAN = 0, 1
 MODEL_LASER, MODEL_STRUCTURED_LIGHT, MODEL_STEREO, MODEL_PERFECT = range(4)
 CLEAN_NONE, CLEAN_REMOVE_NAN, CLEAN_PASSTHROUGH_Z = range(3)
+COMPOSE_SQRT_DOUBLE = 1
 VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTENSITY = range(5)
 
 
@@ -31,6 +32,11 @@ class VoxelParams(C.Structure):
     """gem_voxel_params: one pcl::VoxelGrid stage."""
     _fields_ = [("leaf", c_float * 3), ("field", c_int), ("limit_min", c_double), ("limit_max", c_double),
                 ("limit_negative", c_int), ("reserved", c_int)]
+
+
+class ComposeParams(C.Structure):
+    """gem_compose_params: the outlier filter and split of gem_local_compose."""
+    _fields_ = [("mean_k", c_int), ("stddev_mul", c_double), ("travers_threshold", c_double), ("flags", c_int)]
 
 
 class RejectFilter(C.Structure):
@@ -121,6 +127,8 @@ SIGNATURES = {
     "gem_local_spill": (c_int, [c_void_p, POINTER(c_float), POINTER(c_float), c_void_p, POINTER(c_int), POINTER(c_int)]),
     "gem_local_export": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_longlong), c_int]),
     "gem_local_size": (c_int, [c_void_p, POINTER(c_longlong)]),
+    "gem_local_compose": (c_int, [c_void_p, POINTER(ComposeParams), c_void_p, c_void_p, POINTER(c_int), POINTER(c_double)]),
+    "gem_local_compose_distances": (c_int, [c_void_p, POINTER(ComposeParams), c_void_p, POINTER(c_int)]),
     "gem_global_enable": (c_int, [c_void_p, c_longlong]),
     "gem_global_push_local": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "gem_global_push": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_int)]),

@@ -709,6 +709,35 @@ class ElevationMap:
         self._check(self._lib.gem_local_size(self._h, C.byref(n)), "gem_local_size")
         return int(n.value)
 
+    # -- composingGlobalMap's filter and split (pointCloudtoOctomap, EMg.cpp:1146-1170) on the previous capture -----------------
+    @staticmethod
+    def _compose_params(mean_k, stddev_mul, travers_threshold, sqrt_double):
+        return _lib.ComposeParams(int(mean_k), float(stddev_mul), float(travers_threshold), _lib.COMPOSE_SQRT_DOUBLE if sqrt_double else 0)
+
+    def local_compose(self, mean_k: int = 20, stddev_mul: float = 1.0, travers_threshold: float = 0.0, sqrt_double: bool = False,
+                      want_road: bool = True, want_obstacle: bool = True):
+        """StatisticalOutlierRemoval(mean_k, stddev_mul) on the previous capture's grid cloud, then the split by travers
+        (gem_local_compose): returns (road, obstacle, removed, threshold); a list that was not asked for comes back as its count."""
+        p = self._compose_params(mean_k, stddev_mul, travers_threshold, sqrt_double)
+        cells = self.length * self.length
+        road = np.empty(cells, POINT_DTYPE) if want_road else None
+        obst = np.empty(cells, POINT_DTYPE) if want_obstacle else None
+        counts, thr = (C.c_int * 3)(), C.c_double()
+        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.gem_local_compose(self._h, C.byref(p), vp(road), vp(obst), counts, C.byref(thr)), "gem_local_compose")
+        return (road[:counts[0]].copy() if want_road else int(counts[0]), obst[:counts[1]].copy() if want_obstacle else int(counts[1]),
+                int(counts[2]), float(thr.value))
+
+    def local_compose_distances(self, mean_k: int = 20, stddev_mul: float = 1.0, travers_threshold: float = 0.0,
+                                sqrt_double: bool = False) -> np.ndarray:
+        """The filter's mean neighbour distance of every point of the previous capture, in grid-cloud order."""
+        p = self._compose_params(mean_k, stddev_mul, travers_threshold, sqrt_double)
+        out = np.empty(self.length * self.length, np.float32)
+        n = C.c_int()
+        self._check(self._lib.gem_local_compose_distances(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p), C.byref(n)),
+                    "gem_local_compose_distances")
+        return out[:n.value].copy()
+
     # -- the submap stack (globalMap_: updateLocalMap's new-keyframe branch, EMg.cpp:630-687; updateGlobalMap, :773-905) ----------
     def global_enable(self, capacity: int = 1 << 20) -> None:
         """Switch the device submap stack on, empty, with room for `capacity` records (it grows on demand); 0 switches it off and

@@ -1096,6 +1096,8 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "xfer_download_wait_ns") *out = h->xfer_ns[3];
     else if (k == "xfer_download_memcpy_ns") *out = h->xfer_ns[4];
     else if (k == "sort_fallbacks") *out = h->sort_fallbacks;
+    else if (k == "compose_far_points") *out = h->compose.far_points;
+    else if (k == "compose_sum_ns") *out = h->compose.sum_ns;
     else if (k == "walks_unwaited") *out = h->walks_unwaited;
     else if (k == "walks_left") *out = h->walks_left;
     else if (k == "step_pending") *out = h->step.valid ? 1 : 0;

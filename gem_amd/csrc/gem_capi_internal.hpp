@@ -258,6 +258,17 @@ struct gem_handle {
         Arena small;                    // device words: capture counts [2] | spill total | export total | new keys
         long long log_cap = 0, log_len = 0, table_cap = 0, live = 0;
     } local;
+    // composingGlobalMap's outlier filter and road / obstacle split on the previous capture (gem_local_compose*, gem_capi_compose.cpp;
+    // kernels in gem_compose.hip): part of the local map, freed with it
+    struct Compose {
+        Arena grid, dist, far;          // [cells] record index per unwrapped cell | mean neighbour distance per record | the far list
+        Arena road, obstacle;           // [cells] records each: the two compactions
+        Arena cnt;                      // per-workgroup counts of the three classes
+        Arena small;                    // device words: far count | totals [3]
+        std::vector<float> host_dist;   // the distances on the host: the ordered double sums of the threshold are taken there
+        long long far_points = 0;       // records the last call left to k_compose_knn_far (gem_debug_get "compose_far_points")
+        long long sum_ns = 0;           // host time the last call spent on the ordered double sums ("compose_sum_ns")
+    } compose;
     // the submap stack of updateGlobalMap (gem_global_*, gem_capi_global.cpp; kernels in gem_global.hip)
     struct Global {
         bool enabled = false;
@@ -364,6 +375,7 @@ void local_free(gem_handle* h);                 // gem_capi_local.cpp: the local
 // the local map's export followed by that capture's grid cloud written to dst (device), the map emptied afterwards with clear
 int local_grid_count(gem_handle* h, uint32_t* n);
 int local_export_to(gem_handle* h, void* dst, uint32_t n_grid, bool clear);
+void compose_free(gem_handle* h);               // gem_capi_compose.cpp: the compose arenas (local_free)
 void global_free(gem_handle* h);                // gem_capi_global.cpp: the submap stack's arenas (gem_destroy, gem_global_enable(0))
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);

@@ -89,6 +89,7 @@ void local_free(gem_handle* h)
         a->p = nullptr; a->cap = 0;
     }
     lc = gem_handle::Local{};
+    compose_free(h);
 }
 
 int local_grid_count(gem_handle* h, uint32_t* n)

@@ -411,10 +411,35 @@ public:
         map_.check(gem_local_size(map_.handle(), &n), "gem_local_size");
         return n;
     }
+    // pointCloudtoOctomap(gridMaptoPointCloud(prevMap_)) up to the octree insertion (ElevationMapping.cpp:1146-1170), on the capture
+    // keepPrevious() kept: StatisticalOutlierRemoval(meanK, stddevMul), then the survivors with travers > traversThreshold (road) and
+    // the others (obstacle), both in cloud order.  gem_hip.h states the filter and what of it is not verified against PCL.
+    struct Composed {
+        std::vector<PointXYZRGBICT> road, obstacle;
+        int removed = 0;            // points the filter removed
+        double threshold = 0.0;     // its distance threshold
+    };
+    Composed compose(int meanK = 20, double stddevMul = 1.0, double traversThreshold = 0.0, bool sqrtDouble = false)
+    {
+        // The library wants room for L * L records per list.  That room is kept between calls (one composing thread per LocalMap),
+        // so a call neither allocates nor clears 2 * L * L records; only the records that came back are copied out.
+        if (road_.size() < cells()) { road_.resize(cells()); obstacle_.resize(cells()); }
+        gem_compose_params p{};
+        p.mean_k = meanK; p.stddev_mul = stddevMul; p.travers_threshold = traversThreshold;
+        p.flags = sqrtDouble ? GEM_COMPOSE_SQRT_DOUBLE : 0;
+        int counts[3] = {0, 0, 0};
+        Composed c;
+        map_.check(gem_local_compose(map_.handle(), &p, road_.data(), obstacle_.data(), counts, &c.threshold), "gem_local_compose");
+        c.road.assign(road_.begin(), road_.begin() + counts[0]);
+        c.obstacle.assign(obstacle_.begin(), obstacle_.begin() + counts[1]);
+        c.removed = counts[2];
+        return c;
+    }
 
 private:
     size_t cells() const { const size_t L = static_cast<size_t>(map_.length()); return L * L; }
     ElevationMap& map_;
+    std::vector<PointXYZRGBICT> road_, obstacle_;      // compose()'s landing room, L * L records each once it has been called
 };
 
 // ---------------------------------------------------------------------------------------------

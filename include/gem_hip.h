@@ -442,6 +442,49 @@ int  gem_local_spill(gem_handle* h, const float current_position[2], const float
 int  gem_local_export(gem_handle* h, void* points, long long max_points, long long* out_count, int clear);
 int  gem_local_size(gem_handle* h, long long* out_count);
 
+/* ---- composingGlobalMap without the host filter (EMg.cpp:482-514; pointCloudtoOctomap, :1146-1170) ------------------------------
+ *   gem_local_compose            what pointCloudtoOctomap does to gridMaptoPointCloud(prevMap_) before the octree insertion, on the
+ *                                PREVIOUS capture (gem_local_keep_previous): pcl::StatisticalOutlierRemoval<Anypoint> with
+ *                                setMeanK(mean_k), setStddevMulThresh(stddev_mul), then the split of the survivors by travers.
+ *   gem_local_compose_distances  the filter's per-point mean neighbour distances of the same cloud, in grid-cloud order.
+ * PCL is not part of this library; the filter is RESTATED here from PCL >= 1.10 filters/impl/statistical_outlier_removal.hpp and
+ * FLANN's L2_Simple<float> (tests/compose_ref.py is the same statement in numpy):
+ *   input      the n records of the previous capture in its order (= gem_local_grid_cloud of that capture); the coordinates are the
+ *              records' float x, y, z.  Elevation is assumed finite.
+ *   d2         for point i and every point j, i included: d2 = ((dx*dx) + (dy*dy)) + (dz*dz), every operation rounded in float, no FMA.
+ *   distance   point i's d2 values sorted ascending, the first mean_k + 1 taken (entry 0 is the query or a coincident point: 0 either
+ *              way).  double dist_sum = 0; for k = 1 .. mean_k in that order dist_sum += s(d2[k]); distance[i] = (float)(dist_sum /
+ *              mean_k).  Equal values give the same sum whichever point supplied them, so no tie rule is needed and the result does
+ *              not depend on a search structure's traversal order.
+ *   s()        flags = 0: (double)sqrtf(d2), the float overload;  GEM_COMPOSE_SQRT_DOUBLE: sqrt((double)d2).  Both correctly rounded.
+ *   threshold  double sum = 0, sq_sum = 0; for i = 0 .. n-1 IN ORDER: sum += distance[i]; sq_sum += distance[i] * distance[i], the
+ *              product a FLOAT product, widened when it is added.  mean = sum / n; variance = (sq_sum - sum * sum / n) / (n - 1);
+ *              threshold = mean + stddev_mul * sqrt(variance), all in double.
+ *   filter     point i survives iff (double)distance[i] <= threshold; survivors keep their order.
+ *   split      a survivor with (double)travers > travers_threshold goes to road; otherwise one with (double)travers <=
+ *              travers_threshold (so: travers not NaN) goes to obstacle.  Both lists in survivor order, the records copied unchanged.
+ *              A capture holds no NaN travers, so road + obstacle + removed = n.
+ *   n <= mean_k  the reference reads past the end of its search result (undefined).  Here nothing is removed, every distance and the
+ *              threshold are +inf; n = 0 gives three zero counts.  A deliberate difference, like pad / a in the records.
+ * NOT verified against PCL (there is none here; tools/ros_selfcheck.cpp's `sor` row settles them in a ROS workspace): (1) which
+ * overload PCL's unqualified sqrt(nn_dists[k]) resolves to -- hence the flag; (2) that the product in sq_sum is a float product;
+ * (3) a NaN threshold (a variance rounded below zero: every distance equal) removes every point under the `<=` statement above.
+ * road, obstacle: L * L records each, host memory, either may be NULL (counted only).  out_counts[3]: road points, obstacle points,
+ * points the filter removed.  out_threshold may be NULL.  distances: L * L floats, may be NULL.  The octree insertion itself
+ * (updateNode / integrateNodeColor) and the flags preMapAvail and globalMap_.size() >= 1 stay with the caller.  The calls take the
+ * handle's lock like every other entry: the composing thread may call them while the callback thread runs the frame loop.
+ * GEM_ERR_INVALID, nothing changed: the local map is not enabled, no gem_local_keep_previous yet, a handle with a communicator, p
+ * NULL, mean_k outside 1 .. 32, stddev_mul not finite. */
+#define GEM_COMPOSE_SQRT_DOUBLE 1
+typedef struct gem_compose_params {
+    int    mean_k;            /* setMeanK; the node uses 20.  1 <= mean_k <= 32 */
+    double stddev_mul;        /* setStddevMulThresh; the node uses 1.0 */
+    double travers_threshold; /* traversThre (a double parameter of the node, default 0.0) */
+    int    flags;             /* GEM_COMPOSE_SQRT_DOUBLE or 0 */
+} gem_compose_params;
+int  gem_local_compose(gem_handle* h, const gem_compose_params* p, void* road, void* obstacle, int out_counts[3], double* out_threshold);
+int  gem_local_compose_distances(gem_handle* h, const gem_compose_params* p, float* distances, int* out_count);
+
 /* ---- the submap stack (globalMap_: the new-keyframe branch of updateLocalMap, EMg.cpp:630-687; updateGlobalMap, :773-905) -------
  *   gem_global_enable          capacity > 0: switch the stack on, empty, with room for `capacity` records (it grows on demand); on an
  *                              enabled handle it starts over.  0: switch it off and free its memory.

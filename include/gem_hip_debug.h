@@ -47,6 +47,9 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            "xfer_upload_memcpy_ns", "xfer_upload_enqueue_ns", "xfer_download_enqueue_ns", "xfer_download_wait_ns", "xfer_download_memcpy_ns"
  *            (host time spent so far moving caller-owned host arrays: bench.py's node_host_arrays),
  *            "sort_fallbacks" (passes whose forced sorted form / pass count did not fit the map and took the other form),
+ *            "compose_far_points" (records the last gem_local_compose / gem_local_compose_distances left to k_compose_knn_far: the LDS
+ *            tile's halo could not close their neighbour search; 0 after a call on n <= mean_k records),
+ *            "compose_sum_ns" (host nanoseconds that call spent on the ordered double sums of the threshold),
  *            "walks_left" (walks of the sorted pipeline left to the next call) and "walks_unwaited" (those of them launched without a stream wait: their sort had completed),
  *            "step_pending" (1: the second half of a gem_add_sharded_device step is still to come),
  *            "step_exchange_ns", "step_walk_ns", "step_publish_ns", "step_gather_ns", "step_exchange_to_walk_ns": device time stamps of

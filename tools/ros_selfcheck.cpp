@@ -11,6 +11,11 @@
 //                    form of PCL >= 1.10 on x86-64) and KdTreeFLANN<PointXY>::radiusSearch (d2 < r2 strictly, sorted by d2, ties by
 //                    index) as updateGlobalMap calls them (reference: elevation_mapping/src/ElevationMapping.cpp:790-840);
 //                    tests/global_ref.py restates the same contract in numpy
+//   sor gem_local_compose restates pcl::StatisticalOutlierRemoval<Anypoint> (setMeanK(20), setStddevMulThresh(1.0)) as
+//                    pointCloudtoOctomap runs it on the grid cloud of prevMap_ (reference: elevation_mapping/src/ElevationMapping.cpp:
+//                    1146-1156); tests/compose_ref.py restates the same contract in numpy.  Two details of that statement are decided
+//                    by this row and by nothing else: which sqrt overload PCL's `sqrt(nn_dists[k])` resolves to (the row prints which
+//                    value of gem_compose_params::flags matches) and that the product in sq_sum is a float product
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -19,13 +24,17 @@
 // The voxel row is bit for bit in the output order, the count and every voxel of one or two points; in voxels of three or more points
 // it allows a few ulps, because PCL's std::sort is not stable and may sum such a voxel in another order than input order.
 //
-//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8 pcl_kdtree-1.8) \
+//   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) \
 //       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Lgem_amd/lib -lgem_hip -Wl,-rpath,$PWD/gem_amd/lib -L/opt/rocm/lib -lamdhip64 \
-//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
+//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, OpenCV or PCL there).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
+// The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
+// the vox and glob rows now instantiate VoxelGrid, transformPointCloud and KdTreeFLANN from PCL's headers as well, instead of linking
+// the precompiled instantiations they used before: the same templates, compiled here.
+#define PCL_NO_PRECOMPILE
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -47,12 +56,24 @@
 #include <pcl/filters/voxel_grid.h>
 #include <pcl/common/transforms.h>
 #include <pcl/kdtree/kdtree_flann.h>
+#include <pcl/filters/statistical_outlier_removal.h>
+#include <pcl/search/kdtree.h>
 #include <pcl/point_types.h>
 
 #include <limits>
 #include <map>
 
 #include "gem_hip.h"
+
+// the sor row's point: the fields of the library's 32-byte record (PointXYZRGBICT) as a registered PCL point
+struct SorPoint {
+    PCL_ADD_POINT4D;
+    PCL_ADD_RGB;
+    float covariance, intensity, travers;
+    EIGEN_MAKE_ALIGNED_OPERATOR_NEW
+} EIGEN_ALIGN16;
+POINT_CLOUD_REGISTER_POINT_STRUCT(SorPoint, (float, x, x)(float, y, y)(float, z, z)(float, rgb, rgb)(float, covariance, covariance)
+                                            (float, intensity, intensity)(float, travers, travers))
 
 namespace {
 
@@ -452,6 +473,90 @@ int check_global(uint32_t seed)
     return 0;
 }
 
+// ---- sor -----------------------------------------------------------------------------------------------------------------------
+// A rough 128 x 128 map with holes and spikes, captured and kept as the previous capture.  Its grid cloud goes through the real
+// pcl::StatisticalOutlierRemoval (kept indices) and the real pcl::search::KdTree (the 21 nearest squared distances of every point,
+// summed here in both sqrt forms).  Against them: gem_local_compose_distances for flags 0 and GEM_COMPOSE_SQRT_DOUBLE (every
+// distance, bit for bit), and the kept set each flag value gives (distance <= threshold) against PCL's kept indices.  The row passes
+// when the distances of both forms agree with the search and at least one flag value reproduces PCL's kept indices; it prints which.
+int check_sor(uint32_t seed)
+{
+    const int L = 128, K = 20;
+    gem_map_config cfg{};
+    cfg.length = L; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    std::mt19937 rng(seed);
+    std::normal_distribution<float> rough(0.0f, 0.08f);
+    std::uniform_real_distribution<float> u(0.0f, 1.0f);
+    std::vector<float> elev(L * L), trav(L * L);
+    for (int i = 0; i < L * L; ++i) {
+        elev[i] = rough(rng);
+        if (u(rng) < 0.002f) elev[i] += 1.5f;
+        if (u(rng) < 0.1f) elev[i] = -10.0f;
+        trav[i] = u(rng) - 0.2f;
+    }
+    CHECK_GEM(gem_set_layer(h, GEM_LAYER_ELEVATION, elev.data()));
+    CHECK_GEM(gem_set_layer(h, GEM_LAYER_TRAVER, trav.data()));
+    CHECK_GEM(gem_local_enable(h, 1024));
+    CHECK_GEM(gem_local_capture(h, 0.0, 0.0, nullptr));
+    CHECK_GEM(gem_local_keep_previous(h));
+    std::vector<Rec> grid(L * L);
+    int n = 0;
+    CHECK_GEM(gem_local_grid_cloud(h, grid.data(), &n));
+    pcl::PointCloud<SorPoint>::Ptr cloud(new pcl::PointCloud<SorPoint>);
+    cloud->resize(n);
+    for (int i = 0; i < n; ++i) {
+        SorPoint& p = (*cloud)[i];
+        p.x = grid[i].x; p.y = grid[i].y; p.z = grid[i].z; p.travers = grid[i].travers;
+    }
+    cloud->is_dense = true;
+    pcl::StatisticalOutlierRemoval<SorPoint> sor;
+    sor.setInputCloud(cloud);
+    sor.setMeanK(K);
+    sor.setStddevMulThresh(1.0);
+    std::vector<int> kept;
+    sor.filter(kept);
+    // the search itself, summed in both forms
+    pcl::search::KdTree<SorPoint> tree;
+    tree.setInputCloud(cloud);
+    std::vector<float> want[2] = {std::vector<float>(n), std::vector<float>(n)};
+    std::vector<int> nn(K + 1);
+    std::vector<float> d2(K + 1);
+    for (int i = 0; i < n; ++i) {
+        if (tree.nearestKSearch((*cloud)[i], K + 1, nn, d2) != K + 1) { std::fprintf(stderr, "sor: point %d: fewer than %d neighbours\n", i, K + 1); return 2; }
+        double sf = 0.0, sd = 0.0;
+        for (int k = 1; k <= K; ++k) { sf += (double)sqrtf(d2[k]); sd += std::sqrt((double)d2[k]); }
+        want[0][i] = (float)(sf / K); want[1][i] = (float)(sd / K);
+    }
+    bool matches[2] = {false, false};
+    for (int f = 0; f < 2; ++f) {
+        gem_compose_params p{};
+        p.mean_k = K; p.stddev_mul = 1.0; p.travers_threshold = 0.0; p.flags = f ? GEM_COMPOSE_SQRT_DOUBLE : 0;
+        std::vector<float> dist(L * L);
+        int m = 0, counts[3] = {0, 0, 0};
+        double thr = 0.0;
+        CHECK_GEM(gem_local_compose_distances(h, &p, dist.data(), &m));
+        CHECK_GEM(gem_local_compose(h, &p, nullptr, nullptr, counts, &thr));
+        if (m != n) { std::fprintf(stderr, "sor: flags %d: %d distances for %d points\n", f, m, n); ++g_failures; continue; }
+        for (int i = 0; i < n; ++i)
+            if (std::memcmp(&dist[i], &want[f][i], 4) != 0) {
+                std::fprintf(stderr, "sor: flags %d point %d: search gives %a, device %a\n", f, i, want[f][i], dist[i]);
+                ++g_failures;
+                break;
+            }
+        std::vector<int> dev_kept;
+        for (int i = 0; i < n; ++i) if ((double)dist[i] <= thr) dev_kept.push_back(i);
+        if ((int)dev_kept.size() != counts[0] + counts[1]) { std::fprintf(stderr, "sor: flags %d: kept %zu, road + obstacle %d\n", f, dev_kept.size(), counts[0] + counts[1]); ++g_failures; }
+        matches[f] = dev_kept == kept;
+        std::printf("sor: flags = %d (%s): threshold %.17g, kept %zu of %d, pcl kept %zu: %s\n", f, f ? "sqrt((double)d2)" : "(double)sqrtf(d2)", thr,
+                    dev_kept.size(), n, kept.size(), matches[f] ? "the kept indices MATCH" : "the kept indices differ");
+    }
+    if (!matches[0] && !matches[1]) { std::fprintf(stderr, "sor: neither value of flags reproduces StatisticalOutlierRemoval's kept indices\n"); ++g_failures; }
+    gem_destroy(h);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -461,8 +566,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_colorize(seed + 1u);
     if (rc == 0) rc = check_voxel(seed + 2u);
     if (rc == 0) rc = check_global(seed + 3u);
+    if (rc == 0) rc = check_sor(seed + 4u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all four rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all five rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
     return 0;
 }
