@@ -113,7 +113,7 @@ int gem_local_compose(gem_handle* h, const gem_compose_params* p, void* road, vo
     auto& cp = h->compose;
     const size_t cells = (size_t)h->cells;
     if ((rc = ensure(h, cp.road, cells * kRec)) || (rc = ensure(h, cp.obstacle, cells * kRec)) ||
-        (rc = ensure(h, cp.cnt, (size_t)local_blocks(h->cells) * 3 * 4 + 64))) return rc;
+        (rc = ensure(h, cp.cnt, (size_t)compact_blocks(h->cells) * 3 * 4 + 64))) return rc;
     uint32_t n = 0;
     double thr = 0.0;
     int filter = 0;

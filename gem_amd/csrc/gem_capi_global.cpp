@@ -197,7 +197,7 @@ int gem_global_loop_closure(gem_handle* h, int n_opt, const float* transforms, c
     for (int side = 0; side < 2; ++side) {
         if ((rc = ensure(h, g.out[side], (size_t)maxb * kRec)) || (rc = ensure(h, g.keys[side], (size_t)maxb * 8)) ||
             (rc = ensure(h, g.tkeys[side], (size_t)tcap * 8)) || (rc = ensure(h, g.tvals[side], (size_t)tcap * 4)) ||
-            (rc = ensure(h, g.blk[side], (size_t)global_blocks(maxb) * 4 + 64))) return rc;
+            (rc = ensure(h, g.blk[side], (size_t)compact_blocks(maxb) * 4 + 64))) return rc;
     }
     std::vector<uint32_t> cnt(std::max(n, 1));
     for (int s = 0; s < n; ++s) cnt[s] = (uint32_t)g.cnt[s];

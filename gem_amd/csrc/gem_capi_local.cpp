@@ -63,7 +63,7 @@ int size_logs(gem_handle* h, long long cap)
     auto& lc = h->local;
     int rc;
     if ((rc = ensure(h, lc.log[0], (size_t)cap * kRec)) || (rc = ensure(h, lc.log[1], (size_t)cap * kRec))) return rc;
-    if ((rc = ensure(h, lc.exp_cnt, (size_t)local_blocks(cap) * 4 + 64))) return rc;
+    if ((rc = ensure(h, lc.exp_cnt, (size_t)compact_blocks(cap) * 4 + 64))) return rc;
     lc.log_cap = std::max(lc.log_cap, cap);
     return GEM_OK;
 }
@@ -143,7 +143,7 @@ int gem_local_enable(gem_handle* h, long long capacity)
     auto& lc = h->local;
     int rc;
     if ((rc = ensure(h, lc.small, 64))) return rc;
-    if ((rc = ensure(h, lc.spill_cnt, (size_t)local_blocks(h->cells) * 4 + 64))) return rc;
+    if ((rc = ensure(h, lc.spill_cnt, (size_t)compact_blocks(h->cells) * 4 + 64))) return rc;
     lc.cur = lc.prev = -1;
     lc.log_len = lc.live = 0;
     if ((rc = size_logs(h, std::max(lc.log_cap, capacity)))) return rc;
@@ -247,7 +247,7 @@ int gem_local_spill(gem_handle* h, const float current_position[2], const float 
         const long long need = lc.live + n;
         const long long cap = need > lc.log_cap / 2 ? std::max(2 * lc.log_cap, 2 * need) : lc.log_cap;
         if ((rc = ensure(h, lc.log[1 - lc.act], (size_t)cap * kRec))) return rc;
-        if ((rc = ensure(h, lc.exp_cnt, (size_t)local_blocks(std::max(cap, lc.log_len)) * 4 + 64))) return rc;
+        if ((rc = ensure(h, lc.exp_cnt, (size_t)compact_blocks(std::max(cap, lc.log_len)) * 4 + 64))) return rc;
         LocalExportArgs e{log_at(h, lc.act), lc.log_len, table_of(h), log_at(h, 1 - lc.act)};
         GEM_HIP(h, launch_local_export(h->stream, e, static_cast<uint32_t*>(lc.exp_cnt.p), small_word(h, kWordExport)));
         lc.act = 1 - lc.act;

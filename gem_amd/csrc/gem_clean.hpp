@@ -1,18 +1,15 @@
 // gem_clean.hpp -- cleanPointCloud on the device (internal header): argument block and host launchers of gem_clean.hip.
-//   stable stream compaction of a raw cloud (count per block -> one-workgroup scan -> scatter, three launches, no workgroup ever
-//   waits for another) and the masking pass of the fuse path (dropped points get NaN x, y, z; in place behind k_unpack_aos for AoS).
+//   stable stream compaction of a raw cloud (gem_compact.hpp) and the masking pass of the fuse path (dropped points get NaN x, y, z;
+//   in place behind k_unpack_aos for AoS).
 #pragma once
 
 #include "../../include/gem_hip.h"
+#include "gem_compact.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace gem {
-
-constexpr int kCleanThreads = 256;                          // one workgroup = 4 waves
-constexpr int kCleanItems = 4;                              // points per thread
-constexpr int kCleanTile = kCleanThreads * kCleanItems;     // points per workgroup (1024)
 
 struct CleanArgs {
     long long n;
@@ -25,12 +22,11 @@ struct CleanArgs {
     float4* xyzi_out; uint32_t* rgb_out;
     float* x_out; float* y_out; float* z_out;
     int* orig_out;
-    uint32_t* block_cnt;               // [clean_blocks(n)] scratch: kept points per workgroup, then their exclusive prefix
+    uint32_t* block_cnt;               // [compact_blocks(n)] scratch: kept points per workgroup, then their exclusive prefix
     int* count_out;                    // kept points (device)
 };
 
-inline long long clean_blocks(long long n) { return n > 0 ? (n + kCleanTile - 1) / kCleanTile : 0; }
-inline size_t clean_scratch_bytes(long long n) { return (size_t)clean_blocks(n) * sizeof(uint32_t) + 64; }
+inline size_t clean_scratch_bytes(long long n) { return (size_t)compact_blocks(n) * sizeof(uint32_t) + 64; }
 
 // the three kernels of one compaction on `st`; n == 0 only writes *count_out = 0
 hipError_t launch_clean(hipStream_t st, const CleanArgs& a, bool soa);

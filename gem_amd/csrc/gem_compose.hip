@@ -22,7 +22,6 @@
 // steps whose dz dominates, the map's rim -- are listed, and k_compose_knn_far walks global memory for them from ring 0, at most L
 // rings (ring L - 1 covers the whole map from any cell).  Every record gets its exact distance.
 #include "gem_compose.hpp"
-#include "gem_wave.hpp"
 
 #include <math.h>
 
@@ -193,89 +192,16 @@ __device__ __forceinline__ int compose_class(const ComposeSplitArgs& a, size_t i
     return t > a.travers_threshold ? 0 : (t <= a.travers_threshold ? 1 : 3);
 }
 
-__global__ __launch_bounds__(kLocalThreads) void k_compose_count(ComposeSplitArgs a, uint32_t nb, uint32_t* __restrict__ block_cnt)
-{
-    constexpr int NW = kLocalThreads / 64;
-    __shared__ uint32_t s_w[3 * NW];
-    const size_t base = (size_t)blockIdx.x * kLocalTile, n = *a.count;
-    uint32_t c[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < kLocalItems; ++k) {
-        const size_t i = base + (size_t)k * kLocalThreads + threadIdx.x;
-        const int cls = i < n ? compose_class(a, i) : 3;
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c[j] += (uint32_t)__popcll(__ballot(cls == j));
-    }
-    if (lane_id() == 0) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) s_w[j * NW + (threadIdx.x >> 6)] = c[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        uint32_t t = 0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) t += s_w[threadIdx.x * NW + w];
-        block_cnt[(size_t)threadIdx.x * nb + blockIdx.x] = t;
-    }
-}
-
-// workgroup j scans the counts of class j
-__global__ __launch_bounds__(1024) void k_compose_scan(uint32_t* __restrict__ cnt_all, int nb, uint32_t* __restrict__ totals)
-{
-    __shared__ uint32_t s[16];
-    uint32_t* cnt = cnt_all + (size_t)blockIdx.x * nb;
-    uint32_t carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += 1024) {                                 // workgroup-uniform trip count
-        const int i = b0 + (int)threadIdx.x;
-        const uint32_t v = i < nb ? cnt[i] : 0u;
-        uint32_t tot;
-        const uint32_t ex = block_exclusive_scan<1024>(v, s, &tot);
-        if (i < nb) cnt[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
-}
-
-__global__ __launch_bounds__(kLocalThreads) void k_compose_scatter(ComposeSplitArgs a, uint32_t nb, const uint32_t* __restrict__ block_off)
-{
-    constexpr int NW = kLocalThreads / 64;
-    __shared__ uint32_t s_cnt[2 * kLocalItems * NW];
-    const size_t base = (size_t)blockIdx.x * kLocalTile, n = *a.count;
-    const int w = (int)(threadIdx.x >> 6);
-    uint64_t m[2][kLocalItems];
-#pragma unroll
-    for (int k = 0; k < kLocalItems; ++k) {
-        const size_t i = base + (size_t)k * kLocalThreads + threadIdx.x;
-        const int cls = i < n ? compose_class(a, i) : 3;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            m[j][k] = __ballot(cls == j);
-            if (lane_id() == 0) s_cnt[(j * kLocalItems + k) * NW + w] = (uint32_t)__popcll(m[j][k]);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        LocalRecord* out = j == 0 ? a.road : a.obstacle;
-        if (!out) continue;                                                  // workgroup-uniform
-        uint32_t run = block_off[(size_t)j * nb + blockIdx.x];              // class-j items of the workgroups before this one
-#pragma unroll
-        for (int k = 0; k < kLocalItems; ++k) {
-            uint32_t before = 0, total = 0;
-#pragma unroll
-            for (int ww = 0; ww < NW; ++ww) {
-                const uint32_t cw = s_cnt[(j * kLocalItems + k) * NW + ww];
-                before += ww < w ? cw : 0u;
-                total += cw;
-            }
-            if ((m[j][k] >> lane_id()) & 1ull) {
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[j][k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[j][k], 0u));
-                out[(size_t)run + before + rank] = a.rec[base + (size_t)k * kLocalThreads + threadIdx.x];
-            }
-            run += total;
-        }
-    }
-}
+// one compaction (gem_compact.hpp) over three counted classes; road and obstacle are written, each only where it has somewhere to go
+struct ComposeSplit : CompactSrc {
+    static constexpr int kCounted = 3, kWritten = 2;
+    ComposeSplitArgs a;
+    __device__ LocalRecord* out(int j) const { return j == 0 ? a.road : a.obstacle; }
+    __device__ size_t size() const { return (size_t)*a.count; }
+    __device__ int cls(size_t i, Item) const { return compose_class(a, i); }
+    __device__ bool writes(int j) const { return out(j) != nullptr; }
+    __device__ bool emit(int j, size_t i, Item, size_t o) const { out(j)[o] = a.rec[i]; return false; }
+};
 
 hipError_t launch_compose_knn(hipStream_t st, const ComposeKnnArgs& a, uint32_t n)
 {
@@ -298,12 +224,7 @@ hipError_t launch_compose_knn(hipStream_t st, const ComposeKnnArgs& a, uint32_t 
 
 hipError_t launch_compose_split(hipStream_t st, const ComposeSplitArgs& a, uint32_t n, uint32_t* block_cnt, uint32_t* totals)
 {
-    const unsigned nb = local_blocks(n);
-    if (nb == 0) return hipMemsetAsync(totals, 0, 3 * sizeof(uint32_t), st);
-    hipLaunchKernelGGL(k_compose_count, dim3(nb), dim3(kLocalThreads), 0, st, a, nb, block_cnt);
-    hipLaunchKernelGGL(k_compose_scan, dim3(3), dim3(1024), 0, st, block_cnt, (int)nb, totals);
-    if (a.road || a.obstacle) hipLaunchKernelGGL(k_compose_scatter, dim3(nb), dim3(kLocalThreads), 0, st, a, nb, block_cnt);
-    return hipGetLastError();
+    return compact(st, ComposeSplit{{}, a}, n, block_cnt, totals, true, a.road || a.obstacle);
 }
 
 } // namespace gem

@@ -6,8 +6,7 @@
 //   knn_far  the far list, finished exactly by a ring walk over global memory
 //   (the ordered double sums of the threshold are taken on the host, from the downloaded distances: DESIGN.md has what the device
 //   forms cost)
-//   split    one stable compaction over three classes (road, obstacle, removed; only the first two are written): count per workgroup
-//            -> scan -> scatter, as gem_local.hip
+//   split    one stable compaction (gem_compact.hpp) over three classes: road, obstacle, removed; only the first two are written
 #pragma once
 
 #include "gem_local.hpp"
@@ -36,7 +35,7 @@ struct ComposeSplitArgs {
 };
 
 hipError_t launch_compose_knn(hipStream_t st, const ComposeKnnArgs& a, uint32_t n);
-// block_cnt: [3 * local_blocks(n)] scratch; totals[3]: road, obstacle, removed
+// block_cnt: [3 * compact_blocks(n)] scratch; totals[3]: road, obstacle, removed
 hipError_t launch_compose_split(hipStream_t st, const ComposeSplitArgs& a, uint32_t n, uint32_t* block_cnt, uint32_t* totals);
 
 } // namespace gem

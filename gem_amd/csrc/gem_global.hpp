@@ -3,7 +3,7 @@
 //   keys       pointCloudtoHash's key of every record of a submap, the first record of a key claimed in a LocalTable (atomicMin)
 //   side       stable compaction of one side of a pair step: the first record of every key, NaN keys all kept, each written as
 //              localHashtoPointCloud writes its entry, fused with the other side's first record where the match test holds
-// The compaction is three launches (count per workgroup -> one-workgroup scan -> scatter), gem_clean.hip's form.
+// The compaction is gem_compact.hpp's.
 #pragma once
 
 #include "gem_local.hpp"
@@ -12,12 +12,6 @@
 #include <stdint.h>
 
 namespace gem {
-
-constexpr int kGlobalThreads = 256;                         // one workgroup = 4 waves
-constexpr int kGlobalItems = 4;                             // items per thread
-constexpr int kGlobalTile = kGlobalThreads * kGlobalItems;  // items per workgroup (1024)
-
-inline unsigned global_blocks(long long n) { return n > 0 ? (unsigned)((n + kGlobalTile - 1) / kGlobalTile) : 0u; }
 
 struct GlobalXform { float m[16]; };                        // column-major, as Eigen::Matrix4f::data()
 
@@ -38,7 +32,7 @@ struct GlobalSideArgs {
 hipError_t launch_global_transform(hipStream_t st, LocalRecord* rec, long long n, const GlobalXform& m);
 // table slots [cap] cleared, then the keys of cloud c (at most `bound` records) computed and inserted; res = the quantum (double)
 hipError_t launch_global_keys(hipStream_t st, const GlobalCloud& c, long long bound, double res);
-// block_cnt: [global_blocks(bound)] scratch; *total: records written (device)
+// block_cnt: [compact_blocks(bound)] scratch; *total: records written (device)
 hipError_t launch_global_side(hipStream_t st, const GlobalSideArgs& a, long long bound, uint32_t* block_cnt, uint32_t* total);
 
 } // namespace gem

@@ -3,9 +3,10 @@
 //   spill    the L-shaped band of the previous capture that left the window (EMg.cpp:715-764), appended to the local map's log
 //   insert   upsert of log entries into the open-addressing table (key -> log position, the larger position wins)
 //   export   stable compaction of the live log entries (an entry is live while the table points at it)
-// Every compaction is three launches (count per workgroup -> one-workgroup scan -> scatter), as in gem_clean.hip.
+// Every compaction is gem_compact.hpp's.
 #pragma once
 
+#include "gem_compact.hpp"
 #include "gem_kernels.hpp"
 
 #include <hip/hip_runtime.h>
@@ -13,9 +14,6 @@
 
 namespace gem {
 
-constexpr int kLocalThreads = 256;                          // one workgroup = 4 waves
-constexpr int kLocalItems = 4;                              // items per thread
-constexpr int kLocalTile = kLocalThreads * kLocalItems;     // items per workgroup (1024)
 constexpr unsigned long long kLocalEmpty = ~0ull;           // empty table slot: the bits of the key (NaN, NaN), never a finite position
 
 // PointXYZRGBICT (include/gem/gem.hpp): x, y, z, pad | b, g, r, a | covariance, intensity, travers
@@ -56,8 +54,6 @@ struct LocalExportArgs {
     LocalTable t;
     LocalRecord* out;
 };
-
-inline unsigned local_blocks(long long n) { return n > 0 ? (unsigned)((n + kLocalTile - 1) / kLocalTile) : 0u; }
 
 // The table's device side, shared by the local map (gem_local.hip) and the submap stack (gem_global.hip).
 __device__ __forceinline__ unsigned long long local_key(float x, float y)
@@ -108,7 +104,7 @@ __device__ __forceinline__ bool local_upsert(const LocalTable& t, unsigned long 
     return added;
 }
 
-// block_cnt: [local_blocks(n)] scratch; *total: kept items (device)
+// block_cnt: [compact_blocks(n)] scratch; *total: kept items (device)
 hipError_t launch_local_capture(hipStream_t st, const LocalCaptureArgs& a, uint32_t* block_cnt, uint32_t* total);
 hipError_t launch_local_spill(hipStream_t st, const LocalSpillArgs& a, long long bound, uint32_t* block_cnt, uint32_t* total, bool scatter);
 hipError_t launch_local_export(hipStream_t st, const LocalExportArgs& a, uint32_t* block_cnt, uint32_t* total);

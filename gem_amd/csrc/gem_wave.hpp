@@ -17,6 +17,12 @@ __device__ __forceinline__ uint64_t lanemask_lt()
     return l == 0 ? 0ull : (~0ull >> (64 - l));
 }
 
+// lanes of ballot mask m below this one: the rank of a kept lane among the wave's kept lanes
+__device__ __forceinline__ uint32_t wave_rank(uint64_t m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // Wave-wide inclusive scans on the DPP network (row_shr within rows of 16 lanes, then row_bcast
 // across rows): six VALU instructions instead of six LDS-crossbar permutes.
 #define GEM_DPP(old, src, ctrl, rowmask) \

@@ -1,14 +1,14 @@
 """The device local map (gem_local_*) and submap stack (gem_global_*) at the sizes a node runs them at, and on the edges the CPU tests
 pin only on the restatement, bit for bit against tests/local_ref.py / tests/global_ref.py (their array forms at node sizes):
 
-  1. L = 1025 with every cell set: the capture, spill and export compactions over more than 2^20 items (two trips of k_local_scan),
+  1. L = 1025 with every cell set: the capture, spill and export compactions over more than 2^20 items (two trips of compact_scan),
      from local_enable(16) (one spill grows the log past twice its capacity), a diagonal move and an axis move with dx == 0 exactly,
      the second spill compacting and growing a log of ~460 000 live entries and rebuilding the table;
   2. a back-and-forth trajectory: the log is compacted without growing, spills and export stay exact through it (export order after
      rewritten keys), and a second identical loop allocates nothing;
   3. the CPU-pinned edges on the device: two cells sharing one float key far from the origin within one spill, negative and NaN
      traversability, export order after a reinsert;
-  4. submaps of 1.1-1.3 M records (k_global_keys past 2^20 records, k_global_scan for five trips), one of a million records in 8 keys
+  4. submaps of 1.1-1.3 M records (k_global_keys past 2^20 records, compact_scan for two trips), one of a million records in 8 keys
      (atomicMin contention across every workgroup), one of 2^20 records each its own key (the table at its designed half load);
   5. neighbour lists with exact distance ties, a centre exactly at the radius, lists of 2 and 3 entries, coincident centres (the
      k == i step) and n_opt above the stack size;

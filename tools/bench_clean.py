@@ -9,7 +9,8 @@
   add_raw        a structured-light frame shaped like C3 (the 640 x 480 depth image organised, NaN where no ray hit, d435 cutoffs
                  0.2 / 3.25 m): add_raw of the raw cloud against add of the same cloud cleaned beforehand (with its kept indices), host
                  arrays and device tensors, milliseconds per frame.  The maps of the two are checked to be bit-identical.
-bench.py stays the contract line (C2); kernel times of the three compaction kernels come from rocprofv3 --kernel-trace --stats.
+bench.py stays the contract line (C2); kernel times of the three compaction kernels (gem_compact.hpp over CleanSrc) come from
+rocprofv3 --kernel-trace --stats.
 """
 from __future__ import annotations
 
