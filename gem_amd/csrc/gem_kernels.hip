@@ -1676,6 +1676,8 @@ __device__ __forceinline__ JacobiOut jacobi_3x3(float a00, float a11, float a22,
     return JacobiOut{a00, a11, a22, v20, v21, v22};
 }
 
+// SMALL: maps of at most 8 cells a side (below the staging tile, down to L = 1), whose halo wraps more than once.
+template <bool SMALL>
 __global__ __launch_bounds__(256) void k_map_feature(const float* __restrict__ elevation, float* __restrict__ traver,
                                                      float* __restrict__ rough, float* __restrict__ slope,
                                                      int L, float res, int sx, int sy, int row0, int row1)
@@ -1688,10 +1690,18 @@ __global__ __launch_bounds__(256) void k_map_feature(const float* __restrict__ e
     const int tiles = (L + 15) >> 4;
     const int tr_ = (int)blockIdx.x / tiles, tc_ = (int)blockIdx.x - tr_ * tiles;
     const int R0 = tr_ << 4, C0 = tc_ << 4;
+    // (R0 - 2 + i runs from -2 to R0 + 17, and R0 <= L - 1 is a multiple of 16: on a map of more than 8 cells a side that lies in
+    //  [-L, 2 L) and one wrap brings it into [0, L); SMALL maps -- down to L = 1, where -2 is below -L -- take a true modulo)
     for (int t = (int)threadIdx.x; t < 400; t += 256) {
         const int i = t / 20, j = t - i * 20;
-        int px = R0 - 2 + i; px = px < 0 ? px + L : (px >= L ? px - L : px); px = px >= L ? px - L : px;
-        int py = C0 - 2 + j; py = py < 0 ? py + L : (py >= L ? py - L : py); py = py >= L ? py - L : py;
+        int px = R0 - 2 + i, py = C0 - 2 + j;
+        if (!SMALL) {
+            px = px < 0 ? px + L : (px >= L ? px - L : px);
+            py = py < 0 ? py + L : (py >= L ? py - L : py);
+        } else {
+            px %= L; px = px < 0 ? px + L : px;
+            py %= L; py = py < 0 ? py + L : py;
+        }
         zt[t] = elevation[px * L + py];
     }
     if (threadIdx.x == 0) jn = 0u;
@@ -1714,6 +1724,8 @@ __global__ __launch_bounds__(256) void k_map_feature(const float* __restrict__ e
         for (int k = 0; k < 5; ++k) {
             const int ex = gx + k - 2, ey = gy + k - 2;
             rv[k] = ex >= 0 && ex < L; cv[k] = ey >= 0 && ey < L;
+            // (one wrap is enough wherever rv / cv hold: |k - 2| <= min(2, L - 1) there, so the coordinate lies in [-L, 2 L);
+            //  the others are never read)
             int px = cell_x + k - 2; px = px < 0 ? px + L : (px >= L ? px - L : px);
             int py = cell_y + k - 2; py = py < 0 ? py + L : (py >= L ? py - L : py);
             xs[k] = (float)px * res; ys[k] = (float)py * res;
@@ -2204,7 +2216,8 @@ hipError_t launch_map_feature(hipStream_t st, const float* elevation, float* tra
                               int L, float res, int sx, int sy, int row0, int row1)
 {
     const int tiles = (L + 15) / 16;
-    hipLaunchKernelGGL(k_map_feature, dim3(tiles * tiles), dim3(256), 0, st, elevation, traver, rough, slope, L, res, sx, sy, row0, row1);
+    if (L > 8) hipLaunchKernelGGL(k_map_feature<false>, dim3(tiles * tiles), dim3(256), 0, st, elevation, traver, rough, slope, L, res, sx, sy, row0, row1);
+    else       hipLaunchKernelGGL(k_map_feature<true>, dim3(1), dim3(256), 0, st, elevation, traver, rough, slope, L, res, sx, sy, row0, row1);
     return hipGetLastError();
 }
 

@@ -126,6 +126,21 @@ void gemo_map_closeloop(gemo_map* m, const float update_position[2], float heigh
  * roughness, slope and traversability; updates m->traver like map_traver.  Outputs may be NULL. */
 void gemo_map_feature(gemo_map* m, float* rough, float* slope, float* traver_out);
 
+/* Test switches of gemo_map_feature.  Both are process-wide state and NOT thread-safe; with both off (the default) the
+ * results are those of the plain oracle, bit for bit.
+ *  - trig_nudge: the only licensed difference between the oracle and the HIP kernel is that a double sin / cos / atan2 /
+ *    acos of two libms may round to adjacent floats.  With one_in > 0 each of the four wrappers moves its rounded float
+ *    result to the next float up or the next float down, each with probability 1 / one_in, from a generator seeded
+ *    here; one_in = 0 restores the plain oracle.  acos(1) and acos(0), exact / one constant in every libm and all that a
+ *    cell without rotations reaches, are left alone.  Running the oracle both ways measures what that licence is worth.
+ *  - rotation_layer: a caller-owned L*L byte array that every later gemo_map_feature call fills with the number of
+ *    Jacobi rotations (nCount, 0 .. 31) each fitted cell took, 255 for cells without a fit; NULL turns it off.
+ *  - jacobi_rotations: computerEigenvalue on a copy of one row-major 3x3 matrix (dbEps 0.01, nJt 30): returns nCount,
+ *    normal (may be NULL) receives the eigenvector of the smallest eigenvalue. */
+void gemo_feature_trig_nudge(unsigned long long seed, int one_in);
+void gemo_feature_rotation_layer(unsigned char* layer);
+int  gemo_jacobi_rotations(const float matrix[9], float normal[3]);
+
 /* RMU.cpp:42-145 restated with plain arrays: returns the scalar var_update handed to Mapvar_update.
  * pose: position[3] + rotation matrix R_IB row-major[9]; cov: 6x6 row-major; state carries the
  * previous pose / previous reduced covariance exactly like the class members. */

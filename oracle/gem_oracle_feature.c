@@ -15,13 +15,42 @@
 
 #include <math.h>
 
-static float f_sin(float x)            { return (float)sin((double)x); }
-static float f_cos(float x)            { return (float)cos((double)x); }
-static float f_atan2(float y, float x) { return (float)atan2((double)y, (double)x); }
-static float f_acos(float x)           { return (float)acos((double)x); }
+/* Test switches (gem_oracle.h): both are process-wide state, NOT thread-safe.  With g_nudge_one_in == 0 and no rotation
+ * layer the code below is the plain oracle, bit for bit. */
+static unsigned g_nudge_one_in = 0;
+static unsigned long long g_nudge_state = 0;
+static unsigned char* g_rot_layer = 0;
+
+void gemo_feature_trig_nudge(unsigned long long seed, int one_in)
+{
+    g_nudge_one_in = one_in > 0 ? (unsigned)one_in : 0u;
+    g_nudge_state = seed * 2862933555777941757ULL + 3037000493ULL;
+}
+
+void gemo_feature_rotation_layer(unsigned char* layer) { g_rot_layer = layer; }
+
+/* the licence between two correctly working libms: the double result may round to either neighbouring float */
+static float nudge(float r)
+{
+    if (!g_nudge_one_in) return r;
+    g_nudge_state = g_nudge_state * 6364136223846793005ULL + 1442695040888963407ULL;      /* Knuth's MMIX LCG, high bits */
+    const unsigned k = (unsigned)(g_nudge_state >> 33) % (2u * g_nudge_one_in);
+    if (k == 0) return nextafterf(r, INFINITY);
+    if (k == 1) return nextafterf(r, -INFINITY);
+    return r;
+}
+
+static float f_sin(float x)            { return nudge((float)sin((double)x)); }
+static float f_cos(float x)            { return nudge((float)cos((double)x)); }
+static float f_atan2(float y, float x) { return nudge((float)atan2((double)y, (double)x)); }
+/* acos(1) = 0 is exact and acos(0) is one constant, far from a float rounding boundary, in every libm: cells whose loop does not
+ * rotate (eigenvectors = the axes) reach only these two and carry no licence.  A rotating cell whose |n_z| rounds to exactly
+ * 1.0f is exempt with them (the kernel returns 0 there without calling acos): the measured licence of a near-flat scene is
+ * that much narrower, never wider. */
+static float f_acos(float x)           { const float r = (float)acos((double)x); return (x == 1.0f || x == 0.0f) ? r : nudge(r); }
 
 /* GPU:66-187 */
-static void computer_eigenvalue(float* pMatrix, int nDim, float* maxvector, float dbEps, int nJt)
+static int computer_eigenvalue(float* pMatrix, int nDim, float* maxvector, float dbEps, int nJt)
 {
     float pdblVects[9];
     float pdbEigenValues[3];
@@ -84,6 +113,16 @@ static void computer_eigenvalue(float* pMatrix, int nDim, float* maxvector, floa
         else if (minEigenvalue > pdbEigenValues[i]) { minEigenvalue = pdbEigenValues[i]; min_id = i; }
     }
     for (int i = 0; i < nDim; i++) maxvector[i] = pdblVects[min_id + nDim * i];   /* GPU:183-186 */
+    return nCount;
+}
+
+int gemo_jacobi_rotations(const float matrix[9], float normal[3])
+{
+    float m[9], n[3];
+    for (int i = 0; i < 9; i++) m[i] = matrix[i];
+    const int count = computer_eigenvalue(m, 3, n, (float)0.01, 30);
+    if (normal) for (int i = 0; i < 3; i++) normal[i] = n[i];
+    return count;
 }
 
 /* GPU:549-670.  rough / slope / traver_out: L*L arrays or NULL.  m->traver is updated like map_traver.
@@ -95,6 +134,7 @@ void gemo_map_feature(gemo_map* m, float* rough, float* slope, float* traver_out
     const float Resolution = m->res;
     for (int idx = 0; idx < Length * Length; ++idx) {
         float r_out = 0.0f, s_out = 0.0f;
+        if (g_rot_layer) g_rot_layer[idx] = 255;
         if (m->elevation[idx] != -10.0f) {
             float px[25], py[25], pz[25];
             float px_mean = 0, py_mean = 0, pz_mean = 0;
@@ -131,7 +171,8 @@ void gemo_map_feature(gemo_map* m, float* rough, float* slope, float* traver_out
                     pMatrix[3] = pMatrix[1]; pMatrix[6] = pMatrix[2]; pMatrix[7] = pMatrix[5];
                 }
                 float normal_vec[3];
-                computer_eigenvalue(pMatrix, 3, normal_vec, (float)0.01, 30);     /* GPU:637-642 */
+                const int rotations = computer_eigenvalue(pMatrix, 3, normal_vec, (float)0.01, 30);     /* GPU:637-642 */
+                if (g_rot_layer) g_rot_layer[idx] = (unsigned char)rotations;
                 const float height = m->elevation[idx], smooth_height = pz_mean;
                 float Slope = normal_vec[2] > 0 ? f_acos(normal_vec[2]) : f_acos(-normal_vec[2]);   /* GPU:647-650 */
                 float Rough = fabsf(height - smooth_height);

@@ -66,6 +66,9 @@ def lib() -> C.CDLL:
         l.gemo_fuse_literal.argtypes = [POINTER(OMap), c_int] + [c_void_p] * 7
         l.gemo_mapvar_update.argtypes = [POINTER(OMap), c_float]
         l.gemo_map_feature.argtypes = [POINTER(OMap), c_void_p, c_void_p, c_void_p]
+        l.gemo_feature_trig_nudge.argtypes = [C.c_ulonglong, c_int]
+        l.gemo_feature_rotation_layer.argtypes = [c_void_p]
+        l.gemo_jacobi_rotations.restype = c_int; l.gemo_jacobi_rotations.argtypes = [c_void_p, c_void_p]
         l.gemo_map_optmove.argtypes = [POINTER(OMap), POINTER(c_float), c_float, POINTER(c_float)]
         l.gemo_map_closeloop.argtypes = [POINTER(OMap), POINTER(c_float), c_float]
         l.gemo_raytracing.argtypes = [POINTER(OMap)]
@@ -201,12 +204,28 @@ class OracleMap:
     def set_obstacle_threshold(self, t: float):
         self._l.gemo_set_obstacle_threshold(self._m, c_float(t))
 
-    def map_feature(self):
-        """G_Mapfeature (gpu_process.cu:549-670): returns dict(rough, slope, traver) and updates the traver layer."""
+    def map_feature(self, nudge=None):
+        """G_Mapfeature (gpu_process.cu:549-670): returns dict(rough, slope, traver) and updates the traver layer.
+        nudge = (seed, one_in): run with gemo_feature_trig_nudge on (each trig result moved one float up / down with probability
+        1 / one_in each); the plain oracle otherwise.  The rotation count of every cell is kept for feature_rotations()."""
         n = self.length * self.length
         out = {k: np.zeros(n, np.float32) for k in ("rough", "slope", "traver")}
-        self._l.gemo_map_feature(self._m, _vp(out["rough"]), _vp(out["slope"]), _vp(out["traver"]))
+        self._rotations = np.full(n, 255, np.uint8)
+        self._l.gemo_feature_rotation_layer(_vp(self._rotations))
+        if nudge is not None:
+            self._l.gemo_feature_trig_nudge(int(nudge[0]), int(nudge[1]))
+        try:
+            self._l.gemo_map_feature(self._m, _vp(out["rough"]), _vp(out["slope"]), _vp(out["traver"]))
+        finally:
+            self._l.gemo_feature_trig_nudge(0, 0)
+            self._l.gemo_feature_rotation_layer(None)
         return {k: v.reshape(self.length, self.length) for k, v in out.items()}
+
+    def feature_rotations(self) -> np.ndarray:
+        """[L, L] uint8: Jacobi rotations (nCount) of every fitted cell in the last map_feature call, 255 where nothing was fitted."""
+        if getattr(self, "_rotations", None) is None:
+            raise RuntimeError("feature_rotations() before the first map_feature()")
+        return self._rotations.reshape(self.length, self.length).copy()
 
     def show(self, rough=None, slope=None, map_length=None, resolution=None, position=None):
         """ElevationMap::show's cell loop (ElevationMap.cpp:85-149): dict(visual [9, L, L] column-major layers with NaN, points_xyz,
@@ -259,6 +278,13 @@ def colorize(P, image_bgr, xyzi):
     rgb = np.zeros(pts.shape[0], np.uint32)
     n = lib().gemo_colorize(_vp(P), img.shape[1], img.shape[0], _vp(img), img.strides[0], pts.shape[0], _vp(pts), _vp(rgb))
     return {"rgb": rgb, "xyzi": pts, "image": img, "count": n}
+
+
+def jacobi_rotations(matrix):
+    """computerEigenvalue on one 3x3 matrix: (nCount, eigenvector of the smallest eigenvalue)."""
+    a = np.ascontiguousarray(matrix, np.float32).reshape(9)
+    n = np.zeros(3, np.float32)
+    return int(lib().gemo_jacobi_rotations(_vp(a), _vp(n))), n
 
 
 class OracleMotion:

@@ -11,18 +11,13 @@ last-bit difference near n_z = 1 (slope ~ sqrt(2 (1 - n_z))), hence the absolute
 import numpy as np
 import pytest
 
+import feature_scenes as fs
+
 F32 = np.float32
-SLOPE_ABS, ROUGH_ABS, TRAVER_ABS = 2e-3, 1e-6, 2e-3
+SLOPE_ABS, ROUGH_ABS, TRAVER_ABS = fs.SLOPE_ABS, 1e-6, 2e-3
 
 
-def terrain(L, res, seed=0, amp=0.4):
-    rng = np.random.default_rng(seed)
-    x, y = np.meshgrid(np.arange(L) * res, np.arange(L) * res, indexing="ij")
-    z = 0.6 * x + 0.15 * y + amp * np.sin(2 * np.pi * x / (9 * res)) * np.cos(2 * np.pi * y / (7 * res)) + rng.normal(0, 0.01, (L, L))
-    z[rng.random((L, L)) < 0.15] = -10.0          # holes
-    z[:, L // 2: L // 2 + 3] = -10.0             # a gap wider than the 5x5 window's reach on one side
-    z[L // 3: L // 3 + 1, :] += 0.5              # a step
-    return z.astype(F32)
+terrain = fs.terrain          # slope + waves + noise, 15 % holes, a gap wider than the window's reach on one side, a step
 
 
 # ---- oracle known answers (CPU) -----------------------------------------------------------------------------------------
@@ -72,6 +67,82 @@ def test_neighbourhood_bounds_follow_the_unrolled_index(oracle_mod):
     assert np.all(f["slope"] == 0)
 
 
+# ---- the oracle's test switches: trig nudge and rotation counter (CPU) ------------------------------------------------------------
+def test_nudge_moves_only_the_slopes_of_rotating_cells(oracle_mod):
+    L, res = 64, 0.1
+    m = oracle_mod.OracleMap(L, res)
+    z = fs.terrain(L, res, 1); z[40:60, 5:25] = 0.75                  # a flat patch: cells that do not rotate
+    m.set_layer("elevation", z)
+    plain = m.map_feature(); rot = m.feature_rotations()
+    again = m.map_feature()                                            # the switch is off again after every call
+    nudged = m.map_feature(nudge=(7, 3))
+    after = m.map_feature()
+    for k in ("rough", "slope", "traver"):
+        assert np.array_equal(again[k], plain[k]) and np.array_equal(after[k], plain[k]), k
+    assert np.array_equal(nudged["rough"], plain["rough"])
+    still = rot == 0
+    assert still.sum() > 200 and np.array_equal(nudged["slope"][still], plain["slope"][still])
+    assert np.array_equal(nudged["traver"][still], plain["traver"][still])
+    moved = nudged["slope"] != plain["slope"]
+    assert moved.any() and not moved[rot == 255].any()
+    assert np.array_equal(m.feature_rotations() == 255, plain["traver"] == -10)
+    assert np.array_equal(m.map_feature(nudge=(7, 3))["slope"], nudged["slope"])            # seeded: repeatable
+    assert not np.array_equal(m.map_feature(nudge=(8, 3))["slope"], nudged["slope"])
+
+
+def test_rotation_counter_follows_the_pivot_scan(oracle_mod):
+    def sym(a00, a11, a22, a01, a02, a12):
+        return np.array([[a00, a01, a02], [a01, a11, a12], [a02, a12, a22]], F32)
+    cases = {
+        "diagonal": (sym(2, 1, 0.5, 0, 0, 0), 0, None),
+        "below dbEps": (sym(2, 1, 0.5, 0, 0.0099, 0), 0, None),
+        "at dbEps": (sym(2, 1, 0.5, 0, 0.01, 0), None, (0, 2)),       # 0.01f < 0.01f is false: it rotates
+        "negative a01 wins": (sym(2, 1, 0.5, -0.4, 0.3, 0.2), None, (0, 1)),     # the signed start value loses to its own magnitude
+        "positive a01 ties a02": (sym(2, 1, 0.5, 0.25, 0.25, 0.1), None, (0, 1)),  # strict >: the first of two equals stays
+        "negative a01 ties a02": (sym(2, 1, 0.5, -0.25, 0.25, 0.1), None, (0, 1)),
+        "a02 ties a12": (sym(2, 1, 0.5, 0, 0.25, -0.25), None, (0, 2)),
+    }
+    for name, (m, count, first) in cases.items():
+        assert fs.pivot_replay(m) == first, name
+        c, normal = oracle_mod.jacobi_rotations(m)
+        rc, pivots, rnormal = fs.jacobi_replay(m)
+        assert c == rc and np.array_equal(normal, rnormal), name
+        assert (pivots[0] if pivots else None) == first, name
+        if count is not None:
+            assert c == count, name
+        else:
+            assert 1 <= c <= 31, name
+    # the replay notices a restated scan: with >= the tie goes to the later entry and the result changes
+    for name in ("positive a01 ties a02", "a02 ties a12"):
+        m = cases[name][0]
+        assert fs.jacobi_replay(m, strict=False)[1][0] != fs.jacobi_replay(m)[1][0], name
+    # ... and the layer of gemo_map_feature holds the same counts: a cell's covariance, replayed
+    L, res = 16, 0.125
+    z = fs._tie_holes(fs._plane(L, res, 1, -1).astype(F32))
+    om = oracle_mod.OracleMap(L, res); om.set_layer("elevation", z); om.map_feature()
+    rot = om.feature_rotations()
+    n, a = fs.covariance_replay(z, res)
+    for r in range(L):
+        for c in range(L):
+            if n[r, c] > 7 and z[r, c] != -10:
+                assert rot[r, c] == fs.jacobi_replay(sym(*a[r, c]))[0], (r, c)
+            else:
+                assert rot[r, c] == 255
+
+
+_SCENES = fs.all_scenes()
+
+
+@pytest.mark.parametrize("scene", _SCENES, ids=[s.name for s in _SCENES])
+def test_scene_reaches_what_it_was_written_for(oracle_mod, scene):
+    """The preconditions of the device tests' scenes (tests/test_map_feature_edges_gpu.py) need only the oracle: a scene that
+    stops covering its case fails here, without a GPU.  Every scene's oracle-derived bound stays within SLOPE_ABS."""
+    ev = fs.check_precondition(oracle_mod, scene)
+    assert ev.bound <= SLOPE_ABS, f"{scene.name}: bound {ev.bound:.3e}"
+    if ev.rotating.any() and scene.L > 2:
+        assert ev.bound > 0 or not np.isfinite(ev.out["slope"][ev.rotating]).any()      # the switch does something
+
+
 # ---- GPU parity -------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("L,res,seed", [(64, 0.1, 1), (75, 0.2, 2), (200, 0.05, 3)])
@@ -89,6 +160,11 @@ def test_map_feature_parity(oracle_mod, L, res, seed):
     assert np.max(np.abs(g["slope"] - o["slope"])) <= SLOPE_ABS
     assert np.max(np.abs(g["rough"] - o["rough"])) <= ROUGH_ABS
     assert np.max(np.abs(g["traver"] - o["traver"])) <= TRAVER_ABS
+    # roughness is |h - mean z|, no library call: bit-identical; and the device's traver follows, bit for bit, from the device's
+    # own slope and roughness, so a traver error can only come from a slope error
+    assert np.array_equal(g["rough"], o["rough"])
+    fitted = o["traver"] != -10
+    assert np.array_equal(g["traver"][fitted], fs.traver_from(g["slope"], g["rough"])[fitted])
     assert (o["slope"] > 0.05).mean() > 0.3                          # the Jacobi path is what is being compared
     # the layers are resident: traver / rough / slope can be fetched like any other layer
     assert np.array_equal(gpu.layer("traver"), g["traver"]) and np.array_equal(gpu.layer("slope"), g["slope"])
