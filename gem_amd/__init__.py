@@ -4,8 +4,8 @@ The product is libgem_hip.so (hand-written HIP kernels behind the C ABI of inclu
 this package holds its sources (csrc/), the in-tree build (build.py), the ctypes binding (_lib.py)
 and a Python mirror of the reference's host interface for that path (api.py).
 """
-from .api import (POINT_DTYPE, ElevationMap, Frame, GemError, RejectFilter, RobotMotionMapUpdater, SensorModel,  # noqa: F401
+from .api import (POINT_DTYPE, Costmap, ElevationMap, Frame, GemError, RejectFilter, RobotMotionMapUpdater, SensorModel,  # noqa: F401
                   SensorProcessor, VoxelStage)
 
-__all__ = ["POINT_DTYPE", "ElevationMap", "Frame", "GemError", "RejectFilter", "RobotMotionMapUpdater", "SensorModel",
+__all__ = ["POINT_DTYPE", "Costmap", "ElevationMap", "Frame", "GemError", "RejectFilter", "RobotMotionMapUpdater", "SensorModel",
            "SensorProcessor", "VoxelStage"]

@@ -19,6 +19,8 @@ LAYOUT_STORAGE_ROWMAJOR, LAYOUT_GRIDMAP_COLMAJOR_NAN = 0, 1
 MODEL_LASER, MODEL_STRUCTURED_LIGHT, MODEL_STEREO, MODEL_PERFECT = range(4)
 CLEAN_NONE, CLEAN_REMOVE_NAN, CLEAN_PASSTHROUGH_Z = range(3)
 COMPOSE_SQRT_DOUBLE = 1
+COST_FREE_SPACE, COST_LETHAL_OBSTACLE, COST_NO_INFORMATION = 0, 254, 255
+COSTMAP_OVERWRITE, COSTMAP_MAX = 0, 1
 VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTENSITY = range(5)
 
 
@@ -37,6 +39,12 @@ class VoxelParams(C.Structure):
 class ComposeParams(C.Structure):
     """gem_compose_params: the outlier filter and split of gem_local_compose."""
     _fields_ = [("mean_k", c_int), ("stddev_mul", c_double), ("travers_threshold", c_double), ("flags", c_int)]
+
+
+class CostmapConfig(C.Structure):
+    """gem_costmap_config: a costmap's geometry and the value of a cell nothing has written."""
+    _fields_ = [("size_x", C.c_uint), ("size_y", C.c_uint), ("resolution", c_double), ("origin_x", c_double), ("origin_y", c_double),
+                ("default_value", C.c_ubyte)]
 
 
 class RejectFilter(C.Structure):
@@ -135,6 +143,20 @@ SIGNATURES = {
     "gem_global_loop_closure": (c_int, [c_void_p, c_int, POINTER(c_float), POINTER(c_float), c_float, c_double, POINTER(c_longlong)]),
     "gem_global_export": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_longlong)]),
     "gem_global_count": (c_int, [c_void_p, POINTER(c_int)]),
+    "gem_costmap_create": (c_int, [c_void_p, POINTER(CostmapConfig), POINTER(c_int)]),
+    "gem_costmap_destroy": (c_int, [c_void_p, c_int]),
+    "gem_costmap_geometry": (c_int, [c_void_p, c_int, POINTER(CostmapConfig)]),
+    "gem_costmap_reset": (c_int, [c_void_p, c_int]),
+    "gem_costmap_update_origin": (c_int, [c_void_p, c_int, c_double, c_double]),
+    "gem_costmap_roll_to": (c_int, [c_void_p, c_int, c_double, c_double]),
+    "gem_costmap_mark_points": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_double, POINTER(c_double)]),
+    "gem_costmap_mark_points_device": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_double, POINTER(c_double)]),
+    "gem_costmap_mark_grid_cloud": (c_int, [c_void_p, c_int, c_double, POINTER(c_double)]),
+    "gem_costmap_mark_global": (c_int, [c_void_p, c_int, c_int, c_double, POINTER(c_double)]),
+    "gem_costmap_mark_visual": (c_int, [c_void_p, c_int, c_double, POINTER(c_double)]),
+    "gem_costmap_merge": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "gem_costmap_read": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
+    "gem_costmap_write": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
 }
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {

@@ -788,6 +788,13 @@ class ElevationMap:
         self._check(self._lib.gem_global_count(self._h, C.byref(n)), "gem_global_count")
         return int(n.value)
 
+    # -- the costmap layers (layers/: PointMapLayer, ElevationMapLayer) ------------------------------------------------------------
+    def costmap(self, size_x: int, size_y: int, resolution: float, origin_x: float = 0.0, origin_y: float = 0.0,
+                default_value: int = _lib.COST_NO_INFORMATION) -> "Costmap":
+        """A device-resident layer costmap bound to this map (gem_costmap_create): size in cells, the world position of cell (0, 0)'s
+        lower-left corner, and the value of a cell nothing has written (NO_INFORMATION, or FREE_SPACE without track_unknown_space)."""
+        return Costmap(self, size_x, size_y, resolution, origin_x, origin_y, default_value)
+
     # -- the step in front of the path: input colourisation (EMg.cpp:349-381) -------------------------------
     @staticmethod
     def lidar_to_image(tcamera, tlidar) -> np.ndarray:
@@ -955,6 +962,103 @@ class ElevationMap:
         a_base = None if bases is None else (C.c_uint32 * n)(*[int(b) for b in bases])
         vu = None if var_updates_global is None else (C.c_float * n_global_sweeps)(*[float(v) for v in var_updates_global])
         self._check(self._lib.gem_shard_fuse_device(self._h, n, a_hv, a_key, a_cnt, a_rng, a_base, int(n_global_sweeps), vu), "gem_shard_fuse_device")
+
+
+class Costmap:
+    """One costmap of an ElevationMap's handle (gem_costmap_*): the two layers' updateBounds bodies as marking passes, updateOrigin as
+    the rolling step, the two updateCosts rules and a window read-back.  A mark with bounds=None only enqueues; with bounds =
+    [min_x, min_y, max_x, max_y] it returns them merged with what it touched (touch() of costmap_2d)."""
+
+    def __init__(self, elevation_map: ElevationMap, size_x, size_y, resolution, origin_x=0.0, origin_y=0.0,
+                 default_value=_lib.COST_NO_INFORMATION):
+        self.map = elevation_map
+        cfg = _lib.CostmapConfig(int(size_x), int(size_y), float(resolution), float(origin_x), float(origin_y), int(default_value))
+        i = C.c_int(-1)
+        self.map._check(self.map._lib.gem_costmap_create(self.map._h, C.byref(cfg), C.byref(i)), "gem_costmap_create")
+        self.id = int(i.value)
+        self.size_x, self.size_y = int(size_x), int(size_y)
+
+    def close(self) -> None:
+        if self.id >= 0 and getattr(self.map, "_h", None):
+            self.map._check(self.map._lib.gem_costmap_destroy(self.map._h, self.id), "gem_costmap_destroy")
+        self.id = -1
+
+    def _call(self, name, *args):
+        self.map._check(getattr(self.map._lib, name)(self.map._h, self.id, *args), name)
+
+    @staticmethod
+    def _bounds(bounds):
+        return None if bounds is None else (C.c_double * 4)(*[float(v) for v in bounds])
+
+    def _mark(self, name, bounds, *args):
+        b = self._bounds(bounds)
+        self._call(name, *args, b)
+        return None if b is None else list(b)
+
+    def geometry(self) -> dict:
+        """size, resolution, the origin after rolling, default_value"""
+        c = _lib.CostmapConfig()
+        self._call("gem_costmap_geometry", C.byref(c))
+        return {"size_x": c.size_x, "size_y": c.size_y, "resolution": c.resolution, "origin_x": c.origin_x, "origin_y": c.origin_y,
+                "default_value": c.default_value}
+
+    def reset(self) -> None:
+        self._call("gem_costmap_reset")
+
+    def update_origin(self, new_origin_x: float, new_origin_y: float) -> None:
+        self._call("gem_costmap_update_origin", float(new_origin_x), float(new_origin_y))
+
+    def roll_to(self, robot_x: float, robot_y: float) -> None:
+        """updateOrigin(robot - sizeInMeters / 2): the rolling_window_ line of both layers"""
+        self._call("gem_costmap_roll_to", float(robot_x), float(robot_y))
+
+    def mark_points(self, points, travers_thresh: float = 0.5, bounds=None):
+        """PointMapLayer::updateBounds over POINT_DTYPE records: a host array, or a contiguous device tensor of 32-byte records
+        (uint8 [n, 32] or float32 [n, 8]), which is held until the map is synchronised."""
+        if _is_device_tensor(points):
+            if not points.is_contiguous() or points.numel() * points.element_size() % 32:
+                raise ValueError("points must be a contiguous device tensor of 32-byte records")
+            n = points.numel() * points.element_size() // 32
+            self.map._hold(points)
+            return self._mark("gem_costmap_mark_points_device", bounds, C.c_void_p(points.data_ptr()) if n else None, n, float(travers_thresh))
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        return self._mark("gem_costmap_mark_points", bounds, pts.ctypes.data_as(C.c_void_p) if pts.size else None, pts.shape[0],
+                          float(travers_thresh))
+
+    def mark_grid_cloud(self, travers_thresh: float = 0.5, bounds=None):
+        """... over the last capture's records (grid_pc) where they lie"""
+        return self._mark("gem_costmap_mark_grid_cloud", bounds, float(travers_thresh))
+
+    def mark_global(self, index: int = -1, travers_thresh: float = 0.5, bounds=None):
+        """... over submap `index` of the stack (-1: all of them, in stack order)"""
+        return self._mark("gem_costmap_mark_global", bounds, int(index), float(travers_thresh))
+
+    def mark_visual(self, travers_thresh: float = 0.5, bounds=None):
+        """ElevationMapLayer::updateBounds over the last capture standing for visualMap_"""
+        return self._mark("gem_costmap_mark_visual", bounds, float(travers_thresh))
+
+    def merge(self, master: "Costmap", window=None, mode: int = _lib.COSTMAP_OVERWRITE) -> None:
+        """updateCosts onto `master` inside window = (min_i, min_j, max_i, max_j) (None: the whole map): overwrite or max"""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        self._call("gem_costmap_merge", master.id, *w, int(mode))
+
+    def read(self, window=None, row_stride: int = 0) -> np.ndarray:
+        """The window's bytes as [rows, row_stride or width] (None: the whole map); columns beyond the width are left 0."""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        width, rows = w[2] - w[0], w[3] - w[1]
+        stride = max(int(row_stride), width, 0)
+        out = np.zeros((max(rows, 0), stride), np.uint8)
+        self._call("gem_costmap_read", *w, out.ctypes.data_as(C.c_void_p) if out.size else None, stride)
+        return out
+
+
+    def write(self, values, window=None) -> None:
+        """The window's cells from a uint8 [rows, width] array (None: the whole map): costs other layers left in a master."""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        v = np.ascontiguousarray(values, np.uint8)
+        if v.shape != (w[3] - w[1], w[2] - w[0]):
+            raise ValueError(f"expected a {(w[3] - w[1], w[2] - w[0])} array, got {v.shape}")
+        self._call("gem_costmap_write", *w, v.ctypes.data_as(C.c_void_p) if v.size else None, max(w[2] - w[0], 0))
 
 
 class RobotMotionMapUpdater:

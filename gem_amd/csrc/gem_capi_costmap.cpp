@@ -1,0 +1,370 @@
+// gem_capi_costmap.cpp -- the costmap-layer entry points of include/gem_hip.h (PointMapLayer and ElevationMapLayer of the
+// reference's layers/, with the pieces of costmap_2d they call restated there).  The kernels are in gem_costmap.hip.
+//
+// State (gem_handle::Costmaps):
+//   a costmap      two byte grids (a roll writes the other one and they swap) and a stamp word per cell, all-zero between calls
+//   small          the bounds words of a mark (four accumulated by the mark kernels, four published by the resolve pass)
+//   in, win        a host cloud of gem_costmap_mark_points on the device | the packed window of gem_costmap_read / _write
+// A mark is its mark launches followed by one resolve launch on the handle's stream; the inputs that already live on the device
+// (the capture, the submap stack) are read where they are, a capture's record count from its device word.  Every device buffer comes
+// from ensure(), so gem_debug_get("arena_allocations") counts it.
+#include "gem_capi_internal.hpp"
+#include "gem_costmap.hpp"
+
+#include <algorithm>
+
+namespace {
+
+constexpr size_t kRec = sizeof(LocalRecord);
+constexpr long long kMaxInputs = 2147483646ll;                      // 2^31 - 2: the stamp 2 * (i + 1) + 1 fits 32 bits
+constexpr long long kMaxCells = 1ll << 30;
+using Map = gem_handle::Costmaps::Map;
+
+unsigned long long* acc_words(gem_handle* h) { return static_cast<unsigned long long*>(h->costmap.small.p); }
+unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
+uint32_t cells_of(const Map& m) { return m.cfg.size_x * m.cfg.size_y; }
+CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
+CostAccum accum_of(gem_handle* h, Map& m) { return CostAccum{static_cast<uint32_t*>(m.stamps.p), acc_words(h)}; }
+
+int usable(gem_handle* h, const char* what)
+{
+    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
+    return GEM_OK;
+}
+
+int find(gem_handle* h, int id, const char* what, Map** out)
+{
+    const int rc = usable(h, what);
+    if (rc) return rc;
+    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
+        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
+    *out = &h->costmap.map[id];
+    return GEM_OK;
+}
+
+bool window_ok(const Map& m, int min_i, int min_j, int max_i, int max_j)
+{
+    return min_i >= 0 && min_j >= 0 && min_i <= max_i && min_j <= max_j && (long long)max_i <= (long long)m.cfg.size_x &&
+           (long long)max_j <= (long long)m.cfg.size_y;
+}
+
+// the resolve pass behind a mark's launches, then the caller's bounds merged with the touched ones: touch() of costmap_layer.cpp,
+// *min = std::min(p, *min) and *max = std::max(p, *max) over the accepted inputs
+int finish_mark(gem_handle* h, Map& m, double bounds[4])
+{
+    unsigned long long* acc = acc_words(h);
+    GEM_HIP(h, launch_cost_resolve(h->stream, cells_of(m), static_cast<uint32_t*>(m.stamps.p), grid_of(m), acc, acc + 4));
+    if (!bounds) return GEM_OK;
+    unsigned long long w[4];
+    HostXfer d{w, acc + 4, sizeof(w)};
+    int rc;
+    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
+    double v;
+    for (int k = 0; k < 2; ++k) {
+        if (cost_key_decode(w[k], false, &v)) bounds[k] = bounds[k] < v ? bounds[k] : v;
+        if (cost_key_decode(w[2 + k], true, &v)) bounds[2 + k] = v < bounds[2 + k] ? bounds[2 + k] : v;
+    }
+    return GEM_OK;
+}
+
+int mark_records(gem_handle* h, Map& m, const LocalRecord* d_rec, long long n, double thresh, double bounds[4])
+{
+    if (n > 0) {
+        CostPointsArgs a{d_rec, nullptr, (uint32_t)n, 0u, thresh};
+        GEM_HIP(h, launch_cost_mark_points(h->stream, geom_of(m), a, accum_of(h, m)));
+    }
+    return finish_mark(h, m, bounds);
+}
+
+int check_cloud(gem_handle* h, const char* what, const void* points, long long n, double thresh)
+{
+    if (n < 0 || n > kMaxInputs || (n > 0 && !points)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": bad cloud").c_str());
+    if (!std::isfinite(thresh)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": travers_thresh not finite").c_str());
+    return GEM_OK;
+}
+
+// the last capture: its records, linear indices, device count word (Local::small holds the two slots' counts first) and geometry
+bool capture_of(gem_handle* h, CostVisualArgs* v)
+{
+    const auto& lc = h->local;
+    if (!lc.enabled || lc.cur < 0) return false;
+    const auto& s = lc.slot[lc.cur];
+    v->rec = static_cast<const LocalRecord*>(s.rec.p); v->lin = static_cast<const int*>(s.lin.p);
+    v->count = static_cast<const uint32_t*>(lc.small.p) + lc.cur;
+    v->g = LocalGeom{s.off, s.res, s.px, s.py, h->L, s.sx, s.sy};
+    return true;
+}
+
+// Costmap2D::updateOrigin (costmap_2d.cpp), restated in include/gem_hip.h
+int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const char* what)
+{
+    if (!std::isfinite(new_ox) || !std::isfinite(new_oy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": origin not finite").c_str());
+    const double qx = (new_ox - m.cfg.origin_x) / m.cfg.resolution, qy = (new_oy - m.cfg.origin_y) / m.cfg.resolution;
+    if (!(qx > -2147483649.0 && qx < 2147483648.0 && qy > -2147483649.0 && qy < 2147483648.0))
+        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the step's cell count does not fit an int").c_str());
+    const int cell_ox = (int)qx, cell_oy = (int)qy;
+    if (cell_ox == 0 && cell_oy == 0) return GEM_OK;
+    const double ox = m.cfg.origin_x + cell_ox * m.cfg.resolution, oy = m.cfg.origin_y + cell_oy * m.cfg.resolution;
+    if (!std::isfinite(ox) || !std::isfinite(oy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": origin not finite").c_str());
+    GEM_HIP(h, launch_cost_roll(h->stream, grid_of(m), static_cast<unsigned char*>(m.grid[1 - m.act].p), m.cfg.size_x, m.cfg.size_y,
+                                cell_ox, cell_oy, m.cfg.default_value));
+    m.act = 1 - m.act;
+    m.cfg.origin_x = ox; m.cfg.origin_y = oy;
+    return GEM_OK;
+}
+
+void free_map(Map& m)
+{
+    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps}) {
+        if (a->p) hipFree(a->p);
+        a->p = nullptr; a->cap = 0;
+    }
+    m = Map{};
+}
+
+} // namespace
+
+namespace gemi {
+
+void costmap_free(gem_handle* h)
+{
+    auto& c = h->costmap;
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (auto& m : c.map) free_map(m);
+    for (Arena* a : {&c.small, &c.in, &c.win}) {
+        if (a->p) hipFree(a->p);
+        a->p = nullptr; a->cap = 0;
+    }
+}
+
+} // namespace gemi
+
+#define COSTMAP_ENTRY(name)                                          \
+    ApiRange api_range(h, name);                                     \
+    if (!h) return GEM_ERR_INVALID;                                  \
+    std::lock_guard<std::mutex> lk(h->mu);                           \
+    hipSetDevice(h->device);                                         \
+    int rc;                                                          \
+    (void)rc
+
+extern "C" {
+
+int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id)
+{
+    COSTMAP_ENTRY("gem_costmap_create");
+    if ((rc = usable(h, "gem_costmap_create"))) return rc;
+    if (!cfg || !out_id) return fail(h, GEM_ERR_INVALID, "gem_costmap_create: null argument");
+    if (cfg->size_x == 0 || cfg->size_y == 0 || (long long)cfg->size_x * cfg->size_y > kMaxCells)
+        return fail(h, GEM_ERR_INVALID, "gem_costmap_create: size zero or above 2^30 cells");
+    if (!std::isfinite(cfg->resolution) || !(cfg->resolution > 0.0) || !std::isfinite(cfg->origin_x) || !std::isfinite(cfg->origin_y))
+        return fail(h, GEM_ERR_INVALID, "gem_costmap_create: resolution not finite and positive, or origin not finite");
+    auto& c = h->costmap;
+    int id = 0;
+    while (id < gem_handle::Costmaps::kMax && c.map[id].used) ++id;
+    if (id == gem_handle::Costmaps::kMax) return fail(h, GEM_ERR_INVALID, "gem_costmap_create: every costmap of the handle is in use");
+    Map& m = c.map[id];
+    const size_t cells = (size_t)cfg->size_x * cfg->size_y, stamp_bytes = (cells + 3) / 4 * 16;
+    if (!c.small.p) {
+        if ((rc = ensure(h, c.small, 64))) return rc;
+        GEM_HIP(h, hipMemsetAsync(c.small.p, 0xff, 64, h->stream));            // no input accepted yet
+    }
+    if ((rc = ensure(h, m.grid[0], cells)) || (rc = ensure(h, m.grid[1], cells)) || (rc = ensure(h, m.stamps, stamp_bytes))) {
+        free_map(m);
+        return rc;
+    }
+    m.cfg = *cfg; m.act = 0;
+    GEM_HIP(h, hipMemsetAsync(m.stamps.p, 0, stamp_bytes, h->stream));
+    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(m), (uint32_t)cells, m.cfg.default_value));
+    m.used = true;
+    *out_id = id;
+    return GEM_OK;
+}
+
+int gem_costmap_destroy(gem_handle* h, int id)
+{
+    COSTMAP_ENTRY("gem_costmap_destroy");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_destroy", &m))) return rc;
+    GEM_HIP(h, hipStreamSynchronize(h->stream));
+    free_map(*m);
+    return GEM_OK;
+}
+
+int gem_costmap_geometry(gem_handle* h, int id, gem_costmap_config* out)
+{
+    COSTMAP_ENTRY("gem_costmap_geometry");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_geometry", &m))) return rc;
+    if (!out) return fail(h, GEM_ERR_INVALID, "gem_costmap_geometry: null argument");
+    *out = m->cfg;
+    return GEM_OK;
+}
+
+int gem_costmap_reset(gem_handle* h, int id)
+{
+    COSTMAP_ENTRY("gem_costmap_reset");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_reset", &m))) return rc;
+    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(*m), cells_of(*m), m->cfg.default_value));
+    return GEM_OK;
+}
+
+int gem_costmap_update_origin(gem_handle* h, int id, double new_origin_x, double new_origin_y)
+{
+    COSTMAP_ENTRY("gem_costmap_update_origin");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_update_origin", &m))) return rc;
+    return update_origin(h, *m, new_origin_x, new_origin_y, "gem_costmap_update_origin");
+}
+
+int gem_costmap_roll_to(gem_handle* h, int id, double robot_x, double robot_y)
+{
+    COSTMAP_ENTRY("gem_costmap_roll_to");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_roll_to", &m))) return rc;
+    // getSizeInMetersX() = (size_x - 1 + 0.5) * resolution (costmap_2d.cpp)
+    const double mx = (m->cfg.size_x - 1 + 0.5) * m->cfg.resolution, my = (m->cfg.size_y - 1 + 0.5) * m->cfg.resolution;
+    return update_origin(h, *m, robot_x - mx / 2, robot_y - my / 2, "gem_costmap_roll_to");
+}
+
+int gem_costmap_mark_points(gem_handle* h, int id, const void* points, long long n, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_points");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_points", &m))) return rc;
+    if ((rc = check_cloud(h, "gem_costmap_mark_points", points, n, travers_thresh))) return rc;
+    if (n > 0) {
+        if ((rc = ensure(h, h->costmap.in, (size_t)n * kRec))) return rc;
+        HostXfer x{const_cast<void*>(points), h->costmap.in.p, (size_t)n * kRec};
+        if ((rc = upload_arrays(h, &x, 1))) return rc;
+    }
+    return mark_records(h, *m, static_cast<const LocalRecord*>(h->costmap.in.p), n, travers_thresh, bounds);
+}
+
+int gem_costmap_mark_points_device(gem_handle* h, int id, const void* d_points, long long n, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_points_device");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_points_device", &m))) return rc;
+    if ((rc = check_cloud(h, "gem_costmap_mark_points_device", d_points, n, travers_thresh))) return rc;
+    return mark_records(h, *m, static_cast<const LocalRecord*>(d_points), n, travers_thresh, bounds);
+}
+
+int gem_costmap_mark_grid_cloud(gem_handle* h, int id, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_grid_cloud");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_grid_cloud", &m))) return rc;
+    if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_grid_cloud: travers_thresh not finite");
+    CostVisualArgs cap{};
+    if (!capture_of(h, &cap)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_grid_cloud: the local map is not enabled or has no capture");
+    CostPointsArgs a{cap.rec, cap.count, (uint32_t)h->cells, 0u, travers_thresh};
+    GEM_HIP(h, launch_cost_mark_points(h->stream, geom_of(*m), a, accum_of(h, *m)));
+    return finish_mark(h, *m, bounds);
+}
+
+int gem_costmap_mark_global(gem_handle* h, int id, int index, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_global");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_global", &m))) return rc;
+    if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: travers_thresh not finite");
+    auto& g = h->global;
+    if (!g.enabled) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: the submap stack is not enabled (gem_global_enable)");
+    const int S = (int)g.cnt.size();
+    if (index < -1 || index >= S) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: index out of range");
+    const int first = index < 0 ? 0 : index, last = index < 0 ? S : index + 1;
+    long long total = 0;
+    for (int s = first; s < last; ++s) total += g.cnt[s];
+    if (total > kMaxInputs) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: more than 2^31 - 2 records");
+    long long at = 0;
+    for (int s = first; s < last; ++s) {                                // stack order is input order: the submaps' indices follow each other
+        if (!g.cnt[s]) continue;
+        CostPointsArgs a{static_cast<const LocalRecord*>(g.stack[g.act].p) + g.off[s], nullptr, (uint32_t)g.cnt[s], (uint32_t)at, travers_thresh};
+        GEM_HIP(h, launch_cost_mark_points(h->stream, geom_of(*m), a, accum_of(h, *m)));
+        at += g.cnt[s];
+    }
+    return finish_mark(h, *m, bounds);
+}
+
+int gem_costmap_mark_visual(gem_handle* h, int id, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_visual");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_visual", &m))) return rc;
+    if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_visual: travers_thresh not finite");
+    CostVisualArgs a{};
+    if (!capture_of(h, &a)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_visual: the local map is not enabled or has no capture");
+    a.thresh = travers_thresh;
+    GEM_HIP(h, launch_cost_mark_visual(h->stream, geom_of(*m), a, accum_of(h, *m)));
+    return finish_mark(h, *m, bounds);
+}
+
+int gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_j, int max_i, int max_j, int mode)
+{
+    COSTMAP_ENTRY("gem_costmap_merge");
+    Map *m, *master;
+    if ((rc = find(h, id, "gem_costmap_merge", &m)) || (rc = find(h, master_id, "gem_costmap_merge", &master))) return rc;
+    if (m->cfg.size_x != master->cfg.size_x || m->cfg.size_y != master->cfg.size_y)
+        return fail(h, GEM_ERR_INVALID, "gem_costmap_merge: the two costmaps differ in size");
+    if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_merge: window outside the map");
+    if (mode != 0 && mode != 1) return fail(h, GEM_ERR_INVALID, "gem_costmap_merge: mode is 0 (overwrite) or 1 (max)");
+    if (m == master) return GEM_OK;                                      // either rule leaves a map merged onto itself as it is
+    GEM_HIP(h, launch_cost_merge(h->stream, grid_of(*m), grid_of(*master), m->cfg.size_x, CostWindow{min_i, min_j, max_i, max_j}, mode));
+    return GEM_OK;
+}
+
+int gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, unsigned char* out, size_t row_stride)
+{
+    COSTMAP_ENTRY("gem_costmap_read");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_read", &m))) return rc;
+    if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_read: window outside the map");
+    const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
+    if (!w || !rows) return GEM_OK;
+    if (!out || row_stride < w) return fail(h, GEM_ERR_INVALID, "gem_costmap_read: null output or a row stride below the window's width");
+    const bool whole = w == m->cfg.size_x && rows == m->cfg.size_y;
+    const unsigned char* src = grid_of(*m);
+    if (!whole) {                                                        // a partial window is packed on the device first
+        if ((rc = ensure(h, h->costmap.win, w * rows))) return rc;
+        GEM_HIP(h, launch_cost_window(h->stream, grid_of(*m), m->cfg.size_x, CostWindow{min_i, min_j, max_i, max_j},
+                                      static_cast<unsigned char*>(h->costmap.win.p)));
+        src = static_cast<const unsigned char*>(h->costmap.win.p);
+    }
+    if (row_stride == w) {
+        HostXfer d{out, const_cast<unsigned char*>(src), w * rows};
+        return download_arrays(h, &d, 1, 0);
+    }
+    std::vector<unsigned char>& tmp = h->costmap.host_rows;             // packed rows, then out at the caller's stride
+    tmp.resize(w * rows);
+    HostXfer d{tmp.data(), const_cast<unsigned char*>(src), w * rows};
+    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
+    for (size_t r = 0; r < rows; ++r) memcpy(out + r * row_stride, tmp.data() + r * w, w);
+    return GEM_OK;
+}
+
+int gem_costmap_write(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, const unsigned char* in, size_t row_stride)
+{
+    COSTMAP_ENTRY("gem_costmap_write");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_write", &m))) return rc;
+    if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_write: window outside the map");
+    const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
+    if (!w || !rows) return GEM_OK;
+    if (!in || row_stride < w) return fail(h, GEM_ERR_INVALID, "gem_costmap_write: null input or a row stride below the window's width");
+    if ((rc = ensure(h, h->costmap.win, w * rows))) return rc;
+    const unsigned char* src = in;
+    if (row_stride != w) {
+        std::vector<unsigned char>& tmp = h->costmap.host_rows;
+        tmp.resize(w * rows);
+        for (size_t r = 0; r < rows; ++r) memcpy(tmp.data() + r * w, in + r * row_stride, w);
+        src = tmp.data();
+    }
+    HostXfer x{const_cast<unsigned char*>(src), h->costmap.win.p, w * rows};
+    if ((rc = upload_arrays(h, &x, 1))) return rc;
+    GEM_HIP(h, launch_cost_unpack(h->stream, static_cast<const unsigned char*>(h->costmap.win.p), m->cfg.size_x,
+                                  CostWindow{min_i, min_j, max_i, max_j}, grid_of(*m)));
+    return GEM_OK;
+}
+
+} // extern "C"

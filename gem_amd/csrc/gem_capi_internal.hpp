@@ -280,6 +280,20 @@ struct gem_handle {
         Arena out[2], keys[2], tkeys[2], tvals[2], blk[2];  // a pair step's sides (0 = old, 1 = new): output, keys, table, counts
         Arena small;                    // device words: the sides' totals [2] | fused keys | the local map's export total
     } global;
+    // the costmap layers (gem_costmap_*, gem_capi_costmap.cpp; kernels in gem_costmap.hip)
+    struct Costmaps {
+        static constexpr int kMax = 8;  // a few per handle: a local one, a global one, a master
+        struct Map {
+            bool used = false;
+            gem_costmap_config cfg{};   // the origin is the one after the last roll
+            Arena grid[2];              // the byte grid (`act`) and the target of the next roll
+            int act = 0;
+            Arena stamps;               // a word per cell (padded to four): the verdict of a mark in flight, all-zero between calls
+        } map[kMax];
+        Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
+        Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
+        std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
+    } costmap;
     bool  dbg_on = false;
     bool  dbg_frame = false;            // debug knob: with the stamps on, a stream of single sweeps still runs as k_frame (its tiles AND its binning blocks are stamped)
     long long sort_fallbacks = 0;      // passes whose forced sorted form / pass count did not fit the map and took the other form (gem_debug_get)
@@ -377,6 +391,7 @@ int local_grid_count(gem_handle* h, uint32_t* n);
 int local_export_to(gem_handle* h, void* dst, uint32_t n_grid, bool clear);
 void compose_free(gem_handle* h);               // gem_capi_compose.cpp: the compose arenas (local_free)
 void global_free(gem_handle* h);                // gem_capi_global.cpp: the submap stack's arenas (gem_destroy, gem_global_enable(0))
+void costmap_free(gem_handle* h);               // gem_capi_costmap.cpp: every costmap of the handle and their shared arenas (gem_destroy)
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);
 int flush_pending(gem_handle* h, bool with_floor);

@@ -1,0 +1,284 @@
+// gem_costmap.hip -- the two costmap_2d layers of the reference's layers/ on the device, gfx950: PointMapLayer::updateBounds
+// (layers/src/pointMap_layer.cpp:55-81), ElevationMapLayer::updateBounds (layers/src/elevationMap_layer.cpp:58-81), and the pieces
+// of costmap_2d they call, restated in include/gem_hip.h.
+//
+// The reference's loops write costmap_[index] input by input, so the LAST input of a cell decides between FREE_SPACE and
+// LETHAL_OBSTACLE.  Here every input carries the stamp 2 * (its index + 1) + lethal; a cell keeps the integer maximum of its
+// stamps, which is the stamp of its last input whatever the timing, and k_cost_resolve turns the low bit into the byte.  Nearly all
+// of the cost is contention: the grid cloud of a capture puts some 64 inputs on each costmap cell, neighbouring lanes on the same
+// one.  So a stamp is reduced before it reaches memory:
+//   in the wave       a lane whose successor holds the same cell with a stamp at least as large stays silent (the successor, or a
+//                     lane behind it, issues a stamp that beats this one): in input order only the last lane of a run issues
+//   in the workgroup  a costmap of at most kCostLdsCells cells has a stamp grid in LDS (ds_max_u32); the workgroup's 4096
+//                     consecutive inputs touch few cells, and each non-zero entry leaves with one global atomic max
+//   larger costmaps   the wave-reduced stamps go to global memory directly
+// The touched bounds (min / max of px, py over the accepted inputs) go wave -> workgroup (LDS) -> four global words as
+// order-preserving 64-bit keys under integer min.  Only vector stores and atomics write memory.
+#include "gem_costmap.hpp"
+
+#include <float.h>
+
+namespace gem {
+
+// Costmap2D::worldToMap with the contract's stricter failure: non-finite coordinates and quotients beyond int fail
+__device__ __forceinline__ bool cost_cell(const CostGeom& g, double wx, double wy, uint32_t& cell)
+{
+    if (!(fabs(wx) <= DBL_MAX && fabs(wy) <= DBL_MAX)) return false;
+    if (wx < g.ox || wy < g.oy) return false;
+    const double qx = (wx - g.ox) / g.res, qy = (wy - g.oy) / g.res;
+    if (!(qx < 2147483648.0 && qy < 2147483648.0)) return false;
+    const uint32_t mx = (uint32_t)(int)qx, my = (uint32_t)(int)qy;
+    if (!(mx < g.sx && my < g.sy)) return false;
+    cell = my * g.sx + mx;
+    return true;
+}
+
+// doubles as unsigned integers in the same order (-0 below +0)
+__device__ __forceinline__ unsigned long long cost_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+
+struct CostInput {
+    double px, py;
+    bool lethal;
+    uint32_t order;                     // index in the reference's loop
+};
+
+// PointMapLayer: the records of a cloud; travers > thresh is free, anything else (NaN included) lethal
+struct CostPointsSrc {
+    CostPointsArgs a;
+    struct Item { float x, y, t; };
+    __device__ size_t size() const { return a.count ? (size_t)min(*a.count, a.n) : (size_t)a.n; }
+    __device__ Item load(size_t i) const { return {a.rec[i].x, a.rec[i].y, a.rec[i].travers}; }
+    __device__ CostInput eval(size_t i, const Item& v) const
+    {
+        return {(double)v.x, (double)v.y, !((double)v.t > a.thresh), a.base + (uint32_t)i};
+    }
+};
+
+// ElevationMapLayer: all L^2 cells of the capture's grid in iteration order (= linear index).  Items [0, L^2) are the cells as if
+// none were kept (NaN: never below the threshold, free); items behind them are the kept cells with their traver, under the same
+// order number, so a kept cell's own verdict beats its NaN twin exactly when it is lethal.
+struct CostVisualSrc {
+    CostVisualArgs a;
+    struct Item { uint32_t k; float t; };
+    __device__ size_t cells() const { return (size_t)a.g.L * a.g.L; }
+    __device__ size_t size() const { return cells() + (size_t)min(*a.count, (uint32_t)cells()); }
+    __device__ Item load(size_t i) const
+    {
+        const size_t c = cells();
+        if (i < c) return {(uint32_t)i, __builtin_nanf("")};
+        return {(uint32_t)a.lin[i - c], a.rec[i - c].travers};
+    }
+    __device__ CostInput eval(size_t, const Item& v) const
+    {
+        CostInput in;
+        local_position(a.g, (size_t)v.k, in.px, in.py);
+        in.lethal = (double)v.t < a.thresh;
+        in.order = v.k;
+        return in;
+    }
+};
+
+template <class Src, bool LDS>
+__global__ __launch_bounds__(kCostThreads) void k_cost_mark(Src src, CostGeom g, CostAccum out)
+{
+    extern __shared__ uint32_t s_stamp[];                               // LDS form: [cells]
+    __shared__ unsigned long long s_acc[4];
+    const uint32_t cells = g.sx * g.sy;
+    if (LDS)
+        for (uint32_t c = threadIdx.x; c < cells; c += kCostThreads) s_stamp[c] = 0u;
+    if (threadIdx.x < 4) s_acc[threadIdx.x] = ~0ull;
+    __syncthreads();
+
+    const size_t n = src.size(), base = (size_t)blockIdx.x * kCostChunk;
+    double lo_x = INFINITY, lo_y = INFINITY, hi_x = -INFINITY, hi_y = -INFINITY;
+    constexpr int kBatch = 4;                                           // loads in flight per lane
+    for (int k0 = 0; k0 < kCostItems; k0 += kBatch) {                   // workgroup-uniform trip count
+        if (base + (size_t)k0 * kCostThreads >= n) break;
+        typename Src::Item v[kBatch];
+#pragma unroll
+        for (int k = 0; k < kBatch; ++k) {
+            const size_t i = base + (size_t)(k0 + k) * kCostThreads + threadIdx.x;
+            if (i < n) v[k] = src.load(i);
+        }
+#pragma unroll
+        for (int k = 0; k < kBatch; ++k) {
+            const size_t i = base + (size_t)(k0 + k) * kCostThreads + threadIdx.x;
+            uint32_t cell = 0u, stamp = 0u;                             // stamp 0: no input, or one worldToMap refused
+            if (i < n) {
+                const CostInput in = src.eval(i, v[k]);
+                if (cost_cell(g, in.px, in.py, cell)) {
+                    stamp = 2u * (in.order + 1u) + (in.lethal ? 1u : 0u);
+                    lo_x = fmin(lo_x, in.px); hi_x = fmax(hi_x, in.px);
+                    lo_y = fmin(lo_y, in.py); hi_y = fmax(hi_y, in.py);
+                }
+            }
+            const uint32_t next_cell = (uint32_t)__shfl_down((int)cell, 1), next_stamp = (uint32_t)__shfl_down((int)stamp, 1);
+            const bool beaten = lane_id() < 63 && next_cell == cell && next_stamp >= stamp;
+            const bool issue = stamp != 0u && !beaten;
+            if (issue) {
+                if (LDS) atomicMax(&s_stamp[cell], stamp);
+                else __hip_atomic_fetch_max(out.stamps + cell, stamp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo_x = fmin(lo_x, __shfl_xor(lo_x, off)); hi_x = fmax(hi_x, __shfl_xor(hi_x, off));
+        lo_y = fmin(lo_y, __shfl_xor(lo_y, off)); hi_y = fmax(hi_y, __shfl_xor(hi_y, off));
+    }
+    if (lane_id() == 0 && lo_x <= hi_x) {                               // the wave accepted an input
+        atomicMin(&s_acc[0], cost_key(lo_x)); atomicMin(&s_acc[1], cost_key(lo_y));
+        atomicMin(&s_acc[2], ~cost_key(hi_x)); atomicMin(&s_acc[3], ~cost_key(hi_y));
+    }
+    __syncthreads();
+    if (LDS)
+        for (uint32_t c = threadIdx.x; c < cells; c += kCostThreads) {
+            const uint32_t s = s_stamp[c];
+            if (s) __hip_atomic_fetch_max(out.stamps + c, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    if (threadIdx.x < 4 && s_acc[threadIdx.x] != ~0ull)
+        __hip_atomic_fetch_min(out.acc + threadIdx.x, s_acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// four cells per thread: a touched cell takes its verdict and its stamp goes back to 0; workgroup 0 publishes the bounds words and
+// resets them for the next mark
+__global__ __launch_bounds__(256) void k_cost_resolve(uint32_t cells, uint32_t* __restrict__ stamps, unsigned char* __restrict__ grid,
+                                                      unsigned long long* __restrict__ acc, unsigned long long* __restrict__ published)
+{
+    if (blockIdx.x == 0 && threadIdx.x < 4) {
+        published[threadIdx.x] = acc[threadIdx.x];
+        acc[threadIdx.x] = ~0ull;
+    }
+    const uint32_t c0 = (blockIdx.x * 256u + threadIdx.x) * 4u;         // the stamp array is padded to a multiple of four words
+    if (c0 >= cells) return;
+    const uint4 s = *reinterpret_cast<const uint4*>(stamps + c0);
+    if (!(s.x | s.y | s.z | s.w)) return;
+    const uint32_t w[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (w[k] && c0 + k < cells) grid[c0 + k] = (w[k] & 1u) ? kCostLethal : kCostFree;
+    *reinterpret_cast<uint4*>(stamps + c0) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_cost_fill(unsigned char* __restrict__ grid, uint32_t cells, unsigned char value)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c < cells) grid[c] = value;
+}
+
+__global__ __launch_bounds__(256) void k_cost_roll(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, uint32_t sx,
+                                                   uint32_t sy, long long cell_ox, long long cell_oy, unsigned char value)
+{
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= sx * sy) return;
+    const long long x = (long long)(c % sx) + cell_ox, y = (long long)(c / sx) + cell_oy;
+    const bool in = x >= 0 && x < (long long)sx && y >= 0 && y < (long long)sy;
+    dst[c] = in ? src[(size_t)y * sx + (size_t)x] : value;
+}
+
+__global__ __launch_bounds__(256) void k_cost_merge(const unsigned char* __restrict__ layer, unsigned char* __restrict__ master,
+                                                    uint32_t sx, CostWindow w, int mode)
+{
+    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
+    const size_t c = (size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww));
+    const unsigned char v = layer[c];
+    if (v == kCostNoInfo) return;
+    if (mode == 0) { master[c] = v; return; }                           // updateWithOverwrite
+    const unsigned char old = master[c];
+    if (old == kCostNoInfo || old < v) master[c] = v;                   // updateWithMax
+}
+
+__global__ __launch_bounds__(256) void k_cost_window(const unsigned char* __restrict__ grid, uint32_t sx, CostWindow w,
+                                                     unsigned char* __restrict__ packed)
+{
+    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
+    packed[t] = grid[(size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww))];
+}
+
+__global__ __launch_bounds__(256) void k_cost_unpack(const unsigned char* __restrict__ packed, uint32_t sx, CostWindow w,
+                                                     unsigned char* __restrict__ grid)
+{
+    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
+    grid[(size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww))] = packed[t];
+}
+
+template <class Src>
+static hipError_t launch_mark(hipStream_t st, const Src& src, long long items, const CostGeom& g, CostAccum out)
+{
+    const long long nb = cost_mark_blocks(items);
+    if (nb <= 0) return hipSuccess;
+    if (nb > INT_MAX) return hipErrorInvalidValue;
+    const uint32_t cells = g.sx * g.sy;
+    if (cells <= kCostLdsCells) {
+        hipLaunchKernelGGL((k_cost_mark<Src, true>), dim3((unsigned)nb), dim3(kCostThreads), cells * sizeof(uint32_t), st, src, g, out);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((k_cost_mark<Src, false>), dim3((unsigned)nb), dim3(kCostThreads), 0, st, src, g, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_mark_points(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out)
+{
+    return launch_mark(st, CostPointsSrc{a}, (long long)a.n, g, out);
+}
+
+hipError_t launch_cost_mark_visual(hipStream_t st, const CostGeom& g, const CostVisualArgs& a, CostAccum out)
+{
+    return launch_mark(st, CostVisualSrc{a}, 2ll * a.g.L * a.g.L, g, out);
+}
+
+static unsigned blocks_of(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
+
+hipError_t launch_cost_resolve(hipStream_t st, uint32_t cells, uint32_t* stamps, unsigned char* grid, unsigned long long* acc,
+                               unsigned long long* published)
+{
+    hipLaunchKernelGGL(k_cost_resolve, dim3(blocks_of(((uint64_t)cells + 3) / 4)), dim3(256), 0, st, cells, stamps, grid, acc, published);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_fill(hipStream_t st, unsigned char* grid, uint32_t cells, unsigned char value)
+{
+    hipLaunchKernelGGL(k_cost_fill, dim3(blocks_of(cells)), dim3(256), 0, st, grid, cells, value);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_roll(hipStream_t st, const unsigned char* src, unsigned char* dst, uint32_t sx, uint32_t sy, long long cell_ox,
+                            long long cell_oy, unsigned char value)
+{
+    hipLaunchKernelGGL(k_cost_roll, dim3(blocks_of((uint64_t)sx * sy)), dim3(256), 0, st, src, dst, sx, sy, cell_ox, cell_oy, value);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_merge(hipStream_t st, const unsigned char* layer, unsigned char* master, uint32_t sx, CostWindow w, int mode)
+{
+    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
+    if (!t) return hipSuccess;
+    hipLaunchKernelGGL(k_cost_merge, dim3(blocks_of(t)), dim3(256), 0, st, layer, master, sx, w, mode);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_window(hipStream_t st, const unsigned char* grid, uint32_t sx, CostWindow w, unsigned char* packed)
+{
+    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
+    if (!t) return hipSuccess;
+    hipLaunchKernelGGL(k_cost_window, dim3(blocks_of(t)), dim3(256), 0, st, grid, sx, w, packed);
+    return hipGetLastError();
+}
+
+hipError_t launch_cost_unpack(hipStream_t st, const unsigned char* packed, uint32_t sx, CostWindow w, unsigned char* grid)
+{
+    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
+    if (!t) return hipSuccess;
+    hipLaunchKernelGGL(k_cost_unpack, dim3(blocks_of(t)), dim3(256), 0, st, packed, sx, w, grid);
+    return hipGetLastError();
+}
+
+} // namespace gem

@@ -1,0 +1,77 @@
+// gem_costmap.hpp -- the costmap layers on the device (internal header): argument blocks and host launchers of gem_costmap.hip.
+//   mark     the updateBounds bodies of PointMapLayer (layers/src/pointMap_layer.cpp:55-81) and ElevationMapLayer
+//            (layers/src/elevationMap_layer.cpp:58-81): every input's costmap cell in double, its verdict carried by a stamp
+//   resolve  the stamps into the byte grid (FREE_SPACE / LETHAL_OBSTACLE), the stamps cleared, the touched bounds published
+//   roll     Costmap2D::updateOrigin through a second byte grid
+//   merge    updateWithOverwrite / updateWithMax over a window;  window / unpack: a window's bytes, packed, for the read-back and
+//            the write
+#pragma once
+
+#include "gem_local.hpp"
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace gem {
+
+constexpr unsigned char kCostFree = 0, kCostLethal = 254, kCostNoInfo = 255;
+// The one size-dependent switch: a costmap of at most this many cells keeps a stamp grid per workgroup in LDS (32 KB), a larger one
+// sends its wave-reduced stamps straight to global memory.
+constexpr uint32_t kCostLdsCells = 8192;
+constexpr int kCostThreads = 256, kCostItems = 16;                  // inputs per thread: a workgroup takes 4096 consecutive inputs
+constexpr int kCostChunk = kCostThreads * kCostItems;
+
+struct CostGeom {
+    double ox, oy, res;
+    uint32_t sx, sy;
+};
+
+// what a mark launch accumulates into: a stamp per cell, 2 * (input index + 1) + lethal, 0 = untouched, resolved by integer max; and
+// four 64-bit words, the order-preserving keys of min px, min py, ~max px, ~max py over the accepted inputs, all reduced by integer
+// min (all-ones: no input accepted)
+struct CostAccum {
+    uint32_t* stamps;
+    unsigned long long* acc;
+};
+
+struct CostPointsArgs {
+    const LocalRecord* rec;
+    const uint32_t* count;              // the record count on the device (a capture's), or NULL: n
+    uint32_t n;                         // records (an upper bound with `count`)
+    uint32_t base;                      // index of rec[0] in the whole input (the submaps of one call follow each other)
+    double thresh;
+};
+
+struct CostVisualArgs {
+    const LocalRecord* rec; const int* lin; const uint32_t* count;   // the capture
+    LocalGeom g;
+    double thresh;
+};
+
+// the host side of CostAccum::acc (gem_costmap.hip's cost_key): false when the word is all-ones
+inline bool cost_key_decode(unsigned long long k, bool inverted, double* out)
+{
+    if (k == ~0ull) return false;
+    if (inverted) k = ~k;
+    const unsigned long long b = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+    __builtin_memcpy(out, &b, 8);
+    return true;
+}
+
+inline long long cost_mark_blocks(long long items) { return (items + kCostChunk - 1) / kCostChunk; }
+
+hipError_t launch_cost_mark_points(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out);
+hipError_t launch_cost_mark_visual(hipStream_t st, const CostGeom& g, const CostVisualArgs& a, CostAccum out);
+// stamps -> grid; acc -> published[4] (the words as they are), acc reset to all-ones
+hipError_t launch_cost_resolve(hipStream_t st, uint32_t cells, uint32_t* stamps, unsigned char* grid, unsigned long long* acc,
+                               unsigned long long* published);
+hipError_t launch_cost_fill(hipStream_t st, unsigned char* grid, uint32_t cells, unsigned char value);
+// dst(x, y) = src(x + cell_ox, y + cell_oy) where that lies in the map, `value` elsewhere
+hipError_t launch_cost_roll(hipStream_t st, const unsigned char* src, unsigned char* dst, uint32_t sx, uint32_t sy, long long cell_ox,
+                            long long cell_oy, unsigned char value);
+struct CostWindow { int min_i, min_j, max_i, max_j; };
+hipError_t launch_cost_merge(hipStream_t st, const unsigned char* layer, unsigned char* master, uint32_t sx, CostWindow w, int mode);
+hipError_t launch_cost_window(hipStream_t st, const unsigned char* grid, uint32_t sx, CostWindow w, unsigned char* packed);
+hipError_t launch_cost_unpack(hipStream_t st, const unsigned char* packed, uint32_t sx, CostWindow w, unsigned char* grid);
+
+} // namespace gem

@@ -30,6 +30,16 @@ struct LocalGeom {
     int L, sx, sy;
 };
 
+// getPositionFromIndex of the cell at linear index `lin` (the formula of k_show_emit)
+__device__ __forceinline__ void local_position(const LocalGeom& g, size_t lin, double& x, double& y)
+{
+    const int ix = (int)(lin % (size_t)g.L), iy = (int)(lin / (size_t)g.L);
+    int ux = ix - g.sx, uy = iy - g.sy;                                     // getIndexFromBufferIndex
+    ux += ux < 0 ? g.L : 0; uy += uy < 0 ? g.L : 0;
+    x = (g.px + g.off) + g.res * (double)(-ux);
+    y = (g.py + g.off) + g.res * (double)(-uy);
+}
+
 struct LocalCaptureArgs {
     LayerPtrs m; LocalGeom g;
     LocalRecord* rec; int* lin;         // [L^2] the kept cells in iteration order, their linear (column-major buffer) index

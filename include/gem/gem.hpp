@@ -15,6 +15,7 @@
 //   ElevationMapping::updateLocalMap / visualPointMap (LocalMap)   src/ElevationMapping.cpp:609-767, 520-530
 //   ElevationMapping::updateGlobalMap and globalMap_ (GlobalMap)   src/ElevationMapping.cpp:630-687, 773-905
 //   pcl::VoxelGrid of the launch files' nodelets (VoxelGrid)       filter.launch, filter_kitti.launch
+//   PointMapLayer / ElevationMapLayer ::updateBounds, ::updateCosts (Costmap)   layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87
 #pragma once
 
 #include "../gem_hip.h"
@@ -502,6 +503,87 @@ public:
 
 private:
     ElevationMap& map_;
+};
+
+// ---------------------------------------------------------------------------------------------
+// A layer costmap on the device (gem_costmap_*): the updateBounds bodies of the reference's two costmap_2d plugins
+// (layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87) as marking passes, Costmap2D::updateOrigin as the rolling
+// step, the two updateCosts rules and a window read-back.  costmap_2d itself is restated in gem_hip.h, unverified against the
+// library.  Extra bounds, the footprint, enabled_ and the layered costmap stay with the caller, see INTEGRATION.md.
+// ---------------------------------------------------------------------------------------------
+class Costmap {
+public:
+    static constexpr unsigned char FREE_SPACE = 0, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
+    enum MergeMode { Overwrite = 0, Max = 1 };
+    // a mark's bounds, in / out as updateBounds' four pointers
+    struct Bounds { double min_x, min_y, max_x, max_y; };
+
+    // defaultValue: NO_INFORMATION with track_unknown_space, FREE_SPACE without (ObstacleLayer); PointMapLayer never sets it
+    Costmap(ElevationMap& map, unsigned sizeX, unsigned sizeY, double resolution, double originX = 0.0, double originY = 0.0,
+            unsigned char defaultValue = NO_INFORMATION) : map_(map)
+    {
+        gem_costmap_config c{};
+        c.size_x = sizeX; c.size_y = sizeY; c.resolution = resolution; c.origin_x = originX; c.origin_y = originY;
+        c.default_value = defaultValue;
+        map_.check(gem_costmap_create(map_.handle(), &c, &id_), "gem_costmap_create");
+    }
+    ~Costmap() { gem_costmap_destroy(map_.handle(), id_); }
+    Costmap(const Costmap&) = delete;
+    Costmap& operator=(const Costmap&) = delete;
+
+    int id() const { return id_; }
+    gem_costmap_config geometry() const
+    {
+        gem_costmap_config c{};
+        map_.check(gem_costmap_geometry(map_.handle(), id_, &c), "gem_costmap_geometry");
+        return c;
+    }
+    void resetMaps() { map_.check(gem_costmap_reset(map_.handle(), id_), "gem_costmap_reset"); }
+    void updateOrigin(double newOriginX, double newOriginY)
+    { map_.check(gem_costmap_update_origin(map_.handle(), id_, newOriginX, newOriginY), "gem_costmap_update_origin"); }
+    // if (rolling_window_) updateOrigin(robot_x - getSizeInMetersX() / 2, robot_y - getSizeInMetersY() / 2)
+    void rollTo(double robotX, double robotY) { map_.check(gem_costmap_roll_to(map_.handle(), id_, robotX, robotY), "gem_costmap_roll_to"); }
+
+    // PointMapLayer::updateBounds' loop over a cloud of the caller's; bounds nullptr: only enqueued
+    void markPoints(const std::vector<PointXYZRGBICT>& cloud, double traversThresh, Bounds* bounds = nullptr)
+    {
+        map_.check(gem_costmap_mark_points(map_.handle(), id_, cloud.empty() ? nullptr : cloud.data(), static_cast<long long>(cloud.size()),
+                                           traversThresh, ptr(bounds)), "gem_costmap_mark_points");
+    }
+    // ... over the last capture's grid cloud, and over submap `index` of the stack (-1: all, in stack order), where they lie
+    void markGridCloud(double traversThresh, Bounds* bounds = nullptr)
+    { map_.check(gem_costmap_mark_grid_cloud(map_.handle(), id_, traversThresh, ptr(bounds)), "gem_costmap_mark_grid_cloud"); }
+    void markGlobal(int index, double traversThresh, Bounds* bounds = nullptr)
+    { map_.check(gem_costmap_mark_global(map_.handle(), id_, index, traversThresh, ptr(bounds)), "gem_costmap_mark_global"); }
+    // ElevationMapLayer::updateBounds' loop over the last capture standing for visualMap_
+    void markVisual(double traversThresh, Bounds* bounds = nullptr)
+    { map_.check(gem_costmap_mark_visual(map_.handle(), id_, traversThresh, ptr(bounds)), "gem_costmap_mark_visual"); }
+
+    // updateCosts onto a master of the same size inside [minI, maxI) x [minJ, maxJ)
+    void merge(Costmap& master, int minI, int minJ, int maxI, int maxJ, MergeMode mode = Overwrite)
+    { map_.check(gem_costmap_merge(map_.handle(), id_, master.id_, minI, minJ, maxI, maxJ, mode), "gem_costmap_merge"); }
+    // the window's bytes, row-major, (maxI - minI) per row
+    std::vector<unsigned char> read(int minI, int minJ, int maxI, int maxJ) const
+    {
+        const size_t w = maxI > minI ? static_cast<size_t>(maxI - minI) : 0, rows = maxJ > minJ ? static_cast<size_t>(maxJ - minJ) : 0;
+        std::vector<unsigned char> v(w * rows);
+        map_.check(gem_costmap_read(map_.handle(), id_, minI, minJ, maxI, maxJ, v.empty() ? nullptr : v.data(), w), "gem_costmap_read");
+        return v;
+    }
+
+    // ... and the reverse: (maxI - minI) * (maxJ - minJ) bytes, row-major, into the window (costs of the caller's other layers)
+    void write(int minI, int minJ, int maxI, int maxJ, const std::vector<unsigned char>& values)
+    {
+        const size_t w = maxI > minI ? static_cast<size_t>(maxI - minI) : 0, rows = maxJ > minJ ? static_cast<size_t>(maxJ - minJ) : 0;
+        if (values.size() != w * rows) throw Error(GEM_ERR_INVALID, "Costmap::write: one byte per cell of the window");
+        map_.check(gem_costmap_write(map_.handle(), id_, minI, minJ, maxI, maxJ, values.empty() ? nullptr : values.data(), w), "gem_costmap_write");
+    }
+
+private:
+    static_assert(sizeof(Bounds) == 4 * sizeof(double), "bounds are four packed doubles");
+    static double* ptr(Bounds* b) { return b ? &b->min_x : nullptr; }
+    ElevationMap& map_;
+    int id_ = -1;
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -529,6 +529,76 @@ int  gem_global_loop_closure(gem_handle* h, int n_opt, const float* transforms, 
 int  gem_global_export(gem_handle* h, int index, void* points, long long max_points, long long* out_count);
 int  gem_global_count(gem_handle* h, int* out_submaps);
 
+/* ---- the costmap layers (layers/: PointMapLayer, pointMap_layer.cpp:45-100; ElevationMapLayer, elevationMap_layer.cpp:42-87) -----
+ * A costmap is a device-resident byte grid bound to the handle; a handle holds up to eight (a local one, a global one, a master).
+ * costmap_2d is not part of this library and not part of the reference tree: its pieces are RESTATED here from ROS noetic
+ * costmap_2d/src/costmap_2d.cpp and costmap_layer.cpp (tests/costmap_ref.py is the same statement in numpy).  The restatement is NOT
+ * verified against the library (there is none here; tools/ros_selfcheck.cpp's `cost` row settles it in a ROS workspace).  All
+ * arithmetic is in double unless marked.
+ *   constants    FREE_SPACE 0, LETHAL_OBSTACLE 254, NO_INFORMATION 255.
+ *   geometry     size_x, size_y (cells), resolution, origin_x, origin_y; index = my * size_x + mx;
+ *                sizeInMetersX = (size_x - 1 + 0.5) * resolution, Y likewise.
+ *   worldToMap   fails if wx < origin_x || wy < origin_y; else mx = (int)((wx - origin_x) / resolution), my likewise, and it succeeds
+ *                iff mx < size_x && my < size_y.  A deliberate difference: a non-finite wx or wy, or a quotient that does not fit an
+ *                int, fails (the reference's cast is undefined there).
+ *   gem_costmap_mark_points        PointMapLayer::updateBounds:55-81 over n PointXYZRGBICT records (host; _device: device memory,
+ *                untouched until gem_synchronize as for gem_add_device): for i = 0 .. n-1 IN ORDER px = (double)x, py = (double)y; a
+ *                record worldToMap refuses is skipped; else costmap[index] = ((double)travers > travers_thresh) ? FREE_SPACE :
+ *                LETHAL_OBSTACLE (a NaN travers is lethal), then touch(px, py): min_x = std::min(px, min_x), ... max_y = std::max(py,
+ *                max_y).  The result is that of this sequential loop: the LAST record of a cell decides.
+ *   gem_costmap_mark_grid_cloud    the same over the last capture's records (= gem_local_grid_cloud: grid_pc) where they lie.
+ *   gem_costmap_mark_global        the same over submap `index` of the stack, or with -1 over all of them in stack order, as one
+ *                input (= gem_global_export's records).
+ *   gem_costmap_mark_visual        ElevationMapLayer::updateBounds:58-81 with the last capture (gem_local_capture) standing for
+ *                visualMap_ as show() leaves it (EM.cpp:89-111): every one of the L * L cells is visited in grid_map's iteration order;
+ *                its position is getPositionFromIndex in double from the capture's geometry; a kept cell carries its traver, every
+ *                other cell NaN; is_obstacle = ((double)traver < travers_thresh), so a NaN cell is FREE_SPACE; worldToMap, the write
+ *                and touch as for points.  The test is `<` here and `>` in the point layer: at traver == travers_thresh the two layers
+ *                disagree, as the reference's do.
+ *   gem_costmap_update_origin      Costmap2D::updateOrigin: cell_ox = (int)((new_origin_x - origin_x) / resolution), truncating toward
+ *                zero, cell_oy likewise; both zero: nothing changes.  The new origin is origin + cell_o * resolution.  The overlap of
+ *                the old and the new window keeps its cells at their new places (lower_left = min(max(cell_o, 0), size), upper_right =
+ *                min(max(cell_o + size, 0), size)); every other cell becomes default_value.
+ *   gem_costmap_roll_to            the rolling_window_ line of both updateBounds (:48-49 / :45-46):
+ *                update_origin(robot_x - sizeInMetersX / 2, robot_y - sizeInMetersY / 2).
+ *   gem_costmap_reset              resetMaps: every cell becomes default_value.  default_value is a creation parameter: ObstacleLayer
+ *                (ElevationMapLayer's base) sets it to NO_INFORMATION or FREE_SPACE by track_unknown_space; PointMapLayer::onInitialize
+ *                never sets it.
+ *   gem_costmap_merge              onto master_id inside [min_i, max_i) x [min_j, max_j).  mode 0, PointMapLayer::updateCosts:86-100 =
+ *                CostmapLayer::updateWithOverwrite: a layer cell that is not NO_INFORMATION replaces the master cell.  mode 1,
+ *                updateWithMax: it replaces the master cell if that is NO_INFORMATION or smaller.  Equal sizes.
+ *   gem_costmap_read               the window's bytes, row j at out + (j - min_j) * row_stride (row_stride >= max_i - min_i).
+ *   gem_costmap_write              the reverse: the window's cells from the caller's bytes (setCost over a window): what other
+ *                layers of the caller's left in a master (inflation costs, a footprint) before a merge onto it.
+ *   gem_costmap_geometry           the configuration with the origin after rolling.
+ * bounds = {min_x, min_y, max_x, max_y}, in / out, merged as touch() does; they compare as values, not bits (with std::min a tie
+ * between -0 and +0 depends on the order).  With bounds NULL a mark only enqueues on the handle's stream and nothing waits.
+ * Left with the caller: useExtraBounds, updateFootprint / setConvexPolygonCost (four footprint points and a polygon fill), enabled_,
+ * the subscriptions and the layered costmap itself (master_grid.setCost from gem_costmap_read).  Every entry takes the handle's lock.
+ * GEM_ERR_INVALID, nothing changed: a bad id; a zero size (or more than 2^30 cells), a resolution not finite and positive, a
+ * non-finite origin or threshold; n < 0 or n above 2^31 - 2 (mark_global: the records of the call together); a window outside the
+ * map; mark_grid_cloud or mark_visual without a capture; mark_global without an enabled stack or with an index out of range; an
+ * origin step whose cell count does not fit an int; a merge mode other than 0 or 1; a handle with a communicator. */
+typedef struct gem_costmap_config {
+    unsigned int  size_x, size_y;
+    double        resolution, origin_x, origin_y;
+    unsigned char default_value;       /* 255 or 0 */
+} gem_costmap_config;
+int  gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id);
+int  gem_costmap_destroy(gem_handle* h, int id);
+int  gem_costmap_geometry(gem_handle* h, int id, gem_costmap_config* out);
+int  gem_costmap_reset(gem_handle* h, int id);
+int  gem_costmap_update_origin(gem_handle* h, int id, double new_origin_x, double new_origin_y);
+int  gem_costmap_roll_to(gem_handle* h, int id, double robot_x, double robot_y);
+int  gem_costmap_mark_points(gem_handle* h, int id, const void* points, long long n, double travers_thresh, double bounds[4]);
+int  gem_costmap_mark_points_device(gem_handle* h, int id, const void* d_points, long long n, double travers_thresh, double bounds[4]);
+int  gem_costmap_mark_grid_cloud(gem_handle* h, int id, double travers_thresh, double bounds[4]);
+int  gem_costmap_mark_global(gem_handle* h, int id, int index, double travers_thresh, double bounds[4]);
+int  gem_costmap_mark_visual(gem_handle* h, int id, double travers_thresh, double bounds[4]);
+int  gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_j, int max_i, int max_j, int mode);
+int  gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, unsigned char* out, size_t row_stride);
+int  gem_costmap_write(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, const unsigned char* in, size_t row_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,11 @@
 //                    1146-1156); tests/compose_ref.py restates the same contract in numpy.  Two details of that statement are decided
 //                    by this row and by nothing else: which sqrt overload PCL's `sqrt(nn_dists[k])` resolves to (the row prints which
 //                    value of gem_compose_params::flags matches) and that the product in sq_sum is a float product
+//   cost gem_costmap_* restates costmap_2d (ROS noetic costmap_2d.cpp / costmap_layer.cpp) as the reference's two layers call it
+//                    (layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87): worldToMap, getIndex, getSizeInMetersX / Y,
+//                    updateOrigin, resetMaps, touch, updateWithOverwrite, updateWithMax; tests/costmap_ref.py restates the same
+//                    contract in numpy.  The row drives the real Costmap2D / CostmapLayer calls through PointMapLayer's loop, a rolling
+//                    trajectory and both combination rules, and compares every byte, origin and bound
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -26,9 +31,10 @@
 //
 //   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) \
 //       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Lgem_amd/lib -lgem_hip -Wl,-rpath,$PWD/gem_amd/lib -L/opt/rocm/lib -lamdhip64 \
-//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
+//       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core -lcostmap_2d -llayers -lroscpp -lrosconsole -ltf2_ros $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
 //
-// It cannot be compiled where the test suite runs (no ROS, grid_map, OpenCV or PCL there).
+// It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
+// there, against the library's public headers as documented, and has not been through a compiler.
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -59,6 +65,9 @@
 #include <pcl/filters/statistical_outlier_removal.h>
 #include <pcl/search/kdtree.h>
 #include <pcl/point_types.h>
+#include <costmap_2d/cost_values.h>
+#include <costmap_2d/costmap_2d.h>
+#include <costmap_2d/costmap_layer.h>
 
 #include <limits>
 #include <map>
@@ -557,6 +566,99 @@ int check_sor(uint32_t seed)
     return 0;
 }
 
+// ---- cost ----------------------------------------------------------------------------------------------------------------------
+// The protected pieces of CostmapLayer the two layers use, made callable; no layered costmap behind it (matchSize is not used).
+struct CostProbe : costmap_2d::CostmapLayer {
+    CostProbe(unsigned sx, unsigned sy, double res, double ox, double oy, unsigned char def)
+    {
+        default_value_ = def;
+        enabled_ = true;
+        resizeMap(sx, sy, res, ox, oy);
+    }
+    using costmap_2d::CostmapLayer::touch;
+    using costmap_2d::CostmapLayer::updateWithMax;
+    using costmap_2d::CostmapLayer::updateWithOverwrite;
+    void updateBounds(double, double, double, double*, double*, double*, double*) override {}
+    void updateCosts(costmap_2d::Costmap2D&, int, int, int, int) override {}
+    void reset() override {}
+};
+
+bool same_costmap(gem_handle* h, int id, costmap_2d::Costmap2D& real, const char* what)
+{
+    const unsigned sx = real.getSizeInCellsX(), sy = real.getSizeInCellsY();
+    std::vector<unsigned char> got((size_t)sx * sy);
+    gem_costmap_config c{};
+    if (gem_costmap_read(h, id, 0, 0, (int)sx, (int)sy, got.data(), sx) != 0 || gem_costmap_geometry(h, id, &c) != 0) { ++g_failures; return false; }
+    if (c.origin_x != real.getOriginX() || c.origin_y != real.getOriginY()) { report(what, -1, c.origin_x, real.getOriginX()); return false; }
+    for (size_t i = 0; i < got.size(); ++i)
+        if (got[i] != real.getCharMap()[i]) { report(what, (long long)i, got[i], real.getCharMap()[i]); return false; }
+    return true;
+}
+
+// PointMapLayer::updateBounds' loop over seeded clouds (on and off the map, on its edges, NaN travers) on a real layer costmap, a
+// rolling trajectory through updateOrigin with sub-cell, multi-cell and larger-than-map steps, then both combination rules onto a
+// master that holds 0, 100, 254 and 255 -- against gem_costmap_mark_points / roll_to / merge / read.
+int check_cost(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    const unsigned sx = 75, sy = 40;
+    const double res = 0.2, thresh = 0.5;
+    CostProbe real(sx, sy, res, -7.25, 4.125, costmap_2d::NO_INFORMATION);
+    gem_costmap_config cc{};
+    cc.size_x = sx; cc.size_y = sy; cc.resolution = res; cc.origin_x = -7.25; cc.origin_y = 4.125; cc.default_value = costmap_2d::NO_INFORMATION;
+    int id = -1, master_id = -1;
+    CHECK_GEM(gem_costmap_create(h, &cc, &id));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    double robot_x = -7.25 + real.getSizeInMetersX() / 2, robot_y = 4.125 + real.getSizeInMetersY() / 2;
+    const double steps[6] = {0.07, 0.2, 0.33, 1.7, 9.0, 40.0};
+    for (int k = 0; k < 48; ++k) {
+        const int dx = (k % 8 < 3) - (k % 8 > 4), dy = ((k + 2) % 8 < 3) - ((k + 2) % 8 > 4);
+        robot_x += dx * steps[k % 6]; robot_y += dy * steps[(k + 1) % 6];
+        real.updateOrigin(robot_x - real.getSizeInMetersX() / 2, robot_y - real.getSizeInMetersY() / 2);
+        CHECK_GEM(gem_costmap_roll_to(h, id, robot_x, robot_y));
+        if (!same_costmap(h, id, real, "cost: updateOrigin")) break;
+        std::vector<Rec> cloud(4000);
+        for (size_t i = 0; i < cloud.size(); ++i) {
+            Rec& r = cloud[i];
+            r.x = (float)(real.getOriginX() + (u(rng) * 1.2 - 0.1) * sx * res); r.y = (float)(real.getOriginY() + (u(rng) * 1.2 - 0.1) * sy * res);
+            r.travers = (float)u(rng);
+            if (i % 97 == 0) r.travers = 0.5f;
+            if (i % 101 == 0) r.travers = std::numeric_limits<float>::quiet_NaN();
+            if (i % 503 == 0) { r.x = (float)real.getOriginX(); r.y = (float)real.getOriginY(); }
+        }
+        double want[4] = {1e30, 1e30, -1e30, -1e30}, got[4] = {1e30, 1e30, -1e30, -1e30};
+        for (const Rec& r : cloud) {                                     // pointMap_layer.cpp:55-81
+            unsigned int mx, my;
+            const double px = r.x, py = r.y;
+            if (!real.worldToMap(px, py, mx, my)) continue;
+            real.getCharMap()[real.getIndex(mx, my)] = r.travers > thresh ? costmap_2d::FREE_SPACE : costmap_2d::LETHAL_OBSTACLE;
+            real.touch(px, py, &want[0], &want[1], &want[2], &want[3]);
+        }
+        CHECK_GEM(gem_costmap_mark_points(h, id, cloud.data(), (long long)cloud.size(), thresh, got));
+        for (int b = 0; b < 4; ++b) if (got[b] != want[b]) report("cost: touch bounds", b, got[b], want[b]);
+        if (!same_costmap(h, id, real, "cost: PointMapLayer::updateBounds")) break;
+    }
+    for (int mode = 0; mode < 2; ++mode) {
+        costmap_2d::Costmap2D master(sx, sy, res, real.getOriginX(), real.getOriginY(), costmap_2d::FREE_SPACE);
+        const unsigned char vals[4] = {0, 100, 254, 255};
+        for (size_t i = 0; i < (size_t)sx * sy; ++i) master.getCharMap()[i] = vals[rng() % 4];
+        cc.origin_x = real.getOriginX(); cc.origin_y = real.getOriginY(); cc.default_value = costmap_2d::FREE_SPACE;
+        CHECK_GEM(gem_costmap_create(h, &cc, &master_id));
+        CHECK_GEM(gem_costmap_write(h, master_id, 0, 0, (int)sx, (int)sy, master.getCharMap(), sx));
+        if (mode == 0) real.updateWithOverwrite(master, 7, 3, 61, 33);
+        else real.updateWithMax(master, 7, 3, 61, 33);
+        CHECK_GEM(gem_costmap_merge(h, id, master_id, 7, 3, 61, 33, mode));
+        same_costmap(h, master_id, master, mode ? "cost: updateWithMax" : "cost: updateWithOverwrite");
+        CHECK_GEM(gem_costmap_destroy(h, master_id));
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -567,8 +669,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_voxel(seed + 2u);
     if (rc == 0) rc = check_global(seed + 3u);
     if (rc == 0) rc = check_sor(seed + 4u);
+    if (rc == 0) rc = check_cost(seed + 5u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all five rows pinned on the installed grid_map_core, OpenCV and PCL (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all six rows pinned on the installed grid_map_core, OpenCV, PCL and costmap_2d (seed %u)\n", seed);
     return 0;
 }
