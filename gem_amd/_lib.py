@@ -41,6 +41,22 @@ class ComposeParams(C.Structure):
     _fields_ = [("mean_k", c_int), ("stddev_mul", c_double), ("travers_threshold", c_double), ("flags", c_int)]
 
 
+class OctreeParams(C.Structure):
+    """gem_octree_params: a ColorOcTree's resolution and (0 = octomap's defaults) its hit probability and clamps."""
+    _fields_ = [("resolution", c_double), ("prob_hit", c_double), ("clamp_min", c_double), ("clamp_max", c_double), ("flags", c_int)]
+
+
+class OctreeStats(C.Structure):
+    """gem_octree_stats"""
+    _fields_ = [("points_in", c_longlong), ("points_keyed", c_longlong), ("leaves_depth16", c_longlong), ("pruned_leaves", c_longlong),
+                ("nodes", c_longlong), ("bytes", c_longlong), ("coupled_blocks", c_longlong * 3), ("fallback_points", c_longlong)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "coupled_blocks"}
+        d["coupled_blocks"] = [int(v) for v in self.coupled_blocks]
+        return d
+
+
 class CostmapConfig(C.Structure):
     """gem_costmap_config: a costmap's geometry and the value of a cell nothing has written."""
     _fields_ = [("size_x", C.c_uint), ("size_y", C.c_uint), ("resolution", c_double), ("origin_x", c_double), ("origin_y", c_double),
@@ -137,6 +153,11 @@ SIGNATURES = {
     "gem_local_size": (c_int, [c_void_p, POINTER(c_longlong)]),
     "gem_local_compose": (c_int, [c_void_p, POINTER(ComposeParams), c_void_p, c_void_p, POINTER(c_int), POINTER(c_double)]),
     "gem_local_compose_distances": (c_int, [c_void_p, POINTER(ComposeParams), c_void_p, POINTER(c_int)]),
+    "gem_octree_build": (c_int, [c_void_p, c_int, POINTER(OctreeParams), c_void_p, c_longlong, POINTER(OctreeStats)]),
+    "gem_octree_build_device": (c_int, [c_void_p, c_int, POINTER(OctreeParams), c_void_p, c_longlong, POINTER(OctreeStats)]),
+    "gem_local_compose_octrees": (c_int, [c_void_p, POINTER(ComposeParams), POINTER(OctreeParams), POINTER(OctreeParams), POINTER(c_int),
+                                          POINTER(c_double), POINTER(OctreeStats)]),
+    "gem_octree_read": (c_int, [c_void_p, c_int, c_void_p, C.c_size_t, POINTER(C.c_size_t)]),
     "gem_global_enable": (c_int, [c_void_p, c_longlong]),
     "gem_global_push_local": (c_int, [c_void_p, c_int, POINTER(c_int)]),
     "gem_global_push": (c_int, [c_void_p, c_void_p, c_longlong, POINTER(c_int)]),

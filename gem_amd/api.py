@@ -738,6 +738,54 @@ class ElevationMap:
                     "gem_local_compose_distances")
         return out[:n.value].copy()
 
+    # -- pointCloudtoOctomap's insertion loop and fullMapToMsg (EMg.cpp:1158-1173) ---------------------------------------------------
+    OCTREE_ROAD, OCTREE_OBSTACLE, OCTREE_USER0, OCTREE_USER1 = 0, 1, 2, 3
+
+    @staticmethod
+    def _octree_params(resolution, prob_hit=0.0, clamp_min=0.0, clamp_max=0.0):
+        return _lib.OctreeParams(float(resolution), float(prob_hit), float(clamp_min), float(clamp_max), 0)
+
+    def octree_build(self, slot: int, cloud, resolution: float, prob_hit: float = 0.0, clamp_min: float = 0.0, clamp_max: float = 0.0) -> dict:
+        """A cleared octomap::ColorOcTree(resolution) after updateNode + integrateNodeColor per record of `cloud` in order and
+        updateInnerOccupancy, as fullMapToMsg's byte stream, kept on the device in `slot` (gem_octree_build; a CUDA/HIP torch tensor
+        of 32-byte records goes through gem_octree_build_device).  Returns the build's statistics; octree_read gives the bytes."""
+        p = self._octree_params(resolution, prob_hit, clamp_min, clamp_max)
+        st = _lib.OctreeStats()
+        if _is_device_tensor(cloud):
+            assert cloud.is_contiguous() and cloud.numel() * cloud.element_size() % 32 == 0
+            n = cloud.numel() * cloud.element_size() // 32
+            self._check(self._lib.gem_octree_build_device(self._h, int(slot), C.byref(p), C.c_void_p(cloud.data_ptr()), n, C.byref(st)),
+                        "gem_octree_build_device")
+        else:
+            a = np.ascontiguousarray(cloud, POINT_DTYPE)
+            self._check(self._lib.gem_octree_build(self._h, int(slot), C.byref(p), a.ctypes.data_as(C.c_void_p), a.shape[0], C.byref(st)),
+                        "gem_octree_build")
+        return st.as_dict()
+
+    def octree_size(self, slot: int) -> int:
+        n = C.c_size_t()
+        self._check(self._lib.gem_octree_read(self._h, int(slot), None, 0, C.byref(n)), "gem_octree_read")
+        return int(n.value)
+
+    def octree_read(self, slot: int) -> bytes:
+        """msg.data of the slot's tree (gem_octree_read); id "ColorOcTree", binary = false and the resolution stay with the caller."""
+        out = np.empty(max(self.octree_size(slot), 1), np.uint8)
+        n = C.c_size_t()
+        self._check(self._lib.gem_octree_read(self._h, int(slot), out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)), "gem_octree_read")
+        return out[:n.value].tobytes()
+
+    def local_compose_octrees(self, road_resolution: float = 0.2, obstacle_resolution: float = 0.1, mean_k: int = 20, stddev_mul: float = 1.0,
+                              travers_threshold: float = 0.0, sqrt_double: bool = False, road_params=None, obstacle_params=None):
+        """local_compose with the two lists kept on the device and built into the slots OCTREE_ROAD and OCTREE_OBSTACLE
+        (gem_local_compose_octrees): returns (road count, obstacle count, removed, threshold, [road stats, obstacle stats])."""
+        p = self._compose_params(mean_k, stddev_mul, travers_threshold, sqrt_double)
+        rp = self._octree_params(road_resolution, **(road_params or {}))
+        op = self._octree_params(obstacle_resolution, **(obstacle_params or {}))
+        counts, thr, st = (C.c_int * 3)(), C.c_double(), (_lib.OctreeStats * 2)()
+        self._check(self._lib.gem_local_compose_octrees(self._h, C.byref(p), C.byref(rp), C.byref(op), counts, C.byref(thr), st),
+                    "gem_local_compose_octrees")
+        return int(counts[0]), int(counts[1]), int(counts[2]), float(thr.value), [st[0].as_dict(), st[1].as_dict()]
+
     # -- the submap stack (globalMap_: updateLocalMap's new-keyframe branch, EMg.cpp:630-687; updateGlobalMap, :773-905) ----------
     def global_enable(self, capacity: int = 1 << 20) -> None:
         """Switch the device submap stack on, empty, with room for `capacity` records (it grows on demand); 0 switches it off and

@@ -179,6 +179,7 @@ void gem_destroy(gem_handle* h)
     local_free(h);
     global_free(h);
     costmap_free(h);
+    octree_free(h);
     if (h->layers.elevation) hipFree(h->layers.elevation);      // base of the single layer allocation
     if (h->d_counters) hipFree(h->d_counters);
     for (Arena* a : {&h->stage, &h->scratch, &h->dbg, &h->color, &h->ray, &h->sh_dev, &h->sh_recv_hv[0], &h->sh_recv_key[0], &h->sh_recv_rng[0],

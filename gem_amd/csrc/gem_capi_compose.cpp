@@ -88,6 +88,36 @@ int distances(gem_handle* h, const gem_compose_params* p, uint32_t* out_n, doubl
 
 namespace gemi {
 
+int compose_check(gem_handle* h, const gem_compose_params* p, const char* what) { return check(h, p, what); }
+
+// the filter and the split of the previous capture into Compose::road / Compose::obstacle (device; a list that is not wanted is only
+// counted); tot[3]: road, obstacle, removed
+int compose_split(gem_handle* h, const gem_compose_params* p, bool want_road, bool want_obstacle, uint32_t tot[3], double* out_threshold)
+{
+    auto& cp = h->compose;
+    const size_t cells = (size_t)h->cells;
+    int rc;
+    if ((rc = ensure(h, cp.road, cells * kRec)) || (rc = ensure(h, cp.obstacle, cells * kRec)) ||
+        (rc = ensure(h, cp.cnt, (size_t)compact_blocks(h->cells) * 3 * 4 + 64))) return rc;
+    uint32_t n = 0;
+    double thr = 0.0;
+    int filter = 0;
+    if ((rc = distances(h, p, &n, &thr, &filter))) return rc;
+    ComposeSplitArgs s{};
+    s.rec = static_cast<const LocalRecord*>(h->local.slot[h->local.prev].rec.p);
+    s.dist = static_cast<const float*>(cp.dist.p);
+    s.count = static_cast<uint32_t*>(h->local.small.p) + h->local.prev;
+    s.threshold = thr; s.travers_threshold = p->travers_threshold; s.filter = filter;
+    s.road = want_road ? static_cast<LocalRecord*>(cp.road.p) : nullptr;
+    s.obstacle = want_obstacle ? static_cast<LocalRecord*>(cp.obstacle.p) : nullptr;
+    GEM_HIP(h, launch_compose_split(h->stream, s, n, static_cast<uint32_t*>(cp.cnt.p), word(h, kWordTotals)));
+    tot[0] = tot[1] = tot[2] = 0;
+    { HostXfer c{tot, word(h, kWordTotals), 12}; if ((rc = download_arrays(h, &c, 1, 0))) return rc; }
+    if ((unsigned long long)tot[0] + tot[1] + tot[2] > n) return fail(h, GEM_ERR_HIP, "gem_local_compose: class counts out of range");
+    *out_threshold = thr;
+    return GEM_OK;
+}
+
 void compose_free(gem_handle* h)
 {
     auto& cp = h->compose;
@@ -109,26 +139,11 @@ int gem_local_compose(gem_handle* h, const gem_compose_params* p, void* road, vo
     std::lock_guard<std::mutex> lk(h->mu);
     hipSetDevice(h->device);
     int rc;
-    if ((rc = check(h, p, "gem_local_compose"))) return rc;
+    if ((rc = compose_check(h, p, "gem_local_compose"))) return rc;
     auto& cp = h->compose;
-    const size_t cells = (size_t)h->cells;
-    if ((rc = ensure(h, cp.road, cells * kRec)) || (rc = ensure(h, cp.obstacle, cells * kRec)) ||
-        (rc = ensure(h, cp.cnt, (size_t)compact_blocks(h->cells) * 3 * 4 + 64))) return rc;
-    uint32_t n = 0;
-    double thr = 0.0;
-    int filter = 0;
-    if ((rc = distances(h, p, &n, &thr, &filter))) return rc;
-    ComposeSplitArgs s{};
-    s.rec = static_cast<const LocalRecord*>(h->local.slot[h->local.prev].rec.p);
-    s.dist = static_cast<const float*>(cp.dist.p);
-    s.count = static_cast<uint32_t*>(h->local.small.p) + h->local.prev;
-    s.threshold = thr; s.travers_threshold = p->travers_threshold; s.filter = filter;
-    s.road = road ? static_cast<LocalRecord*>(cp.road.p) : nullptr;
-    s.obstacle = obstacle ? static_cast<LocalRecord*>(cp.obstacle.p) : nullptr;
-    GEM_HIP(h, launch_compose_split(h->stream, s, n, static_cast<uint32_t*>(cp.cnt.p), word(h, kWordTotals)));
     uint32_t tot[3] = {0, 0, 0};
-    { HostXfer c{tot, word(h, kWordTotals), 12}; if ((rc = download_arrays(h, &c, 1, 0))) return rc; }
-    if ((unsigned long long)tot[0] + tot[1] + tot[2] > n) return fail(h, GEM_ERR_HIP, "gem_local_compose: class counts out of range");
+    double thr = 0.0;
+    if ((rc = compose_split(h, p, road != nullptr, obstacle != nullptr, tot, &thr))) return rc;
     HostXfer d[2];
     int nd = 0;
     if (road && tot[0]) d[nd++] = HostXfer{road, cp.road.p, (size_t)tot[0] * kRec};

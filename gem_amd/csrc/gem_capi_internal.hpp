@@ -294,6 +294,20 @@ struct gem_handle {
         Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
         std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
     } costmap;
+    // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)
+    struct Octree {
+        static constexpr int kSlots = 4;
+        Arena state, hist;              // OctState and the two digit histograms: kept between builds as the kernels leave them
+        bool dirty = false;             // a build did not run to its end: both are set again before the next one
+        Arena tab;                      // value (float) and blend p (double) per hit count
+        double tab_key[3] = {-1, -1, -1};   // the probabilities the device tables were built from
+        Arena in, work;                 // a host cloud of gem_octree_build | everything sized by the call's n (gem_capi_octree.cpp carves it)
+        struct Slot {
+            Arena out;                  // the stream
+            long long bytes = 0;
+            gem_octree_stats stats{};
+        } slot[kSlots];
+    } octree;
     bool  dbg_on = false;
     bool  dbg_frame = false;            // debug knob: with the stamps on, a stream of single sweeps still runs as k_frame (its tiles AND its binning blocks are stamped)
     long long sort_fallbacks = 0;      // passes whose forced sorted form / pass count did not fit the map and took the other form (gem_debug_get)
@@ -390,6 +404,11 @@ void local_free(gem_handle* h);                 // gem_capi_local.cpp: the local
 int local_grid_count(gem_handle* h, uint32_t* n);
 int local_export_to(gem_handle* h, void* dst, uint32_t n_grid, bool clear);
 void compose_free(gem_handle* h);               // gem_capi_compose.cpp: the compose arenas (local_free)
+// gem_capi_compose.cpp, for gem_local_compose_octrees: gem_local_compose's argument checks, and its filter and split with the two
+// lists left in Compose::road / Compose::obstacle on the device; tot[3]: road, obstacle, removed
+int compose_check(gem_handle* h, const gem_compose_params* p, const char* what);
+int compose_split(gem_handle* h, const gem_compose_params* p, bool want_road, bool want_obstacle, uint32_t tot[3], double* out_threshold);
+void octree_free(gem_handle* h);                // gem_capi_octree.cpp: the octree builder's arenas and the slots' streams (gem_destroy)
 void global_free(gem_handle* h);                // gem_capi_global.cpp: the submap stack's arenas (gem_destroy, gem_global_enable(0))
 void costmap_free(gem_handle* h);               // gem_capi_costmap.cpp: every costmap of the handle and their shared arenas (gem_destroy)
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points

@@ -1,10 +1,7 @@
 // gem_voxel.hip -- one pcl::VoxelGrid<pcl::PCLPointCloud2> stage (as pcl_ros's nodelet runs it) on the device, gfx950.
 // The contract is in include/gem_hip.h (gem_voxel_device); the launch structure in gem_voxel.hpp.
 //
-// Records: workgroup b owns positions [b * 4096, b * 4096 + 4096); wave w of it the 512 from b * 4096 + w * 512, item k the 64 from
-// there + k * 64.  The order (w, k, lane) IS the position order, so every per-workgroup rank below is stable.
-// Hand-overs inside a launch: every workgroup publishes with plain stores / atomics, fences (agent release) and adds one to the
-// launch's ticket; the workgroup that draws the last ticket acquires and finishes the step.  Nothing waits for another workgroup.
+// The record layout of a workgroup, the hand-over to the last workgroup to arrive and the stable LSD passes are gem_lsd.hpp's.
 #include "gem_voxel.hpp"
 #include "gem_wave.hpp"
 
@@ -68,52 +65,9 @@ __device__ __forceinline__ uint32_t vox_key(float4 p, const Geo& g)
     return i * g.mul[0] + j * g.mul[1] + k * g.mul[2];
 }
 
-__device__ __forceinline__ long long rec_pos(int k)
-{
-    return (long long)blockIdx.x * kVoxTile + (long long)(threadIdx.x >> 6) * (64 * kVoxItems) + k * 64 + lane_id();
-}
+__device__ __forceinline__ long long rec_pos(int k) { return lsd_pos(k); }
 
 __device__ __forceinline__ long long input_count(const VoxStageArgs& a) { return a.n_dev ? (long long)*a.n_dev : a.n; }
-
-// every thread fences its own stores / atomics (agent release), ONE lane draws a ticket; true in the workgroup that drew the last
-// one (which resets the ticket for the next launch and acquires: its loads below see every other workgroup's data)
-__device__ __forceinline__ bool last_arrival(uint32_t* ticket, int nb, uint32_t* s_flag)
-{
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = t == (uint32_t)nb - 1u;
-        if (last) __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        *s_flag = last ? 1u : 0u;
-    }
-    __syncthreads();
-    const bool last = *s_flag != 0u;
-    if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return last;
-}
-
-// in place: counts [nb][kVoxBins] -> the position of every (workgroup, digit) run in the next pass's output (digit-major, then
-// workgroup).  One workgroup; thread t owns digits 4t .. 4t + 3.
-__device__ void scan_hist(uint32_t* hist, int nb, uint32_t* s_scan)
-{
-    uint4* h4 = reinterpret_cast<uint4*>(hist);
-    uint4 tot = make_uint4(0u, 0u, 0u, 0u);
-    for (int b = 0; b < nb; ++b) {
-        const uint4 v = h4[(size_t)b * (kVoxBins / 4) + threadIdx.x];
-        tot.x += v.x; tot.y += v.y; tot.z += v.z; tot.w += v.w;
-    }
-    uint32_t all;
-    const uint32_t ex = block_exclusive_scan<kVoxThreads>(tot.x + tot.y + tot.z + tot.w, s_scan, &all);
-    uint4 run = make_uint4(ex, ex + tot.x, ex + tot.x + tot.y, ex + tot.x + tot.y + tot.z);
-    for (int b = 0; b < nb; ++b) {
-        const uint4 v = h4[(size_t)b * (kVoxBins / 4) + threadIdx.x];
-        h4[(size_t)b * (kVoxBins / 4) + threadIdx.x] = run;
-        run.x += v.x; run.y += v.y; run.z += v.z; run.w += v.w;
-    }
-}
-
-static_assert(kVoxThreads * 4 == kVoxBins, "thread t owns digits 4t .. 4t + 3");
 
 } // namespace
 
@@ -241,86 +195,34 @@ __global__ __launch_bounds__(kVoxThreads) void k_vox_hist(VoxStageArgs a)
     }
     __syncthreads();
     reinterpret_cast<uint4*>(a.hist[0])[(size_t)blockIdx.x * (kVoxBins / 4) + threadIdx.x] = reinterpret_cast<const uint4*>(s_h)[threadIdx.x];
-    if (last_arrival(&a.st->ticket[1], a.nb, &s_last)) scan_hist(a.hist[0], a.nb, s_scan);
+    if (last_arrival(&a.st->ticket[1], a.nb, &s_last)) lsd_scan_hist(a.hist[0], a.nb, s_scan);
 }
 
 // ---- 3-5: stable LSD passes over (key, input position) ---------------------------------------------------------------------
 template <int PASS>
 __global__ __launch_bounds__(kVoxThreads) void k_vox_scatter(VoxStageArgs a)
 {
-    constexpr int NW = kVoxThreads / 64;
-    __shared__ uint32_t s_off[kVoxBins];
-    __shared__ uint16_t s_w[NW][kVoxBins];               // per wave: running count per digit, then the waves' exclusive prefix
-    __shared__ uint32_t s_scan[16];
-    __shared__ uint32_t s_last;
     if (a.st->mode != kVoxSort) return;
     const uint32_t S = a.st->S;
     const long long n = input_count(a);
     const Geo g = load_geo(a.st);
-    {   // this workgroup's run positions; the row is zeroed behind the read (pass PASS + 2 counts into it)
-        uint4* row = reinterpret_cast<uint4*>(a.hist[PASS & 1]) + (size_t)blockIdx.x * (kVoxBins / 4);
-        reinterpret_cast<uint4*>(s_off)[threadIdx.x] = row[threadIdx.x];
-        row[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-        uint32_t* w32 = reinterpret_cast<uint32_t*>(&s_w[0][0]);
-        for (int i = threadIdx.x; i < NW * kVoxBins / 2; i += kVoxThreads) w32[i] = 0u;
-    }
-    __syncthreads();
-    const int w = (int)(threadIdx.x >> 6);
-    const uint64_t lt = lanemask_lt();
-    uint32_t key[kVoxItems], src[kVoxItems], rank[kVoxItems];
-    bool valid[kVoxItems];
-#pragma unroll
-    for (int k = 0; k < kVoxItems; ++k) {
-        const long long j = rec_pos(k);
+    auto load = [&](long long j, uint32_t& key, uint32_t& src) -> bool {
         if constexpr (PASS == 0) {
-            valid[k] = false; key[k] = 0u;
+            src = (uint32_t)j;
             if (j < n) {
                 const float4 p = a.in[j];
-                if (survives(p, a)) { valid[k] = true; key[k] = vox_key(p, g); }
+                if (survives(p, a)) { key = vox_key(p, g); return true; }
             }
-            src[k] = (uint32_t)j;
+            return false;
         } else {
-            valid[k] = j < (long long)S;
-            key[k] = valid[k] ? a.key[(PASS - 1) & 1][j] : 0u;
-            src[k] = valid[k] ? a.src[(PASS - 1) & 1][j] : 0u;
+            const bool valid = j < (long long)S;
+            key = valid ? a.key[(PASS - 1) & 1][j] : 0u;
+            src = valid ? a.src[(PASS - 1) & 1][j] : 0u;
+            return valid;
         }
-        const uint32_t d = (key[k] >> (kVoxDigit * PASS)) & (kVoxBins - 1);
-        const uint64_t peers = wave_peers(valid[k], d, kVoxDigit);
-        const uint32_t before = (uint32_t)__popcll(peers & lt);
-        rank[k] = 0u;
-        if (valid[k]) {
-            const uint32_t run = s_w[w][d];
-            rank[k] = run + before;
-            if (before == 0u) s_w[w][d] = (uint16_t)(run + (uint32_t)__popcll(peers));
-        }
-    }
-    __syncthreads();
-    for (int d = threadIdx.x; d < kVoxBins; d += kVoxThreads) {
-        uint32_t acc = 0u;
-#pragma unroll
-        for (int ww = 0; ww < NW; ++ww) { const uint32_t c = s_w[ww][d]; s_w[ww][d] = (uint16_t)acc; acc += c; }
-    }
-    __syncthreads();
-    uint32_t* key_out = a.key[PASS & 1];
-    uint32_t* src_out = a.src[PASS & 1];
-#pragma unroll
-    for (int k = 0; k < kVoxItems; ++k) {
-        const uint32_t d = (key[k] >> (kVoxDigit * PASS)) & (kVoxBins - 1);
-        uint32_t p = 0u;
-        if (valid[k]) {
-            p = s_off[d] + s_w[w][d] + rank[k];
-            key_out[p] = key[k];
-            src_out[p] = src[k];
-        }
-        if constexpr (PASS < 2) {                          // digit PASS + 1 of the record, counted for the workgroup that reads it next
-            const uint32_t comb = (p / (uint32_t)kVoxTile) * (uint32_t)kVoxBins + ((key[k] >> (kVoxDigit * (PASS + 1))) & (kVoxBins - 1));
-            const uint64_t pe = wave_peers_few(valid[k], comb, 32);
-            if (valid[k] && (pe & lt) == 0ull) atomicAdd(&a.hist[(PASS + 1) & 1][comb], (uint32_t)__popcll(pe));
-        }
-    }
-    if constexpr (PASS < 2) {
-        if (last_arrival(&a.st->ticket[2 + PASS], a.nb, &s_last)) scan_hist(a.hist[(PASS + 1) & 1], a.nb, s_scan);
-    }
+    };
+    lsd_scatter_pass<uint32_t, (PASS < 2)>(kVoxDigit * PASS, true, load, a.key[PASS & 1], a.src[PASS & 1], a.hist[PASS & 1], a.hist[(PASS + 1) & 1],
+                               &a.st->ticket[2 + PASS], a.nb);
 }
 
 // ---- 6: voxel heads, m -----------------------------------------------------------------------------------------------------

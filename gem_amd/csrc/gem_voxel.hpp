@@ -10,17 +10,19 @@
 #pragma once
 
 #include "../../include/gem_hip.h"
+#include "gem_lsd.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace gem {
 
-constexpr int kVoxThreads = 512;                      // 8 waves
-constexpr int kVoxItems = 8;                          // records per thread
-constexpr int kVoxTile = kVoxThreads * kVoxItems;     // records per workgroup (4096): wave w takes [w * 512, w * 512 + 512)
-constexpr int kVoxDigit = 11;                         // bits per sort pass (three passes cover the 32-bit key)
-constexpr int kVoxBins = 1 << kVoxDigit;
+// the sort's geometry is gem_lsd.hpp's (shared with the octree builder); the other kernels of a stage walk the records the same way
+constexpr int kVoxThreads = kLsdThreads;              // 8 waves
+constexpr int kVoxItems = kLsdItems;                  // records per thread
+constexpr int kVoxTile = kLsdTile;                    // records per workgroup (4096): wave w takes [w * 512, w * 512 + 512)
+constexpr int kVoxDigit = kLsdDigit;                  // bits per sort pass (three passes cover the 32-bit key)
+constexpr int kVoxBins = kLsdBins;
 
 enum { kVoxSort = 0, kVoxPassThrough = 1, kVoxEmpty = 2 };
 

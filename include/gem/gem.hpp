@@ -362,6 +362,15 @@ private:
 // INTEGRATION.md.  Records: PointXYZRGBICT with pad = 1 and a = 0; exported entries carry their intensity (the reference's
 // localHashtoPointCloud leaves it unset).
 // ---------------------------------------------------------------------------------------------
+// What octomap_msgs::fullMapToMsg would put into an Octomap message for the ColorOcTree pointCloudtoOctomap fills
+// (ElevationMapping.cpp:1158-1173): msg.data, msg.resolution; msg.id = id(), msg.binary = false.  gem_hip.h states the contract.
+struct ColorOcTreeData {
+    std::vector<int8_t> data;           // msg.data (octomap_msgs/Octomap: int8[])
+    double resolution = 0.0;
+    gem_octree_stats stats{};
+    static const char* id() { return "ColorOcTree"; }
+};
+
 class LocalMap {
 public:
     // capacity: initial entries (grows on demand)
@@ -436,8 +445,50 @@ public:
         c.removed = counts[2];
         return c;
     }
+    // ... and with the insertion loop: composingGlobalMap's two trees as their message bytes.  The two lists never leave the device.
+    struct ComposedOcTrees {
+        ColorOcTreeData road, obstacle;
+        int roadPoints = 0, obstaclePoints = 0, removed = 0;
+        double threshold = 0.0;
+    };
+    ComposedOcTrees compose_octrees(double roadResolution = 0.2, double obstacleResolution = 0.1, int meanK = 20, double stddevMul = 1.0,
+                                   double traversThreshold = 0.0, bool sqrtDouble = false)
+    {
+        gem_compose_params p{};
+        p.mean_k = meanK; p.stddev_mul = stddevMul; p.travers_threshold = traversThreshold;
+        p.flags = sqrtDouble ? GEM_COMPOSE_SQRT_DOUBLE : 0;
+        gem_octree_params rp{}, op{};
+        rp.resolution = roadResolution; op.resolution = obstacleResolution;
+        int counts[3] = {0, 0, 0};
+        gem_octree_stats st[2] = {};
+        ComposedOcTrees c;
+        map_.check(gem_local_compose_octrees(map_.handle(), &p, &rp, &op, counts, &c.threshold, st), "gem_local_compose_octrees");
+        c.roadPoints = counts[0]; c.obstaclePoints = counts[1]; c.removed = counts[2];
+        c.road = readOcTree(GEM_OCTREE_ROAD, roadResolution, st[0]);
+        c.obstacle = readOcTree(GEM_OCTREE_OBSTACLE, obstacleResolution, st[1]);
+        return c;
+    }
+    // pointCloudtoOctomap's loop over a caller's cloud (e.g. visualOctomap's visualCloud_) in slot GEM_OCTREE_USER0 / _USER1
+    ColorOcTreeData build_octree(const std::vector<PointXYZRGBICT>& cloud, double resolution, int slot = GEM_OCTREE_USER0)
+    {
+        gem_octree_params q{};
+        q.resolution = resolution;
+        gem_octree_stats st{};
+        map_.check(gem_octree_build(map_.handle(), slot, &q, cloud.data(), static_cast<long long>(cloud.size()), &st), "gem_octree_build");
+        return readOcTree(slot, resolution, st);
+    }
 
 private:
+    ColorOcTreeData readOcTree(int slot, double resolution, const gem_octree_stats& st)
+    {
+        ColorOcTreeData t;
+        t.resolution = resolution; t.stats = st;
+        t.data.resize(static_cast<size_t>(st.bytes));
+        size_t n = 0;
+        map_.check(gem_octree_read(map_.handle(), slot, t.data.empty() ? nullptr : t.data.data(), t.data.size(), &n), "gem_octree_read");
+        if (n != t.data.size()) throw Error(GEM_ERR_INVALID, "gem_octree_read: the slot was rebuilt by another thread");
+        return t;
+    }
     size_t cells() const { const size_t L = static_cast<size_t>(map_.length()); return L * L; }
     ElevationMap& map_;
     std::vector<PointXYZRGBICT> road_, obstacle_;      // compose()'s landing room, L * L records each once it has been called

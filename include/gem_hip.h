@@ -599,6 +599,79 @@ int  gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_
 int  gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, unsigned char* out, size_t row_stride);
 int  gem_costmap_write(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, const unsigned char* in, size_t row_stride);
 
+/* ---- pointCloudtoOctomap's insertion loop (EMg.cpp:1158-1173) and fullMapToMsg on the device ---------------------------------------
+ *   gem_octree_build           a host PointXYZRGBICT cloud -> the byte stream octomap_msgs::fullMapToMsg would put into msg.data for
+ *                              a cleared octomap::ColorOcTree after, per record IN ORDER, updateNode(point3d(x, y, z), true) and
+ *                              integrateNodeColor(x, y, z, r, g, b), then updateInnerOccupancy().  The stream stays on the device.
+ *   gem_octree_build_device    the same for a cloud in device memory (untouched until gem_synchronize, as for gem_add_device).
+ *   gem_local_compose_octrees  gem_local_compose with the road and obstacle lists kept on the device and built into slots
+ *                              GEM_OCTREE_ROAD and GEM_OCTREE_OBSTACLE: same counts and threshold, bit for bit, same preconditions.
+ *   gem_octree_read            the stream of a slot.  data NULL: only *out_bytes.  capacity below the size: GEM_ERR_INVALID with
+ *                              *out_bytes filled in.
+ * octomap is not part of this library; the contract is RESTATED here from octomap 1.8 / 1.9 (OcTreeBaseImpl.hxx, OccupancyOcTreeBase.hxx,
+ * ColorOcTree.cpp; tests/octree_ref.py is the same statement in Python, as a literal pointer tree and in the array form of the device):
+ *   constants  tree_depth 16 (a root-to-leaf path has 17 nodes), tree_max_val 32768, rf = 1.0 / resolution in double.
+ *              hit = (float)log(0.7 / 0.3); clamps cmax = (float)log(0.971 / 0.029), cmin = (float)log(0.1192 / 0.8808); a non-zero
+ *              probability P of the parameters gives (float)log(P / (1 - P)) instead.  A new node has value 0.0f and colour
+ *              (255, 255, 255), which means "not set": isColorSet is "any channel != 255".
+ *   key        per axis k = (int)floor(rf * (double)coord) + 32768, valid iff 0 <= k < 65536; a point with an invalid key on any axis
+ *              is skipped by both calls.  DELIBERATE DIFFERENCE: a non-finite coordinate is skipped (the library's cast is undefined).
+ *              The child index at bit d of the keys is xbit + 2 ybit + 4 zbit.
+ *   updateNode if search(key) finds a node whose value is >= cmax: nothing (search returns a childless node above depth 16: a pruned
+ *              leaf).  Otherwise descend from the root: a missing child of a node that has no children and was not created in this
+ *              call means the node is pruned, and it is expanded first (eight children, each copying its value and colour); otherwise
+ *              the missing child is created.  At depth 16 value = value + hit in float, clamped to [cmin, cmax].  On the way back up,
+ *              at every ancestor: pruneNode succeeds iff all eight children exist, none has children and all eight VALUES are equal
+ *              (colour is ignored); the node then takes child 0's value and colour, and if that colour is set its colour becomes
+ *              getAverageChildColor(); the children are deleted.  Otherwise value = max(children).
+ *   integrateNodeColor   n = search(key).  Colour not set: n takes (r, g, b).  Otherwise p = 1. - 1. / (1. + exp((double)value)) and each
+ *              channel becomes (uint8_t)((double)prev * p + (double)c * (0.99 - p)), in double, no FMA.
+ *   updateInnerOccupancy bottom-up over every node that has children: value = max over the existing children; colour = per-channel
+ *              integer mean (int sums, /= count) over the children whose colour is set, (255, 255, 255) if none is.  Nothing is pruned
+ *              here or in the writer.
+ *   stream     pre-order from the root; each node 8 bytes: value (float, little-endian), r, g, b, one byte with bit i set iff child i
+ *              exists; children in index order.  DELIBERATE DIFFERENCE: an empty tree (no valid point) gives zero bytes.  The message's
+ *              id "ColorOcTree", binary = false and resolution stay with the caller.
+ * NOT verified against octomap (there is none here; tools/ros_selfcheck.cpp's `octo` row settles them in a ROS workspace): (1) that the
+ * installed version prunes on value only and recolours a pruned node as above (1.8 and 1.9 should; 1.6 differs); (2) the host libm's
+ * exp for the handful of values that occur; (3) that the colour blend is compiled without contraction; (4) the (uint8_t) cast of the
+ * blend, which is always < 253 here; (5) the empty-tree case.
+ * How it is built (gem_octree.hip): a leaf's value depends only on its number of hits, so the device carries saturating counts and two
+ * host-built tables (value and p per count, at most 64 entries).  Colour depends on the prune / expand history, which is local to a
+ * leaf's largest aligned block of 8^k leaves that are all hit (k*): the records are sorted stably by Morton key and every block is
+ * walked in input order -- k* = 0 one lane per leaf, k* = 1 eight lanes per block, k* = 2 one wave per block; k* >= 3 (512 leaves
+ * jointly) is finished by an exact sequential routine on the host, its records counted in fallback_points.
+ * stats may be NULL.  GEM_ERR_INVALID, nothing changed: a slot outside 0 .. 3, params NULL, a resolution not finite and positive,
+ * prob_hit <= 0.5 (when not 0), values not strictly increasing up to the clamp within 64 steps, n < 0 or above 2^31 - 2, points NULL
+ * with n > 0, a handle with a communicator; gem_local_compose_octrees: gem_local_compose's cases too.  Every entry takes the handle's
+ * lock. */
+#define GEM_OCTREE_ROAD     0
+#define GEM_OCTREE_OBSTACLE 1
+#define GEM_OCTREE_USER0    2
+#define GEM_OCTREE_USER1    3
+typedef struct gem_octree_params {
+    double resolution;        /* the tree's; the node uses 0.2 (road) and 0.1 (obstacle) */
+    double prob_hit;          /* 0: octomap's 0.7 */
+    double clamp_min;         /* 0: octomap's 0.1192 */
+    double clamp_max;         /* 0: octomap's 0.971 */
+    int    flags;             /* 0 */
+} gem_octree_params;
+typedef struct gem_octree_stats {
+    long long points_in;          /* records of the call */
+    long long points_keyed;       /* ... with a valid key */
+    long long leaves_depth16;     /* childless nodes at depth 16 */
+    long long pruned_leaves;      /* childless nodes above it */
+    long long nodes;
+    long long bytes;              /* 8 * nodes */
+    long long coupled_blocks[3];  /* full aligned blocks walked jointly: k* = 1, 2, >= 3 */
+    long long fallback_points;    /* records of the k* >= 3 blocks (host routine) */
+} gem_octree_stats;
+int  gem_octree_build(gem_handle* h, int slot, const gem_octree_params* params, const void* points, long long n, gem_octree_stats* stats);
+int  gem_octree_build_device(gem_handle* h, int slot, const gem_octree_params* params, const void* d_points, long long n, gem_octree_stats* stats);
+int  gem_local_compose_octrees(gem_handle* h, const gem_compose_params* p, const gem_octree_params* road_params,
+                               const gem_octree_params* obstacle_params, int out_counts[3], double* out_threshold, gem_octree_stats stats[2]);
+int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_t* out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

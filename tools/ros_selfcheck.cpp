@@ -21,6 +21,13 @@
 //                    updateOrigin, resetMaps, touch, updateWithOverwrite, updateWithMax; tests/costmap_ref.py restates the same
 //                    contract in numpy.  The row drives the real Costmap2D / CostmapLayer calls through PointMapLayer's loop, a rolling
 //                    trajectory and both combination rules, and compares every byte, origin and bound
+//   octo gem_octree_build restates octomap::ColorOcTree (octomap 1.8 / 1.9: updateNode, integrateNodeColor, pruneNode, expandNode,
+//                    updateInnerOccupancy, writeData behind octomap_msgs::fullMapToMsg) as pointCloudtoOctomap calls it (reference:
+//                    elevation_mapping/src/ElevationMapping.cpp:1158-1173); tests/octree_ref.py restates the same contract in Python.
+//                    The row inserts seeded clouds that prune and expand (rounds over full 2^3, 4^3 and 8^3 blocks of leaves merged
+//                    with scattered points) into a real ColorOcTree and compares the stream byte for byte; it settles the five points
+//                    include/gem_hip.h lists as not verified (prune on value only and the pruned node's colour, the host's exp, no
+//                    contraction in the blend, the uint8_t cast, the empty tree)
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -34,7 +41,8 @@
 //       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core -lcostmap_2d -llayers -lroscpp -lrosconsole -ltf2_ros $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
-// there, against the library's public headers as documented, and has not been through a compiler.
+// there, against the library's public headers as documented, and has not been through a compiler; neither has the octo row
+// (add -loctomap -loctomath to the link line).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -68,6 +76,8 @@
 #include <costmap_2d/cost_values.h>
 #include <costmap_2d/costmap_2d.h>
 #include <costmap_2d/costmap_layer.h>
+#include <octomap/ColorOcTree.h>
+#include <sstream>
 
 #include <limits>
 #include <map>
@@ -659,6 +669,74 @@ int check_cost(uint32_t seed)
     return 0;
 }
 
+// ---- octo ----------------------------------------------------------------------------------------------------------------------
+// fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
+// only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
+bool same_octree(gem_handle* h, const std::vector<Rec>& cloud, double res, const char* what)
+{
+    octomap::ColorOcTree tree(res);
+    tree.clear();
+    for (const Rec& r : cloud) {                                         // ElevationMapping.cpp:1158-1170
+        tree.updateNode(octomap::point3d(r.x, r.y, r.z), true);
+        tree.integrateNodeColor(r.x, r.y, r.z, r.r, r.g, r.b);
+    }
+    tree.updateInnerOccupancy();
+    std::stringstream ss;
+    tree.writeData(ss);
+    const std::string want = ss.str();
+    gem_octree_params q{};
+    q.resolution = res;
+    gem_octree_stats st{};
+    if (gem_octree_build(h, GEM_OCTREE_USER0, &q, cloud.data(), (long long)cloud.size(), &st) != 0) { ++g_failures; return false; }
+    std::vector<char> got((size_t)st.bytes + 1);
+    size_t n = 0;
+    if (gem_octree_read(h, GEM_OCTREE_USER0, got.data(), got.size(), &n) != 0) { ++g_failures; return false; }
+    const bool same = n == want.size() && std::memcmp(got.data(), want.data(), n) == 0;
+    std::printf("octo: %s: %zu points, octomap %zu bytes (%zu nodes), device %zu bytes, pruned leaves %lld, blocks %lld / %lld / %lld: %s\n", what,
+                cloud.size(), want.size(), tree.size(), n, st.pruned_leaves, st.coupled_blocks[0], st.coupled_blocks[1], st.coupled_blocks[2],
+                same ? "equal" : "DIFFERENT");
+    if (!same) ++g_failures;
+    return same;
+}
+
+int check_octo(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(-4.0, 4.0);
+    same_octree(h, {}, 0.1, "empty cloud");
+    for (int levels = 1; levels <= 3; ++levels) {
+        for (const double res : {0.2, 0.1}) {
+            // `rounds` rounds over one aligned block of 8^levels leaves, every round in a new order (the block collapses at the end of
+            // a round, the next round's first point expands it; from round 5 on the leaves are saturated), scattered points in between
+            const int side = 1 << levels, rounds = 7;
+            std::vector<Rec> cloud;
+            std::vector<int> order(side * side * side);
+            for (int r = 0; r < rounds; ++r) {
+                for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+                std::shuffle(order.begin(), order.end(), rng);
+                for (int i : order) {
+                    Rec p{};
+                    p.x = (float)(((i % side) + 3 * side + 0.5) * res); p.y = (float)((((i / side) % side) - 5 * side + 0.5) * res);
+                    p.z = (float)(((i / side / side) + 2 * side + 0.5) * res);
+                    p.r = (uint8_t)rng(); p.g = (uint8_t)rng(); p.b = (uint8_t)rng();
+                    if (rng() % 50 == 0) p.r = p.g = p.b = 255;          // a white point leaves the colour unset
+                    cloud.push_back(p);
+                    if (rng() % 4 == 0) { Rec e{}; e.x = (float)u(rng); e.y = (float)u(rng); e.z = (float)(0.1 * u(rng)); e.r = (uint8_t)rng(); e.g = (uint8_t)rng(); e.b = (uint8_t)rng(); cloud.push_back(e); }
+                }
+            }
+            char what[64];
+            std::snprintf(what, sizeof what, "block of %d^3 leaves, res %.1f", side, res);
+            same_octree(h, cloud, res, what);
+        }
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
@@ -670,8 +748,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_global(seed + 3u);
     if (rc == 0) rc = check_sor(seed + 4u);
     if (rc == 0) rc = check_cost(seed + 5u);
+    if (rc == 0) rc = check_octo(seed + 6u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all six rows pinned on the installed grid_map_core, OpenCV, PCL and costmap_2d (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / octomap does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all seven rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d and octomap (seed %u)\n", seed);
     return 0;
 }
