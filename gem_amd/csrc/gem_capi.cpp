@@ -10,6 +10,40 @@
 
 namespace gemi {
 
+// gem_raytracing's list of walking cells, its two counters (zeroed once; every call zeroes the next one's), the snapshot
+int ensure_ray(gem_handle* h)
+{
+    if (h->ray.p) return GEM_OK;
+    const int rc = ensure(h, h->ray, ((size_t)h->cells * 2 + 4) * sizeof(uint32_t));
+    if (rc) return rc;
+    GEM_HIP(h, hipMemsetAsync(static_cast<uint32_t*>(h->ray.p) + h->cells, 0, 4 * sizeof(uint32_t), h->stream));
+    return GEM_OK;
+}
+
+// A Mapvar_update increment: queued and folded into the next fuse's single pass over the tiles; a negative (or NaN)
+// increment can push a variance under the floor, which the next Fuse must repair everywhere
+static int queue_increment(gem_handle* h, float var_update)
+{
+    if (!(var_update >= 0.f)) h->floor_dirty = true;
+    if (h->n_pending == kMaxPending) { int rc = flush_pending(h, false); if (rc) return rc; }
+    h->pending[h->n_pending++] = var_update;
+    return GEM_OK;
+}
+
+// The pass of the batch entries: the sweeps at `offsets` of the cloud at xyzi (device memory; caller_device: the caller's own).  A batch
+// of ONE sweep is a single cloud (k_frame may take it) with its increment queued in front
+static int run_batch(gem_handle* h, int n_sweeps, const gem_frame_params* params, const float4* xyzi, const long long* offsets, const float* var_updates, bool caller_device)
+{
+    PassInput in; in.src = 0; in.params = params; in.caller_device = caller_device;
+    if (n_sweeps == 1) {
+        if (var_updates) { const int rc = queue_increment(h, var_updates[0]); if (rc) return rc; }
+        in.n = offsets[1] - offsets[0]; in.device_input = true; in.xyzi = xyzi + offsets[0];
+    } else {
+        in.n_sweeps = n_sweeps; in.n = offsets[n_sweeps]; in.offsets = offsets; in.var_updates = var_updates; in.xyzi = xyzi;
+    }
+    return run_pipeline(h, in);
+}
+
 bool aos_fields_ok(int point_step, int off_x, int off_y, int off_z, int off_intensity, int off_rgb)
 {
     auto field_ok = [&](int o, bool optional) { return (optional && o < 0) || (o >= 0 && (o & 3) == 0 && o + 4 <= point_step); };
@@ -367,7 +401,7 @@ int gem_process_points(gem_handle* h, const gem_frame_params* p, int n, float* x
         h->xfer_ns[3] += t1 - t0; h->xfer_ns[4] += host_ns() - t1;
         return GEM_OK;
     }
-    if ((rc = ensure(h, h->stage, S * 9))) return rc;
+    if ((rc = ensure(h, h->stage, stage_words_bytes(n, 9)))) return rc;
     unsigned char* d = static_cast<unsigned char*>(h->stage.p);
     float* dx = reinterpret_cast<float*>(d);           float* dy = reinterpret_cast<float*>(d + S);
     float* dz = reinterpret_cast<float*>(d + 2 * S);   int* dorig = reinterpret_cast<int*>(d + 3 * S);
@@ -404,7 +438,7 @@ int gem_fuse(gem_handle* h, int n, const int* index, const int* R, const int* G,
     if (n > 0) {
         int rc;
         const size_t P = (S + 255) & ~(size_t)255;                  // the arrays' stride on the device = in the staging buffer (upload_arrays)
-        if ((rc = ensure(h, h->stage, P * 7))) return rc;
+        if ((rc = ensure(h, h->stage, stage_words_bytes(n, 7)))) return rc;
         unsigned char* d = static_cast<unsigned char*>(h->stage.p);
         HostXfer up[7] = {{const_cast<int*>(index), d, S}, {const_cast<float*>(height), d + P, S}, {const_cast<float*>(var), d + 2 * P, S},
                           {const_cast<int*>(R), d + 3 * P, S}, {const_cast<int*>(G), d + 4 * P, S}, {const_cast<int*>(B), d + 5 * P, S},
@@ -474,20 +508,7 @@ int gem_add_batch(gem_handle* h, int n_sweeps, const gem_frame_params* params, c
             i0 = i1;
         }
     }
-    if (n_sweeps == 1) {
-        if (var_updates) {
-            if (!(var_updates[0] >= 0.f)) h->floor_dirty = true;
-            if (h->n_pending == kMaxPending) { rc = flush_pending(h, false); if (rc) return rc; }
-            h->pending[h->n_pending++] = var_updates[0];
-        }
-        PassInput in; in.src = 0; in.n = N; in.params = params; in.device_input = true;
-        in.xyzi = reinterpret_cast<const float4*>(d);
-        return run_pipeline(h, in);
-    }
-    PassInput in; in.src = 0; in.n_sweeps = n_sweeps; in.n = N; in.params = params;
-    in.offsets = offsets.data(); in.var_updates = var_updates;
-    in.xyzi = reinterpret_cast<const float4*>(d);
-    return run_pipeline(h, in);
+    return run_batch(h, n_sweeps, params, reinterpret_cast<const float4*>(d), offsets.data(), var_updates, false);
 }
 
 int gem_add_aos(gem_handle* h, const gem_frame_params* p, int n, const void* points, int point_step,
@@ -510,165 +531,7 @@ int gem_add_batch_device(gem_handle* h, int n_sweeps, const gem_frame_params* pa
     hipSetDevice(h->device);
     { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }
     for (int s = 0; s < n_sweeps; ++s) if (offsets[s + 1] < offsets[s]) return fail(h, GEM_ERR_INVALID, "gem_add_batch_device: offsets not monotone");
-    if (n_sweeps == 1) {
-        if (var_updates) {
-            if (!(var_updates[0] >= 0.f)) h->floor_dirty = true;
-            if (h->n_pending == kMaxPending) { int rc = flush_pending(h, false); if (rc) return rc; }
-            h->pending[h->n_pending++] = var_updates[0];
-        }
-        PassInput in; in.src = 0; in.n = offsets[1] - offsets[0]; in.params = params; in.device_input = true; in.caller_device = true;
-        in.xyzi = static_cast<const float4*>(d_xyzi) + offsets[0];
-        return run_pipeline(h, in);
-    }
-    PassInput in; in.src = 0; in.n_sweeps = n_sweeps; in.n = offsets[n_sweeps]; in.params = params; in.caller_device = true;
-    in.offsets = offsets; in.var_updates = var_updates;
-    in.xyzi = static_cast<const float4*>(d_xyzi);
-    return run_pipeline(h, in);
-}
-
-// Arenas for the largest pass the caller is going to make, allocated NOW: the arenas only ever grow, but growing means waiting for
-// everything in flight, hipFree and hipMalloc -- in the middle of a stream of frames that is a stall of a millisecond or more the
-// first time a bigger cloud arrives (measured: tools/bench_configs.py --configs reserve).  max_points points in at most max_sweeps
-// sweeps per call (1 for gem_add*); colours as they will be passed.  Sizes follow run_pipeline / run_sort_pipeline, for EVERY
-// pipeline a pass within the bounds can take: the sorted forms (cell-sorted for single clouds, block-sorted for batches) from their
-// thresholds on, the tile pipeline below them.  On a handle that joined a communicator with tile strips, max_points / max_sweeps
-// bound the GLOBAL points / sweeps of a gem_add_sharded_device step: the shard's sort (its W-th of the points), both sets of
-// receive buffers (no strip gets more records than the step has points) and the published copies are sized as well.
-int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_colours)
-{
-    if (!h || max_points < 0 || max_sweeps < 1 || max_points >= (1ll << 31)) return h ? fail(h, GEM_ERR_INVALID, "gem_reserve: bad argument") : GEM_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipSetDevice(h->device);
-    { const int rcd = settle(h); if (rcd) return rcd; }
-    if (max_points == 0) return GEM_OK;
-    int rc;
-    const long long blocks = 4ll * ((h->L + 31) / 32) * ((h->L + 31) / 32);
-    // staging of host-pointer inputs: a host cloud of the add entries (cloud_layout, where the clean mask also writes), gem_fuse's
-    // seven arrays, gem_process_points' nine
-    const size_t stage = std::max(cloud_layout(max_points, true, true).bytes, ((size_t)max_points * 4 + 256) * 9);
-    if ((rc = ensure(h, h->stage, stage))) return rc;
-    // (the raw-cloud compactions, gem_capi_clean.cpp, add a count per 1024 points)
-    if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
-    if ((rc = voxel_reserve(h, max_points))) return rc;        // (the VoxelGrid entries, gem_capi_voxel.cpp)
-    {   // ... and its pinned counterpart for callers with host arrays (gem_process_points: nine arrays; gem_map_feature: nine layers),
-        // where that is a modest amount: larger ones grow on first use
-        constexpr size_t kReserveMax = 64u << 20;
-        const size_t a = ((size_t)max_points * 4 + 256) * 9, b = ((size_t)h->cells * 4 + 256) * 9;
-        // the deferred / zero-copy uploads (upload_arrays) keep TWO calls' arrays in the buffer, a half each: gem_fuse's seven arrays
-        // are the largest (28 B per point; gem_add with rgb + orig_index: 24), as long as one call stays below the 16 MB from which
-        // uploads go to the runtime's pageable path
-        const size_t one = ((size_t)max_points * 4 + 256) * 7;
-        const size_t c = one < (16u << 20) ? 2 * one + 512 : 0;
-        const size_t want = std::max(std::max(a <= kReserveMax ? a : 0, b <= kReserveMax ? b : 0), c);
-        if (want) (void)host_stage(h, want);
-    }
-    auto reserve_tables = [&](int sweeps) -> int {                       // the batched calls' tables and their pinned staging copies
-        const size_t tables = sizeof(FrameConst) * sweeps + (sizeof(int) + sizeof(long long)) * (sweeps + 1) + (sizeof(float) + sizeof(int)) * sweeps + 64;
-        for (auto& pb : h->pb) {
-            int r;
-            if (tables > pb.tables.cap) pb.tab_key.clear();          // (the cached tables of this buffer set go with the old allocation)
-            if ((r = ensure(h, pb.tables, tables))) return r;
-            if (tables > pb.host_cap) {
-                if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));
-                if (pb.host_tables) GEM_HIP(h, hipHostFree(pb.host_tables));
-                pb.host_tables = nullptr; pb.host_cap = 0;
-                GEM_HIP(h, hipHostMalloc(&pb.host_tables, tables * 2, hipHostMallocDefault));
-                pb.host_cap = tables * 2;
-            }
-        }
-        return GEM_OK;
-    };
-    auto reserve_sorted = [&](long long points, int sweeps, bool block_form, bool shard) -> int {
-        SortGeometry geo = sort_geometry(h, sweeps, block_form);
-        if (!geo.ok) geo = sort_geometry(h, sweeps, !block_form);
-        if (!geo.ok) return GEM_OK;                                      // (such a pass takes the tile pipeline)
-        // chunks: a pass of fewer points may take the small chunk (sort_chunk_for) and then has MORE chunks than the largest pass
-        const size_t N = (size_t)points;
-        size_t nc_max = 0;
-        for (const long long pts : {points, std::min<long long>(points, 2ll * 256 * kSortChunkRecords - 1)}) {
-            const size_t c = (size_t)sort_chunk_for(pts, h->sort_chunk);
-            nc_max = std::max(nc_max, ((size_t)pts + c - 1) / c);
-        }
-        const size_t NC1 = nc_max + (size_t)sweeps, nc2 = nc_max;
-        int bins_hi = 1;
-        for (int i = 1; i < geo.n_passes; ++i) bins_hi = std::max(bins_hi, geo.dbins[i]);
-        size_t misc = 0;
-        for (int i = 0; i < geo.n_passes; ++i) misc += (size_t)geo.dbins[i] * 16;
-        misc = ((misc + 4 + 15) & ~(size_t)15) + (((size_t)geo.dbins[geo.n_passes - 1] + 1) * 4 + 15) + NC1 * kSortSegsPerChunk * 4 + 64;
-        const int slots = std::max(1, std::min(h->sort_ring, 4));
-        for (int k = 0; k < slots; ++k) {
-            gem_handle::PassBuffers& pb = h->pb[k];
-            int r;
-            if ((r = ensure(h, pb.s_hv1, N * 8 + 64)) || (r = ensure(h, pb.s_hv2, N * 8 + 64)) ||
-                (r = ensure(h, pb.s_key1, N * 4 + 64)) || (r = ensure(h, pb.s_key2, N * 4 + 64))) return r;
-            if (with_colours && ((r = ensure(h, pb.s_src1, N * 4 + 64)) || (r = ensure(h, pb.s_src2, N * 4 + 64)))) return r;
-            if ((r = ensure(h, pb.s_cnt1, NC1 * geo.dbins[0] * 4)) || (r = ensure(h, pb.s_cnt2, nc2 * bins_hi * 4 + 16)) ||
-                (r = ensure(h, pb.s_misc, misc))) return r;
-            if (((geo.block_form && geo.n_passes > 1) || shard) &&
-                ((r = ensure(h, pb.s_ranges, (size_t)blocks * sizeof(uint2))) || (r = ensure_zeroed(h, pb.s_blkcnt, (size_t)blocks * sizeof(uint32_t))))) return r;
-            if (shard && (r = ensure(h, pb.s_shard, 64 * sizeof(uint32_t)))) return r;
-        }
-        return GEM_OK;
-    };
-    auto reserve_tiles = [&](long long points, int sweeps) -> int {
-        // units of 64 points, every sweep rounded up to 32 units; the descriptor table is [sweep][tile][units of the longest sweep].
-        // A single cloud beyond kSweepPoints is cut into sweeps of that size (run_pipeline); the sweeps of a batch are taken to be at
-        // most twice their mean length (or kSweepPoints) -- the table for "all points in one of 32 sweeps" would be 32 times the useful one.
-        auto units_of = [](long long pts) { return ((pts + kUnit - 1) / kUnit + 31) & ~31ll; };
-        long long units1, B;
-        if (sweeps == 1 && points > kSweepPoints) { sweeps = (int)((points + kSweepPoints - 1) / kSweepPoints); units1 = units_of(kSweepPoints); B = units1 * sweeps; }
-        else if (sweeps == 1) { units1 = units_of(points); B = units1; }
-        else { units1 = units_of(std::min(points, std::max(kSweepPoints, 2 * points / sweeps))); B = units_of(points) + 32ll * (sweeps - 1); }
-        const int ts = h->ts ? h->ts : 4;
-        const long long tpr = (h->L + (1 << ts) - 1) >> ts, T = tpr * tpr;
-        const size_t seg = (size_t)sweeps * T * units1 * sizeof(uint16_t);
-        if (seg > ((size_t)1 << 31)) return GEM_OK;           // (not a shape the tile pipeline is meant for: such a pass sizes its own table, or fails there)
-        for (int k = 0; k < 2; ++k) {
-            gem_handle::PassBuffers& pb = h->pb[k];
-            int r;
-            if ((r = ensure(h, pb.rec, (size_t)B * kUnit * sizeof(uint4))) || (r = ensure(h, pb.srt, (size_t)B * kUnit * sizeof(uint4) + 16))) return r;
-            if (seg > pb.seg.cap) {                          // (the table is all-zero between passes: cleared when it is (re)allocated)
-                if ((r = ensure(h, pb.seg, seg))) return r;
-                GEM_HIP(h, hipMemsetAsync(pb.seg.p, 0, pb.seg.cap, h->stream));
-            }
-            const size_t flag = (size_t)T * sweeps * sizeof(uint32_t), gflag = (size_t)sweeps * T * (units1 / 32) * sizeof(uint32_t);
-            if (flag > pb.flag.cap || gflag > pb.gflag.cap) {
-                if ((r = ensure(h, pb.flag, flag)) || (r = ensure(h, pb.gflag, gflag))) return r;
-                GEM_HIP(h, hipMemsetAsync(pb.flag.p, 0, pb.flag.cap, h->stream));
-                GEM_HIP(h, hipMemsetAsync(pb.gflag.p, 0, pb.gflag.cap, h->stream));
-                pb.epoch = 0;
-            }
-            // a stream of single sweeps (k_frame): any one of them up to the bound -- clouds beyond kSweepPoints are cut into a batch
-            if (ts == 4 && (r = ensure_frame_buckets(h, pb, (int)T, (int)units_of(std::min(points, kSweepPoints))))) return r;
-        }
-        return GEM_OK;
-    };
-    if (h->tp_x && h->tile_strips) {
-        // a step of the sharded path: this rank sorts its W-th of the points, block-sorted; every strip's owner receives at most all of them
-        const int W = h->nranks;
-        const long long share = (max_points + W - 1) / W + 1;
-        if ((rc = reserve_sorted(share, max_sweeps, true, true)) || (rc = reserve_tables(max_sweeps))) return rc;
-        if (!h->sh_host) GEM_HIP(h, hipHostMalloc(&h->sh_host, kShardHostBytes, hipHostMallocDefault));
-        if ((rc = ensure(h, h->sh_dev, kShardDevBytes)) || (rc = ensure(h, h->sh_ranges, (size_t)blocks * sizeof(uint2)))) return rc;
-        h->recv_bound = max_points;
-        if (W > 1 && ((rc = ensure_recv(h, 0, (size_t)max_points + 4 * W)) || (rc = ensure_recv(h, 1, (size_t)max_points + 4 * W)))) return rc;
-        GEM_HIP(h, hipStreamSynchronize(h->stream));
-        return GEM_OK;                                                   // (a handle of the sharded path: its steps are what the bounds describe)
-    }
-    const bool sorted_single = h->sort_path && max_points >= h->sort_min_points;
-    const bool sorted_batch = h->sort_path && max_sweeps > 1 && max_points >= h->sort_min_points_batch;
-    if (sorted_single && (rc = reserve_sorted(max_points, 1, h->sort_form == 2, false))) return rc;
-    if (sorted_batch && ((rc = reserve_sorted(max_points, max_sweeps, h->sort_form != 1, false)))) return rc;
-    if (max_sweeps > 1 && (rc = reserve_tables(max_sweeps))) return rc;
-    // the tile pipeline takes what stays below the thresholds (and everything when the sorted forms are off)
-    if ((rc = reserve_tiles(sorted_single ? std::min(max_points, h->sort_min_points - 1) : max_points, 1))) return rc;
-    if (max_sweeps > 1 && (rc = reserve_tiles(sorted_batch ? std::min(max_points, h->sort_min_points_batch - 1) : max_points, max_sweeps))) return rc;
-    if (h->track_lowest && !h->ray.p) {                                  // gem_raytracing's list of walking cells, counters and snapshot
-        if ((rc = ensure(h, h->ray, ((size_t)h->cells * 2 + 4) * sizeof(uint32_t)))) return rc;
-        GEM_HIP(h, hipMemsetAsync(static_cast<uint32_t*>(h->ray.p) + h->cells, 0, 4 * sizeof(uint32_t), h->stream));
-    }
-    GEM_HIP(h, hipStreamSynchronize(h->stream));
-    return GEM_OK;
+    return run_batch(h, n_sweeps, params, static_cast<const float4*>(d_xyzi), offsets, var_updates, true);
 }
 
 int gem_mapvar_update(gem_handle* h, float var_update)
@@ -678,12 +541,7 @@ int gem_mapvar_update(gem_handle* h, float var_update)
     std::lock_guard<std::mutex> lk(h->mu);
     hipSetDevice(h->device);
     { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }       // (the increment belongs behind a pending step's walk)
-    // queued and folded into the next fuse's single pass over the tiles; a negative (or NaN)
-    // increment can push a variance under the floor, which the next Fuse must repair everywhere
-    if (!(var_update >= 0.f)) h->floor_dirty = true;
-    if (h->n_pending == kMaxPending) { int rc = flush_pending(h, false); if (rc) return rc; }
-    h->pending[h->n_pending++] = var_update;
-    return GEM_OK;
+    return queue_increment(h, var_update);
 }
 
 static void* layer_ptr(gem_handle* h, int layer)
@@ -874,23 +732,21 @@ static int colorize_device(gem_handle* h, const gem_camera* cam, int n, float* d
     SortArgs sa{};
     sa.id_bits = std::max(2, ceil_log2((int)std::min<long long>(pixels, 1ll << 30)));
     sa.n_passes = sa.id_bits <= 10 ? 1 : (sa.id_bits <= 20 ? 2 : 3);
-    int shift = 0, bins_hi = 1;
+    int shift = 0;
     for (int i = 0; i < sa.n_passes; ++i) {
         const int left = sa.n_passes - i;
         const int bits = i == sa.n_passes - 1 ? sa.id_bits - shift : (sa.id_bits - shift + left - 1) / left;
         sa.dshift[i] = shift; sa.dbits[i] = bits;
         sa.dbins[i] = i == sa.n_passes - 1 ? (int)((pixels - 1) >> shift) + 1 : 1 << bits;
-        if (i > 0) bins_hi = std::max(bins_hi, sa.dbins[i]);
         shift += bits;
     }
     const size_t N = (size_t)n, NC = (N + kSortChunkRecords - 1) / kSortChunkRecords;
     size_t o = 0;
     auto take = [&](size_t bytes) { const size_t at = o; o = (o + bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_hv1 = take(N * 8 + 64), o_hv2 = take(N * 8 + 64), o_key1 = take(N * 4 + 64), o_key2 = take(N * 4 + 64);
-    const size_t o_cnt1 = take(NC * sa.dbins[0] * 4), o_cnt2 = take(NC * bins_hi * 4 + 16);
-    size_t o_seg[3] = {0, 0, 0};
-    for (int i = 0; i < sa.n_passes; ++i) o_seg[i] = take((size_t)sa.dbins[i] * 16);
-    const size_t o_total = take(16), o_base = take(((size_t)sa.dbins[sa.n_passes - 1] + 1) * 4), o_segcnt = take(NC * kSortSegsPerChunk * 4);
+    // the sort's buffers as a pass of the sorted pipeline has them (gem_plan.hpp), carved out of the one arena
+    const SortPlan sp = sort_plan(sa.n_passes, sa.dbins, n, NC, NC, 1, false, 0, false);
+    const size_t o_hv1 = take(sp.hv), o_hv2 = take(sp.hv), o_key1 = take(sp.key), o_key2 = take(sp.key);
+    const size_t o_cnt1 = take(sp.cnt1), o_cnt2 = take(sp.cnt2), o_misc = take(sp.misc);
     const size_t o_first = take((size_t)pixels * 4), o_pix = take(N * 4), o_link = take(N * 4);
     int rc;
     if ((rc = ensure(h, h->color, o))) return rc;
@@ -899,14 +755,8 @@ static int colorize_device(gem_handle* h, const gem_camera* cam, int n, float* d
     for (int k = 0; k < 12; ++k) sa.cam.P[k] = cam->lidar_to_image[k];
     sa.cam.width = cam->width; sa.cam.height = cam->height;
     sa.tiles_per_row = 1; sa.T = 1; sa.n_chunks1 = (int)NC; sa.chunk = kSortChunkRecords;
-    for (int i = 0; i < sa.n_passes; ++i) {
-        sa.cnt[i] = reinterpret_cast<uint32_t*>(d + (i == 0 ? o_cnt1 : o_cnt2));
-        sa.segtot[i] = reinterpret_cast<uint32_t*>(d + o_seg[i]);
-    }
-    sa.total = reinterpret_cast<uint32_t*>(d + o_total); sa.bin_base = reinterpret_cast<uint32_t*>(d + o_base);
-    sa.seg_cnt = reinterpret_cast<uint32_t*>(d + o_segcnt);
-    sa.hv_a = reinterpret_cast<uint2*>(d + o_hv2); sa.hv_b = reinterpret_cast<uint2*>(d + o_hv1);
-    sa.key_a = reinterpret_cast<uint32_t*>(d + o_key2); sa.key_b = reinterpret_cast<uint32_t*>(d + o_key1);
+    bind_sort_buffers(sp, sa.n_passes, {d + o_hv1, d + o_hv2, d + o_key1, d + o_key2, nullptr, nullptr, d + o_cnt1, d + o_cnt2, d + o_misc}, sa);
+    sa.odd_flag = nullptr;                              // (no walk behind this sort: nothing reads the word)
     const LaunchEvents ev[9] = {};
     GEM_HIP(h, hipMemsetAsync(d + o_first, 0xff, (size_t)pixels * 4, h->stream));
     GEM_HIP(h, hipMemsetAsync(d + o_pix, 0xff, N * 4, h->stream));
@@ -973,10 +823,7 @@ int gem_raytracing(gem_handle* h)
     if (h->row0 != 0 || h->row1 != h->L) return fail(h, GEM_ERR_INVALID, "gem_raytracing: not available on a row-strip handle");
     int rc = flush_pending(h, false);               // the queued variance increments are part of what the kernel reads
     if (rc) return rc;
-    if (!h->ray.p) {                                    // the list of walking cells, its two counters (zeroed once; every call zeroes the next one's), the snapshot
-        if ((rc = ensure(h, h->ray, ((size_t)h->cells * 2 + 4) * sizeof(uint32_t)))) return rc;
-        GEM_HIP(h, hipMemsetAsync(static_cast<uint32_t*>(h->ray.p) + h->cells, 0, 4 * sizeof(uint32_t), h->stream));
-    }
+    if ((rc = ensure_ray(h))) return rc;
     uint32_t* list = static_cast<uint32_t*>(h->ray.p);
     GEM_HIP(h, launch_raytracing(h->stream, h->layers, h->L, h->start[0], h->start[1], h->sensor_z, h->cfg.obstacle_threshold,
                                  h->row0, h->row1, list, list + h->cells, (int)(h->ray_calls++ & 1u), reinterpret_cast<float*>(list + h->cells + 4), h->ray_depth, h->ray_lanes));

@@ -104,7 +104,7 @@ int gem_process_points_raw(gem_handle* h, const gem_frame_params* p, const gem_c
     // nine arrays of SP bytes in the staging arena (what gem_reserve sizes for gem_process_points) + the kept count:
     //   0-2 the raw x, y, z -- after the compaction the outputs index, var, x_ts | 3-5 the kept x, y, z | 6 their raw positions |
     //   7-8 the outputs y_ts, height | 9 SP + 0 the kept count
-    if ((rc = ensure(h, h->stage, SP * 9 + 16))) return rc;
+    if ((rc = ensure(h, h->stage, stage_words_bytes(n, 9)))) return rc;
     if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(n)))) return rc;
     unsigned char* o = static_cast<unsigned char*>(h->stage.p);
     float* dx = reinterpret_cast<float*>(o); float* dy = reinterpret_cast<float*>(o + SP); float* dz = reinterpret_cast<float*>(o + 2 * SP);

@@ -174,6 +174,13 @@ namespace gemi {
 // (gem_shard_sort_device); the sorted records of every strip go to the strip's owner, which walks its cells through the
 // sources in rank order -- ranks hold ascending index ranges, so rank order is input order and the result is the
 // single-device one bit for bit (gem_shard_fuse_device).  gem_add_sharded_device does both with an RCCL exchange in between.
+int ensure_shard_tables(gem_handle* h, size_t blocks)
+{
+    if (!h->sh_host) GEM_HIP(h, hipHostMalloc(&h->sh_host, kShardHostBytes, hipHostMallocDefault));
+    int rc = ensure(h, h->sh_dev, kShardDevBytes);
+    return rc ? rc : ensure(h, h->sh_ranges, blocks * sizeof(uint2));
+}
+
 int shard_checks(gem_handle* h, int n_global_sweeps, SortGeometry* geo)
 {
     if (h->track_lowest) return fail(h, GEM_ERR_INVALID, "sharded path: lowest tracking is not supported (use the replicated path)");
@@ -204,8 +211,7 @@ int shard_sort_locked(gem_handle* h, int n_local_sweeps, const gem_frame_params*
     if (n >= (1ll << 31)) return fail(h, GEM_ERR_INVALID, "gem_shard_sort_device: shard too large");
     if (n == 0) {                                        // an empty shard contributes nothing to any strip: no records, empty ranges, zero bounds
         const size_t n_blocks = (size_t)4 * geo.T;
-        if ((rc = ensure(h, h->sh_ranges, n_blocks * sizeof(uint2)))) return rc;
-        if ((rc = ensure(h, h->sh_dev, kShardDevBytes))) return rc;
+        if ((rc = ensure_shard_tables(h, n_blocks))) return rc;
         GEM_HIP(h, hipMemsetAsync(h->sh_ranges.p, 0, n_blocks * sizeof(uint2), h->stream));
         GEM_HIP(h, hipMemsetAsync(static_cast<uint32_t*>(h->sh_dev.p) + 16, 0, 16 * sizeof(uint32_t), h->stream));
         sd.valid = true; sd.hv = nullptr; sd.key = nullptr; sd.nstrips = nstrips; sd.slot = -1;
@@ -305,8 +311,7 @@ int shard_fuse_locked(gem_handle* h, int n_src, const void* const* d_hv, const v
         // staged in pinned memory, two buffers in turn: the upload from a buffer is long done when its turn comes again (the event
         // is there for the caller who gets ahead), so no step waits for the handle's stream here
         if (n_global_sweeps > 512) return fail(h, GEM_ERR_INVALID, "sharded path: more than 512 sweeps");
-        if (!h->sh_host) GEM_HIP(h, hipHostMalloc(&h->sh_host, kShardHostBytes, hipHostMallocDefault));
-        if ((rc = ensure(h, h->sh_dev, kShardDevBytes))) return rc;
+        if ((rc = ensure_shard_tables(h))) return rc;
         const int b = (int)(h->vu_seq++ & 1u);
         if (!h->ev_vu[b]) GEM_HIP(h, hipEventCreateWithFlags(&h->ev_vu[b], hipEventDisableTiming));
         if (h->vu_recorded[b]) GEM_HIP(h, hipEventSynchronize(h->ev_vu[b]));
@@ -479,8 +484,7 @@ int gem_add_sharded_device(gem_handle* h, int n_local_sweeps, const gem_frame_pa
         if (n_local_sweeps < 0 || first_global_sweep < 0 || first_global_sweep + n_local_sweeps > n_global_sweeps || first_point_in_sweep < 0 ||
             (n_local_sweeps > 0 && (!params || !offsets || !d_xyzi)) || n_local < 0 || n_local >= (1ll << 31) || n_global_sweeps > 512)
             return fail(h, GEM_ERR_INVALID, "gem_add_sharded_device: bad argument");
-        if (!h->sh_host) GEM_HIP(h, hipHostMalloc(&h->sh_host, kShardHostBytes, hipHostMallocDefault));
-        if ((rc0 = ensure(h, h->sh_dev, kShardDevBytes))) return rc0;
+        if ((rc0 = ensure_shard_tables(h))) return rc0;
         if (W > 1) {
             // both sets of receive buffers, for what a step can bring at most: gem_reserve's bound when there is
             // one, else W shares like this rank's (the ranks hold N / W points each, and no strip gets more records than there are points)

@@ -69,21 +69,6 @@ int ensure(gem_handle* h, Arena& a, size_t bytes)
     return GEM_OK;
 }
 
-// k_frame's records (gem_kernels.hpp, kFrameBucket): the kernel leaves every count zero and every spill slot free behind it, so
-// they are only set when (re)allocated
-int ensure_frame_buckets(gem_handle* h, gem_handle::PassBuffers& pb, int T, int B)
-{
-    int rc;
-    if ((rc = ensure(h, pb.bkt, (size_t)T * kFrameBucket * 3 * sizeof(uint32_t))) || (rc = ensure_zeroed(h, pb.bcnt, (size_t)T * sizeof(uint32_t))) ||
-        (rc = ensure_zeroed(h, pb.fctl, 2 * sizeof(uint32_t)))) return rc;     // (the form words: bucket form until a tile needs more)
-    const size_t spill = (size_t)B * kUnit * sizeof(uint4);
-    if (spill > pb.spill.cap) {
-        if ((rc = ensure(h, pb.spill, spill))) return rc;
-        GEM_HIP(h, hipMemsetAsync(pb.spill.p, 0xff, pb.spill.cap, h->stream));     // tile word == kSpillFree
-    }
-    return GEM_OK;
-}
-
 // ... for tables the kernels keep all-zero between passes: cleared when (re)allocated (allocation synchronises anyway)
 int ensure_zeroed(gem_handle* h, Arena& a, size_t bytes)
 {
@@ -94,7 +79,6 @@ int ensure_zeroed(gem_handle* h, Arena& a, size_t bytes)
     GEM_HIP(h, hipStreamSynchronize(h->stream));
     return GEM_OK;
 }
-
 
 // the pinned staging buffer, at least `bytes` large -- or nullptr: switched off, too large, or the allocation failed (the callers
 // then hand the arrays to the runtime, which stages pageable memory itself: slower, never wrong)

@@ -2,7 +2,9 @@
 // the multi-rank step.  Internal to libgem_hip.so (nothing here is installed); the ABI itself is include/gem_hip.h.
 //   gem_capi_core.cpp      errors, arenas, the pinned staging buffer and the host <-> device transfers, frame constants, the deferred
 //                          launches (flush_* / settle), the process-lifetime stream pools
-//   gem_capi_pipeline.cpp  run_pipeline / run_sort_pipeline: which kernels a pass takes, on which streams, with which buffers
+//   gem_plan.hpp           the pass plan: which pipeline a pass takes and the size and layout of every buffer of it (pure functions)
+//   gem_capi_pipeline.cpp  run_pipeline / run_sort_pipeline: which kernels a pass takes, on which streams, in the buffers of its plan;
+//                          gem_reserve: the same plans for the extremal passes inside its bounds
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
 #pragma once
@@ -10,6 +12,7 @@
 #include "../../include/gem_hip.h"
 #include "../../include/gem_hip_debug.h"
 #include "gem_kernels.hpp"
+#include "gem_plan.hpp"
 #include "gem_hostcopy.hpp"
 #include "gem_transport.hpp"
 
@@ -26,13 +29,11 @@
 #include <string>
 #include <vector>
 
-
 using namespace gem;
 
 namespace gemi {
 
 extern thread_local std::string g_create_error;
-
 
 struct Arena {
     void*  p = nullptr;
@@ -343,7 +344,7 @@ int step_abort(gem_handle* h, int rc);
 
 int ensure(gem_handle* h, Arena& a, size_t bytes);
 int ensure_zeroed(gem_handle* h, Arena& a, size_t bytes);
-int ensure_frame_buckets(gem_handle* h, gem_handle::PassBuffers& pb, int T, int B);   // k_frame's record arenas for T tiles and B units
+int ensure_ray(gem_handle* h);                  // gem_capi.cpp: gem_raytracing's arena
 
 struct HostXfer { void* host; void* dev; size_t bytes; };
 
@@ -438,20 +439,18 @@ struct PassInput {
 // device or the host reads -- the record exchange and the all-gathers of the multi-rank step -- is ordered by events WITH the
 // fence (ev_sorted and the other step events, comm_attach), never by these.
 constexpr unsigned  kDeviceEventFlags = hipEventDisableTiming | hipEventDisableSystemFence;
-constexpr int       kUnit = 64;                      // points per unit (one wave of k_bin_wave)
-constexpr long long kSweepPoints = 2048ll * kUnit;   // a single cloud longer than this is processed as a batch of sweeps of this size
 
 hipError_t acquire_streams(int device, StreamSet& out);
 void release_streams(int device, const StreamSet& set);
 hipError_t acquire_comm_stream(int device, hipStream_t* out);
 void release_comm_stream(int device, hipStream_t st);
-inline int ceil_log2(int v) { int b = 0; while ((1 << b) < v) ++b; return b; }
 
-// The key geometry of the sorted pipelines for this map, and whether a pass of `n_sweeps` sweeps fits the 32-bit record key.
-// block_form: the digits cover the BLOCK id (id >> 8) only and k_fuse_block orders a block's records by cell itself; otherwise
-// they cover the whole id and k_fuse_walk streams every cell's run (gem_kernels.hpp).
-struct SortGeometry { int tiles_per_row, T, id_bits, n_passes, dshift[3], dbits[3], dbins[3]; bool block_form, ok; };
-SortGeometry sort_geometry(const gem_handle* h, int n_sweeps, bool block_form);
+// gem_capi_pipeline.cpp: the plans (gem_plan.hpp) of this handle
+PlanEnv plan_env(const gem_handle* h);
+SortGeometry sort_geometry(const gem_handle* h, int n_sweeps, bool block_form);      // sort_digits for this map, the kernels' LDS checked
+// the sort kernels' pointers into buffers of a plan's sizes: arrays 1 / 2, the two count tables, the carved s_misc
+struct SortBuffers { void *hv1, *hv2, *key1, *key2, *src1, *src2, *cnt1, *cnt2, *misc; };
+void bind_sort_buffers(const SortPlan& p, int n_passes, const SortBuffers& b, SortArgs& sa);
 
 // pinned host staging of the sharded path: per parity (4096 B each) strip ids at word 0, own bounds at word 32, the gathered bounds
 // [W][16] at word 64; the variance increments' two buffers at byte 8192 + 2048 b.  The device twin has the same layout.
@@ -485,6 +484,7 @@ int voxel_front(gem_handle* h, const gem_voxel_params* stages, int ns, int n, co
 // gem_capi_comm.cpp
 int shard_finish_locked(gem_handle* h);       // the second half of a pending gem_add_sharded_device step
 int ensure_recv(gem_handle* h, int parity, size_t records);
+int ensure_shard_tables(gem_handle* h, size_t blocks = 0);     // the small tables' pinned block and device twin; blocks: an empty shard's block ranges too
 size_t strip_blocks_of(const gem_handle* h, int p);
 bool shard_sort_rotates(const gem_handle* h, long long n);
 int shard_checks(gem_handle* h, int n_global_sweeps, SortGeometry* geo);

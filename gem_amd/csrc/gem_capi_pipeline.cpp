@@ -1,47 +1,136 @@
 // gem_capi_pipeline.cpp -- one pass over points that are on the device (see gem_capi_internal.hpp): the tile pipeline (k_frame / k_bin_wave +
 // k_fuse_list) and the two sorted forms (gem_sort.hip), their buffers, streams and hand-overs.
 #include "gem_capi_internal.hpp"
+#include "gem_clean.hpp"
 
 namespace gemi {
 
-SortGeometry sort_geometry(const gem_handle* h, int n_sweeps, bool block_form)
+static bool sort_bins_fit(int bins) { return sort_shape(bins, true, kSortChunkRecords).lds <= 160 * 1024; }   // what launch_sort checks (the big chunk needs the most)
+PlanEnv plan_env(const gem_handle* h)
 {
-    SortGeometry g{};
-    g.block_form = block_form;
-    g.tiles_per_row = (h->L + 31) / 32;
-    g.T = g.tiles_per_row * g.tiles_per_row;
-    g.id_bits = 10 + std::max(1, ceil_log2(g.T));                 // id = tile << 10 | cell in tile
-    const int lo = block_form ? 8 : 0;                            // first bit the digits cover
-    const long long values = (((long long)g.T) << 10) >> lo;      // ids / block ids in use: 0 .. values - 1
-    // Digits of about equal width, at most ten bits: the records of a (chunk, bin) leave k_sort_scatter as one run, and with
-    // thousands of bins a 4096-record chunk has one or two records per run -- no coalescing left (cell-sorted, the 2400^2 map in
-    // two passes of 2048 / 2813 bins: 206 + 158 us; in three passes of 256 / 256 / 88 bins: see DESIGN.md).  Block ids are
-    // different: consecutive points of a scan fall into few blocks, the runs are long whatever the number of bins, and a map of
-    // up to kOnePassMaxBins blocks (600^2: 1444) is sorted by ONE pass.
-    if (h->sort_passes) g.n_passes = h->sort_passes;
-    else if (block_form) g.n_passes = values <= kOnePassMaxBins ? 1 : (g.id_bits - lo <= 20 ? 2 : 3);
-    else g.n_passes = g.id_bits <= 20 ? 2 : 3;
-    int shift = lo;
-    for (int i = 0; i < g.n_passes; ++i) {
-        const int left = g.n_passes - i;
-        // (rounded down: the lowest digit sees the records in input order -- every bin in use, a run per bin and chunk -- and pays
-        //  for its bins; the higher digits see them sorted by the lower ones, longer runs.  Cell-sorted 600^2: 512 x 722 bins
-        //  28.7 + 26.4 us, 1024 x 361 37.7 + 21.4, 256 x 1444 27.6 + 38.8)
-        int bits = (g.id_bits - shift) / left;
-        if (i == 0 && !block_form) bits = std::max(bits, 8);      // the 256 cells of a k_fuse_walk workgroup never straddle a bin of the last pass
-        if (i == g.n_passes - 1) bits = g.id_bits - shift;
-        bits = std::max(bits, 1);
-        g.dshift[i] = shift; g.dbits[i] = bits;
-        g.dbins[i] = i == g.n_passes - 1 ? (int)(((((long long)g.T) << 10) - 1) >> shift) + 1 : 1 << bits;
-        shift += bits;
+    PlanEnv e{};
+    e.L = h->L; e.ts = h->ts; e.sort_form = h->sort_form; e.sort_passes = h->sort_passes; e.sort_chunk = h->sort_chunk; e.sort_ring = h->sort_ring;
+    e.sort_path = h->sort_path; e.track_lowest = h->track_lowest; e.sort_min_points = h->sort_min_points; e.sort_min_points_batch = h->sort_min_points_batch;
+    return e;
+}
+SortGeometry sort_geometry(const gem_handle* h, int n_sweeps, bool block_form) { return sort_digits(h->L, h->sort_passes, n_sweeps, block_form, sort_bins_fit); }
+
+// ---- the plans' buffers (gem_plan.hpp) in a set of pass buffers: the pipelines below and gem_reserve allocate through these
+// A batched pass's tables and their pinned staging copy (twice the size: the next, slightly longer batch does not allocate again);
+// with `host`: the zeroed host block to fill, once the previous upload from it has been read.  Staged in pinned memory so that the upload
+// does not make the host wait for the stream (a pageable source would: the call then cost a whole k_bin of host time, 240 us per C4 batch)
+static int stage_batch_tables(gem_handle* h, gem_handle::PassBuffers& pb, const TablesPlan& t, unsigned char** host = nullptr)
+{
+    if (t.total > pb.tables.cap) pb.tab_key.clear();                 // (a new allocation holds nothing, even at the old address)
+    const int rc = ensure(h, pb.tables, t.total);
+    if (rc) return rc;
+    if (t.total > pb.host_cap) {
+        if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));
+        if (pb.host_tables) GEM_HIP(h, hipHostFree(pb.host_tables));
+        pb.host_tables = nullptr; pb.host_cap = 0;
+        GEM_HIP(h, hipHostMalloc(&pb.host_tables, t.total * 2, hipHostMallocDefault));
+        pb.host_cap = t.total * 2;
     }
-    const long long max_sweeps = std::min<long long>(512, (1ll << (32 - g.id_bits)) - 1);     // the sweep field is never all ones
-    g.ok = g.id_bits <= 26 && n_sweeps <= max_sweeps && g.dshift[g.n_passes - 1] >= 8 && shift == g.id_bits;
-    for (int i = 0; i < g.n_passes; ++i) {
-        g.ok = g.ok && g.dbins[i] <= kSortMaxBins && g.dbits[i] >= 1;
-        g.ok = g.ok && sort_shape(g.dbins[i], true, kSortChunkRecords).lds <= 160 * 1024;   // what launch_sort checks (a forced pass count may not fit; the big chunk needs the most)
+    if (!host || !t.total) return GEM_OK;
+    if (!pb.tables_done) GEM_HIP(h, hipEventCreateWithFlags(&pb.tables_done, hipEventDisableTiming));
+    if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));
+    pb.tab_key.clear();                                              // (not valid until the upload is enqueued)
+    *host = static_cast<unsigned char*>(pb.host_tables);
+    memset(*host, 0, t.total);
+    return GEM_OK;
+}
+// ... filled: the frames, the first unit / chunk of every sweep, what the pass input has of the rest.  Returns the k_sort_project
+// instantiation the frames take: clouds whose frames all use the laser model (the reference's only GPU model, GPU:403-408) take the one
+// without the camera models' double-precision code: 2; with every frame's rotation variance zero (height_variance, kModelLaserFast): 4
+static int fill_batch_tables(const gem_handle* h, unsigned char* host, const TablesPlan& t, const PassInput& in, const int* first0)
+{
+    bool laser = in.src == 0, fast = true;
+    for (int s = 0; s < in.n_sweeps; ++s) {
+        FrameConst& fc = reinterpret_cast<FrameConst*>(host + t.o_frames)[s];
+        fill_frame(h, in.src == 0 ? &in.params[s] : nullptr, fc);
+        laser = laser && in.params[s].sensor_model == GEM_MODEL_LASER;
+        fast = fast && fc.fast_laser != 0;
     }
-    return g;
+    memcpy(host + t.o_first0, first0, sizeof(int) * (in.n_sweeps + 1));
+    memcpy(host + t.o_first, in.offsets, sizeof(long long) * (in.n_sweeps + 1));
+    if (in.sweep_orig0) memcpy(host + t.o_orig, in.sweep_orig0, sizeof(int) * in.n_sweeps);
+    if (in.var_updates) memcpy(host + t.o_var, in.var_updates, sizeof(float) * in.n_sweeps);
+    return laser ? (fast ? 4 : 2) : 0;
+}
+static int ensure_sort_buffers(gem_handle* h, gem_handle::PassBuffers& pb, const SortPlan& p)
+{
+    int rc;
+    if ((rc = ensure(h, pb.s_hv1, p.hv)) || (rc = ensure(h, pb.s_hv2, p.hv)) || (rc = ensure(h, pb.s_key1, p.key)) || (rc = ensure(h, pb.s_key2, p.key)) ||
+        (rc = ensure(h, pb.s_src1, p.src)) || (rc = ensure(h, pb.s_src2, p.src)) ||
+        (rc = ensure(h, pb.s_cnt1, p.cnt1)) || (rc = ensure(h, pb.s_cnt2, p.cnt2)) || (rc = ensure(h, pb.s_misc, p.misc)) ||
+        (rc = ensure_zeroed(h, pb.s_blkcnt, p.blkcnt)) || (rc = ensure(h, pb.s_ranges, p.ranges)) || (rc = ensure(h, pb.s_shard, p.shard))) return rc;
+    return stage_batch_tables(h, pb, p.tables);
+}
+void bind_sort_buffers(const SortPlan& p, int n_passes, const SortBuffers& b, SortArgs& sa)
+{
+    unsigned char* misc = static_cast<unsigned char*>(b.misc);
+    for (int i = 0; i < n_passes; ++i) {
+        sa.cnt[i] = static_cast<uint32_t*>(i == 0 ? b.cnt1 : b.cnt2);
+        sa.segtot[i] = reinterpret_cast<uint32_t*>(misc + p.o_seg[i]);
+    }
+    sa.total = reinterpret_cast<uint32_t*>(misc + p.o_total); sa.bin_base = reinterpret_cast<uint32_t*>(misc + p.o_base);
+    // (word 1 behind the record count: k_sort_project stores the pass's epoch there when a record is outside the plain range of
+    //  the walks' chain loops; epochs never repeat, so the word needs no clearing)
+    sa.odd_flag = sa.total + 1;
+    sa.seg_cnt = reinterpret_cast<uint32_t*>(misc + p.o_segcnt);
+    // arrays a: the projected records in input order, later the final order; arrays b: the order after pass 1
+    sa.hv_a = static_cast<uint2*>(b.hv2); sa.hv_b = static_cast<uint2*>(b.hv1);
+    sa.key_a = static_cast<uint32_t*>(b.key2); sa.key_b = static_cast<uint32_t*>(b.key1);
+    sa.src_a = p.src ? static_cast<uint32_t*>(b.src2) : nullptr; sa.src_b = p.src ? static_cast<uint32_t*>(b.src1) : nullptr;
+}
+// The tile pipeline's buffers; what a pass expects cleared is cleared on `st` when it is (re)allocated.  frame: k_frame's arenas too
+// (only a handle that runs it pays for them); host: the block of a batch's tables to fill (stage_batch_tables)
+static int ensure_tile_buffers(gem_handle* h, gem_handle::PassBuffers& pb, const TilePlan& p, hipStream_t st, bool frame, unsigned char** host = nullptr)
+{
+    int rc;
+    if ((rc = ensure(h, pb.rec, p.rec)) || (rc = ensure(h, pb.srt, p.srt))) return rc;
+    if (p.seg > pb.seg.cap) {                                        // k_fuse_list zeroes the descriptors it consumes: all-zero between passes
+        if ((rc = ensure(h, pb.seg, p.seg))) return rc;
+        GEM_HIP(h, hipMemsetAsync(pb.seg.p, 0, pb.seg.cap, st));
+    }
+    if (p.flag > pb.flag.cap || p.gflag > pb.gflag.cap) {            // the touched flags are stamped with the pass's epoch instead of being cleared
+        if ((rc = ensure(h, pb.flag, p.flag)) || (rc = ensure(h, pb.gflag, p.gflag))) return rc;
+        GEM_HIP(h, hipMemsetAsync(pb.flag.p, 0, pb.flag.cap, st));
+        GEM_HIP(h, hipMemsetAsync(pb.gflag.p, 0, pb.gflag.cap, st));
+        pb.epoch = 0;
+    }
+    if (!frame) return stage_batch_tables(h, pb, p.tables, host);
+    // k_frame's records (gem_kernels.hpp, kFrameBucket; sizes 0 where the plan rules it out): the kernel leaves every count zero and
+    // every spill slot free behind it, so the arenas are set once, when they are (re)allocated -- on the handle's stream, k_frame's
+    if ((rc = ensure(h, pb.bkt, p.bkt)) || (rc = ensure_zeroed(h, pb.bcnt, p.bcnt)) || (rc = ensure_zeroed(h, pb.fctl, p.fctl))) return rc;     // (the form words: bucket form until a tile needs more)
+    if (p.spill > pb.spill.cap) {
+        if ((rc = ensure(h, pb.spill, p.spill))) return rc;
+        GEM_HIP(h, hipMemsetAsync(pb.spill.p, 0xff, pb.spill.cap, h->stream));     // tile word == kSpillFree
+    }
+    return stage_batch_tables(h, pb, p.tables, host);
+}
+// the queued increments and a dirty floor have gone into the pass that was just enqueued
+static int pass_done(gem_handle* h, long long n)
+{
+    h->n_pending = 0;
+    h->floor_dirty = false;
+    h->stats.points_in = n;
+    return GEM_OK;
+}
+// Passes that ran entirely on the handle's stream (single sweeps, k_frame, a flushed deferred fuse) read either half of the double
+// buffer without recording a per-half event.  Before a pass on another stream may overwrite a half, those streams wait for
+// everything enqueued on the handle's stream so far (one event at the switch, none per frame).
+static int switch_to_bin_streams(gem_handle* h, bool overlap)
+{
+    if (!overlap) h->main_reads_pb = true;
+    if (!overlap || !h->main_reads_pb) return GEM_OK;
+    GEM_HIP(h, hipEventRecord(h->switch_done, h->stream));
+    GEM_HIP(h, hipStreamWaitEvent(h->bin_stream, h->switch_done, 0));
+    if (h->bin_stream2) GEM_HIP(h, hipStreamWaitEvent(h->bin_stream2, h->switch_done, 0));
+    if (h->tab_stream) GEM_HIP(h, hipStreamWaitEvent(h->tab_stream, h->switch_done, 0));      // (the batch tables of a pass buffer are uploaded there)
+    h->main_reads_pb = false;
+    for (auto& b : h->pb) b.fuse_recorded = false;      // covered by the wait above
+    return GEM_OK;
 }
 
 // Everything a batched pass's device tables are a function of, as bytes: equal keys = equal tables.
@@ -67,13 +156,11 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
     const bool batched = in.n_sweeps > 1;
     const bool with_src = (attr & 3) != 0;
     const int chunk = sort_chunk_for(in.n, h->sort_chunk);              // 1024-record chunks for passes that 4096-record ones would leave on a third of the chip
-    const SortShape sh1 = sort_shape(geo.dbins[0], with_src, chunk);
-    std::vector<int> chunk0(in.n_sweeps + 1, 0);
-    for (int s = 0; s < in.n_sweeps; ++s) {
-        const long long cnt = batched ? in.offsets[s + 1] - in.offsets[s] : in.n;
-        chunk0[s + 1] = chunk0[s] + (int)((cnt + sh1.chunk - 1) / sh1.chunk);
-    }
-    const int NC1 = chunk0[in.n_sweeps];
+    const long long nc2max = (in.n + chunk - 1) / chunk;
+    std::vector<int> chunk0(batched ? in.n_sweeps + 1 : 0, 0);        // first chunk of every sweep: a batch's table (a single cloud: no heap)
+    for (int s = 0; batched && s < in.n_sweeps; ++s) chunk0[s + 1] = chunk0[s] + (int)((in.offsets[s + 1] - in.offsets[s] + chunk - 1) / chunk);
+    const int NC1 = batched ? chunk0[in.n_sweeps] : (int)nc2max;
+    const SortPlan plan = sort_plan(geo.n_passes, geo.dbins, in.n, (size_t)NC1, (size_t)nc2max, in.n_sweeps, with_src, walk_blocks(geo, shard != nullptr), shard != nullptr);
     const bool dense = h->n_pending > 0 || h->floor_dirty || (batched && in.var_updates != nullptr);
     const int T = geo.T;
     h->T = T;
@@ -96,42 +183,14 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
     const unsigned slot = overlap ? seq % (unsigned)h->sort_ring : 0u;
     gem_handle::PassBuffers& pb = h->pb[slot];
     hipStream_t sbin = overlap ? (((seq & 1u) && h->sort_streams > 1 && h->bin_stream2) ? h->bin_stream2 : h->bin_stream) : h->stream;
-    if (overlap && h->main_reads_pb) {                   // see run_pipeline
-        GEM_HIP(h, hipEventRecord(h->switch_done, h->stream));
-        GEM_HIP(h, hipStreamWaitEvent(h->bin_stream, h->switch_done, 0));
-        if (h->bin_stream2) GEM_HIP(h, hipStreamWaitEvent(h->bin_stream2, h->switch_done, 0));
-        if (h->tab_stream) GEM_HIP(h, hipStreamWaitEvent(h->tab_stream, h->switch_done, 0));      // (the batch tables of a pass buffer are uploaded there)
-        h->main_reads_pb = false;
-        for (auto& b : h->pb) b.fuse_recorded = false;
-    }
-    if (!overlap) h->main_reads_pb = true;
+    int rc;
+    if ((rc = switch_to_bin_streams(h, overlap))) return rc;
     if (h->trace)
         fprintf(stderr, "[gem] sorted pass: n=%lld sweeps=%d overlap=%d (knob %d, min %lld, own stream %d, counting %d, shard %d) slot=%u stream=%s\n",
                 (long long)in.n, in.n_sweeps, (int)overlap, (int)h->overlap, (long long)std::min(h->overlap_min_points, h->sort_overlap_min_points), (int)(h->stream == h->own_stream),
                 (int)h->counting, (int)(shard != nullptr), slot, sbin == h->stream ? "main" : (sbin == h->bin_stream ? "bin" : "bin2"));
 
-    const long long nc2max = (in.n + sh1.chunk - 1) / sh1.chunk;
-    const size_t N = (size_t)in.n;
-    int rc;
-    // (+64 bytes: k_fuse_walk fetches whole groups of four records; a cell's last group may reach past the last record)
-    if ((rc = ensure(h, pb.s_hv1, N * 8 + 64))) return rc;
-    if ((rc = ensure(h, pb.s_hv2, N * 8 + 64))) return rc;
-    if ((rc = ensure(h, pb.s_key1, N * 4 + 64))) return rc;
-    if ((rc = ensure(h, pb.s_key2, N * 4 + 64))) return rc;
-    if (with_src) {
-        if ((rc = ensure(h, pb.s_src1, N * 4 + 64))) return rc;
-        if ((rc = ensure(h, pb.s_src2, N * 4 + 64))) return rc;
-    }
-    int bins_hi = 1;                                                  // the later passes share one count table
-    for (int i = 1; i < geo.n_passes; ++i) bins_hi = std::max(bins_hi, geo.dbins[i]);
-    if ((rc = ensure(h, pb.s_cnt1, (size_t)NC1 * geo.dbins[0] * 4))) return rc;
-    if ((rc = ensure(h, pb.s_cnt2, (size_t)nc2max * bins_hi * 4 + 16))) return rc;
-    // segment sums [pass][4][bins] | record count | bin bases of the last pass [bins + 1]
-    size_t o_seg[3] = {0, 0, 0}, o_next = 0;
-    for (int i = 0; i < geo.n_passes; ++i) { o_seg[i] = o_next; o_next += (size_t)geo.dbins[i] * 16; }
-    const size_t o_total = o_next, o_base = (o_total + 4 + 15) & ~(size_t)15;
-    const size_t o_segcnt = (o_base + ((size_t)geo.dbins[geo.n_passes - 1] + 1) * 4 + 15) & ~(size_t)15;
-    if ((rc = ensure(h, pb.s_misc, o_segcnt + (size_t)NC1 * kSortSegsPerChunk * 4))) return rc;
+    if ((rc = ensure_sort_buffers(h, pb, plan))) return rc;
     // the walk of pass p-2 has read these buffers (host-side wait, see run_pipeline)
     if (overlap && pb.fuse_recorded) GEM_HIP(h, hipEventSynchronize(pb.fuse_done));
 
@@ -139,50 +198,19 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
     WalkArgs wa{};
     int batch_src = -1;                                               // which k_sort_project instantiation the batch's frames take (cached with the tables)
     if (batched) {
-        // tables: frames | chunk0 | first | var_updates
-        const size_t o_frames = 0;
-        const size_t o_chunk0 = o_frames + sizeof(FrameConst) * in.n_sweeps;
-        const size_t o_first = (o_chunk0 + sizeof(int) * (in.n_sweeps + 1) + 15) & ~(size_t)15;
-        const size_t o_var = o_first + sizeof(long long) * (in.n_sweeps + 1);
-        const size_t o_orig = o_var + sizeof(float) * in.n_sweeps;
-        const size_t total = o_orig + sizeof(int) * in.n_sweeps;
-        if (total > pb.tables.cap) pb.tab_key.clear();               // (a new allocation holds nothing, even at the old address)
-        if ((rc = ensure(h, pb.tables, total))) return rc;
+        const TablesPlan& t = plan.tables;
         batch_tables_key(h, in, 0, pb.tables.p, chunk0, h->key_scratch);
         const bool tables_cached = h->cache_tables && h->key_scratch == pb.tab_key;
         if (!tables_cached) {
-            if (total > pb.host_cap) {
-                if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));
-                if (pb.host_tables) GEM_HIP(h, hipHostFree(pb.host_tables));
-                pb.host_tables = nullptr; pb.host_cap = 0;
-                GEM_HIP(h, hipHostMalloc(&pb.host_tables, total * 2, hipHostMallocDefault));
-                pb.host_cap = total * 2;
-            }
-            if (!pb.tables_done) GEM_HIP(h, hipEventCreateWithFlags(&pb.tables_done, hipEventDisableTiming));
-            if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));     // the previous upload from this buffer has been read
-            unsigned char* host = static_cast<unsigned char*>(pb.host_tables);
-            memset(host, 0, total);
-            // clouds whose frames all use the laser model (the reference's only GPU model, GPU:403-408) take the instantiation without
-            // the camera models' double-precision code: 2; with every frame's rotation variance zero (height_variance, kModelLaserFast): 4
-            bool laser = true, fast = true;
-            for (int s = 0; s < in.n_sweeps; ++s) {
-                FrameConst& fc = reinterpret_cast<FrameConst*>(host + o_frames)[s];
-                fill_frame(h, &in.params[s], fc);
-                laser = laser && in.params[s].sensor_model == GEM_MODEL_LASER;
-                fast = fast && fc.fast_laser != 0;
-            }
-            pb.tab_src = laser ? (fast ? 4 : 2) : 0;
-            memcpy(host + o_chunk0, chunk0.data(), sizeof(int) * (in.n_sweeps + 1));
-            memcpy(host + o_first, in.offsets, sizeof(long long) * (in.n_sweeps + 1));
-            if (in.var_updates) memcpy(host + o_var, in.var_updates, sizeof(float) * in.n_sweeps);
-            if (in.sweep_orig0) memcpy(host + o_orig, in.sweep_orig0, sizeof(int) * in.n_sweeps);
+            unsigned char* host;
+            if ((rc = stage_batch_tables(h, pb, t, &host))) return rc;
+            pb.tab_src = fill_batch_tables(h, host, t, in, chunk0.data());
             // on a stream of its own when the passes overlap: the upload (a 5 us blit + two kernel boundaries) then runs while the
             // binning stream is still sorting the pass before, instead of at the head of this pass's chain (the buffer's last
             // readers -- the pass before the previous one -- are done: fuse_done above)
             hipStream_t stab = sbin;
             if (overlap && h->tab_stream) stab = h->tab_stream;
-            pb.tab_key.clear();                                        // (not valid until the upload is enqueued)
-            GEM_HIP(h, hipMemcpyAsync(pb.tables.p, host, total, hipMemcpyHostToDevice, stab));
+            GEM_HIP(h, hipMemcpyAsync(pb.tables.p, host, t.total, hipMemcpyHostToDevice, stab));
             GEM_HIP(h, hipEventRecord(pb.tables_done, stab)); pb.tables_recorded = true;
             if (stab != sbin) GEM_HIP(h, hipStreamWaitEvent(sbin, pb.tables_done, 0));
             pb.tab_key = h->key_scratch;
@@ -194,11 +222,11 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
         }
         batch_src = pb.tab_src;
         unsigned char* d = static_cast<unsigned char*>(pb.tables.p);
-        sa.frames = reinterpret_cast<const FrameConst*>(d + o_frames);
-        sa.sweep_chunk0 = reinterpret_cast<const int*>(d + o_chunk0);
-        sa.sweep_first = reinterpret_cast<const long long*>(d + o_first);
-        sa.sweep_orig0 = in.sweep_orig0 ? reinterpret_cast<const int*>(d + o_orig) : nullptr;
-        wa.var_updates = in.var_updates ? reinterpret_cast<const float*>(d + o_var) : nullptr;
+        sa.frames = reinterpret_cast<const FrameConst*>(d + t.o_frames);
+        sa.sweep_chunk0 = reinterpret_cast<const int*>(d + t.o_first0);
+        sa.sweep_first = reinterpret_cast<const long long*>(d + t.o_first);
+        sa.sweep_orig0 = in.sweep_orig0 ? reinterpret_cast<const int*>(d + t.o_orig) : nullptr;
+        wa.var_updates = in.var_updates ? reinterpret_cast<const float*>(d + t.o_var) : nullptr;
     } else {
         fill_frame(h, in.src == 0 ? in.params : nullptr, sa.frame0);
         sa.orig0_single = in.sweep_orig0 ? in.sweep_orig0[0] : 0;
@@ -219,30 +247,17 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
     // were 4.4 ns each).
     constexpr long long kFuseCountMaxPoints = 600000;
     sa.fuse_count = (geo.n_passes >= 2 && (h->fuse_count == 2 || (h->fuse_count == 1 && in.n <= kFuseCountMaxPoints))) ? 1 : 0;
-    unsigned char* misc = static_cast<unsigned char*>(pb.s_misc.p);
-    for (int i = 0; i < geo.n_passes; ++i) {
-        sa.cnt[i] = static_cast<uint32_t*>(i == 0 ? pb.s_cnt1.p : pb.s_cnt2.p);
-        sa.segtot[i] = reinterpret_cast<uint32_t*>(misc + o_seg[i]);
-    }
-    sa.total = reinterpret_cast<uint32_t*>(misc + o_total); sa.bin_base = reinterpret_cast<uint32_t*>(misc + o_base);
-    // (word 1 behind the record count: k_sort_project stores the pass's epoch there when a record is outside the plain range of
-    //  the walks' chain loops; epochs never repeat, so the word needs no clearing)
-    sa.odd_flag = sa.total + 1; sa.epoch = ++h->sort_epoch; if (sa.epoch == 0u) sa.epoch = ++h->sort_epoch;
+    bind_sort_buffers(plan, geo.n_passes, {pb.s_hv1.p, pb.s_hv2.p, pb.s_key1.p, pb.s_key2.p, pb.s_src1.p, pb.s_src2.p, pb.s_cnt1.p, pb.s_cnt2.p, pb.s_misc.p}, sa);
+    sa.epoch = ++h->sort_epoch; if (sa.epoch == 0u) sa.epoch = ++h->sort_epoch;
     wa.odd_flag = sa.odd_flag; wa.epoch = sa.epoch;
     sa.blk_cnt = nullptr;
-    if ((geo.block_form && geo.n_passes > 1) || shard) {             // the walk will want every block's range (the last pass's bins are not the blocks)
-        if ((rc = ensure_zeroed(h, pb.s_blkcnt, (size_t)4 * T * sizeof(uint32_t))) || (rc = ensure(h, pb.s_ranges, (size_t)4 * T * sizeof(uint2)))) return rc;
+    if (plan.blkcnt) {                                                // the walk will want every block's range (the last pass's bins are not the blocks)
         sa.blk_cnt = static_cast<uint32_t*>(pb.s_blkcnt.p);
         // the counts are zero between passes because k_block_prefix leaves them so; a pass that failed between the two leaves them
         // dirty: cleared here before the next one counts
         if (pb.blkcnt_dirty) GEM_HIP(h, hipMemsetAsync(pb.s_blkcnt.p, 0, pb.s_blkcnt.cap, sbin));
         pb.blkcnt_dirty = true;
     }
-    sa.seg_cnt = reinterpret_cast<uint32_t*>(misc + o_segcnt);
-    // arrays a: the projected records in input order, later the final order; arrays b: the order after pass 1
-    sa.hv_a = static_cast<uint2*>(pb.s_hv2.p); sa.hv_b = static_cast<uint2*>(pb.s_hv1.p);
-    sa.key_a = static_cast<uint32_t*>(pb.s_key2.p); sa.key_b = static_cast<uint32_t*>(pb.s_key1.p);
-    sa.src_a = with_src ? static_cast<uint32_t*>(pb.s_src2.p) : nullptr; sa.src_b = with_src ? static_cast<uint32_t*>(pb.s_src1.p) : nullptr;
     sa.counters = h->counting ? h->d_counters : nullptr;
 
     const bool final_b = (geo.n_passes & 1) != 0;                     // the passes ping-pong between the arrays: a -> b -> a (-> b)
@@ -296,8 +311,7 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
         // (k_block_prefix): behind the sort, on its stream
         gem_handle::Shard& sd = h->shard;
         sd.valid = false;
-        if (!h->sh_host) GEM_HIP(h, hipHostMalloc(&h->sh_host, kShardHostBytes, hipHostMallocDefault));
-        if ((rc = ensure(h, pb.s_shard, 64 * sizeof(uint32_t)))) return rc;
+        if ((rc = ensure_shard_tables(h))) return rc;
         uint32_t* host = static_cast<uint32_t*>(h->sh_host);
         for (int k = 0; k <= shard->nstrips; ++k) {
             const int tile_row = shard->strip_rows[k] >= h->L ? geo.tiles_per_row : shard->strip_rows[k] / 32;
@@ -337,10 +351,7 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
         h->dwalk.wa = wa; h->dwalk.block_form = geo.block_form; h->dwalk.attr = attr; h->dwalk.slot = slot; h->dwalk.valid = true;
         ++h->walks_left;
         h->dbg_rows = 0;
-        h->n_pending = 0;
-        h->floor_dirty = false;
-        h->stats.points_in = in.n;
-        return GEM_OK;
+        return pass_done(h, in.n);
     }
     if (overlap) {
         if (!ride_bin) GEM_HIP(h, hipEventRecord(pb.bin_done, sbin));
@@ -355,72 +366,42 @@ int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGe
     }
     { Timed t(h, 9); GEM_HIP(h, geo.block_form ? launch_block_walk(h->stream, wa, attr, t.events()) : launch_walk(h->stream, wa, attr, t.events())); }
     if (overlap) { GEM_HIP(h, hipEventRecord(pb.fuse_done, h->stream)); pb.fuse_recorded = true; }
-    h->n_pending = 0;
-    h->floor_dirty = false;
-    h->stats.points_in = in.n;
-    return GEM_OK;
+    return pass_done(h, in.n);
 }
 
 int run_pipeline(gem_handle* h, const PassInput& in0)
 {
-    // Big passes (batches of sweeps, aggregated clouds, depth images) go through the sorted pipeline: a global two-digit counting
-    // sort of the in-map points by (tile, cell), then one walk per cell (gem_sort.hip).  Small ones -- a single LiDAR sweep -- keep
-    // the tile pipeline below, whose one or two launches cost less than the sort's seven.
-    // Measured crossover (tools/dbg/crossover.py): batches of LiDAR sweeps -- a few points per cell and sweep -- are faster on the tile
-    // pipeline up to about 8 sweeps (1 M points); a single dense cloud (a depth image: hundreds of points per cell) from ~150 k points.
-    const long long sort_from = in0.n_sweeps > 1 ? h->sort_min_points_batch : h->sort_min_points;
-    if (h->sort_path && in0.n >= sort_from && in0.n < (1ll << 31)) {
-        int attr = 0;
-        if (in0.src == 0 && in0.rgb) attr = 1;
-        if (in0.src == 1 && in0.f_R && in0.f_G && in0.f_B && in0.f_I) attr = 2;
-        if (h->track_lowest) attr |= 4;
-        // Batches of sweeps -- a few records per cell and sweep, every batch of a block's records spread over its cells -- take the
-        // block-sorted form (one counting-sort pass for the 600^2 map instead of two, no per-cell order in HBM at all); a single
-        // dense cloud (a depth image: a quarter of its points in one block, hundreds per cell, image row by image row) needs the
-        // whole chip to order it by cell: the cell-sorted form.
-        // (Maps of more than kOnePassMaxBins blocks take two passes over the block id and k_block_prefix; with k_fuse_block's rounds
-        //  of 512 records for light blocks that is still the shorter way -- C5, 2400^2, same box: 351-365 us cell-sorted in three
-        //  passes, 333-340 block-sorted in two.)
-        const bool block_form = h->sort_form == 2 || (h->sort_form == 0 && in0.n_sweeps > 1);
-        SortGeometry geo = sort_geometry(h, in0.n_sweeps, block_form);
-        if (!geo.ok) { geo = sort_geometry(h, in0.n_sweeps, !block_form); ++h->sort_fallbacks; }    // (a forced form / pass count that does not fit this map: counted, gem_debug_get)
-        if (geo.ok) return run_sort_pipeline(h, in0, attr, geo);
-    }
+    const PlanEnv env = plan_env(h);
+    const PassChoice choice = choose_pass(env, in0.n, in0.n_sweeps, sort_bins_fit);
+    if (choice.fell_back) ++h->sort_fallbacks;                        // (a forced form / pass count that does not fit this map: counted, gem_debug_get)
+    int attr = 0;
+    if (in0.src == 0 && in0.rgb) attr = 1;
+    if (in0.src == 1 && in0.f_R && in0.f_G && in0.f_B && in0.f_I) attr = 2;
+    if (h->track_lowest) attr |= 4;                  // the kernel variants that also maintain map_lowest (16x16 tiles)
+    if (choice.geo.ok) return run_sort_pipeline(h, in0, attr, choice.geo);
     { const int rcw = flush_walk(h); if (rcw) return rcw; }           // (a sorted pass's walk still to be launched: before anything of this pass fuses)
-    // A big single cloud becomes a batch of sweeps with one frame: every tile then only reads the descriptor
-    // rows of the sweeps that reach it (flag[tile][sweep]) instead of one row over all units.  The
-    // recurrence is unchanged: the per-sweep variance floor is idempotent with the floor at the start of every
-    // step (GPU:500-501), and no variance increment is applied between these sweeps.
+    // A big single cloud becomes a batch of sweeps with one frame (cut_sweeps).  The recurrence is unchanged: the per-sweep variance
+    // floor is idempotent with the floor at the start of every step (GPU:500-501), and no variance increment is applied between
+    // these sweeps.
+    // (Fuse's arrays too, src == 1: a descriptor row holds the units of ONE sweep, k_fuse_list reads one chunk of kChunkUnits of it --
+    //  until round 4 the cut was only made for clouds, and a Fuse of more than 131 072 points that stayed below the sorted pipeline's
+    //  threshold lost every point behind the first 131 072.)
+    TilePlan plan = tile_plan(env, in0.n, in0.n_sweeps, in0.offsets);
+    if (plan.err) return fail(h, GEM_ERR_INVALID, plan.err == 1 ? "cloud too large" : "lowest tracking: the pass is too large for 16x16 tiles (cut it into smaller calls)");
     PassInput in = in0;
     std::vector<gem_frame_params> cut_params;
     std::vector<long long> cut_offsets;
     std::vector<int> orig0;
-    // (Fuse's arrays too, src == 1: a descriptor row holds the units of ONE sweep, k_fuse_list reads one chunk of kChunkUnits of it --
-    //  until round 4 the cut was only made for clouds, and a Fuse of more than 131 072 points that stayed below the sorted pipeline's
-    //  threshold lost every point behind the first 131 072.)
-    if (in.n_sweeps == 1 && in.n > kSweepPoints) {
-        const int ns = (int)((in.n + kSweepPoints - 1) / kSweepPoints);
+    if (plan.n_sweeps != in.n_sweeps) {
+        const int ns = plan.n_sweeps;
         if (in.src == 0) cut_params.assign(ns, *in.params);
         cut_offsets.resize(ns + 1); orig0.resize(ns);
         for (int s = 0; s <= ns; ++s) cut_offsets[s] = std::min<long long>(in.n, (long long)s * kSweepPoints);
         for (int s = 0; s < ns; ++s) orig0[s] = (int)cut_offsets[s];
-        in.n_sweeps = ns; in.params = in.src == 0 ? cut_params.data() : nullptr; in.offsets = cut_offsets.data(); in.var_updates = nullptr;
+        in.n_sweeps = ns; in.params = in.src == 0 ? cut_params.data() : nullptr; in.offsets = cut_offsets.data(); in.var_updates = nullptr; in.sweep_orig0 = orig0.data();
     }
     const bool batched = in.n_sweeps > 1;
-    const int U = kUnit;
-
-    // units per sweep
-    std::vector<int> unit0(in.n_sweeps + 1, 0);
-    int bpad = 0;
-    for (int s = 0; s < in.n_sweeps; ++s) {
-        const long long cnt = batched ? in.offsets[s + 1] - in.offsets[s] : in.n;
-        long long units = (cnt + U - 1) / U;
-        units = (units + 31) & ~31ll;               // descriptor rows are flagged in groups of 32 units (64 B)
-        if (units > 0x3fffffff) return fail(h, GEM_ERR_INVALID, "cloud too large");
-        unit0[s + 1] = unit0[s] + (int)units;
-        bpad = std::max(bpad, (int)units);
-    }
-    const int B = unit0[in.n_sweeps];
+    const int U = kUnit, B = plan.B, bpad = plan.bpad;
     const bool dense = h->n_pending > 0 || h->floor_dirty || (batched && in.var_updates != nullptr);
 
     if (B == 0) {
@@ -432,27 +413,7 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
             }
         return (h->n_pending || h->floor_dirty) ? flush_pending(h, true) : GEM_OK;
     }
-    int attr = 0;
-    if (in.src == 0 && in.rgb) attr = 1;
-    if (in.src == 1 && in.f_R && in.f_G && in.f_B && in.f_I) attr = 2;
-    if (h->track_lowest) attr |= 4;                  // the kernel variants that also maintain map_lowest (16x16 tiles)
-    // tile size of this pass: 16x16 cells (more, lighter workgroups: better balance and latency hiding)
-    // unless the [sweep][tile][unit] descriptor table would get too big, then 32x32
-    int ts = h->ts;
-    {
-        const long long tpr4 = (h->L + 15) / 16;
-        const long long table4 = tpr4 * tpr4 * (long long)bpad * in.n_sweeps * (long long)sizeof(uint16_t);
-        if (ts == 0) ts = table4 <= (1ll << 29) ? 4 : 5;
-        // the kernel variants that maintain map_lowest exist for 16x16 tiles only: the choice is made HERE, before the tile
-        // geometry (te, tiles_per_row, T, table sizes) is derived from it
-        if (h->track_lowest) {
-            if (table4 > (16ll << 30)) return fail(h, GEM_ERR_INVALID, "lowest tracking: the pass is too large for 16x16 tiles (cut it into smaller calls)");
-            ts = 4;
-        }
-    }
-    const int te = 1 << ts;
-    const int tiles_per_row = (h->L + te - 1) / te;
-    const int T = tiles_per_row * tiles_per_row;
+    const int ts = plan.ts, tiles_per_row = plan.tiles_per_row, T = plan.T;
     h->T = T;
     if (fuse_lds_bytes(ts, h->fuse_variant, attr & 3) > 160 * 1024) return fail(h, GEM_ERR_INVALID, "fuse kernel geometry exceeds the LDS");
 
@@ -469,86 +430,39 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     if (!defer) { const int rcd = flush_deferred(h); if (rcd) return rcd; }
     gem_handle::PassBuffers& pb = h->pb[(overlap || defer) ? (h->pass++ & 1u) : 0u];
     hipStream_t sbin = overlap ? h->bin_stream : h->stream;
-    if (overlap && h->main_reads_pb) {
-        // Passes that ran entirely on the handle's stream (single sweeps, k_frame, a flushed deferred fuse) read either half of
-        // the double buffer without recording a per-half event.  Before k_bin on the other stream may overwrite a half, that
-        // stream waits for everything enqueued on the handle's stream so far (one event at the switch, none per frame).
-        GEM_HIP(h, hipEventRecord(h->switch_done, h->stream));
-        GEM_HIP(h, hipStreamWaitEvent(h->bin_stream, h->switch_done, 0));
-        if (h->bin_stream2) GEM_HIP(h, hipStreamWaitEvent(h->bin_stream2, h->switch_done, 0));
-        if (h->tab_stream) GEM_HIP(h, hipStreamWaitEvent(h->tab_stream, h->switch_done, 0));      // (the batch tables of a pass buffer are uploaded there)
-        h->main_reads_pb = false;
-        for (auto& b : h->pb) b.fuse_recorded = false;      // covered by the wait above
-    }
-    if (!overlap) h->main_reads_pb = true;
     int rc;
-    if ((rc = ensure(h, pb.rec, (size_t)B * U * sizeof(uint4)))) return rc;
-    if ((rc = ensure(h, pb.srt, (size_t)B * U * sizeof(uint4) + 16))) return rc;     // sorted arena + its bump pointer (last 16 bytes)
+    if ((rc = switch_to_bin_streams(h, overlap))) return rc;
     // k_fuse of pass p-2 has read these buffers.  Waited for on the HOST: a hipStreamWaitEvent on an event that is still
     // far from complete delayed the start of k_bin behind it (C5: 1.52 -> 1.64-1.81 ms per pass, the overlap mostly lost);
     // the host stays at most two (big) passes ahead of the device, which costs nothing.
     if (overlap && pb.fuse_recorded) GEM_HIP(h, hipEventSynchronize(pb.fuse_done));
-    {   // descriptor table [sweep][tile][unit in sweep]: k_fuse_list zeroes what it consumes, so the table only
-        // has to be cleared when it is (re)allocated
-        const size_t need = (size_t)in.n_sweeps * T * bpad * sizeof(uint16_t);
-        if (need > pb.seg.cap) {
-            if ((rc = ensure(h, pb.seg, need))) return rc;
-            GEM_HIP(h, hipMemsetAsync(pb.seg.p, 0, pb.seg.cap, sbin));
-        }
-        // touched flags [tile][sweep]: stamped with the pass's epoch instead of being cleared
-        const size_t need_flag = (size_t)T * in.n_sweeps * sizeof(uint32_t);
-        const size_t need_gflag = (size_t)in.n_sweeps * T * (bpad / 32) * sizeof(uint32_t);
-        const bool grow_flag = need_flag > pb.flag.cap || need_gflag > pb.gflag.cap;
-        if ((rc = ensure(h, pb.flag, need_flag))) return rc;
-        if ((rc = ensure(h, pb.gflag, need_gflag))) return rc;
-        if (grow_flag || pb.epoch >= kFlagEpochMax) {
-            GEM_HIP(h, hipMemsetAsync(pb.flag.p, 0, pb.flag.cap, sbin));
-            GEM_HIP(h, hipMemsetAsync(pb.gflag.p, 0, pb.gflag.cap, sbin));
-            pb.epoch = 0;
-        }
-        ++pb.epoch;
+    // k_frame bins into per-tile buckets: the point index rides in 22 bits of a record (a single sweep has at most kSweepPoints)
+    static_assert(kSweepPoints <= (1ll << 22), "k_frame's record format");
+    unsigned char* host = nullptr;
+    if ((rc = ensure_tile_buffers(h, pb, plan, sbin, defer, &host))) return rc;       // (a batch: the sorted pipeline's cached tables of this buffer set are overwritten)
+    if (pb.epoch >= kFlagEpochMax) {
+        GEM_HIP(h, hipMemsetAsync(pb.flag.p, 0, pb.flag.cap, sbin));
+        GEM_HIP(h, hipMemsetAsync(pb.gflag.p, 0, pb.gflag.cap, sbin));
+        pb.epoch = 0;
     }
+    ++pb.epoch;
 
     BinArgs ba{};
     FuseArgs fa{};
+    const TablesPlan& tab = plan.tables;
     if (batched) {
-        // tables: frames | unit0 | first | orig0 | var_updates
-        const size_t o_frames = 0;
-        const size_t o_unit0 = o_frames + sizeof(FrameConst) * in.n_sweeps;
-        const size_t o_first = (o_unit0 + sizeof(int) * (in.n_sweeps + 1) + 15) & ~(size_t)15;
-        const size_t o_orig = o_first + sizeof(long long) * (in.n_sweeps + 1);
-        const size_t o_var = o_orig + sizeof(int) * in.n_sweeps;
-        const size_t total = o_var + sizeof(float) * in.n_sweeps;
-        pb.tab_key.clear();                                          // (the sorted pipeline's cached tables of this buffer set are overwritten below)
-        if ((rc = ensure(h, pb.tables, total))) return rc;
-        // staged in pinned memory so that the upload does not make the host wait for the stream (a pageable source would:
-        // the call then cost a whole k_bin of host time, 240 us per C4 batch)
-        if (total > pb.host_cap) {
-            if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));
-            if (pb.host_tables) GEM_HIP(h, hipHostFree(pb.host_tables));
-            pb.host_tables = nullptr; pb.host_cap = 0;
-            GEM_HIP(h, hipHostMalloc(&pb.host_tables, total * 2, hipHostMallocDefault));
-            pb.host_cap = total * 2;
-        }
-        if (!pb.tables_done) GEM_HIP(h, hipEventCreateWithFlags(&pb.tables_done, hipEventDisableTiming));
-        if (pb.tables_recorded) GEM_HIP(h, hipEventSynchronize(pb.tables_done));     // the previous upload from this buffer has been read
-        unsigned char* host = static_cast<unsigned char*>(pb.host_tables);
-        memset(host, 0, total);
-        for (int s = 0; s < in.n_sweeps; ++s) fill_frame(h, in.src == 0 ? &in.params[s] : nullptr, reinterpret_cast<FrameConst*>(host + o_frames)[s]);
-        memcpy(host + o_unit0, unit0.data(), sizeof(int) * (in.n_sweeps + 1));
-        memcpy(host + o_first, in.offsets, sizeof(long long) * (in.n_sweeps + 1));
-        if (!orig0.empty()) memcpy(host + o_orig, orig0.data(), sizeof(int) * in.n_sweeps);
-        if (in.var_updates) memcpy(host + o_var, in.var_updates, sizeof(float) * in.n_sweeps);
-        pb.tab_key.clear();                                  // (the sorted pipeline's cached tables of this buffer set are overwritten)
-        GEM_HIP(h, hipMemcpyAsync(pb.tables.p, host, total, hipMemcpyHostToDevice, sbin));
+        std::vector<int> unit0(in.n_sweeps + 1, 0);
+        for (int s = 0; s < in.n_sweeps; ++s) unit0[s + 1] = unit0[s] + (int)sweep_units(in.offsets[s + 1] - in.offsets[s]);
+        (void)fill_batch_tables(h, host, tab, in, unit0.data());
+        GEM_HIP(h, hipMemcpyAsync(pb.tables.p, host, tab.total, hipMemcpyHostToDevice, sbin));
         GEM_HIP(h, hipEventRecord(pb.tables_done, sbin)); pb.tables_recorded = true;
         unsigned char* d = static_cast<unsigned char*>(pb.tables.p);
-        ba.frames = reinterpret_cast<const FrameConst*>(d + o_frames);
-        ba.sweep_unit0 = reinterpret_cast<const int*>(d + o_unit0);
-        ba.sweep_first = reinterpret_cast<const long long*>(d + o_first);
-        ba.sweep_orig0 = orig0.empty() ? nullptr : reinterpret_cast<const int*>(d + o_orig);
+        ba.frames = reinterpret_cast<const FrameConst*>(d + tab.o_frames);
+        ba.sweep_unit0 = reinterpret_cast<const int*>(d + tab.o_first0);
+        ba.sweep_first = reinterpret_cast<const long long*>(d + tab.o_first);
+        ba.sweep_orig0 = in.sweep_orig0 ? reinterpret_cast<const int*>(d + tab.o_orig) : nullptr;
         fa.sweep_unit0 = ba.sweep_unit0;
-        fa.var_updates = in.var_updates ? reinterpret_cast<const float*>(d + o_var) : nullptr;
+        fa.var_updates = in.var_updates ? reinterpret_cast<const float*>(d + tab.o_var) : nullptr;
     } else {
         fill_frame(h, in.src == 0 ? in.params : nullptr, ba.frame0);
     }
@@ -592,9 +506,6 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     }
 
     if (defer) {
-        // k_frame bins into per-tile buckets: the point index rides in 22 bits of a record (a single sweep has at most kSweepPoints)
-        static_assert(kSweepPoints <= (1ll << 22), "k_frame's record format");
-        if ((rc = ensure_frame_buckets(h, pb, T, B))) return rc;
         ba.bkt = static_cast<uint32_t*>(pb.bkt.p); ba.bcount = static_cast<uint32_t*>(pb.bcnt.p); ba.spill = static_cast<uint4*>(pb.spill.p);
         ba.ctl = static_cast<uint32_t*>(pb.fctl.p);
         fa.bkt = ba.bkt; fa.bcount = ba.bcount; fa.spill = ba.spill; fa.ctl = ba.ctl;
@@ -602,10 +513,7 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
         if (h->deferred.valid) { Timed t(h, 2); GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, ba, attr, t.events())); }
         else                   { Timed t(h, 0); GEM_HIP(h, launch_frame(h->stream, FuseArgs{}, ba, attr, t.events())); }   // (no tile blocks: binning only)
         h->deferred.fa = fa; h->deferred.ts = ts; h->deferred.attr = attr; h->deferred.valid = true;
-        h->n_pending = 0;
-        h->floor_dirty = false;
-        h->stats.points_in = in.n;
-        return GEM_OK;
+        return pass_done(h, in.n);
     }
     if (h->counting) GEM_HIP(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(unsigned long long), h->stream));
     { Timed t(h, 0); GEM_HIP(h, launch_bin(sbin, ba, in.src, ts, t.events())); }
@@ -615,11 +523,55 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     }
     { Timed t(h, 1); GEM_HIP(h, launch_fuse(h->stream, fa, ts, attr, h->fuse_variant, t.events())); }
     if (overlap) { GEM_HIP(h, hipEventRecord(pb.fuse_done, h->stream)); pb.fuse_recorded = true; }
-    h->n_pending = 0;
-    h->floor_dirty = false;
-    h->stats.points_in = in.n;
-    return GEM_OK;
+    return pass_done(h, in.n);
 }
 
-
 } // namespace gemi
+
+// Arenas for the largest pass the caller is going to make, allocated NOW: the arenas only ever grow, but growing means waiting for
+// everything in flight, hipFree and hipMalloc -- in the middle of a stream of frames that is a stall of a millisecond or more the
+// first time a bigger cloud arrives (measured: tools/bench_configs.py --configs reserve).  max_points points in at most max_sweeps
+// sweeps per call (1 for gem_add*); colours as they will be passed.  Every extremal pass inside the bounds (bound_plans,
+// gem_plan.hpp) is planned as the pipelines plan theirs and allocated through the same ensure_* functions: the sorted forms in the
+// buffer sets their overlapped passes rotate through, the tile pipeline in its two.  On a handle that joined a communicator with
+// tile strips, max_points / max_sweeps bound the GLOBAL points / sweeps of a gem_add_sharded_device step: the shard's sort (its W-th
+// of the points), both sets of receive buffers (no strip gets more records than the step has points) and the small tables.
+int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_colours)
+{
+    if (!h || max_points < 0 || max_sweeps < 1 || max_points >= (1ll << 31)) return h ? fail(h, GEM_ERR_INVALID, "gem_reserve: bad argument") : GEM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipSetDevice(h->device);
+    { const int rcd = settle(h); if (rcd) return rcd; }
+    if (max_points == 0) return GEM_OK;
+    int rc;
+    // staging of host-pointer inputs: a host cloud of the add entries (cloud_layout, where the clean mask also writes), gem_fuse's
+    // seven arrays, gem_process_points' nine
+    if ((rc = ensure(h, h->stage, std::max(cloud_layout(max_points, true, true).bytes, stage_words_bytes(max_points, 9))))) return rc;
+    // (the raw-cloud compactions, gem_capi_clean.cpp, add a count per 1024 points)
+    if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
+    if ((rc = voxel_reserve(h, max_points))) return rc;        // (the VoxelGrid entries, gem_capi_voxel.cpp)
+    // ... and its pinned counterpart.  The deferred / zero-copy uploads (upload_arrays) keep TWO calls' arrays in the buffer, a half
+    // each: gem_fuse's seven arrays are the largest (28 B per point; gem_add with rgb + orig_index: 24), as long as one call stays
+    // below the 16 MB from which uploads go to the runtime's pageable path; callers with host arrays (gem_process_points: nine arrays;
+    // gem_map_feature: nine layers) where that is a modest amount: larger ones grow on first use
+    const size_t one = stage_words_bytes(max_points, 7);
+    size_t want = one < (16u << 20) ? 2 * one + 512 : 0;
+    for (const size_t nine : {stage_words_bytes(max_points, 9), stage_words_bytes(h->cells, 9)}) if (nine <= (64u << 20)) want = std::max(want, nine);
+    if (want) (void)host_stage(h, want);
+    const bool sharded = h->tp_x && h->tile_strips;          // (a handle of the sharded path: its steps are what the bounds describe)
+    const PlanEnv env = plan_env(h);
+    BoundPlan plan[kMaxBoundPlans];
+    const int n_plans = bound_plans(env, max_points, max_sweeps, sharded ? h->nranks : 0, with_colours != 0, sort_bins_fit, plan);
+    for (int i = 0; i < n_plans; ++i) {
+        const BoundPlan& p = plan[i];
+        for (int k = 0; p.kind == 1 && k < env.sort_ring; ++k) if ((rc = ensure_sort_buffers(h, h->pb[k], p.sort))) return rc;
+        for (int k = 0; p.kind == 2 && k < 2; ++k) if ((rc = ensure_tile_buffers(h, h->pb[k], p.tile, h->stream, true))) return rc;
+        if (sharded && p.kind == 1 && (rc = ensure_shard_tables(h, p.sort.blocks))) return rc;
+    }
+    if (sharded) {                                           // every strip's owner receives at most all of the step's points
+        h->recv_bound = max_points;
+        for (int q = 0; h->nranks > 1 && q < 2; ++q) if ((rc = ensure_recv(h, q, (size_t)max_points + 4 * h->nranks))) return rc;
+    } else if (h->track_lowest && (rc = ensure_ray(h))) return rc;
+    GEM_HIP(h, hipStreamSynchronize(h->stream));
+    return GEM_OK;
+}

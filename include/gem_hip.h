@@ -344,7 +344,8 @@ int  gem_get_stats(gem_handle* h, gem_stats* out, int reset);
  * per call (1 for gem_add / gem_add_device / gem_fuse), with or without colours.  The arenas only ever grow, but growing in the
  * middle of a stream -- the first bigger cloud after smaller ones -- waits for everything in flight and re-allocates; after
  * gem_reserve no pass within these bounds allocates, whichever pipeline it takes (the sorted forms from their thresholds on, the
- * tile pipeline below them; the sweeps of a batch below the sorted threshold are taken to be at most twice their mean length).
+ * tile pipeline below them -- a single cloud of more than 131 072 points is fused there as several sweeps, which max_sweeps = 1
+ * covers; the sweeps of a batch below the sorted threshold are taken to be at most twice their mean length).
  * On a handle that joined a communicator with gem_comm_init_tiles the bounds are those of a gem_add_sharded_device STEP -- the
  * GLOBAL points and sweeps: the shard's sort (its W-th of the points), both sets of receive buffers (no strip gets more records
  * than the step has points) and the staging tables are sized.  Synchronous; call it once after gem_create / gem_comm_init*.    */

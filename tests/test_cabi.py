@@ -80,6 +80,20 @@ def test_the_copy_thread_pool_moves_every_byte(tmp_path):
     assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout + run.stderr
 
 
+def test_gem_reserve_covers_the_plan_of_every_pass_inside_its_bounds(tmp_path):
+    """gem_amd/csrc/gem_plan.hpp on its own (tests/cpp/plan_cover.cpp): over map sizes, sorted forms, pass counts, chunks, thresholds,
+    rings, bounds and colours, every buffer of every pass drawn from inside the bounds is no larger than what gem_reserve's bound
+    passes are planned to allocate, exactly; the sub-tables of s_misc do not overlap.  A host-only HIP build: runs without a GPU."""
+    from gem_amd.build import hipcc_path
+    exe = tmp_path / "plan_cover"
+    res = subprocess.run([hipcc_path(), "--offload-host-only", "-x", "hip", "-std=c++17", "-O2", "-Wall", "-Werror",
+                          str(ROOT / "tests" / "cpp" / "plan_cover.cpp"), "-o", str(exe)], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    print(run.stdout)
+    assert run.returncode == 0 and run.stdout.strip().endswith("ok"), run.stdout + run.stderr
+
+
 def test_struct_layouts_match_the_header(tmp_path):
     from gem_amd import _lib
     src = tmp_path / "layout.c"

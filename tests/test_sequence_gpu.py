@@ -101,13 +101,16 @@ def test_random_call_sequence(oracle_mod, monkeypatch, seed):
 
 def test_reserve_then_no_allocation_in_the_stream(oracle_mod):
     """gem_reserve sizes the arenas for the largest pass to come: a stream that starts with small clouds and then meets the big
-    one -- on either pipeline, single sweeps and a batch -- allocates nothing on the way, and the map is the oracle's."""
+    one -- on either pipeline, single sweeps and a batch -- allocates nothing on the way, and the map is the oracle's.  The last
+    input is a coloured single cloud of 150 000 points: with the library's own choice the tile pipeline cuts it into two sweeps,
+    which need the batch tables although the call has one sweep; the forced sorted forms take it with their source arrays."""
     import torch
     wl = synth.config_c4(n_sweeps=6)
     gpu, ref = ElevationMap(wl.length, wl.resolution), oracle_mod.OracleMap(wl.length, wl.resolution)
     n = wl.clouds[0].shape[0]
     gpu.reserve(n, 1)
     gpu.reserve(6 * n, 6)
+    gpu.reserve(150_000, 1, with_colours=True)
     before = gpu.debug_get("arena_allocations")
     assert before > 0
     d = [torch.from_numpy(c).cuda() for c in wl.clouds]
@@ -119,6 +122,9 @@ def test_reserve_then_no_allocation_in_the_stream(oracle_mod):
     gpu.add_batch(wl.frames, torch.from_numpy(np.concatenate(wl.clouds)).cuda(), off, wl.var_updates)
     for k in range(6):
         ref.mapvar_update(wl.var_updates[k]); ref.add(wl.frames[k], wl.clouds[k])
-    for name in ("elevation", "variance"):
+    big = np.concatenate([wl.clouds[0], wl.clouds[1][:150_000 - n]])                           # one sweep and the head of the next
+    rgb = np.random.default_rng(7).integers(0, 1 << 24, big.shape[0]).astype(np.uint32)
+    gpu.add(wl.frames[0], torch.from_numpy(big).cuda(), rgb=torch.from_numpy(rgb.view(np.int32)).cuda()); ref.add(wl.frames[0], big, rgb=rgb)
+    for name in ("elevation", "variance", "color_r"):
         assert np.array_equal(gpu.layer(name), ref.layer(name)), name
     assert gpu.debug_get("arena_allocations") == before, "a pass inside the reserved bounds allocated"

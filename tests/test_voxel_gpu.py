@@ -208,7 +208,7 @@ def test_reserve_then_voxel_stream_allocates_nothing(oracle_mod):
     stages = VoxelStage.filter_kitti_launch()
     rng = np.random.default_rng(8)
     gpu, ref = ElevationMap(L, res), oracle_mod.OracleMap(L, res)
-    gpu.reserve(200_000, max_sweeps=2)                         # (a single cloud above 131 072 points is fused as two sweeps)
+    gpu.reserve(200_000)
     before = gpu.debug_get("arena_allocations")
     grew = []
     f, base = seq[0]
