@@ -22,6 +22,8 @@ COMPOSE_SQRT_DOUBLE = 1
 COST_FREE_SPACE, COST_LETHAL_OBSTACLE, COST_NO_INFORMATION = 0, 254, 255
 COSTMAP_OVERWRITE, COSTMAP_MAX = 0, 1
 VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTENSITY = range(5)
+DEPTH_U16, DEPTH_F32 = 0, 1
+COLOR_NONE, COLOR_BGR8, COLOR_RGB8 = range(3)
 
 
 class MapConfig(C.Structure):
@@ -80,6 +82,13 @@ class Camera(C.Structure):
 
 class CleanParams(C.Structure):
     _fields_ = [("mode", c_int), ("z_min", c_float), ("z_max", c_float)]
+
+
+class DepthImage(C.Structure):
+    """gem_depth_image: a depth image's geometry, format and pinhole intrinsics (+ the format of its registered colour image)."""
+    _fields_ = [("width", c_int), ("height", c_int), ("format", c_int), ("row_stride", C.c_size_t),
+                ("fx", c_double), ("fy", c_double), ("cx", c_double), ("cy", c_double),
+                ("depth_unit", c_float), ("intensity", c_float), ("color_format", c_int), ("color_row_stride", C.c_size_t)]
 
 
 class Stats(C.Structure):
@@ -144,6 +153,12 @@ SIGNATURES = {
     "gem_voxel_device": (c_int, [c_void_p, POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gem_add_voxel": (c_int, [c_void_p, POINTER(FrameParams), POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p]),
     "gem_add_voxel_device": (c_int, [c_void_p, POINTER(FrameParams), POINTER(VoxelParams), c_int, c_int, c_void_p, c_void_p]),
+    "gem_depth_constants": (c_int, [POINTER(DepthImage), POINTER(c_float)]),
+    "gem_depth_unproject_device": (c_int, [c_void_p, POINTER(DepthImage), c_void_p, c_void_p, POINTER(CleanParams), c_void_p, c_void_p]),
+    "gem_add_depth": (c_int, [c_void_p, POINTER(FrameParams), POINTER(DepthImage), c_void_p, c_void_p, POINTER(CleanParams),
+                              POINTER(VoxelParams), c_int]),
+    "gem_add_depth_device": (c_int, [c_void_p, POINTER(FrameParams), POINTER(DepthImage), c_void_p, c_void_p, POINTER(CleanParams),
+                                     POINTER(VoxelParams), c_int]),
     "gem_local_enable": (c_int, [c_void_p, c_longlong]),
     "gem_local_capture": (c_int, [c_void_p, c_double, c_double, POINTER(c_double)]),
     "gem_local_keep_previous": (c_int, [c_void_p]),

@@ -539,6 +539,73 @@ class ElevationMap:
         else:
             self._check(self._lib.gem_add_voxel(self._h, C.byref(p), arr, len(arr), n, px, pr), "gem_add_voxel")
 
+    # -- depth images: the pinhole unprojection (depth_image_proc::convert, restated in include/gem_hip.h) on the device ---------------
+    @staticmethod
+    def _depth_images(image: "_lib.DepthImage", depth, color, device_only: bool = False):
+        """The images of depth_unproject / add_depth, numpy arrays or device tensors laid out as `image` says (rows row_stride bytes
+        apart, 0 = tight) -> (on_device, depth void*, colour void*, what the call must keep alive).  Each must reach to the end of
+        its last row; None is passed on as NULL (the library rejects it where there are pixels)."""
+        w, h = int(image.width), int(image.height)
+        esz = 2 if image.format == _lib.DEPTH_U16 else 4
+        need = [0, 0]
+        if w > 0 and h > 0:
+            need = [(h - 1) * (int(image.row_stride) or w * esz) + w * esz, (h - 1) * (int(image.color_row_stride) or w * 3) + w * 3]
+        on_device = _is_device_tensor(depth)
+        if device_only and depth is not None and not on_device:
+            raise ValueError("depth must be a device tensor")
+        ptrs, keep = [], []
+        for t, what, size, nbytes in ((depth, "depth", esz, need[0]), (color, "color", 1, need[1])):
+            if t is None:
+                ptrs.append(None)
+            elif on_device:
+                if not _is_device_tensor(t) or t.device != depth.device or t.element_size() != size:
+                    raise ValueError(f"{what} must be a device tensor of {size}-byte elements on {depth.device}")
+                if t.untyped_storage().nbytes() - t.storage_offset() * size < nbytes:
+                    raise ValueError(f"{what} ends before the image's last row ({nbytes} bytes)")
+                ptrs.append(C.c_void_p(t.data_ptr())); keep.append(t)
+            else:
+                a = np.ascontiguousarray(t)
+                if a.dtype.itemsize != size or a.nbytes < nbytes:
+                    raise ValueError(f"{what} must be an array of {size}-byte elements of at least {nbytes} bytes")
+                ptrs.append(a.ctypes.data_as(C.c_void_p)); keep.append(a)
+        return on_device, ptrs[0], ptrs[1], keep
+
+    def depth_unproject(self, image: "_lib.DepthImage", depth, color=None, clean=None, sync: bool = True):
+        """gem_depth_unproject_device: the organised cloud of a depth image (a uint16 / float32 device tensor laid out as `image`
+        says, + an optional uint8 colour image) -> (xyzi [H * W, 4] float32, rgb [H * W] int32 or None), new device tensors.  `clean`:
+        a SensorModel or CleanParams whose PASSTHROUGH_Z mask is applied in the same kernel, None for the plain cloud.  Enqueued on
+        the handle's stream; with sync=False the caller synchronises the handle before reading them."""
+        import torch
+        _, pd, pc, keep = self._depth_images(image, depth, color, device_only=True)
+        if depth is None:
+            raise ValueError("depth must be a device tensor")
+        n = max(int(image.width), 0) * max(int(image.height), 0)
+        cp = None if clean is None else self._clean(clean)
+        out = torch.empty((n, 4), dtype=torch.float32, device=depth.device)
+        rgb_out = torch.empty(n, dtype=torch.int32, device=depth.device) if color is not None and image.color_format != _lib.COLOR_NONE else None
+        dp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self._check(self._lib.gem_depth_unproject_device(self._h, C.byref(image), pd, pc, None if cp is None else C.byref(cp), dp(out), dp(rgb_out)),
+                    "gem_depth_unproject_device")
+        self._hold(depth, color, out, rgb_out)
+        if sync:
+            self.synchronize()
+        return out, rgb_out
+
+    def add_depth(self, frame: Frame, image: "_lib.DepthImage", depth, color=None, clean=None, stages=None) -> None:
+        """add_raw() -- or, with `stages`, add_voxel() -- of the cloud a depth image unprojects to, without that cloud ever crossing
+        the link: numpy images go through gem_add_depth (read before the call returns), device tensors through gem_add_depth_device
+        (held until synchronize()).  `clean` as for add_raw (None: the frame's model); it and `stages` exclude each other."""
+        p = frame.to_struct()
+        arr = None if stages is None else _voxel_stages(stages)
+        if arr is not None and clean is not None:
+            raise ValueError("add_depth: clean and stages exclude each other")
+        cp = None if arr is not None else self._clean(clean, frame)
+        dev, pd, pc, keep = self._depth_images(image, depth, color)
+        fn, what = (self._lib.gem_add_depth_device, "gem_add_depth_device") if dev else (self._lib.gem_add_depth, "gem_add_depth")
+        self._check(fn(self._h, C.byref(p), C.byref(image), pd, pc, None if cp is None else C.byref(cp), arr, 0 if arr is None else len(arr)), what)
+        if dev:
+            self._hold(depth, color)
+
     def add_aos_raw(self, frame: Frame, points: np.ndarray, off_x: int = 0, off_y: int = 4, off_z: int = 8, off_intensity: int = 24,
                     off_rgb: int = 16, clean=None) -> None:
         """add_aos() of a RAW cloud of point structs (gem_add_aos_raw)."""

@@ -52,7 +52,8 @@ bool aos_fields_ok(int point_step, int off_x, int off_y, int off_z, int off_inte
 }
 
 // One add pass.  The cloud is read where the caller has it (device buffers), from the half of the pinned staging buffer it was
-// copied into, or from the staging arena (host arrays, stage_cloud; the point structs, unpacked there by k_unpack_aos); a front end
+// copied into, or from the staging arena (host arrays, stage_cloud; the point structs, unpacked there by k_unpack_aos; a depth image,
+// unprojected there by k_depth_unproject, which also applies the clean mask); a front end
 // on h->stream turns it into the pass's input in handle-owned memory: the clean mask writes the arena's XYZI slot (in place on the
 // arena copy of a host cloud or on the unpacked structs, into h->stage for a device cloud; rgb is read from the source unmasked), the
 // VoxelGrid writes vox_out (voxel_front).  Such a pass is never one that leaves its walk to the next call (caller_device): every
@@ -100,15 +101,42 @@ int add_cloud(gem_handle* h, const gem_frame_params* p, const AddCloud& c, const
             in.xyzi = slot; in.rgb = rgb;
             break;
         }
+        case AddSource::depth: {
+            // the images as the caller has them (host ones: read before the call returns, into a half of the pinned staging buffer
+            // where the kernel reads them over the link, or into the arena), unprojected into the arena's XYZI slot, rgb behind it;
+            // the clean front end is the same kernel's mask
+            const DepthSource& ds = *c.image;
+            const gem_depth_image& g = ds.img;
+            const bool colour = g.color_format != GEM_COLOR_NONE;
+            const size_t esz = g.format == GEM_DEPTH_U16 ? 2 : 4;
+            const size_t db = ds.on_device ? 0 : (size_t)(g.height - 1) * g.row_stride + (size_t)g.width * esz;
+            const size_t cb = ds.on_device || !colour ? 0 : (size_t)(g.height - 1) * g.color_row_stride + (size_t)g.width * 3;
+            const DepthPlan dp = depth_plan(c.n, db, cb);
+            if ((rc = ensure(h, h->stage, dp.bytes))) return rc;
+            unsigned char* d = static_cast<unsigned char*>(h->stage.p);
+            const void* depth = c.xyzi; const void* color = colour ? c.rgb : nullptr;
+            if (!ds.on_device) {
+                HostXfer up[2] = {{const_cast<void*>(c.xyzi), d, db}, {const_cast<void*>(c.rgb), d + dp.o_color, cb}};
+                unsigned char* region = nullptr;
+                if ((rc = upload_arrays(h, up, colour ? 2 : 1, true, &region, &half))) return rc;
+                const unsigned char* src = region ? region : d;     // (the half has the arena's strides)
+                depth = src; color = colour ? src + dp.o_color : nullptr;
+            }
+            slot = reinterpret_cast<float4*>(d + dp.o_xyzi);
+            uint32_t* rgb = colour ? reinterpret_cast<uint32_t*>(d + dp.o_rgb) : nullptr;
+            if ((rc = depth_unproject(h, ds, depth, color, fe.kind == FrontEnd::clean ? fe.clean : nullptr, slot, rgb))) return release_half(h, half, rc);
+            in.xyzi = slot; in.rgb = rgb;
+            break;
         }
-        if (fe.kind == FrontEnd::clean) {
+        }
+        if (fe.kind == FrontEnd::clean && c.source != AddSource::depth) {
             const hipError_t e = launch_clean_mask(h->stream, in.xyzi, slot, c.n, fe.clean->mode, fe.clean->z_min, fe.clean->z_max);
             if (e != hipSuccess) return release_half(h, half, fail(h, GEM_ERR_HIP, "launch_clean_mask", e));
             in.xyzi = slot;
         }
         if (fe.kind == FrontEnd::voxel && (rc = voxel_front(h, fe.stages, fe.n_stages, c.n, in.xyzi, in.rgb, &in.xyzi, &in.rgb)))
             return release_half(h, half, rc);
-        if (c.source == AddSource::aos || fe.kind != FrontEnd::none) h->main_reads_pb = true;     // (binning streams wait for them)
+        if (c.source == AddSource::aos || c.source == AddSource::depth || fe.kind != FrontEnd::none) h->main_reads_pb = true;     // (binning streams wait for them)
     }
     return release_half(h, half, run_pipeline(h, in));
 }

@@ -460,15 +460,21 @@ struct ShardOpts { int sweep_id0; int nstrips; const int* strip_rows; bool bound
 int run_sort_pipeline(gem_handle* h, const PassInput& in, int attr, const SortGeometry& geo, const ShardOpts* shard = nullptr);
 int run_pipeline(gem_handle* h, const PassInput& in0);
 
-// The add entries (gem_add*, gem_add_raw*, gem_add_voxel*, gem_add_aos*) as one body (gem_capi.cpp): a cloud from one of three
-// sources, one of three front ends between it and the pass
-enum class AddSource { host, device, aos };     // XYZI (+ rgb, + orig) in host arrays | in device buffers | host point structs
+// The add entries (gem_add*, gem_add_raw*, gem_add_voxel*, gem_add_aos*, gem_add_depth*) as one body (gem_capi.cpp): a cloud from one
+// of four sources, one of three front ends between it and the pass
+enum class AddSource { host, device, aos, depth };     // XYZI (+ rgb, + orig) in host arrays | in device buffers | host point structs | a depth image (+ colour image)
 enum class FrontEnd { none, clean, voxel };     // the pass reads the cloud | a copy with the dropped points' x, y, z NaN | the centroids
+struct DepthSource {             // a checked gem_depth_image (gem_capi_depth.cpp: depth_source): strides filled in, constants computed
+    gem_depth_image img;
+    float k[4], unit;            // kx, ky, cxf, cyf | metres per count
+    bool on_device;              // the images are in device memory (gem_add_depth_device), else in the caller's host memory
+};
 struct AddCloud {
     AddSource source;
     int n;
     const void* xyzi; const void* rgb = nullptr; const void* orig = nullptr;                  // aos: xyzi = the point structs
     int point_step = 0, off_x = 0, off_y = 0, off_z = 0, off_intensity = -1, off_rgb = -1;   // aos
+    const DepthSource* image = nullptr;             // depth: xyzi = the depth image, rgb = the colour image or NULL, n = width * height
 };
 struct AddFront {
     FrontEnd kind = FrontEnd::none;
@@ -480,6 +486,11 @@ bool aos_fields_ok(int point_step, int off_x, int off_y, int off_z, int off_inte
 // gem_capi_voxel.cpp: the stages of a gem_add_voxel* call into vox_out[vox_flip], which flips: the n filtered points (NaN tail)
 int voxel_front(gem_handle* h, const gem_voxel_params* stages, int ns, int n, const float4* xyzi, const uint32_t* rgb,
                 const float4** out, const uint32_t** rgb_out);
+bool voxel_stages_ok(const gem_voxel_params* stages, int ns);      // gem_capi_voxel.cpp: what the gem_add_voxel* entries accept
+// gem_capi_depth.cpp: the unprojection of `s` (depth / colour as the kernel reads them: device-visible) into xyzi / rgb on h->stream,
+// the PASSTHROUGH_Z mask of `clean` (may be NULL) folded in
+int depth_unproject(gem_handle* h, const DepthSource& s, const void* depth, const void* color, const gem_clean_params* clean,
+                    float4* xyzi, uint32_t* rgb);
 
 // gem_capi_comm.cpp
 int shard_finish_locked(gem_handle* h);       // the second half of a pending gem_add_sharded_device step

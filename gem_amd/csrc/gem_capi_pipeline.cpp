@@ -545,8 +545,8 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
     if (max_points == 0) return GEM_OK;
     int rc;
     // staging of host-pointer inputs: a host cloud of the add entries (cloud_layout, where the clean mask also writes), gem_fuse's
-    // seven arrays, gem_process_points' nine
-    if ((rc = ensure(h, h->stage, std::max(cloud_layout(max_points, true, true).bytes, stage_words_bytes(max_points, 9))))) return rc;
+    // seven arrays, gem_process_points' nine, a depth image and the cloud unprojected from it (depth_plan)
+    if ((rc = ensure(h, h->stage, std::max({cloud_layout(max_points, true, true).bytes, stage_words_bytes(max_points, 9), depth_stage_bytes(max_points)})))) return rc;
     // (the raw-cloud compactions, gem_capi_clean.cpp, add a count per 1024 points)
     if ((rc = ensure(h, h->clean_cnt, clean_scratch_bytes(max_points)))) return rc;
     if ((rc = voxel_reserve(h, max_points))) return rc;        // (the VoxelGrid entries, gem_capi_voxel.cpp)

@@ -79,6 +79,8 @@ int enqueue(gem_handle* h, const gem_voxel_params* stages, int ns, long long n, 
 
 namespace gemi {
 
+bool voxel_stages_ok(const gem_voxel_params* stages, int ns) { return stages_ok(stages, ns); }
+
 int voxel_front(gem_handle* h, const gem_voxel_params* stages, int ns, int n, const float4* xyzi, const uint32_t* rgb,
                 const float4** out, const uint32_t** rgb_out)
 {

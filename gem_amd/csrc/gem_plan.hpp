@@ -14,6 +14,21 @@ constexpr long long kSweepPoints = 2048ll * kUnit;   // a single cloud longer th
 inline int ceil_log2(int v) { int b = 0; while ((1 << b) < v) ++b; return b; }
 // k arrays of n 32-bit words in a staging buffer, each 256-byte aligned behind the one before, and a few words behind the last
 inline size_t stage_words_bytes(long long n, int k) { return ((size_t)n * 4 + 256) * k; }
+// A depth image of the add entries in the staging arena (gem_add_depth*): the depth rows | the colour rows, as the caller has them
+// (host images only; at the stride upload_arrays gives a half of the staging buffer) | the XYZI slot the unprojection writes | its
+// rgb, each 256-byte aligned.  gem_reserve plans the largest image with tight rows: four-byte depths and a colour image.
+struct DepthPlan { size_t o_color, o_xyzi, o_rgb, bytes; };
+inline DepthPlan depth_plan(long long n, size_t depth_bytes, size_t color_bytes)
+{
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    DepthPlan p{};
+    p.o_color = pad(depth_bytes);
+    p.o_xyzi = p.o_color + pad(color_bytes);
+    p.o_rgb = p.o_xyzi + pad((size_t)n * 16);
+    p.bytes = p.o_rgb + pad((size_t)n * 4);
+    return p;
+}
+inline size_t depth_stage_bytes(long long max_points) { return depth_plan(max_points, (size_t)max_points * 4, (size_t)max_points * 3).bytes; }
 // What the choice and the sizes depend on, copied from the handle in one place (plan_env)
 struct PlanEnv { int L, ts, sort_form, sort_passes, sort_chunk, sort_ring; bool sort_path, track_lowest; long long sort_min_points, sort_min_points_batch; };
 

@@ -182,3 +182,27 @@ def random_cloud(seed: int, n: int, extent: float, z_sigma: float = 0.3, dup_fra
         xy[dst] = xy[src] + rng.normal(0, 0.004, (k, 2))
     z = rng.normal(0, z_sigma, n)
     return np.concatenate([xy, z[:, None], rng.uniform(0, 3, (n, 1)).round()], 1).astype(np.float32)
+
+
+def depth_image_c3(seed: int = 3, fmt: str = "u16"):
+    """C3 as the camera produces it: (image, depth, bgr) -- the gem_depth_image fields (640 x 480, fx = fy = 380, principal point
+    (320, 240), tight rows, BGR8), the depth image [480, 640] (fmt "u16": uint16 millimetres, 0 where config_c3 drops the ray;
+    "f32": float32 metres, NaN there) and a [480, 640, 3] uint8 colour image from the seed.  The depths are the z of config_c3's
+    points, rounded to the format."""
+    from . import _lib
+    wl = config_c3(seed)
+    W, H = 640, 480
+    z = wl.clouds[0][:, 2].astype(np.float64)
+    if fmt == "u16":
+        depth = np.zeros(W * H, np.uint16)
+        depth[wl.orig_index] = np.clip(np.rint(z / 0.001), 1, 65535).astype(np.uint16)
+    elif fmt == "f32":
+        depth = np.full(W * H, np.nan, np.float32)
+        depth[wl.orig_index] = z.astype(np.float32)
+    else:
+        raise ValueError("fmt: 'u16' or 'f32'")
+    bgr = np.random.default_rng([seed, 0xC3]).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    image = _lib.DepthImage(width=W, height=H, format=_lib.DEPTH_U16 if fmt == "u16" else _lib.DEPTH_F32, row_stride=0,
+                            fx=380.0, fy=380.0, cx=320.0, cy=240.0, depth_unit=0.001 if fmt == "u16" else 0.0, intensity=100.0,
+                            color_format=_lib.COLOR_BGR8, color_row_stride=0)
+    return image, depth.reshape(H, W), bgr

@@ -64,6 +64,10 @@ inline Vec3 translation_of(const Mat4& t) { return {t[3], t[7], t[11]}; }
 
 class ElevationMap;
 
+// A depth image as sensor_msgs/Image + CameraInfo describe it: gem_depth_image, field for field (width, height, format GEM_DEPTH_*,
+// row_stride = msg.step, fx = K[0], fy = K[4], cx = K[2], cy = K[5], depth_unit, intensity, color_format GEM_COLOR_*, color_row_stride)
+using DepthImage = gem_depth_image;
+
 // ---------------------------------------------------------------------------------------------
 // SensorProcessorBase and its four subclasses
 // ---------------------------------------------------------------------------------------------
@@ -128,6 +132,11 @@ public:
     int processRaw(ElevationMap& map, const PointXYZRGBICT* cloud, int n, int width,
                    int* point_colorR, int* point_colorG, int* point_colorB, int* point_index,
                    float* point_intensity, float* point_height, float* point_var);
+
+    // SensorProcessorBase::process + Fuse on a depth image (image_rect_raw + camera_info instead of the cloud topic): this processor's
+    // frame with originalWidth_ = the image's width (the pixel index is the raw position) and its cleanParams(), the unprojection
+    // and the clean step on the device (ElevationMap::addDepth)
+    void addDepth(ElevationMap& map, const DepthImage& image, const void* depth, const void* color = nullptr);
 
     // the cleanPointCloud step of this processor: removeNaNFromPointCloud (Laser.cpp:50-59, Perfect.cpp:41-49, Stereo.cpp:37-48);
     // the structured-light processor overrides it with its PassThrough on z
@@ -250,6 +259,15 @@ public:
     { check(gem_add_raw(h_, &frame, &clean, n, xyzi, rgb), "gem_add_raw"); }
     void addRawDevice(const gem_frame_params& frame, const gem_clean_params& clean, const void* d_xyzi, int n, const void* d_rgb = nullptr)
     { check(gem_add_raw_device(h_, &frame, &clean, n, d_xyzi, d_rgb), "gem_add_raw_device"); }
+
+    // ... of the cloud a DEPTH IMAGE unprojects to (gem_hip.h: depth_image_proc::convert, restated), made on the device: the image
+    // crosses the link, not the cloud.  depth / color: host images laid out as `image` says; clean may be NULL
+    void addDepth(const gem_frame_params& frame, const DepthImage& image, const void* depth, const void* color = nullptr,
+                  const gem_clean_params* clean = nullptr)
+    { check(gem_add_depth(h_, &frame, &image, depth, color, clean, nullptr, 0), "gem_add_depth"); }
+    void addDepthDevice(const gem_frame_params& frame, const DepthImage& image, const void* d_depth, const void* d_color = nullptr,
+                        const gem_clean_params* clean = nullptr)
+    { check(gem_add_depth_device(h_, &frame, &image, d_depth, d_color, clean, nullptr, 0), "gem_add_depth_device"); }
 
     // Fuse(length, point_num, index, R, G, B, intensity, height, var)  (ElevationMapping.cpp:280)
     void fuse(int n, const int* index, const int* R, const int* G, const int* B, const float* intensity, const float* height, const float* var)
@@ -730,6 +748,14 @@ inline bool SensorProcessorBase::process(ElevationMap& map, const PointXYZRGBICT
     const int rc = gem_process_points(map.handle(), &p, n, x.data(), y.data(), z.data(), nullptr, 0,
                                       point_index, point_var, nullptr, nullptr, point_height);     // SensorProcessorBase.cpp:208
     return rc == GEM_OK;
+}
+
+inline void SensorProcessorBase::addDepth(ElevationMap& map, const DepthImage& image, const void* depth, const void* color)
+{
+    originalWidth_ = image.width;                                                            // StereoSensorProcessor.cpp:41
+    const gem_frame_params p = frameParams();
+    const gem_clean_params c = cleanParams();
+    map.addDepth(p, image, depth, color, &c);
 }
 
 inline int SensorProcessorBase::processRaw(ElevationMap& map, const PointXYZRGBICT* cloud, int n, int width,

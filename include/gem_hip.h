@@ -253,6 +253,61 @@ int  gem_add_voxel(gem_handle* h, const gem_frame_params* p, const gem_voxel_par
 int  gem_add_voxel_device(gem_handle* h, const gem_frame_params* p, const gem_voxel_params* stages, int n_stages, int n,
                           const void* d_xyzi, const void* d_rgb);
 
+/* ---- depth images: the pinhole unprojection in front of the fused path.  A depth camera produces a depth image; the organised XYZ
+ *      cloud the node receives was made from it on the host (depth_image_proc, or the driver's point-cloud filter) at 16 B a pixel
+ *      (+ 4 B packed colour), where the image is 2 B (uint16 millimetres; + 3 B BGR8).  These entries take the image itself.
+ *      The semantics RESTATE depth_image_proc::convert<T> (ROS noetic, depth_conversions.h, range_max = 0) and are NOT verified against
+ *      an installation (there is none here); tests/depth_ref.py is the same statement in numpy.
+ *        host constants (double, then one rounding each; gem_depth_constants):
+ *          unit = (double)depth_unit for GEM_DEPTH_U16, a depth_unit of 0 replaced by 0.001f first (DepthTraits<uint16_t>); 1.0 for F32
+ *          kx = (float)(unit / fx), ky = (float)(unit / fy), cxf = (float)cx, cyf = (float)cy
+ *        per pixel (u, v), point i = v * width + u, all arithmetic in float, every operation rounded:
+ *          U16  d = the count; invalid iff d == 0; df = (float)d; z = df * depth_unit (0 -> 0.001f)
+ *          F32  d = the value; invalid iff !isfinite(d) -- negative depths, zeros and denormals are valid, as in the original;
+ *               df = d; z = d
+ *          valid    x = (((float)u - cxf) * df) * kx,  y = (((float)v - cyf) * df) * ky
+ *          invalid  x = y = z = NaN (the quiet NaN 0x7fc00000)
+ *          I = intensity for every pixel; rgb = 0x00RRGGBB from the pixel of the colour image (taken as registered to the depth
+ *          image: same width x height), for every pixel, valid or not.  GEM_COLOR_NONE: no rgb array.
+ *      NOT covered: range_max substitution for invalid pixels, depth-to-colour registration, lens distortion (the input is rectified,
+ *      as depth_image_proc assumes), disparity images.                                                                             */
+enum { GEM_DEPTH_U16 = 0, GEM_DEPTH_F32 = 1 };
+enum { GEM_COLOR_NONE = 0, GEM_COLOR_BGR8 = 1, GEM_COLOR_RGB8 = 2 };
+typedef struct gem_depth_image {
+    int    width, height;         /* pixels; width * height <= 2^26 */
+    int    format;                /* GEM_DEPTH_* */
+    size_t row_stride;            /* bytes; 0 = tight; a multiple of the element size, >= width * element size */
+    double fx, fy, cx, cy;        /* CameraInfo K, as image_geometry returns them */
+    float  depth_unit;            /* U16: metres per count; 0 -> 0.001f (DepthTraits<uint16_t>).  F32: ignored */
+    float  intensity;             /* written to the I channel of every pixel */
+    int    color_format;          /* GEM_COLOR_*: a registered colour image of the same width x height */
+    size_t color_row_stride;      /* bytes; 0 = tight (width * 3) */
+} gem_depth_image;
+/*      GEM_ERR_INVALID from every entry below, nothing changed: a NULL image, NULL depth with pixels present, color_format != NONE
+ *      with NULL colour (pixels present), a negative size, more than 2^26 pixels, an unknown format, a bad stride, fx or fy zero or not
+ *      finite, cx or cy not finite, a non-finite or negative depth_unit, a bad clean mode.  An image with width == 0 or height == 0
+ *      is not an error: it holds no pixels and adds nothing (as n == 0 of gem_add).
+ *      The four constants kx, ky, cxf, cyf.  Pure host function: needs no device.                                               */
+int  gem_depth_constants(const gem_depth_image* img, float out[4]);
+/*      The organised cloud: width * height XYZI points in row-major pixel order into d_xyzi_out (16-byte aligned; + packed rgb into
+ *      d_rgb_out unless GEM_COLOR_NONE or d_rgb_out is NULL), device pointers, enqueued on the handle's stream (the host is never
+ *      synchronised).  It takes nothing from the map.  With clean->mode == GEM_CLEAN_PASSTHROUGH_Z every point the filter drops has
+ *      x = y = z = NaN: the cleanPointCloud mask of the fuse entries applied to the plain output, bit for bit, in the same kernel.
+ *      NONE, REMOVE_NAN and a NULL clean change nothing.                                                                         */
+int  gem_depth_unproject_device(gem_handle* h, const gem_depth_image* img, const void* d_depth, const void* d_color,
+                                const gem_clean_params* clean /* may be NULL */, void* d_xyzi_out, void* d_rgb_out /* may be NULL */);
+/*      gem_add_raw_device on that cloud (clean; may be NULL) or gem_add_voxel_device on it (stages, n_stages > 0) -- the same map --
+ *      from an image in host memory (read when the call returns, as for gem_add_aos) or in device memory (complete at the call,
+ *      untouched until gem_synchronize, as for gem_add_device).  There is no orig array: the raw position is the pixel index, so a
+ *      stereo frame's getI / getJ need p->original_width == img->width (GEM_ERR_INVALID otherwise).  clean and stages both non-NULL:
+ *      GEM_ERR_INVALID (the front ends are exclusive).  The image is unprojected into the handle's staging arena, the PASSTHROUGH_Z
+ *      mask in the same kernel; gem_reserve(width * height, 1, with_colours) covers images with tight rows.  gem_stats.points_in
+ *      counts width * height.                                                                                                    */
+int  gem_add_depth(gem_handle* h, const gem_frame_params* p, const gem_depth_image* img, const void* depth, const void* color,
+                   const gem_clean_params* clean, const gem_voxel_params* stages, int n_stages);
+int  gem_add_depth_device(gem_handle* h, const gem_frame_params* p, const gem_depth_image* img, const void* d_depth, const void* d_color,
+                          const gem_clean_params* clean, const gem_voxel_params* stages, int n_stages);
+
 /* ---- batched sweeps (BASELINE config 4): for s in 0..n_sweeps-1:
  *        Mapvar_update(var_updates[s]) ; add(params[s], cloud s)
  *      with the map pose fixed for the batch.  Clouds are device-resident, concatenated:
