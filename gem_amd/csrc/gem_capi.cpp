@@ -248,6 +248,7 @@ void gem_destroy(gem_handle* h)
                      &h->sh_recv_hv[1], &h->sh_recv_key[1], &h->sh_recv_rng[1], &h->sh_ranges, &h->published[0], &h->published[1],
                      &h->clean_cnt, &h->vox_state, &h->vox_hist, &h->vox_rec, &h->vox_tmp, &h->vox_out[0], &h->vox_out[1]}) if (a->p) hipFree(a->p);
     if (h->sh_host) hipHostFree(h->sh_host);
+    if (h->form_seen) hipHostFree(h->form_seen);
     for (auto& b : h->pb) {
         for (Arena* a : {&b.rec, &b.srt, &b.seg, &b.flag, &b.gflag, &b.tables, &b.s_hv1, &b.s_hv2, &b.s_key1, &b.s_key2, &b.s_src1, &b.s_src2,
                          &b.s_cnt1, &b.s_cnt2, &b.s_misc, &b.s_ranges, &b.s_shard, &b.s_blkcnt}) if (a->p) hipFree(a->p);
@@ -915,6 +916,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "dense_min")          { if (value < 0 || value > 0xffffffffll) return fail(h, GEM_ERR_INVALID, "dense_min: 0 .. 2^32 - 1"); h->dense_min = (unsigned)value; }
     else if (k == "dbg_sweep")          h->dbg_sweep = (int)value;
     else if (k == "dbg_frame")          h->dbg_frame = value != 0;
+    else if (k == "frame_lean")         { if (value < 0 || value > 2) return fail(h, GEM_ERR_INVALID, "frame_lean: 0 (generic), 1 (lean) or 2 (the host picks)"); h->frame_lean = (int)value; }   // (settle above flushed the deferred pass)
     else if (k == "overlap")            h->overlap = value != 0;
     else if (k == "overlap_min_points") { if (value < 0) return fail(h, GEM_ERR_INVALID, "overlap_min_points: >= 0"); h->overlap_min_points = value; h->sort_overlap_min_points = value; }
     else if (k == "sort_path")          h->sort_path = value != 0;
@@ -976,6 +978,9 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "compose_far_points") *out = h->compose.far_points;
     else if (k == "compose_sum_ns") *out = h->compose.sum_ns;
     else if (k == "walks_unwaited") *out = h->walks_unwaited;
+    else if (k == "frame_lean_launches") *out = h->frame_lean_launches;
+    else if (k == "frame_generic_launches") *out = h->frame_generic_launches;
+    else if (k == "frame_form_seen") *out = h->form_seen ? (long long)*static_cast<volatile const uint32_t*>(h->form_seen) : 0;
     else if (k == "walks_left") *out = h->walks_left;
     else if (k == "step_pending") *out = h->step.valid ? 1 : 0;
     else if (k == "step_exchange_bytes_out") *out = h->xbytes_out;

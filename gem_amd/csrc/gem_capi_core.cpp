@@ -407,6 +407,17 @@ void fold_events(gem_handle* h)
     h->events.clear();
 }
 
+// The form of the next k_frame launch (gem_handle::form_seen): lean only if the pass it fuses was binned lean (`fused_lean`; true where
+// there is nothing to fuse), the frame it bins takes the fast laser projection -- the only one the lean form carries (`bin_fast`; true
+// where there is nothing to bin) -- and no tile has reported the slow path yet: a plain load of the pinned word.  Counts the launch.
+bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast)
+{
+    const bool seen = h->form_seen && *static_cast<volatile const uint32_t*>(h->form_seen) != 0u;
+    const bool lean = fused_lean && bin_fast && (h->frame_lean == 1 || (h->frame_lean == 2 && !seen));
+    ++(lean ? h->frame_lean_launches : h->frame_generic_launches);
+    return lean;
+}
+
 // the fuse of the newest frame, if it is still pending (see gem_handle::deferred)
 int flush_deferred(gem_handle* h)
 {
@@ -419,7 +430,8 @@ int flush_deferred(gem_handle* h)
     // the same kernel without a binning half -- six workgroups per CU hold every tile of a 600^2 map at once, k_fuse_list's four
     // take two tile lifetimes (10.0-10.4 us against ~6.5 for the C2 sweep; this launch ends every synchronised run of sweeps)
     gem::BinArgs no_bin{};
-    GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, no_bin, h->deferred.attr, t.events()));
+    const bool lean = frame_launch_lean(h, h->deferred.lean_binned, true);
+    GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, no_bin, h->deferred.attr, lean, t.events()));
     return GEM_OK;
 }
 

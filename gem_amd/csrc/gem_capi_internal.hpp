@@ -100,7 +100,15 @@ struct gem_handle {
     // A stream of single device-resident sweeps runs as ONE launch per frame: k_frame fuses the previous
     // frame's records next to the binning of the new cloud.  The fuse of the newest frame is therefore
     // deferred until the next gem_add_device -- or until anything observes or modifies the map.
-    struct Deferred { bool valid = false; FuseArgs fa{}; int ts = 0, attr = 0; } deferred;
+    struct Deferred { bool valid = false; FuseArgs fa{}; int ts = 0, attr = 0; bool lean_binned = false; } deferred;   // lean_binned: its binning ran with BinArgs::lean
+    // k_frame has two forms (gem_kernels.hip): the generic one, which switches a buffer set to the descriptor form on the device, and
+    // a lean one that carries the bucket form only.  The HOST picks per launch: lean while the word `form_seen` -- pinned host memory
+    // that frame_tile's slow path stores 1 into -- reads zero and the pass to fuse was binned lean; generic for good after that.  The
+    // word is read with a plain load on every call, no event and no wait: a lean launch enqueued before the store lands is still
+    // right (the lean form has the slow path), only slow.
+    uint32_t* form_seen = nullptr;      // allocated once, with k_frame's arenas (ensure_tile_buffers)
+    int  frame_lean = 2;                // debug knob "frame_lean": 0 = always generic, 1 = always lean, 2 = the host's choice as above
+    long long frame_lean_launches = 0, frame_generic_launches = 0;   // launches of either form: k_frame, the first frame's binning, the fuse-only flush
     // The sorted pipeline's walk of an overlapped pass is launched by the NEXT call (or by whatever observes the map): by then its sort
     // has usually completed, and a walk that need not be put behind a hipStreamWaitEvent starts 1.4 us after the walk before it
     // instead of 5-7 (tools/ubench/handover.hip: the wait costs that much even when the event completed long before).  A stream of
@@ -396,6 +404,7 @@ struct Timed {
 
 void fold_events(gem_handle* h);
 int flush_deferred(gem_handle* h);
+bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast);   // the host's pick of k_frame's form for the next launch (gem_handle::form_seen)
 int flush_walk(gem_handle* h);
 int flush_local(gem_handle* h);
 int wait_gather(gem_handle* h);

@@ -103,6 +103,10 @@ static int ensure_tile_buffers(gem_handle* h, gem_handle::PassBuffers& pb, const
     // k_frame's records (gem_kernels.hpp, kFrameBucket; sizes 0 where the plan rules it out): the kernel leaves every count zero and
     // every spill slot free behind it, so the arenas are set once, when they are (re)allocated -- on the handle's stream, k_frame's
     if ((rc = ensure(h, pb.bkt, p.bkt)) || (rc = ensure_zeroed(h, pb.bcnt, p.bcnt)) || (rc = ensure_zeroed(h, pb.fctl, p.fctl))) return rc;     // (the form words: bucket form until a tile needs more)
+    if (!h->form_seen) {                                             // the word the slow path reports to the host in (gem_handle::form_seen): once per handle
+        GEM_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&h->form_seen), 64, hipHostMallocDefault));
+        *h->form_seen = 0u;
+    }
     if (p.spill > pb.spill.cap) {
         if ((rc = ensure(h, pb.spill, p.spill))) return rc;
         GEM_HIP(h, hipMemsetAsync(pb.spill.p, 0xff, pb.spill.cap, h->stream));     // tile word == kSpillFree
@@ -508,11 +512,14 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     if (defer) {
         ba.bkt = static_cast<uint32_t*>(pb.bkt.p); ba.bcount = static_cast<uint32_t*>(pb.bcnt.p); ba.spill = static_cast<uint4*>(pb.spill.p);
         ba.ctl = static_cast<uint32_t*>(pb.fctl.p);
-        fa.bkt = ba.bkt; fa.bcount = ba.bcount; fa.spill = ba.spill; fa.ctl = ba.ctl;
+        fa.bkt = ba.bkt; fa.bcount = ba.bcount; fa.spill = ba.spill; fa.ctl = ba.ctl; fa.form_seen = h->form_seen;
         if (h->deferred.valid && h->deferred.attr != attr) { const int rcd = flush_deferred(h); if (rcd) return rcd; }   // (cannot happen: toggling the tracking flushes)
-        if (h->deferred.valid) { Timed t(h, 2); GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, ba, attr, t.events())); }
-        else                   { Timed t(h, 0); GEM_HIP(h, launch_frame(h->stream, FuseArgs{}, ba, attr, t.events())); }   // (no tile blocks: binning only)
-        h->deferred.fa = fa; h->deferred.ts = ts; h->deferred.attr = attr; h->deferred.valid = true;
+        // the host's pick of k_frame's form: the launch is lean as a whole -- its fuse half AND the binning of this pass -- or generic
+        const bool lean = frame_launch_lean(h, !h->deferred.valid || h->deferred.lean_binned, ba.frame0.fast_laser != 0 && !ba.rgb);
+        ba.lean = lean ? 1 : 0;
+        if (h->deferred.valid) { Timed t(h, 2); GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, ba, attr, lean, t.events())); }
+        else                   { Timed t(h, 0); GEM_HIP(h, launch_frame(h->stream, FuseArgs{}, ba, attr, lean, t.events())); }   // (no tile blocks: binning only)
+        h->deferred.fa = fa; h->deferred.ts = ts; h->deferred.attr = attr; h->deferred.valid = true; h->deferred.lean_binned = lean;
         return pass_done(h, in.n);
     }
     if (h->counting) GEM_HIP(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(unsigned long long), h->stream));

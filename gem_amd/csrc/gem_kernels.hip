@@ -74,12 +74,15 @@ template <int W> __device__ __forceinline__ uint32_t rec_load_cell(const uint4* 
 // of the tile's bucket with ONE returning atomic on bcount[tile] and the group's lanes store their records there, the point index
 // above the cell in the third word ({h, var, cell | index << 8}; a sweep holds at most 2^17 points).  A record whose position lies
 // past the bucket's kFrameBucket slots goes to spill[point index] = {h, var, cell | index << 8, tile} instead (frame_tile's slow path).
-template <int SRC, int TS, bool BATCH, bool BUCKET = false>
+// FAST_ONLY (k_frame's lean form): the caller has checked fc.fast_laser && !a.rgb on the host -- the generic projection, its doubles and
+// the two thirds of FrameConst only it reads are not compiled in (the lean form's scalar registers: 80 for eight workgroups per CU).
+template <int SRC, int TS, bool BATCH, bool BUCKET = false, bool FAST_ONLY = false>
 __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
 {
     constexpr int TE = 1 << TS;
     constexpr int U = 64;
     static_assert(!BUCKET || (SRC == 0 && TS == 4 && !BATCH), "bucket form: single sweeps of XYZI on 16x16 tiles");
+    static_assert(!FAST_ONLY || BUCKET, "the fast projection alone: k_frame's lean form");
     const int lane = lane_id();
     if (unit >= a.B) return;                               // whole wave leaves together
     if (!BUCKET && unit == 0 && lane == 0) *a.srt_top = 0u; // bump pointer of the sorted arena (dense tiles of k_fuse_list, same pass)
@@ -101,7 +104,7 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
 
     bool valid = false;
     uint32_t tile = 0, cl = 0, src = 0; float hh = 0.0f, vv = 0.0f;
-    if (SRC == 0 && fc.fast_laser && !a.rgb) {
+    if (FAST_ONLY || (SRC == 0 && fc.fast_laser && !a.rgb)) {
         // (wave-uniform) a laser frame whose rotation variance is zero, no colours: projection + binning as straight-line code
         const float4 p = a.xyzi[i < sweep_end ? i : sweep_begin];
         int row, col;
@@ -110,7 +113,7 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
         cl = (uint32_t)(((row & (TE - 1)) << TS) | (col & (TE - 1)));
         src = (uint32_t)i;
         if (!valid) { tile = 0; cl = 0; }
-    } else if (i < sweep_end) {
+    } else if (!FAST_ONLY && i < sweep_end) {
         int row, col; float h, v; bool colour_ok = false;
         if (SRC == 0) {
             const float4 p = a.xyzi[i];
@@ -193,11 +196,11 @@ __device__ __forceinline__ void bin_stamp_end(const BinArgs& a, int block)
     }
 }
 
-template <int SRC, int TS, bool BATCH, bool BUCKET = false>
+template <int SRC, int TS, bool BATCH, bool BUCKET = false, bool FAST_ONLY = false>
 __device__ __forceinline__ void bin_wave_body(const BinArgs& a, int block)
 {
     bin_stamp_begin(a, block);
-    bin_unit<SRC, TS, BATCH, BUCKET>(a, (int)(block * 4 + (threadIdx.x >> 6)));
+    bin_unit<SRC, TS, BATCH, BUCKET, FAST_ONLY>(a, (int)(block * 4 + (threadIdx.x >> 6)));
     bin_stamp_end(a, block);
 }
 
@@ -1298,7 +1301,11 @@ __device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigne
         // ---- slow path: windows [lo, lo + PB) of point indices, in order.  It re-reads the tile's records per window (and the
         //      whole spill arena when the bucket overflowed): the pass buffer set is switched to the descriptor form for good
         //      (frame_form), so a stream pays this once per buffer set
-        if (tid == 0) a.ctl[0] = 1u;
+        if (tid == 0) {
+            a.ctl[0] = 1u;
+            // ... and the host is told (a word of pinned memory it reads before every launch: it stops picking k_frame's lean form)
+            if (a.form_seen) __hip_atomic_store(a.form_seen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
         const uint32_t nb = min(nrec, (uint32_t)kFrameBucket);
         const uint32_t nspill = fits ? 0u : (uint32_t)a.B_total * (uint32_t)a.U;
         const uint64_t lt = lanemask_lt();
@@ -1408,29 +1415,49 @@ __device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigne
 //   of kFramePB records read every record once however heavy the tile, which is what maps at 0.1-0.2 m (tiles of thousands of
 //   records, tens per cell) need.  ctl[0] (sticky) is set by the fuse of a pass and read by the binning of the set's next pass,
 //   two launches later; ctl[1] = the form the binning chose, read by the fuse of the same pass one launch later.
+template <bool MAY_LEAN>
 __device__ __forceinline__ void bin_frame_body(const BinArgs& ba, int block)
 {
-    const bool desc = ba.ctl[0] != 0u;                                   // uniform: written two launches ago
+    const bool desc = (!MAY_LEAN || ba.lean == 0) && ba.ctl[0] != 0u;    // uniform: written two launches ago
     if (block == 0 && threadIdx.x == 0) ba.ctl[1] = desc ? 1u : 0u;
     if (desc) bin_wave_body<0, 4, false, false>(ba, block);
     else      bin_wave_body<0, 4, false, true>(ba, block);
 }
 
-template <int FLAGS>
-__global__ __launch_bounds__(256, kFrameWG) void k_frame(FuseArgs fa, BinArgs ba)
+// LEAN: the form the HOST picks per launch while no tile of the handle has needed frame_tile's slow path (gem_capi_pipeline.cpp,
+// frame_launch_lean).  It carries the bucket form only -- frame_tile for the tile blocks (its slow path included, so the form is
+// right for any input, only slow for heavy tiles), bucket binning that does not read ctl[0] and sets ctl[1] = 0 -- and so fits
+// the budget of kFrameLeanWG workgroups per CU: at most 64 VGPRs, at most 80 SGPRs (the CU admits min(8, 800 / (sgprs rounded up
+// to 16 + 16)) blocks of four waves), kFrameLds of LDS.  With 1472 + 512 workgroups of a C2 frame and 2048 slots every block is
+// resident from the start; nothing in the kernel depends on that.  The generic form (LEAN = false) is the kernel as it was.
+#ifndef GEM_FRAME_LEAN_WG
+#define GEM_FRAME_LEAN_WG 8
+#endif
+constexpr int kFrameLeanWG = GEM_FRAME_LEAN_WG;                         // (build define: 6 tells "lean" and "eight per CU" apart on the GPU)
+static_assert(kFrameLeanWG >= 1 && kFrameLeanWG <= 8 && (size_t)kFrameLeanWG * kFrameLds <= 160 * 1024, "kFrameLeanWG lean workgroups fit the CU's LDS");
+
+template <int FLAGS, bool LEAN = false>
+__global__ __launch_bounds__(256, LEAN ? kFrameLeanWG : kFrameWG) void k_frame(FuseArgs fa, BinArgs ba)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
     const int nf = (fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1);     // fuse blocks (see frame_tile_of)
-    if ((int)blockIdx.x < nf) {
+    if constexpr (LEAN) {
+        if ((int)blockIdx.x < nf) frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
+        else {
+            const int block = (int)blockIdx.x - nf;
+            if (block == 0 && threadIdx.x == 0) ba.ctl[1] = 0u;
+            bin_wave_body<0, 4, false, true, true>(ba, block);                // (the host launches this form for fast-laser frames only)
+        }
+    } else if ((int)blockIdx.x < nf) {
         if (fa.ctl[1] != 0u) { TileState<1> st; fuse_list_body<4, 256, kFramePB, FLAGS, false, 0, true>(fa, (int)blockIdx.x, lds_dyn, st); }
         else frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
     } else {
-        bin_frame_body(ba, (int)blockIdx.x - nf);
+        bin_frame_body<false>(ba, (int)blockIdx.x - nf);
     }
 }
 
-// the binning of the first frame of a stream, with nothing to fuse beside it (no LDS, the occupancy of k_bin_wave)
-__global__ __launch_bounds__(256) void k_bin_frame(BinArgs ba) { bin_frame_body(ba, (int)blockIdx.x); }
+// the binning of the first frame of a stream, with nothing to fuse beside it (no LDS, the occupancy of k_bin_wave); ba.lean: bucket form unconditionally
+__global__ __launch_bounds__(256) void k_bin_frame(BinArgs ba) { bin_frame_body<true>(ba, (int)blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------
 // dense / state kernels
@@ -1936,7 +1963,7 @@ hipError_t launch_fuse(hipStream_t st, const FuseArgs& a, int ts, int attr, int 
 }
 
 // fuse of the previous frame + bin of this one (single sweeps on 16x16 tiles, no attributes); fa.T == 0: binning only (k_bin_frame), ba.B == 0: fuse only
-hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, int attr, LaunchEvents ev)
+hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, int attr, bool lean, LaunchEvents ev)
 {
     if (attr != 0 && attr != 4) return hipErrorInvalidValue;
     if (fa.T == 0) {                                                     // binning only
@@ -1944,9 +1971,14 @@ hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, i
         return hipGetLastError();
     }
     const dim3 grid(((fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1)) + (ba.B + 3) / 4), block(256);
+    if (lean) {                                                          // (the bucket form alone: kFrameLds, kFrameLeanWG workgroups per CU)
+        if (attr == 4) GEM_LAUNCH((k_frame<4, true>), grid, block, kFrameLds, st, ev, fa, ba);
+        else           GEM_LAUNCH((k_frame<0, true>), grid, block, kFrameLds, st, ev, fa, ba);
+        return hipGetLastError();
+    }
     const size_t lds = std::max(kFrameLds, fuse_list_lds(256, 4, kFramePB, 0));      // (either form of the fuse half)
-    if (attr == 4) GEM_LAUNCH((k_frame<4>), grid, block, lds, st, ev, fa, ba);
-    else           GEM_LAUNCH((k_frame<0>), grid, block, lds, st, ev, fa, ba);
+    if (attr == 4) GEM_LAUNCH((k_frame<4, false>), grid, block, lds, st, ev, fa, ba);
+    else           GEM_LAUNCH((k_frame<0, false>), grid, block, lds, st, ev, fa, ba);
     return hipGetLastError();
 }
 

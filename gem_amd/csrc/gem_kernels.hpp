@@ -65,6 +65,7 @@ struct BinArgs {
     uint32_t* bcount;                  // [T] records reserved in each bucket (all-zero between passes: the fuse zeroes what it reads)
     uint4*    spill;                   // [B * U] by point index: {h, var, cell | index << 8, tile} past a full bucket, else tile == kSpillFree
     uint32_t* ctl;                     // [2] of the pass buffer set: [0] != 0 -> bin in the descriptor form (rec / seg / flag / gflag); [1] := the form chosen
+    int       lean;                    // 1: bucket form whatever ctl[0] says (it is not read), ctl[1] := 0 -- the binning of a lean launch (launch_frame)
 };
 
 struct FuseArgs {
@@ -104,6 +105,7 @@ struct FuseArgs {
     uint32_t* bcount;                  // zeroed as read
     uint4*    spill;                   // slots taken are set back to kSpillFree
     uint32_t* ctl;                     // [1] = the form the binning of this pass chose; [0] := 1 when a tile takes the bucket form's slow path
+    uint32_t* form_seen;               // ... and this word of pinned host memory := 1 with it (the host picks the form of its next launches by it), or NULL
 };
 
 // ---- the sorted pipelines of big passes (gem_sort.hip) -----------------------------------------------------------------------
@@ -243,7 +245,8 @@ hipError_t launch_project(hipStream_t st, const FrameConst& fc, int first, int n
 
 hipError_t launch_bin(hipStream_t st, const BinArgs& a, int src, int ts, LaunchEvents ev);
 hipError_t launch_fuse(hipStream_t st, const FuseArgs& a, int ts, int attr, int variant, LaunchEvents ev);
-hipError_t launch_frame(hipStream_t st, const FuseArgs& fuse_prev, const BinArgs& bin_this, int attr, LaunchEvents ev);   // attr: 0, or 4 = lowest tracking
+hipError_t launch_frame(hipStream_t st, const FuseArgs& fuse_prev, const BinArgs& bin_this, int attr, bool lean, LaunchEvents ev);   // attr: 0, or 4 = lowest tracking;
+                                       // lean: the bucket-only form (fuse_prev's pass was binned with BinArgs::lean; bin_this.lean is set by the caller)
 size_t     fuse_lds_bytes(int ts, int variant, int attr);
 hipError_t launch_init(hipStream_t st, const LayerPtrs& m, int cells, int clear_lowest);
 hipError_t launch_unpack_aos(hipStream_t st, const void* src, int n, int step, int ox, int oy, int oz, int oi, int orgb, float4* xyzi, uint32_t* rgb);

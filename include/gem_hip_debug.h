@@ -39,7 +39,12 @@ extern "C" {
  *       "roctx" (0/1: roctx ranges named after the entry points around every call that enqueues or transfers -- the marker library is
  *       loaded at run time, GEM_ERR_INVALID if there is none; `rocprofv3 --kernel-trace --marker-trace` shows them beside the kernels),
  *       "trace" (0/1: one line on stderr per pass of the sorted pipeline), "stream_roles" (a permutation of 0123 as a decimal
- *       number: which of the handle's current own / bin / bin2 / upload streams takes each role; tools/dbg/roles.py).  Returns GEM_ERR_INVALID for an unknown key or a value out of range. */
+ *       number: which of the handle's current own / bin / bin2 / upload streams takes each role; tools/dbg/roles.py),
+ *       "frame_lean" (which form of k_frame a stream of single sweeps launches: 0 = always the generic form, which switches a buffer
+ *       set to the descriptor form on the device; 1 = always the lean, bucket-only form, whose slow path takes whatever the buckets
+ *       cannot; 2, the default = the host picks per launch: lean while no tile of the handle has reported the slow path and the pass
+ *       to fuse was binned lean, generic from then on.  A frame that does not take the fast laser projection is binned by the generic
+ *       form in every mode.  Setting it flushes the deferred pass).  Returns GEM_ERR_INVALID for an unknown key or a value out of range. */
 int gem_debug_set(gem_handle* h, const char* key, long long value);
 
 /* read-outs: "arena_allocations" (device allocations the handle's arenas have made so far: none may follow gem_reserve),
@@ -51,6 +56,9 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            tile's halo could not close their neighbour search; 0 after a call on n <= mean_k records),
  *            "compose_sum_ns" (host nanoseconds that call spent on the ordered double sums of the threshold),
  *            "walks_left" (walks of the sorted pipeline left to the next call) and "walks_unwaited" (those of them launched without a stream wait: their sort had completed),
+ *            "frame_lean_launches", "frame_generic_launches" (launches of k_frame's lean / generic form so far: k_frame itself, the first
+ *            frame's binning, the fuse-only launch at a synchronisation), "frame_form_seen" (the word of pinned host memory a tile's slow
+ *            path sets: 1 = the host's choice is the generic form from now on),
  *            "step_pending" (1: the second half of a gem_add_sharded_device step is still to come),
  *            "step_exchange_ns", "step_walk_ns", "step_publish_ns", "step_gather_ns", "step_exchange_to_walk_ns": device time stamps of
  *            the last finished multi-rank step (recorded while gem_set_timing is on; read after gem_synchronize; -2^62 = not recorded),

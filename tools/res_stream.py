@@ -31,5 +31,21 @@ for L, res in ((600, 0.05), (120, 0.1), (75, 0.2)):
         m.add(f, clouds[k % 8])
     m.synchronize()
     dt = (time.perf_counter() - t0) / n_frames
-    print(json.dumps({"L": L, "res": res, "frames": n_frames, "us_per_frame": dt * 1e6, "first_frames_us_synchronised": [round(x, 1) for x in first]}))
+    out = {"L": L, "res": res, "frames": n_frames, "us_per_frame": dt * 1e6, "first_frames_us_synchronised": [round(x, 1) for x in first]}
+    try:                                             # launches of k_frame's lean / generic form ("frame_lean"; a library without the lean form has no such keys)
+        out.update({k: m.debug_get(k) for k in ("frame_lean_launches", "frame_generic_launches", "frame_form_seen")})
+    except Exception:
+        pass
+    print(json.dumps(out))
+    m.close()
+    # the same map WITHOUT a synchronisation behind its first frames: how many launches the host enqueues lean before the slow
+    # path's report lands (a handle whose tiles overflow pays the lean slow path on those frames)
+    m = ElevationMap(L, res)
+    for k in range(64):
+        m.add(f, clouds[k % 8])
+    m.synchronize()
+    try:
+        print(json.dumps({"L": L, "res": res, "tight_loop_frames": 64, **{k: m.debug_get(k) for k in ("frame_lean_launches", "frame_generic_launches", "frame_form_seen")}}))
+    except Exception:
+        pass
     m.close()
