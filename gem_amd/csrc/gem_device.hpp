@@ -208,15 +208,20 @@ __device__ __forceinline__ float div_binning(float n, float d, float r)
     return __builtin_fmaf(t, r, q);
 }
 
+// (F: FrameConst, or the part of it k_frame's lean form carries -- FrameLeanBin, gem_frame_lean.hpp)
+template <class F>
+__device__ __forceinline__ float height_variance_laser_fast(const F& f, float x, float y, float z)
+{
+    const float d = sqrt_plain(dot3(x, x, y, y, z, z));                 // GPU:404
+    const float t = f.beam_c + f.beam_a * d;
+    const float vl = t * t;                                             // GPU:407
+    return ((f.Js[0] * vl) * f.Js[0] + (f.Js[1] * vl) * f.Js[1]) + f.t2;
+}
+
 template <int MODEL = -1>
 __device__ __forceinline__ float height_variance(const FrameConst& f, float x, float y, float z, int orig)
 {
-    if constexpr (MODEL == kModelLaserFast) {
-        const float d = sqrt_plain(dot3(x, x, y, y, z, z));             // GPU:404
-        const float t = f.beam_c + f.beam_a * d;
-        const float vl = t * t;                                         // GPU:407
-        return ((f.Js[0] * vl) * f.Js[0] + (f.Js[1] * vl) * f.Js[1]) + f.t2;
-    }
+    if constexpr (MODEL == kModelLaserFast) return height_variance_laser_fast(f, x, y, z);
     float vn, vl;
     sensor_variances<MODEL>(f, x, y, z, orig, vn, vl);
     const float q0 = dot3(f.C[0], x, f.C[1], y, f.C[2], z);
@@ -264,7 +269,8 @@ __device__ __forceinline__ Projected project_point(const FrameConst& f, float x,
 // project_point<kModelLaserFast> + the binning as STRAIGHT-LINE code: the same expressions, every decision a select (the branchy form
 // spends a third of its issue slots on exec-mask bookkeeping; computing the variance of a rejected point costs less).  Returns
 // "accepted, inside the map, inside this device's strip, not the h == -1 sentinel (GPU:482) unless those are kept".
-__device__ __forceinline__ bool project_bin_laser_fast(const FrameConst& fc, float x, float y, float z, bool in_range, bool keep_sentinel,
+template <class F>
+__device__ __forceinline__ bool project_bin_laser_fast(const F& fc, float x, float y, float z, bool in_range, bool keep_sentinel,
                                                        int& row, int& col, float& h_out, float& var_out)
 {
     const float h = fc.T[8] * x + fc.T[9] * y + fc.T[10] * z + fc.T[11];           // GPU:389
@@ -273,7 +279,7 @@ __device__ __forceinline__ bool project_bin_laser_fast(const FrameConst& fc, flo
         acc = acc && !((x > -fc.fbx && x < fc.fbx && y > -fc.fby && y < fc.fby) || (y > -fc.fband && y < fc.fband) || (y > fc.fplane));
     const float xt = fc.T[0] * x + fc.T[1] * y + fc.T[2] * z + fc.T[3];            // GPU:399
     const float yt = fc.T[4] * x + fc.T[5] * y + fc.T[6] * z + fc.T[7];            // GPU:400
-    var_out = height_variance<kModelLaserFast>(fc, x, y, z, 0);
+    var_out = height_variance_laser_fast(fc, x, y, z);
     h_out = h;
     const float shx = xt - fc.cx, shy = yt - fc.cy;
     int ix, iy;

@@ -20,6 +20,7 @@
 //
 // Built with -ffp-contract=off (see gem_device.hpp).
 #include "gem_kernels.hpp"
+#include "gem_frame_lean.hpp"
 #include "gem_wave.hpp"
 
 #include <hip/hip_ext.h>
@@ -74,15 +75,33 @@ template <int W> __device__ __forceinline__ uint32_t rec_load_cell(const uint4* 
 // of the tile's bucket with ONE returning atomic on bcount[tile] and the group's lanes store their records there, the point index
 // above the cell in the third word ({h, var, cell | index << 8}; a sweep holds at most 2^17 points).  A record whose position lies
 // past the bucket's kFrameBucket slots goes to spill[point index] = {h, var, cell | index << 8, tile} instead (frame_tile's slow path).
-// FAST_ONLY (k_frame's lean form): the caller has checked fc.fast_laser && !a.rgb on the host -- the generic projection, its doubles and
-// the two thirds of FrameConst only it reads are not compiled in (the lean form's scalar registers: 80 for eight workgroups per CU).
-template <int SRC, int TS, bool BATCH, bool BUCKET = false, bool FAST_ONLY = false>
+// (k_frame's lean form has its own unit, bin_unit_lean below: the fast laser projection alone, from its own argument block.)
+// the bucket form's stores (A: BinArgs or FrameLeanBin): the wave's points grouped by tile, stable in lane (= input) order
+template <class A>
+__device__ __forceinline__ void bucket_store(const A& a, bool valid, uint32_t tile, uint32_t cl, uint32_t src, float hh, float vv)
+{
+    const int lane = lane_id();
+    const uint64_t peers = wave_peers_few(valid, tile, a.tile_bits);
+    const uint64_t lt = lanemask_lt();
+    const uint32_t rank = (uint32_t)__popcll(peers & lt);
+    const uint32_t cnt = (uint32_t)__popcll(peers);
+    const bool leader = valid && rank == 0;
+    uint32_t old = 0;
+    if (leader) old = atomicAdd(&a.bcount[tile], cnt);
+    old = (uint32_t)__shfl((int)old, valid ? (__ffsll((unsigned long long)peers) - 1) : lane, 64);
+    if (valid) {
+        const uint32_t pos = old + rank, z = cl | (src << 8);
+        if (pos < (uint32_t)kFrameBucket) rec_store3(reinterpret_cast<uint4*>(a.bkt), (size_t)tile * kFrameBucket + pos, __float_as_uint(hh), __float_as_uint(vv), z);
+        else a.spill[src] = make_uint4(__float_as_uint(hh), __float_as_uint(vv), z, tile);
+    }
+}
+
+template <int SRC, int TS, bool BATCH, bool BUCKET = false>
 __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
 {
     constexpr int TE = 1 << TS;
     constexpr int U = 64;
     static_assert(!BUCKET || (SRC == 0 && TS == 4 && !BATCH), "bucket form: single sweeps of XYZI on 16x16 tiles");
-    static_assert(!FAST_ONLY || BUCKET, "the fast projection alone: k_frame's lean form");
     const int lane = lane_id();
     if (unit >= a.B) return;                               // whole wave leaves together
     if (!BUCKET && unit == 0 && lane == 0) *a.srt_top = 0u; // bump pointer of the sorted arena (dense tiles of k_fuse_list, same pass)
@@ -104,7 +123,7 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
 
     bool valid = false;
     uint32_t tile = 0, cl = 0, src = 0; float hh = 0.0f, vv = 0.0f;
-    if (FAST_ONLY || (SRC == 0 && fc.fast_laser && !a.rgb)) {
+    if (SRC == 0 && fc.fast_laser && !a.rgb) {
         // (wave-uniform) a laser frame whose rotation variance is zero, no colours: projection + binning as straight-line code
         const float4 p = a.xyzi[i < sweep_end ? i : sweep_begin];
         int row, col;
@@ -113,7 +132,7 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
         cl = (uint32_t)(((row & (TE - 1)) << TS) | (col & (TE - 1)));
         src = (uint32_t)i;
         if (!valid) { tile = 0; cl = 0; }
-    } else if (!FAST_ONLY && i < sweep_end) {
+    } else if (i < sweep_end) {
         int row, col; float h, v; bool colour_ok = false;
         if (SRC == 0) {
             const float4 p = a.xyzi[i];
@@ -141,23 +160,13 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
         }
     }
 
+    if constexpr (BUCKET) { bucket_store(a, valid, tile, cl, src, hh, vv); return; }
     // group the wave's points by tile, stable in lane (= input) order
     const uint64_t peers = wave_peers_few(valid, tile, a.tile_bits);
     const uint64_t lt = lanemask_lt();
     const uint32_t rank = (uint32_t)__popcll(peers & lt);
     const uint32_t cnt = (uint32_t)__popcll(peers);
     const bool leader = valid && rank == 0;
-    if constexpr (BUCKET) {
-        uint32_t old = 0;
-        if (leader) old = atomicAdd(&a.bcount[tile], cnt);
-        old = (uint32_t)__shfl((int)old, valid ? (__ffsll((unsigned long long)peers) - 1) : lane, 64);
-        if (valid) {
-            const uint32_t pos = old + rank, z = cl | (src << 8);
-            if (pos < (uint32_t)kFrameBucket) rec_store3(reinterpret_cast<uint4*>(a.bkt), (size_t)tile * kFrameBucket + pos, __float_as_uint(hh), __float_as_uint(vv), z);
-            else a.spill[src] = make_uint4(__float_as_uint(hh), __float_as_uint(vv), z, tile);
-        }
-        return;
-    }
     const uint32_t x = leader ? cnt : 0u;
     const uint32_t start_leader = wave_inclusive_scan(x) - x;       // groups laid out in order of first appearance
     const int my_leader = valid ? (__ffsll((unsigned long long)peers) - 1) : lane;
@@ -180,7 +189,8 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
     }
 }
 
-__device__ __forceinline__ void bin_stamp_begin(const BinArgs& a, int block)
+template <class A>
+__device__ __forceinline__ void bin_stamp_begin(const A& a, int block)
 {
     if (a.dbg && threadIdx.x == 0) {
         a.dbg[(size_t)block * 16] = (unsigned long long)__builtin_readcyclecounter(); a.dbg[(size_t)block * 16 + 15] = (unsigned long long)blockIdx.x + 1ull;
@@ -188,7 +198,8 @@ __device__ __forceinline__ void bin_stamp_begin(const BinArgs& a, int block)
         a.dbg[(size_t)block * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID
     }
 }
-__device__ __forceinline__ void bin_stamp_end(const BinArgs& a, int block)
+template <class A>
+__device__ __forceinline__ void bin_stamp_end(const A& a, int block)
 {
     if (a.dbg && threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -196,12 +207,49 @@ __device__ __forceinline__ void bin_stamp_end(const BinArgs& a, int block)
     }
 }
 
-template <int SRC, int TS, bool BATCH, bool BUCKET = false, bool FAST_ONLY = false>
+template <int SRC, int TS, bool BATCH, bool BUCKET = false>
 __device__ __forceinline__ void bin_wave_body(const BinArgs& a, int block)
 {
     bin_stamp_begin(a, block);
-    bin_unit<SRC, TS, BATCH, BUCKET, FAST_ONLY>(a, (int)(block * 4 + (threadIdx.x >> 6)));
+    bin_unit<SRC, TS, BATCH, BUCKET>(a, (int)(block * 4 + (threadIdx.x >> 6)));
     bin_stamp_end(a, block);
+}
+
+// The lean form's arguments are pinned in scalar registers where the kernel starts: an empty asm statement the value has to pass
+// through in an SGPR.  Left alone the compiler sinks every argument load into the block that first uses it and a wave waits out a
+// scalar-cache round trip per block; pinned, the loads of one path are one batch of wide s_load and one wait.
+// (A pointer that went through the statement is a global one all the same: the cast says so, or its accesses would be flat ones.)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GEM_PIN(x) asm volatile("" : "+s"(x))
+#define GEM_PIN_PTR(p) do { uintptr_t u_ = reinterpret_cast<uintptr_t>(p); asm volatile("" : "+s"(u_)); (p) = (decltype(p))(__attribute__((address_space(1))) std::remove_pointer_t<decltype(p)>*)u_; } while (0)
+#else
+#define GEM_PIN(x) (void)(x)
+#define GEM_PIN_PTR(p) (void)(p)
+#endif
+
+// k_frame's lean form: one unit of a single fast-laser sweep without colours (the host has checked that: frame_launch_lean) into the
+// buckets, from the lean argument block -- the generic projection, its doubles and the two thirds of FrameConst only it reads are
+// not carried.  The point count is a word here (a single sweep), the arithmetic is bin_unit's.
+__device__ __forceinline__ void bin_unit_lean(const FrameLeanBin& a, int unit)
+{
+    constexpr int TS = 4, TE = 16;
+    if (unit >= a.B) return;                               // whole wave leaves together
+    const uint32_t i = (uint32_t)unit * 64u + (uint32_t)lane_id();
+    const float4 p = a.xyzi[i < a.n ? i : 0u];
+    // the frame's constants arrive while the load of the points is in flight: one batch, no scalar load is waited for behind it
+    FrameLeanBin f = a;
+    GEM_PIN(f.keep_sentinel); GEM_PIN(f.tile_bits); GEM_PIN(f.tiles_per_row); GEM_PIN(f.filter_on); GEM_PIN_PTR(f.bkt); GEM_PIN_PTR(f.bcount);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) GEM_PIN(f.T[k]);
+    GEM_PIN(f.lower_f); GEM_PIN(f.upper_f); GEM_PIN(f.fbx); GEM_PIN(f.fby); GEM_PIN(f.fband); GEM_PIN(f.fplane);
+    GEM_PIN(f.cx); GEM_PIN(f.cy); GEM_PIN(f.sx); GEM_PIN(f.sy); GEM_PIN(f.L); GEM_PIN(f.res); GEM_PIN(f.row0); GEM_PIN(f.row1);
+    GEM_PIN(f.beam_a); GEM_PIN(f.beam_c); GEM_PIN(f.t2); GEM_PIN(f.Js[0]); GEM_PIN(f.Js[1]);
+    int row, col; float hh, vv;
+    const bool valid = project_bin_laser_fast(f, p.x, p.y, p.z, i < a.n, f.keep_sentinel != 0, row, col, hh, vv);
+    uint32_t tile = (uint32_t)((row >> TS) * f.tiles_per_row + (col >> TS));
+    uint32_t cl = (uint32_t)(((row & (TE - 1)) << TS) | (col & (TE - 1)));
+    if (!valid) { tile = 0; cl = 0; }
+    bucket_store(f, valid, tile, cl, i, hh, vv);
 }
 
 template <int SRC, int TS, bool BATCH>
@@ -387,34 +435,13 @@ __device__ __forceinline__ DenseResult dense_tile(const uint4* __restrict__ rec,
 // kernel keep the dense path's registers (and spills) out of the code every LiDAR tile runs.
 template <int CPT> struct TileState { float e[CPT], s[CPT], lw[CPT]; uint32_t tmask, acc_nd, acc_P; int sweep; };
 
-constexpr int kFrameRunBits = 3;                    // runs of 2^kFrameRunBits neighbouring tiles per XCD (runs of 2 / 4 / 8: FETCH_SIZE 4.9 / 4.35 / 4.03 MB per C2 frame, 8.56 / 8.41 / 8.40 us per step)
-constexpr int kFrameGridUnit = 8 << kFrameRunBits;  // ... the tile blocks come in multiples of this
 constexpr int kFramePB = kFrameBucket;              // records per tile the fast path holds in LDS
 constexpr int kFrameSpec = 256;                     // records requested before the count is known: one per thread
 constexpr int kFrameWG = 6;                         // workgroups per CU the register budget is set for
 // LDS: rank rows [256] x 8 u16 | generic lists head / tail [256][4] u16 (aliased), cell of a slot [PB] u16, next [PB] u16, stage [PB] x 16 B, misc
 constexpr size_t kFrameLds = 256 * 16 + kFramePB * 2 * 2 + kFramePB * 16 + 16;
 
-// block -> tile: centre-first in dispatch order (the heaviest tiles of a robot-centric map start first), and XCD-AWARE --
-// workgroup b runs on XCD b % 8, each XCD has its own L2, and four tiles that follow each other in a tile row share their
-// 128-byte lines of the layers: runs of 2^kFrameRunBits consecutive ranks go to ONE XCD (with plain rank = block the neighbours
-// sat on eight different XCDs and every shared line was fetched twice: FETCH_SIZE 5.6 MB per frame instead of 3.6,
-// profiles/r05_c2_bench.txt).  Rows c, c-1, c+1, ...; columns in runs of neighbours on alternating sides: 0 1 2 3 | -1 -2 -3 -4 | 4 5 6 7 | ...
-__device__ __forceinline__ bool frame_tile_of(const FuseArgs& a, int block, int& tr, int& tc)
-{
-    const int tpr = a.tiles_per_row;
-    const int x = block & 7, i = block >> 3;
-    const int rnk = ((((i >> kFrameRunBits) << 3) + x) << kFrameRunBits) + (i & ((1 << kFrameRunBits) - 1));
-    if (rnk >= a.T) return false;
-    const int bi = rnk / tpr, bj = rnk - bi * tpr;
-    const int oi = (bi & 1) ? -((bi + 1) >> 1) : (bi >> 1);
-    const int cj = bj >> kFrameRunBits, t = bj & ((1 << kFrameRunBits) - 1);
-    const int oj = (cj & 1) ? -(((cj - 1) >> 1) << kFrameRunBits) - 1 - t : ((cj >> 1) << kFrameRunBits) + t;
-    tr = a.center_tr + oi; tr = tr < 0 ? tr + tpr : (tr >= tpr ? tr - tpr : tr);
-    tc = a.center_tc + oj; tc = tc < 0 ? tc + tpr : (tc >= tpr ? tc - tpr : tc);
-    return true;
-}
-
+// (block -> tile of k_frame: frame_tile_of, gem_frame_lean.hpp)
 // FLAGS: bits 0-1 = ATTR (0 none, 1 colours from the cloud, 2 colours from gem_fuse's arrays), bit 2 = LOWEST (also maintain the
 // map_lowest layer, GPU:432-439, for gem_raytracing)
 // RANKED: k_frame's descriptor form (frame_tile_of maps blocks to tiles)
@@ -1173,10 +1200,13 @@ __global__ __launch_bounds__(NT, fuse_list_waves(TS, NT, PB, ATTR, BATCH)) void 
 //     indices.  A record of the window goes to slot (index - window start), so slot order IS input order, and the per-wave in-order
 //     linked lists of k_fuse_list's generic path give every cell its records in that order.  Each round re-reads the bucket (and
 //     scans the whole spill arena when the bucket overflowed); the next window starts at the smallest index left.
-template <int FLAGS>
-__device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigned char* lds_raw)
+// A: FuseArgs (the generic form), or FrameLeanTile (the lean form's own argument block, gem_frame_lean.hpp: k_frame<FLAGS, true>
+// has every word a tile reads before its chains are done in scalar registers when it calls this).
+template <int FLAGS, class A>
+__device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char* lds_raw)
 {
     constexpr bool LOWEST = (FLAGS & 4) != 0;
+    constexpr bool LEAN = std::is_same_v<A, FrameLeanTile>;
     constexpr int TS = 4, TE = 16, CELLS = 256, NT = 256, NW = 4, PB = kFramePB;
     constexpr uint32_t NIL = 0xffffu;
     static_assert(PB % 64 == 0 && PB % NT == 0 && kFrameSpec == NT && PB <= 1024, "geometry");
@@ -1239,7 +1269,12 @@ __device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigne
     if (tid == 0 && nrec != 0) a.bcount[tile] = 0u;
 
     // queued Mapvar_update increments (GPU:540-547), before the first record
-    for (int k = 0; k < a.n_pending; ++k) if (cs != kInitVariance) cs += a.pending[k];
+    if constexpr (LEAN) {                                                // (static indices: the four words stay scalar registers)
+#pragma unroll
+        for (int k = 0; k < kMaxPending; ++k) if (k < a.n_pending && cs != kInitVariance) cs += a.pending[k];
+    } else {
+        for (int k = 0; k < a.n_pending; ++k) if (cs != kInitVariance) cs += a.pending[k];
+    }
 
     bool slow = !fits;
     if (fits) {
@@ -1307,7 +1342,7 @@ __device__ __forceinline__ void frame_tile(const FuseArgs& a, int block, unsigne
             if (a.form_seen) __hip_atomic_store(a.form_seen, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         const uint32_t nb = min(nrec, (uint32_t)kFrameBucket);
-        const uint32_t nspill = fits ? 0u : (uint32_t)a.B_total * (uint32_t)a.U;
+        const uint32_t nspill = fits ? 0u : frame_spill_slots(a);
         const uint64_t lt = lanemask_lt();
         uint32_t lo = 0;
         for (;;) {                                                       // block-uniform
@@ -1437,22 +1472,43 @@ constexpr int kFrameLeanWG = GEM_FRAME_LEAN_WG;                         // (buil
 static_assert(kFrameLeanWG >= 1 && kFrameLeanWG <= 8 && (size_t)kFrameLeanWG * kFrameLds <= 160 * 1024, "kFrameLeanWG lean workgroups fit the CU's LDS");
 
 template <int FLAGS, bool LEAN = false>
-__global__ __launch_bounds__(256, LEAN ? kFrameLeanWG : kFrameWG) void k_frame(FuseArgs fa, BinArgs ba)
+__global__ __launch_bounds__(256, kFrameWG) void k_frame(FuseArgs fa, BinArgs ba)
 {
+    static_assert(!LEAN, "the lean form takes FrameLeanArgs (below)");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
-    const int nf = (fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1);     // fuse blocks (see frame_tile_of)
-    if constexpr (LEAN) {
-        if ((int)blockIdx.x < nf) frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
-        else {
-            const int block = (int)blockIdx.x - nf;
-            if (block == 0 && threadIdx.x == 0) ba.ctl[1] = 0u;
-            bin_wave_body<0, 4, false, true, true>(ba, block);                // (the host launches this form for fast-laser frames only)
-        }
-    } else if ((int)blockIdx.x < nf) {
+    const int nf = frame_tile_blocks(fa.T);                                 // fuse blocks (see frame_tile_of)
+    if ((int)blockIdx.x < nf) {
         if (fa.ctl[1] != 0u) { TileState<1> st; fuse_list_body<4, 256, kFramePB, FLAGS, false, 0, true>(fa, (int)blockIdx.x, lds_dyn, st); }
         else frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
     } else {
         bin_frame_body<false>(ba, (int)blockIdx.x - nf);
+    }
+}
+
+template <int FLAGS, bool LEAN>
+__global__ __launch_bounds__(256, kFrameLeanWG) void k_frame(FrameLeanArgs la)
+{
+    static_assert(LEAN, "the generic form takes FuseArgs and BinArgs (above)");
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
+    const int nf = la.t.nf;
+    if ((int)blockIdx.x < nf) {
+        // one scalar round trip behind the branch: what a tile reads before its chains are done (the slow path's three pointers are fetched there)
+        FrameLeanTile t = la.t;
+        GEM_PIN(t.T); GEM_PIN(t.tiles_per_row); GEM_PIN(t.tile_div); GEM_PIN_PTR(t.dbg); GEM_PIN_PTR(t.bkt); GEM_PIN_PTR(t.bcount);
+        GEM_PIN_PTR(t.elevation); GEM_PIN_PTR(t.variance); if constexpr ((FLAGS & 4) != 0) { GEM_PIN_PTR(t.lowest); GEM_PIN(t.start0); GEM_PIN(t.start1); }
+        GEM_PIN(t.L); GEM_PIN(t.center_tr); GEM_PIN(t.center_tc); GEM_PIN(t.row0); GEM_PIN(t.row1);
+        GEM_PIN(t.n_pending); GEM_PIN(t.pending[0]); GEM_PIN(t.pending[1]); GEM_PIN(t.pending[2]); GEM_PIN(t.pending[3]);
+        GEM_PIN(t.dense); GEM_PIN(t.mahal); GEM_PIN(t.var_floor);
+        frame_tile<FLAGS>(t, (int)blockIdx.x, lds_dyn);
+    } else {
+        // ... and what a binning block needs to issue the load of its points (the frame's constants follow behind that load: bin_unit_lean)
+        const int block = (int)blockIdx.x - nf;
+        FrameLeanBin b = la.b;
+        GEM_PIN_PTR(b.xyzi); GEM_PIN(b.B); GEM_PIN(b.n); GEM_PIN_PTR(b.dbg);
+        bin_stamp_begin(b, block);
+        bin_unit_lean(b, (int)(block * 4 + (threadIdx.x >> 6)));          // (the host launches this form for fast-laser frames only)
+        if (block == 0 && threadIdx.x == 0) b.ctl[1] = 0u;                // (behind the unit: its pointer is not waited for in front of the points)
+        bin_stamp_end(b, block);
     }
 }
 
@@ -1970,10 +2026,12 @@ hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, i
         if (ba.B > 0) GEM_LAUNCH((k_bin_frame), dim3((ba.B + 3) / 4), dim3(256), 0, st, ev, ba);
         return hipGetLastError();
     }
-    const dim3 grid(((fa.T + kFrameGridUnit - 1) & ~(kFrameGridUnit - 1)) + (ba.B + 3) / 4), block(256);
+    const dim3 grid(frame_tile_blocks(fa.T) + (ba.B + 3) / 4), block(256);
     if (lean) {                                                          // (the bucket form alone: kFrameLds, kFrameLeanWG workgroups per CU)
-        if (attr == 4) GEM_LAUNCH((k_frame<4, true>), grid, block, kFrameLds, st, ev, fa, ba);
-        else           GEM_LAUNCH((k_frame<0, true>), grid, block, kFrameLds, st, ev, fa, ba);
+        using LeanKernel = void (*)(FrameLeanArgs);                      // (k_frame<FLAGS, true> names both overloads)
+        const FrameLeanArgs la = frame_lean_args(fa, ba);
+        if (attr == 4) GEM_LAUNCH((static_cast<LeanKernel>(k_frame<4, true>)), grid, block, kFrameLds, st, ev, la);
+        else           GEM_LAUNCH((static_cast<LeanKernel>(k_frame<0, true>)), grid, block, kFrameLds, st, ev, la);
         return hipGetLastError();
     }
     const size_t lds = std::max(kFrameLds, fuse_list_lds(256, 4, kFramePB, 0));      // (either form of the fuse half)
