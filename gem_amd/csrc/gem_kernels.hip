@@ -21,6 +21,7 @@
 // Built with -ffp-contract=off (see gem_device.hpp).
 #include "gem_kernels.hpp"
 #include "gem_frame_lean.hpp"
+#include "gem_frame_sort.hpp"
 #include "gem_wave.hpp"
 
 #include <hip/hip_ext.h>
@@ -189,19 +190,22 @@ __device__ __forceinline__ void bin_unit(const BinArgs& a, int unit)
     }
 }
 
-template <class A>
+// STAMPS = false (k_frame's lean production form): no stamp code at all, a.dbg is not read
+template <bool STAMPS = true, class A>
 __device__ __forceinline__ void bin_stamp_begin(const A& a, int block)
 {
-    if (a.dbg && threadIdx.x == 0) {
+    if constexpr (!STAMPS) return;
+    else if (a.dbg && threadIdx.x == 0) {
         a.dbg[(size_t)block * 16] = (unsigned long long)__builtin_readcyclecounter(); a.dbg[(size_t)block * 16 + 15] = (unsigned long long)blockIdx.x + 1ull;
         a.dbg[(size_t)block * 16 + 12] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
         a.dbg[(size_t)block * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID
     }
 }
-template <class A>
+template <bool STAMPS = true, class A>
 __device__ __forceinline__ void bin_stamp_end(const A& a, int block)
 {
-    if (a.dbg && threadIdx.x == 0) {
+    if constexpr (!STAMPS) return;
+    else if (a.dbg && threadIdx.x == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         a.dbg[(size_t)block * 16 + 1] = (unsigned long long)__builtin_readcyclecounter(); a.dbg[(size_t)block * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
     }
@@ -437,6 +441,14 @@ template <int CPT> struct TileState { float e[CPT], s[CPT], lw[CPT]; uint32_t tm
 
 constexpr int kFramePB = kFrameBucket;              // records per tile the fast path holds in LDS
 constexpr int kFrameSpec = 256;                     // records requested before the count is known: one per thread
+#ifndef GEM_FRAME_SIZED_SORT
+#define GEM_FRAME_SIZED_SORT 1
+#endif
+constexpr bool kFrameSizedSort = GEM_FRAME_SIZED_SORT != 0;          // (build define: 0 = every wave runs the 8-key network, for A/B builds)
+#ifndef GEM_FRAME_RANK_ONE
+#define GEM_FRAME_RANK_ONE 1
+#endif
+constexpr bool kFrameRankOne = GEM_FRAME_RANK_ONE != 0;              // (build define: 0 = every tile ranks kFramePB / 256 slots per thread, for A/B builds)
 constexpr int kFrameWG = 6;                         // workgroups per CU the register budget is set for
 // LDS: rank rows [256] x 8 u16 | generic lists head / tail [256][4] u16 (aliased), cell of a slot [PB] u16, next [PB] u16, stage [PB] x 16 B, misc
 constexpr size_t kFrameLds = 256 * 16 + kFramePB * 2 * 2 + kFramePB * 16 + 16;
@@ -1202,7 +1214,9 @@ __global__ __launch_bounds__(NT, fuse_list_waves(TS, NT, PB, ATTR, BATCH)) void 
 //     scans the whole spill arena when the bucket overflowed); the next window starts at the smallest index left.
 // A: FuseArgs (the generic form), or FrameLeanTile (the lean form's own argument block, gem_frame_lean.hpp: k_frame<FLAGS, true>
 // has every word a tile reads before its chains are done in scalar registers when it calls this).
-template <int FLAGS, class A>
+// STAMPS: the cycle stamps of tools/frame_phases.py (a.dbg, thread 0) are compiled in -- the generic form and k_frame_stamped; the
+// lean production kernel carries none of it: no a.dbg, no stamp counter, no tid == 0 masks kept alive for them.
+template <int FLAGS, bool STAMPS, class A>
 __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char* lds_raw)
 {
     constexpr bool LOWEST = (FLAGS & 4) != 0;
@@ -1225,10 +1239,10 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
     const int tile = tr * a.tiles_per_row + tc;
     const int row_base = tr << TS, col_base = tc << TS;
     const int L = a.L;
-    int dbg_k = 0;
-#define GEM_STAMP() do { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + dbg_k++] = (unsigned long long)__builtin_readcyclecounter(); } while (0)
+    [[maybe_unused]] int dbg_k = 0;
+#define GEM_STAMP() do { if constexpr (STAMPS) { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + dbg_k++] = (unsigned long long)__builtin_readcyclecounter(); } } while (0)
     GEM_STAMP();                                                         // 0: start
-    if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + 12] = (unsigned long long)__builtin_amdgcn_s_memrealtime();   // (100 MHz, one clock for the chip)
+    if constexpr (STAMPS) { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + 12] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); }   // (100 MHz, one clock for the chip)
 
     // ---- one round trip: the count, the first kFrameSpec records of the bucket and the tile ------------------
     const uint32_t nrec = a.bcount[tile];                                // block-uniform
@@ -1280,57 +1294,79 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
     if (fits) {
         // ---- ranks: PB / NT slots per thread, all cell reads, then all rank atomics, then all row writes in flight together
         constexpr int RK = PB / NT;
-        uint32_t rcell[RK], rold[RK];
+        auto ranks = [&](auto rounds) {
+            constexpr int R = decltype(rounds)::value;
+            uint32_t rcell[R], rold[R];
 #pragma unroll
-        for (int r = 0; r < RK; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rcell[r] = k < nrec ? (stage[k].z & 0xffu) : 0u; }
+            for (int r = 0; r < R; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rcell[r] = k < nrec ? (stage[k].z & 0xffu) : 0u; }
 #pragma unroll
-        for (int r = 0; r < RK; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rold[r] = 0; if (k < nrec) rold[r] = atomicAdd(reinterpret_cast<uint32_t*>(rowp) + rcell[r] * 4 + 3, 0x10000u); }
+            for (int r = 0; r < R; ++r) { const uint32_t k = (uint32_t)(tid + r * NT); rold[r] = 0; if (k < nrec) rold[r] = atomicAdd(reinterpret_cast<uint32_t*>(rowp) + rcell[r] * 4 + 3, 0x10000u); }
 #pragma unroll
-        for (int r = 0; r < RK; ++r) {
-            const uint32_t k = (uint32_t)(tid + r * NT);
-            if (k < nrec) { const uint32_t rk = rold[r] >> 16; if (rk < (uint32_t)kRankMax) rowp[rcell[r] * 8 + rk] = (uint16_t)k; else misc[0] = 1u; }
-        }
+            for (int r = 0; r < R; ++r) {
+                const uint32_t k = (uint32_t)(tid + r * NT);
+                if (k < nrec) { const uint32_t rk = rold[r] >> 16; if (rk < (uint32_t)kRankMax) rowp[rcell[r] * 8 + rk] = (uint16_t)k; else misc[0] = 1u; }
+            }
+        };
+        if (kFrameRankOne && nrec <= (uint32_t)NT) ranks(std::integral_constant<int, 1>{});     // block-uniform: one slot per thread (about 1240 of a C2 sweep's 1330 live tiles)
+        else ranks(std::integral_constant<int, RK>{});
         __syncthreads();
         GEM_STAMP();                                                     // 3: ranked
         slow = misc[0] != 0;                                             // block-uniform
     }
     if (!slow) {
-        // ---- owner: sort <= 7 keys (point index << 10 | slot), run the chain from registers
+        // ---- owner: sort <= 7 keys (point index << 10 | slot), run the chain from registers.  Sized by the WAVE's largest count
+        //      (ballots: wave-uniform branches): most waves of a LiDAR sweep hold at most two records per cell (gem_frame_sort.hpp)
         const uint4 rw = *reinterpret_cast<const uint4*>(rowp + tid * 8);
         const uint32_t n = rw.w >> 16;
         const uint32_t p[kRankMax] = {rw.x & 0xffffu, rw.x >> 16, rw.y & 0xffffu, rw.y >> 16, rw.z & 0xffffu, rw.z >> 16, rw.w & 0xffffu};
-        uint32_t k[8];                                                   // ~0 = no record: sorted behind the live keys
-#pragma unroll
-        for (int i = 0; i < 8; ++i) k[i] = 0xffffffffu;
-#pragma unroll
-        for (int i = 0; i < kRankMax; ++i) {
-            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
-            const uint32_t sl = (uint32_t)i < n ? p[i] : 0u;             // slot 0 is always a valid address
-            if ((uint32_t)i < n) k[i] = ((stage[sl].z >> 8) << 10) | sl;
-        }
-        GEM_CSWAP(k[0], k[1]); GEM_CSWAP(k[2], k[3]); GEM_CSWAP(k[4], k[5]); GEM_CSWAP(k[6], k[7]);
-        GEM_CSWAP(k[0], k[2]); GEM_CSWAP(k[1], k[3]); GEM_CSWAP(k[4], k[6]); GEM_CSWAP(k[5], k[7]);
-        GEM_CSWAP(k[1], k[2]); GEM_CSWAP(k[5], k[6]); GEM_CSWAP(k[0], k[4]); GEM_CSWAP(k[3], k[7]);
-        GEM_CSWAP(k[1], k[5]); GEM_CSWAP(k[2], k[6]);
-        GEM_CSWAP(k[1], k[4]); GEM_CSWAP(k[3], k[6]);
-        GEM_CSWAP(k[2], k[4]); GEM_CSWAP(k[3], k[5]);
-        GEM_CSWAP(k[3], k[4]);
-        float hh[kRankMax], vv[kRankMax];
-#pragma unroll
-        for (int i = 0; i < kRankMax; ++i) {
-            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
-            const uint32_t sl = (uint32_t)i < n ? (k[i] & 1023u) : 0u;
-            hh[i] = __uint_as_float(stage[sl].x); vv[i] = __uint_as_float(stage[sl].y);
-        }
-#pragma unroll
-        for (int i = 0; i < kRankMax; ++i) {
-            if (__ballot((uint32_t)i < n) == 0) break;                   // wave-uniform
+        auto chain = [&](float h, float v, bool live) {                  // one step of the reference's recurrence (GPU:480-531)
             float e2 = ce, s2 = cs;
-            (void)fuse_step(e2, s2, hh[i], vv[i], a.mahal, a.var_floor);
-            const bool live = (uint32_t)i < n;
-            const bool fl = live && (!LOWEST || hh[i] != -1.0f);         // GPU:482 (only LOWEST passes carry such records)
+            (void)fuse_step(e2, s2, h, v, a.mahal, a.var_floor);
+            const bool fl = live && (!LOWEST || h != -1.0f);             // GPU:482 (only LOWEST passes carry such records)
             ce = fl ? e2 : ce; cs = fl ? s2 : cs;
-            if constexpr (LOWEST) { const float l2 = lowest_step(lw, hh[i], vv[i]); lw = live ? l2 : lw; }
+            if constexpr (LOWEST) { const float l2 = lowest_step(lw, h, v); lw = live ? l2 : lw; }
+        };
+        // N keys for a wave whose largest count is in [NMIN, min(N, kRankMax)]: entries at or beyond a lane's n stay ~0 and sort
+        // behind its live keys, all of which are among the first N -- the order the full network gives
+        auto owner = [&](auto size, auto least) {
+            constexpr int N = decltype(size)::value, NMIN = decltype(least)::value, M = N < kRankMax ? N : kRankMax;
+            uint32_t k[N];                                               // ~0 = no record
+#pragma unroll
+            for (int i = 0; i < N; ++i) k[i] = 0xffffffffu;
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                if (i >= NMIN && __ballot((uint32_t)i < n) == 0) break;  // wave-uniform
+                const uint32_t sl = (uint32_t)i < n ? p[i] : 0u;         // slot 0 is always a valid address
+                if ((uint32_t)i < n) k[i] = ((stage[sl].z >> 8) << 10) | sl;
+            }
+            frame_sort_keys<N>(k);
+            float hh[M], vv[M];
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                if (i >= NMIN && __ballot((uint32_t)i < n) == 0) break;  // wave-uniform
+                const uint32_t sl = (uint32_t)i < n ? (k[i] & 1023u) : 0u;
+                hh[i] = __uint_as_float(stage[sl].x); vv[i] = __uint_as_float(stage[sl].y);
+            }
+#pragma unroll
+            for (int i = 0; i < M; ++i) {
+                if (i >= NMIN && __ballot((uint32_t)i < n) == 0) break;  // wave-uniform
+                chain(hh[i], vv[i], (uint32_t)i < n);
+            }
+        };
+        static_assert(frame_sort_size(2) == 2 && frame_sort_size(3) == 4 && frame_sort_size(4) == 4 && frame_sort_size(5) == 8, "the classes below");
+        if (!kFrameSizedSort) {
+            owner(std::integral_constant<int, 8>{}, std::integral_constant<int, 0>{});
+        } else if (__ballot(n > 0u) == 0) {
+            // no record in this wave's 64 cells: nothing to do (the queued increments are in cs already)
+        } else if (__ballot(n > 1u) == 0) {                              // largest count 1: the record is the row's first entry, no key
+            const uint32_t sl = n != 0u ? p[0] : 0u;
+            chain(__uint_as_float(stage[sl].x), __uint_as_float(stage[sl].y), n != 0u);
+        } else if (__ballot(n > 2u) == 0) {
+            owner(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+        } else if (__ballot(n > 4u) == 0) {
+            owner(std::integral_constant<int, 4>{}, std::integral_constant<int, 3>{});
+        } else {
+            owner(std::integral_constant<int, 8>{}, std::integral_constant<int, 5>{});
         }
     } else {
         // ---- slow path: windows [lo, lo + PB) of point indices, in order.  It re-reads the tile's records per window (and the
@@ -1436,10 +1472,12 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
         }
     }
     GEM_STAMP();                                                         // 5: stores issued
-    if (a.dbg && tid == 0) {
-        a.dbg[(size_t)tile * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
-        a.dbg[(size_t)tile * 16 + 15] = (unsigned long long)block + 1ull;
-        a.dbg[(size_t)tile * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID: the XCD's clock is its own
+    if constexpr (STAMPS) {
+        if (a.dbg && tid == 0) {
+            a.dbg[(size_t)tile * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
+            a.dbg[(size_t)tile * 16 + 15] = (unsigned long long)block + 1ull;
+            a.dbg[(size_t)tile * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID: the XCD's clock is its own
+        }
     }
 #undef GEM_STAMP
 }
@@ -1479,38 +1517,53 @@ __global__ __launch_bounds__(256, kFrameWG) void k_frame(FuseArgs fa, BinArgs ba
     const int nf = frame_tile_blocks(fa.T);                                 // fuse blocks (see frame_tile_of)
     if ((int)blockIdx.x < nf) {
         if (fa.ctl[1] != 0u) { TileState<1> st; fuse_list_body<4, 256, kFramePB, FLAGS, false, 0, true>(fa, (int)blockIdx.x, lds_dyn, st); }
-        else frame_tile<FLAGS>(fa, (int)blockIdx.x, lds_dyn);
+        else frame_tile<FLAGS, true>(fa, (int)blockIdx.x, lds_dyn);
     } else {
         bin_frame_body<false>(ba, (int)blockIdx.x - nf);
     }
 }
 
-template <int FLAGS, bool LEAN>
-__global__ __launch_bounds__(256, kFrameLeanWG) void k_frame(FrameLeanArgs la)
+template <int FLAGS, bool STAMPS>
+__device__ __forceinline__ void frame_lean_body(const FrameLeanArgs& la)
 {
-    static_assert(LEAN, "the generic form takes FuseArgs and BinArgs (above)");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_dyn[];
     const int nf = la.t.nf;
     if ((int)blockIdx.x < nf) {
         // one scalar round trip behind the branch: what a tile reads before its chains are done (the slow path's three pointers are fetched there)
         FrameLeanTile t = la.t;
-        GEM_PIN(t.T); GEM_PIN(t.tiles_per_row); GEM_PIN(t.tile_div); GEM_PIN_PTR(t.dbg); GEM_PIN_PTR(t.bkt); GEM_PIN_PTR(t.bcount);
+        GEM_PIN(t.T); GEM_PIN(t.tiles_per_row); GEM_PIN(t.tile_div); if constexpr (STAMPS) GEM_PIN_PTR(t.dbg); GEM_PIN_PTR(t.bkt); GEM_PIN_PTR(t.bcount);
         GEM_PIN_PTR(t.elevation); GEM_PIN_PTR(t.variance); if constexpr ((FLAGS & 4) != 0) { GEM_PIN_PTR(t.lowest); GEM_PIN(t.start0); GEM_PIN(t.start1); }
         GEM_PIN(t.L); GEM_PIN(t.center_tr); GEM_PIN(t.center_tc); GEM_PIN(t.row0); GEM_PIN(t.row1);
         GEM_PIN(t.n_pending); GEM_PIN(t.pending[0]); GEM_PIN(t.pending[1]); GEM_PIN(t.pending[2]); GEM_PIN(t.pending[3]);
         GEM_PIN(t.dense); GEM_PIN(t.mahal); GEM_PIN(t.var_floor);
-        frame_tile<FLAGS>(t, (int)blockIdx.x, lds_dyn);
+        frame_tile<FLAGS, STAMPS>(t, (int)blockIdx.x, lds_dyn);
     } else {
         // ... and what a binning block needs to issue the load of its points (the frame's constants follow behind that load: bin_unit_lean)
         const int block = (int)blockIdx.x - nf;
         FrameLeanBin b = la.b;
-        GEM_PIN_PTR(b.xyzi); GEM_PIN(b.B); GEM_PIN(b.n); GEM_PIN_PTR(b.dbg);
-        bin_stamp_begin(b, block);
+        GEM_PIN_PTR(b.xyzi); GEM_PIN(b.B); GEM_PIN(b.n); if constexpr (STAMPS) GEM_PIN_PTR(b.dbg);
+        bin_stamp_begin<STAMPS>(b, block);
         bin_unit_lean(b, (int)(block * 4 + (threadIdx.x >> 6)));          // (the host launches this form for fast-laser frames only)
         if (block == 0 && threadIdx.x == 0) b.ctl[1] = 0u;                // (behind the unit: its pointer is not waited for in front of the points)
-        bin_stamp_end(b, block);
+        bin_stamp_end<STAMPS>(b, block);
     }
 }
+
+#ifndef GEM_FRAME_LEAN_STAMPS
+#define GEM_FRAME_LEAN_STAMPS 0
+#endif
+constexpr bool kFrameLeanStamps = GEM_FRAME_LEAN_STAMPS != 0;          // (build define: 1 = the production kernel carries the stamps as it did, for A/B builds)
+
+template <int FLAGS, bool LEAN>
+__global__ __launch_bounds__(256, kFrameLeanWG) void k_frame(FrameLeanArgs la)
+{
+    static_assert(LEAN, "the generic form takes FuseArgs and BinArgs (above)");
+    frame_lean_body<FLAGS, kFrameLeanStamps>(la);
+}
+
+// the lean form with the stamps of tools/frame_phases.py: what launch_frame picks when the handle's stamp buffer is set
+template <int FLAGS>
+__global__ __launch_bounds__(256, kFrameLeanWG) void k_frame_stamped(FrameLeanArgs la) { frame_lean_body<FLAGS, true>(la); }
 
 // the binning of the first frame of a stream, with nothing to fuse beside it (no LDS, the occupancy of k_bin_wave); ba.lean: bucket form unconditionally
 __global__ __launch_bounds__(256) void k_bin_frame(BinArgs ba) { bin_frame_body<true>(ba, (int)blockIdx.x); }
@@ -2030,6 +2083,11 @@ hipError_t launch_frame(hipStream_t st, const FuseArgs& fa, const BinArgs& ba, i
     if (lean) {                                                          // (the bucket form alone: kFrameLds, kFrameLeanWG workgroups per CU)
         using LeanKernel = void (*)(FrameLeanArgs);                      // (k_frame<FLAGS, true> names both overloads)
         const FrameLeanArgs la = frame_lean_args(fa, ba);
+        if (la.t.dbg || la.b.dbg) {                                      // the handle's stamp buffer is set: the diagnostic kernel
+            if (attr == 4) GEM_LAUNCH((k_frame_stamped<4>), grid, block, kFrameLds, st, ev, la);
+            else           GEM_LAUNCH((k_frame_stamped<0>), grid, block, kFrameLds, st, ev, la);
+            return hipGetLastError();
+        }
         if (attr == 4) GEM_LAUNCH((static_cast<LeanKernel>(k_frame<4, true>)), grid, block, kFrameLds, st, ev, la);
         else           GEM_LAUNCH((static_cast<LeanKernel>(k_frame<0, true>)), grid, block, kFrameLds, st, ev, la);
         return hipGetLastError();

@@ -19,6 +19,10 @@ m = ElevationMap(wl.length, wl.resolution)
 lib = _lib.load()
 d = [torch.from_numpy(c).cuda() for c in wl.clouds]
 for k in range(n_sw - 2):
+    if k == max(0, n_sw - 5):                    # the last frames of the lead-in run stamped as well: the lean form's stamped kernel is a
+        m.synchronize()                          # kernel of its own (k_frame_stamped), and its first launch would be timed with cold code
+        assert lib.gem_debug_set(m._h, b"dbg_frame", 1) == 0
+        lib.gem_debug_fuse_stamps(m._h, 1, None, 0)
     m.add(wl.frames[k], d[k])
 m.synchronize()
 assert lib.gem_debug_set(m._h, b"dbg_frame", 1) == 0
