@@ -194,6 +194,17 @@ SIGNATURES = {
     "gem_costmap_read": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
     "gem_costmap_write": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
 }
+# include/gem_hip_history.h (the history cloud; gem_hip.h includes it)
+HISTORY_SIGNATURES = {
+    "gem_history_enable": (c_int, [c_void_p, c_longlong]),
+    "gem_history_append": (c_int, [c_void_p, c_void_p, c_longlong]),
+    "gem_history_append_device": (c_int, [c_void_p, c_void_p, c_longlong]),
+    "gem_history_reset_from_global": (c_int, [c_void_p]),
+    "gem_history_clear": (c_int, [c_void_p]),
+    "gem_history_size": (c_int, [c_void_p, POINTER(c_longlong)]),
+    "gem_history_export": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_longlong)]),
+    "gem_costmap_mark_history": (c_int, [c_void_p, c_int, c_double, POINTER(c_double)]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -219,7 +230,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **DEBUG_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

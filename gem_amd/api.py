@@ -753,13 +753,18 @@ class ElevationMap:
         self._check(self._lib.gem_local_grid_cloud(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)), "gem_local_grid_cloud")
         return out[:n.value].copy()
 
-    def local_spill(self, current_position, position_shift):
+    def local_spill(self, current_position, position_shift, download: bool = True):
         """The "Local mapping" block of updateLocalMap (EMg.cpp:715-764) without its gate, on the previous capture: returns
-        (records spilled in iteration order, replaced = the reference's `count`).  Positions and shifts are taken as float."""
+        (records spilled in iteration order, replaced = the reference's `count`).  Positions and shifts are taken as float.
+        download=False leaves the records on the device (the history cloud takes them there while it is enabled) and returns
+        (their number, replaced)."""
         cp = (C.c_float * 2)(*[float(np.float32(v)) for v in current_position[:2]])
         ps = (C.c_float * 2)(*[float(np.float32(v)) for v in position_shift[:2]])
-        out = np.empty(self.length * self.length, POINT_DTYPE)
         n, rep = C.c_int(), C.c_int()
+        if not download:
+            self._check(self._lib.gem_local_spill(self._h, cp, ps, None, C.byref(n), C.byref(rep)), "gem_local_spill")
+            return int(n.value), int(rep.value)
+        out = np.empty(self.length * self.length, POINT_DTYPE)
         self._check(self._lib.gem_local_spill(self._h, cp, ps, out.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(rep)), "gem_local_spill")
         return out[:n.value].copy(), int(rep.value)
 
@@ -902,6 +907,47 @@ class ElevationMap:
         n = C.c_int()
         self._check(self._lib.gem_global_count(self._h, C.byref(n)), "gem_global_count")
         return int(n.value)
+
+    # -- the history cloud (visualCloud_: EMg.cpp:750-760 push_back, :788 / :894-897 rebuild, visualPointMap :520-530) -------------
+    def history_enable(self, capacity: int = 1 << 20) -> None:
+        """Switch the device history cloud on, empty, with room for `capacity` records (it grows on demand); 0 switches it off and
+        frees its memory (gem_history_enable).  While it is on, local_spill appends what it selects."""
+        self._check(self._lib.gem_history_enable(self._h, int(capacity)), "gem_history_enable")
+
+    def history_append(self, points) -> None:
+        """POINT_DTYPE records behind the history: a host array, or a contiguous device tensor of 32-byte records (uint8 [n, 32] or
+        float32 [n, 8]), which is held until the map is synchronised."""
+        if _is_device_tensor(points):
+            if not points.is_contiguous() or points.numel() * points.element_size() % 32:
+                raise ValueError("points must be a contiguous device tensor of 32-byte records")
+            n = points.numel() * points.element_size() // 32
+            self._hold(points)
+            self._check(self._lib.gem_history_append_device(self._h, C.c_void_p(points.data_ptr()) if n else None, n), "gem_history_append_device")
+            return
+        pts = np.ascontiguousarray(points, POINT_DTYPE)
+        self._check(self._lib.gem_history_append(self._h, pts.ctypes.data_as(C.c_void_p) if pts.size else None, pts.shape[0]), "gem_history_append")
+
+    def history_reset_from_global(self) -> None:
+        """visualCloud_.clear() and the "Visual step" of updateGlobalMap: the history becomes every submap of the stack, in stack order."""
+        self._check(self._lib.gem_history_reset_from_global(self._h), "gem_history_reset_from_global")
+
+    def history_clear(self) -> None:
+        self._check(self._lib.gem_history_clear(self._h), "gem_history_clear")
+
+    def history_size(self) -> int:
+        n = C.c_longlong()
+        self._check(self._lib.gem_history_size(self._h, C.byref(n)), "gem_history_size")
+        return int(n.value)
+
+    def history_export(self, with_grid_cloud: bool = False) -> np.ndarray:
+        """The history as POINT_DTYPE records (savingMap's cloud); with_grid_cloud=True: followed by the last capture's grid cloud
+        (visualPointMap's visualCloud_ + grid_pc)."""
+        w = int(bool(with_grid_cloud))
+        n = C.c_longlong()
+        self._check(self._lib.gem_history_export(self._h, w, None, 0, C.byref(n)), "gem_history_export")
+        out = np.empty(max(n.value, 1), POINT_DTYPE)
+        self._check(self._lib.gem_history_export(self._h, w, out.ctypes.data_as(C.c_void_p), out.shape[0], C.byref(n)), "gem_history_export")
+        return out[:n.value].copy()
 
     # -- the costmap layers (layers/: PointMapLayer, ElevationMapLayer) ------------------------------------------------------------
     def costmap(self, size_x: int, size_y: int, resolution: float, origin_x: float = 0.0, origin_y: float = 0.0,
@@ -1147,6 +1193,10 @@ class Costmap:
     def mark_global(self, index: int = -1, travers_thresh: float = 0.5, bounds=None):
         """... over submap `index` of the stack (-1: all of them, in stack order)"""
         return self._mark("gem_costmap_mark_global", bounds, int(index), float(travers_thresh))
+
+    def mark_history(self, travers_thresh: float = 0.5, bounds=None):
+        """... over the history cloud where it lies, as one input; mark_grid_cloud after it is PointMapLayer's visualCloud_ + grid_pc"""
+        return self._mark("gem_costmap_mark_history", bounds, float(travers_thresh))
 
     def mark_visual(self, travers_thresh: float = 0.5, bounds=None):
         """ElevationMapLayer::updateBounds over the last capture standing for visualMap_"""

@@ -7,6 +7,7 @@
 // stream, and nothing returns to the host unless the caller asks for it.
 #include "gem_capi_internal.hpp"
 #include "gem_clean.hpp"
+#include "gem_costmap.hpp"
 
 namespace gemi {
 
@@ -241,6 +242,7 @@ void gem_destroy(gem_handle* h)
     local_free(h);
     global_free(h);
     costmap_free(h);
+    history_free(h);
     octree_free(h);
     if (h->layers.elevation) hipFree(h->layers.elevation);      // base of the single layer allocation
     if (h->d_counters) hipFree(h->d_counters);
@@ -957,6 +959,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "ray_lanes")          { if (value != 1 && value != 4 && value != 8 && value != 16) return fail(h, GEM_ERR_INVALID, "ray_lanes: 1, 4, 8 or 16"); h->ray_lanes = (int)value; }
     else if (k == "fast_laser")         h->fast_laser = value != 0;
     else if (k == "sort_form")          { if (value < 0 || value > 2) return fail(h, GEM_ERR_INVALID, "sort_form: 0 (by pass), 1 (cell-sorted), 2 (block-sorted)"); h->sort_form = (int)value; }
+    else if (k == "history_cull")       { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "history_cull: 0 or 1"); h->history_cull = value != 0; }
     else return fail(h, GEM_ERR_INVALID, "gem_debug_set: unknown key");
     return GEM_OK;
 }
@@ -982,6 +985,9 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "frame_generic_launches") *out = h->frame_generic_launches;
     else if (k == "frame_form_seen") *out = h->form_seen ? (long long)*static_cast<volatile const uint32_t*>(h->form_seen) : 0;
     else if (k == "walks_left") *out = h->walks_left;
+    else if (k == "history_cull") *out = h->history_cull ? 1 : 0;
+    else if (k == "history_blocks") *out = h->history.enabled ? cost_mark_blocks(h->history.len) : 0;
+    else if (k == "history_blocks_culled") { hipSetDevice(h->device); return history_blocks_culled(h, out); }
     else if (k == "step_pending") *out = h->step.valid ? 1 : 0;
     else if (k == "step_exchange_bytes_out") *out = h->xbytes_out;
     else if (k == "step_exchange_bytes_in") *out = h->xbytes_in;

@@ -5,6 +5,7 @@
 //   a costmap      two byte grids (a roll writes the other one and they swap) and a stamp word per cell, all-zero between calls
 //   small          the bounds words of a mark (four accumulated by the mark kernels, four published by the resolve pass)
 //   in, win        a host cloud of gem_costmap_mark_points on the device | the packed window of gem_costmap_read / _write
+// gem_costmap_mark_history reads the history cloud (gem_handle::History, gem_capi_history.cpp) and its box table where they lie.
 // A mark is its mark launches followed by one resolve launch on the handle's stream; the inputs that already live on the device
 // (the capture, the submap stack) are read where they are, a capture's record count from its device word.  Every device buffer comes
 // from ensure(), so gem_debug_get("arena_allocations") counts it.
@@ -283,6 +284,26 @@ int gem_costmap_mark_global(gem_handle* h, int id, int index, double travers_thr
         CostPointsArgs a{static_cast<const LocalRecord*>(g.stack[g.act].p) + g.off[s], nullptr, (uint32_t)g.cnt[s], (uint32_t)at, travers_thresh};
         GEM_HIP(h, launch_cost_mark_points(h->stream, geom_of(*m), a, accum_of(h, *m)));
         at += g.cnt[s];
+    }
+    return finish_mark(h, *m, bounds);
+}
+
+// PointMapLayer over the history cloud where it lies (gem_hip_history.h): one launch, a workgroup per block of the box table
+int gem_costmap_mark_history(gem_handle* h, int id, double travers_thresh, double bounds[4])
+{
+    COSTMAP_ENTRY("gem_costmap_mark_history");
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mark_history", &m))) return rc;
+    if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_history: travers_thresh not finite");
+    auto& hs = h->history;
+    if (!hs.enabled) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_history: the history is not enabled (gem_history_enable)");
+    if (hs.len > kMaxInputs) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_history: more than 2^31 - 2 records");
+    uint32_t* culled = static_cast<uint32_t*>(hs.small.p);
+    GEM_HIP(h, hipMemsetAsync(culled, 0, 4, h->stream));
+    if (hs.len > 0) {
+        CostPointsArgs a{static_cast<const LocalRecord*>(hs.log[hs.act].p), nullptr, (uint32_t)hs.len, 0u, travers_thresh};
+        GEM_HIP(h, launch_cost_mark_history(h->stream, geom_of(*m), a, accum_of(h, *m),
+                                            h->history_cull ? static_cast<const float4*>(hs.box.p) : nullptr, culled));
     }
     return finish_mark(h, *m, bounds);
 }

@@ -303,6 +303,17 @@ struct gem_handle {
         Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
         std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
     } costmap;
+    // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping
+    struct History {
+        bool enabled = false;
+        Arena log[2];                   // the records in history order, one arena in use (`act`), the other the target when it grows
+        int act = 0;
+        long long len = 0, cap = 0;     // records the log holds / records the active arena has room for
+        Arena box;                      // four floats per block of kCostChunk records (gem_history.hpp)
+        long long box_cap = 0;          // blocks the table has room for
+        Arena small;                    // device words: workgroups the last gem_costmap_mark_history culled
+    } history;
+    bool history_cull = true;           // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
     // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)
     struct Octree {
         static constexpr int kSlots = 4;
@@ -420,6 +431,13 @@ int compose_check(gem_handle* h, const gem_compose_params* p, const char* what);
 int compose_split(gem_handle* h, const gem_compose_params* p, bool want_road, bool want_obstacle, uint32_t tot[3], double* out_threshold);
 void octree_free(gem_handle* h);                // gem_capi_octree.cpp: the octree builder's arenas and the slots' streams (gem_destroy)
 void global_free(gem_handle* h);                // gem_capi_global.cpp: the submap stack's arenas (gem_destroy, gem_global_enable(0))
+void history_free(gem_handle* h);               // gem_capi_history.cpp: the history cloud's arenas (gem_destroy, gem_history_enable(0))
+// gem_capi_history.cpp, for gem_local_spill: whether n more records fit the stamp limit of a mark (GEM_ERR_INVALID otherwise), room for
+// them (the only step that allocates), and n records at d_src (device) appended on h->stream with their blocks' boxes recomputed
+int history_check_room(gem_handle* h, long long n, const char* what);
+int history_reserve(gem_handle* h, long long extra);
+int history_append_device(gem_handle* h, const void* d_src, long long n);
+int history_blocks_culled(gem_handle* h, long long* out);      // the last gem_costmap_mark_history's count, downloaded
 void costmap_free(gem_handle* h);               // gem_capi_costmap.cpp: every costmap of the handle and their shared arenas (gem_destroy)
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);

@@ -241,6 +241,8 @@ int gem_local_spill(gem_handle* h, const float current_position[2], const float 
     uint32_t n = 0;
     { HostXfer c{&n, small_word(h, kWordSpill), 4}; if ((rc = download_arrays(h, &c, 1, 0))) return rc; }
     if (n > (uint32_t)h->cells) return fail(h, GEM_ERR_HIP, "gem_local_spill: spill count out of range");
+    // the history cloud takes the same records (visualCloud_.push_back, EMg.cpp:750-760): its limit and its room before anything changes
+    if (h->history.enabled && ((rc = history_check_room(h, n, "gem_local_spill")) || (rc = history_reserve(h, n)))) return rc;
     // room for n more entries: compact a full log (growing it when less than half of it would be free), keep the table at most half full
     bool rebuild = false;
     if (lc.log_len + n > lc.log_cap) {
@@ -260,6 +262,7 @@ int gem_local_spill(gem_handle* h, const float current_position[2], const float 
     if (rebuild && (rc = rebuild_table(h, tcap))) return rc;
     a.out = log_at(h, lc.act) + lc.log_len;
     GEM_HIP(h, launch_local_spill(h->stream, a, h->cells, cnt, small_word(h, kWordSpill), true));
+    if (h->history.enabled && (rc = history_append_device(h, a.out, n))) return rc;     // from the log, before anything can compact it
     GEM_HIP(h, hipMemsetAsync(small_word(h, kWordNewKeys), 0, 4, h->stream));
     GEM_HIP(h, launch_local_insert(h->stream, log_at(h, lc.act), lc.log_len, n, table_of(h), small_word(h, kWordNewKeys)));
     uint32_t added = 0;

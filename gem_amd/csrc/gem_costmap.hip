@@ -82,8 +82,9 @@ struct CostVisualSrc {
     }
 };
 
+// the body of a mark workgroup: inputs [4096 blockIdx.x, 4096 (blockIdx.x + 1)) of src
 template <class Src, bool LDS>
-__global__ __launch_bounds__(kCostThreads) void k_cost_mark(Src src, CostGeom g, CostAccum out)
+__device__ __forceinline__ void cost_mark_block(const Src& src, const CostGeom& g, const CostAccum& out)
 {
     extern __shared__ uint32_t s_stamp[];                               // LDS form: [cells]
     __shared__ unsigned long long s_acc[4];
@@ -143,6 +144,44 @@ __global__ __launch_bounds__(kCostThreads) void k_cost_mark(Src src, CostGeom g,
         }
     if (threadIdx.x < 4 && s_acc[threadIdx.x] != ~0ull)
         __hip_atomic_fetch_min(out.acc + threadIdx.x, s_acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <class Src, bool LDS>
+__global__ __launch_bounds__(kCostThreads) void k_cost_mark(Src src, CostGeom g, CostAccum out)
+{
+    cost_mark_block<Src, LDS>(src, g, out);
+}
+
+// PointMapLayer over the history cloud (gem_history.hpp): workgroup b first reads the box of its 4096 records and leaves when no
+// record of the block can pass worldToMap -- before it touches LDS, the stamps or the bounds words.  The rule, in double:
+//   culled  <=>  !(max_x >= ox) || !(max_y >= oy) || !(min_x < ox + (sx + 1) * res) || !(min_y < oy + (sy + 1) * res)
+// It never drops an accepted record.  cost_cell accepts wx only if wx >= ox, which the box's max_x then satisfies too (floats widen
+// exactly), and if q = fl(fl(wx - ox) / res) < sx.  q is a double below the integer sx, so q <= sx (1 - u) with u = 2^-53, and the
+// two roundings give wx - ox < sx res (1 + u).  The limit is lim = fl(ox + fl((sx + 1) res)) >= ox + (sx + 1) res (1 - u) - u |lim|,
+// so wx < lim follows from u (2 sx + 1 + |lim| / res) <= 1: the extra cell absorbs every rounding as long as |lim| <= 2^51 res, which
+// the host checks before it hands a box table over (cost_cull_exact; otherwise the launch culls nothing).  NaN coordinates are not
+// in a box and are refused anyway; a block without a coordinate has the box {+inf, +inf, -inf, -inf} and fails the first test.
+struct CostCull {
+    const float4* box;                  // a box per workgroup {min_x, min_y, max_x, max_y}, or NULL: nothing is culled
+    uint32_t* culled;                   // culled workgroups of this launch (one vector atomic each)
+};
+
+__device__ __forceinline__ bool cost_block_culled(const CostGeom& g, const float4& b)
+{
+    const double lim_x = g.ox + (double)(g.sx + 1u) * g.res, lim_y = g.oy + (double)(g.sy + 1u) * g.res;
+    return !((double)b.z >= g.ox) || !((double)b.w >= g.oy) || !((double)b.x < lim_x) || !((double)b.y < lim_y);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kCostThreads) void k_cost_mark_history(CostPointsSrc src, CostGeom g, CostAccum out, CostCull c)
+{
+    if (c.box) {
+        if (cost_block_culled(g, c.box[blockIdx.x])) {                  // workgroup-uniform
+            if (threadIdx.x == 0) __hip_atomic_fetch_add(c.culled, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+    }
+    cost_mark_block<CostPointsSrc, LDS>(src, g, out);
 }
 
 // four cells per thread: a touched cell takes its verdict and its stamp goes back to 0; workgroup 0 publishes the bounds words and
@@ -228,6 +267,21 @@ static hipError_t launch_mark(hipStream_t st, const Src& src, long long items, c
 hipError_t launch_cost_mark_points(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out)
 {
     return launch_mark(st, CostPointsSrc{a}, (long long)a.n, g, out);
+}
+
+hipError_t launch_cost_mark_history(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out, const float4* box,
+                                    uint32_t* culled)
+{
+    const long long nb = cost_mark_blocks((long long)a.n);
+    if (nb <= 0) return hipSuccess;
+    const CostPointsSrc src{a};
+    const CostCull c{cost_cull_exact(g) ? box : nullptr, culled};
+    const uint32_t cells = g.sx * g.sy;
+    if (cells <= kCostLdsCells)
+        hipLaunchKernelGGL((k_cost_mark_history<true>), dim3((unsigned)nb), dim3(kCostThreads), cells * sizeof(uint32_t), st, src, g, out, c);
+    else
+        hipLaunchKernelGGL((k_cost_mark_history<false>), dim3((unsigned)nb), dim3(kCostThreads), 0, st, src, g, out, c);
+    return hipGetLastError();
 }
 
 hipError_t launch_cost_mark_visual(hipStream_t st, const CostGeom& g, const CostVisualArgs& a, CostAccum out)

@@ -60,8 +60,20 @@ inline bool cost_key_decode(unsigned long long k, bool inverted, double* out)
 
 inline long long cost_mark_blocks(long long items) { return (items + kCostChunk - 1) / kCostChunk; }
 
+// whether the culling rule of k_cost_mark_history is exact for this geometry: the far limits ox + (sx + 1) res are fine enough
+// in double that the extra cell covers the roundings of worldToMap (the argument is next to the rule in gem_costmap.hip)
+inline bool cost_cull_exact(const CostGeom& g)
+{
+    const double lim_x = g.ox + (double)(g.sx + 1u) * g.res, lim_y = g.oy + (double)(g.sy + 1u) * g.res, span = g.res * 2251799813685248.0;   // 2^51
+    return __builtin_fabs(lim_x) <= span && __builtin_fabs(lim_y) <= span;
+}
+
 hipError_t launch_cost_mark_points(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out);
 hipError_t launch_cost_mark_visual(hipStream_t st, const CostGeom& g, const CostVisualArgs& a, CostAccum out);
+// launch_cost_mark_points (count NULL, base 0) with a box {min_x, min_y, max_x, max_y} per workgroup: a workgroup whose box lies off
+// the map leaves at once and adds one to *culled (gem_costmap.hip states the rule).  box NULL: nothing is culled.
+hipError_t launch_cost_mark_history(hipStream_t st, const CostGeom& g, const CostPointsArgs& a, CostAccum out, const float4* box,
+                                    uint32_t* culled);
 // stamps -> grid; acc -> published[4] (the words as they are), acc reset to all-ones
 hipError_t launch_cost_resolve(hipStream_t st, uint32_t cells, uint32_t* stamps, unsigned char* grid, unsigned long long* acc,
                                unsigned long long* published);

@@ -575,6 +575,51 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------
+// visualCloud_ of ElevationMapping on the device (gem_history_*): while a History lives, LocalMap::spill appends what it selects
+// (ElevationMapping.cpp:750-760), resetFromGlobal is visualCloud_.clear() plus the "Visual step" of updateGlobalMap (:788, :894-897),
+// exportCloud(true) is visualPointMap's visualCloud_ + grid_pc (:524-526), and Costmap::markHistory marks it where it lies.
+// ---------------------------------------------------------------------------------------------
+class History {
+public:
+    // capacity: initial records (grows on demand)
+    explicit History(ElevationMap& map, long long capacity = 1 << 20) : map_(map)
+    { map_.check(gem_history_enable(map_.handle(), capacity), "gem_history_enable"); }
+    ~History() { gem_history_enable(map_.handle(), 0); }
+    History(const History&) = delete;
+    History& operator=(const History&) = delete;
+
+    // records of the caller's behind the history (a saved map loaded again)
+    void append(const std::vector<PointXYZRGBICT>& cloud)
+    {
+        map_.check(gem_history_append(map_.handle(), cloud.empty() ? nullptr : cloud.data(), static_cast<long long>(cloud.size())),
+                   "gem_history_append");
+    }
+    // ... in device memory: only enqueued, the buffer is untouched until ElevationMap::synchronize
+    void appendDevice(const void* d_points, long long n)
+    { map_.check(gem_history_append_device(map_.handle(), d_points, n), "gem_history_append_device"); }
+    void resetFromGlobal() { map_.check(gem_history_reset_from_global(map_.handle()), "gem_history_reset_from_global"); }
+    void clear() { map_.check(gem_history_clear(map_.handle()), "gem_history_clear"); }
+    long long size() const
+    {
+        long long n = 0;
+        map_.check(gem_history_size(map_.handle(), &n), "gem_history_size");
+        return n;
+    }
+    // the history (savingMap); withGridCloud: followed by the last capture's grid cloud (visualPointMap)
+    std::vector<PointXYZRGBICT> exportCloud(bool withGridCloud = false)
+    {
+        long long n = 0;
+        map_.check(gem_history_export(map_.handle(), withGridCloud ? 1 : 0, nullptr, 0, &n), "gem_history_export");
+        std::vector<PointXYZRGBICT> v(static_cast<size_t>(n));
+        map_.check(gem_history_export(map_.handle(), withGridCloud ? 1 : 0, v.empty() ? nullptr : v.data(), n, &n), "gem_history_export");
+        return v;
+    }
+
+private:
+    ElevationMap& map_;
+};
+
+// ---------------------------------------------------------------------------------------------
 // A layer costmap on the device (gem_costmap_*): the updateBounds bodies of the reference's two costmap_2d plugins
 // (layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87) as marking passes, Costmap2D::updateOrigin as the rolling
 // step, the two updateCosts rules and a window read-back.  costmap_2d itself is restated in gem_hip.h, unverified against the
@@ -624,6 +669,9 @@ public:
     { map_.check(gem_costmap_mark_grid_cloud(map_.handle(), id_, traversThresh, ptr(bounds)), "gem_costmap_mark_grid_cloud"); }
     void markGlobal(int index, double traversThresh, Bounds* bounds = nullptr)
     { map_.check(gem_costmap_mark_global(map_.handle(), id_, index, traversThresh, ptr(bounds)), "gem_costmap_mark_global"); }
+    // ... over the history cloud (gem::History) where it lies, as one input; markGridCloud after it is visualCloud_ + grid_pc
+    void markHistory(double traversThresh, Bounds* bounds = nullptr)
+    { map_.check(gem_costmap_mark_history(map_.handle(), id_, traversThresh, ptr(bounds)), "gem_costmap_mark_history"); }
     // ElevationMapLayer::updateBounds' loop over the last capture standing for visualMap_
     void markVisual(double traversThresh, Bounds* bounds = nullptr)
     { map_.check(gem_costmap_mark_visual(map_.handle(), id_, traversThresh, ptr(bounds)), "gem_costmap_mark_visual"); }

@@ -728,6 +728,9 @@ int  gem_local_compose_octrees(gem_handle* h, const gem_compose_params* p, const
                                const gem_octree_params* obstacle_params, int out_counts[3], double* out_threshold, gem_octree_stats stats[2]);
 int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_t* out_bytes);
 
+/* ---- the history cloud (visualCloud_): gem_history_*, gem_costmap_mark_history ------------------------------------------------ */
+#include "gem_hip_history.h"
+
 #ifdef __cplusplus
 }
 #endif
