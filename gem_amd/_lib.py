@@ -23,6 +23,8 @@ COST_FREE_SPACE, COST_LETHAL_OBSTACLE, COST_NO_INFORMATION = 0, 254, 255
 COSTMAP_OVERWRITE, COSTMAP_MAX = 0, 1
 VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTENSITY = range(5)
 DEPTH_U16, DEPTH_F32 = 0, 1
+FOOTPRINT_MAX_VERTICES = 32
+FOOTPRINT_INSCRIBED_LETHAL, FOOTPRINT_SUM = 1, 2
 COLOR_NONE, COLOR_BGR8, COLOR_RGB8 = range(3)
 
 
@@ -63,6 +65,11 @@ class CostmapConfig(C.Structure):
     """gem_costmap_config: a costmap's geometry and the value of a cell nothing has written."""
     _fields_ = [("size_x", C.c_uint), ("size_y", C.c_uint), ("resolution", c_double), ("origin_x", c_double), ("origin_y", c_double),
                 ("default_value", C.c_ubyte)]
+
+
+class FootprintPose(C.Structure):
+    """gem_footprint_pose: a pose with the cosine and sine of its heading (the kernels hold no transcendental)."""
+    _fields_ = [("x", c_double), ("y", c_double), ("cos_th", c_double), ("sin_th", c_double)]
 
 
 class RejectFilter(C.Structure):
@@ -205,6 +212,14 @@ HISTORY_SIGNATURES = {
     "gem_history_export": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_longlong)]),
     "gem_costmap_mark_history": (c_int, [c_void_p, c_int, c_double, POINTER(c_double)]),
 }
+# include/gem_hip_footprint.h (footprints on the costmap; gem_hip.h includes it)
+FOOTPRINT_SIGNATURES = {
+    "gem_costmap_clear_footprint": (c_int, [c_void_p, c_int, POINTER(FootprintPose), POINTER(c_double), c_int, POINTER(c_double), POINTER(c_int)]),
+    "gem_costmap_footprint_cost": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_double), c_int, c_int, c_void_p]),
+    "gem_costmap_footprint_cost_device": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_double), c_int, c_int, c_void_p]),
+    "gem_costmap_score_trajectories": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_int, POINTER(c_double), c_int, c_int, c_void_p, c_void_p]),
+    "gem_costmap_score_trajectories_device": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_int, POINTER(c_double), c_int, c_int, c_void_p, c_void_p]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -230,7 +245,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **DEBUG_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

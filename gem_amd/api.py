@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes as C
+import math
 import sys
 import weakref
 from dataclasses import dataclass, field
@@ -1224,6 +1225,92 @@ class Costmap:
         if v.shape != (w[3] - w[1], w[2] - w[0]):
             raise ValueError(f"expected a {(w[3] - w[1], w[2] - w[0])} array, got {v.shape}")
         self._call("gem_costmap_write", *w, v.ctypes.data_as(C.c_void_p) if v.size else None, max(w[2] - w[0], 0))
+
+    # -- footprints (gem_hip_footprint.h) ---------------------------------------------------------------------------------------------
+    @staticmethod
+    def _spec(spec):
+        """[n, 2] footprint vertices -> (keepalive array, double*, n)"""
+        v = np.ascontiguousarray(spec, np.float64).reshape(-1, 2)
+        return v, (v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None), int(v.shape[0])
+
+    @staticmethod
+    def poses_from_yaw(poses) -> np.ndarray:
+        """[n, 3] (x, y, theta) -> [n, 4] (x, y, cos, sin) with math.cos / math.sin element by element: the host's libm, as the C++
+        facade's std::cos / std::sin"""
+        p = np.asarray(poses, np.float64).reshape(-1, 3)
+        out = np.empty((p.shape[0], 4), np.float64)
+        out[:, :2] = p[:, :2]
+        out[:, 2] = [math.cos(float(t)) for t in p[:, 2]]
+        out[:, 3] = [math.sin(float(t)) for t in p[:, 2]]
+        return out
+
+    def _poses(self, poses):
+        """host [n, 3] (x, y, theta) or [n, 4] (x, y, cos, sin), or a contiguous float64 device tensor [n, 4] -> (keepalive, void*, n,
+        on the device)"""
+        if _is_device_tensor(poses):
+            import torch
+            if poses.dtype != torch.float64 or not poses.is_contiguous() or poses.dim() != 2 or poses.shape[1] != 4:
+                raise ValueError("device poses must be a contiguous float64 tensor [n, 4]: x, y, cos, sin")
+            n = int(poses.shape[0])
+            return poses, (C.c_void_p(poses.data_ptr()) if n else None), n, True
+        p = np.asarray(poses, np.float64)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("poses must be [n, 3] (x, y, theta) or [n, 4] (x, y, cos, sin)")
+        p = self.poses_from_yaw(p) if p.shape[1] == 3 else np.ascontiguousarray(p)
+        return p, (p.ctypes.data_as(C.c_void_p) if p.size else None), int(p.shape[0]), False
+
+    def clear_footprint(self, pose, spec, bounds=None):
+        """updateFootprint + setConvexPolygonCost(FREE_SPACE): pose = (x, y, theta) or (x, y, cos, sin), spec = [n, 2] vertices in
+        the robot's frame.  Returns (ok, bounds): every transformed vertex is touched into bounds (None stays None); the call only
+        enqueues."""
+        p = [float(v) for v in pose]
+        if len(p) == 3:
+            p = [p[0], p[1], math.cos(p[2]), math.sin(p[2])]
+        fp = _lib.FootprintPose(*p)
+        keep, ps, n = self._spec(spec)
+        b, ok = self._bounds(bounds), C.c_int(-1)
+        self._call("gem_costmap_clear_footprint", C.byref(fp), ps, n, b, C.byref(ok))
+        return bool(ok.value), (None if b is None else list(b))
+
+    def footprint_cost(self, poses, spec, flags: int = 0):
+        """CostmapModel::footprintCost of every pose: -3 off the map, -2 unknown, -1 lethal, else the largest cost on the outline.
+        Host poses give an int32 numpy array (the call waits); a device tensor gives an int32 device tensor, only enqueued, held
+        with the poses until the map is synchronised."""
+        keep, pp, n, dev = self._poses(poses)
+        ks, ps, nv = self._spec(spec)
+        if dev:
+            import torch
+            out = torch.empty((n,), dtype=torch.int32, device=poses.device)
+            self.map._hold(poses, out)
+            self._call("gem_costmap_footprint_cost_device", pp, n, ps, nv, int(flags), C.c_void_p(out.data_ptr()) if n else None)
+            return out
+        out = np.zeros(n, np.int32)
+        self._call("gem_costmap_footprint_cost", pp, n, ps, nv, int(flags), out.ctypes.data_as(C.c_void_p) if n else None)
+        return out
+
+    def score_trajectories(self, poses, poses_per_traj: int, spec, flags: int = 0, pose_costs: bool = False):
+        """ObstacleCostFunction::scoreTrajectory's loop over trajectories of poses_per_traj consecutive poses each: the first negative
+        pose cost, else the maximum (FOOTPRINT_SUM: the sum).  Returns the trajectory costs, or (trajectory costs, pose costs) with
+        pose_costs; numpy for host poses, device tensors (only enqueued) for a device tensor."""
+        keep, pp, n, dev = self._poses(poses)
+        T = int(poses_per_traj)
+        if T < 1 or n % T:
+            raise ValueError("the poses are not a whole number of trajectories")
+        nt = n // T
+        ks, ps, nv = self._spec(spec)
+        if dev:
+            import torch
+            traj = torch.empty((nt,), dtype=torch.int32, device=poses.device)
+            each = torch.empty((n,), dtype=torch.int32, device=poses.device) if pose_costs else None
+            self.map._hold(poses, traj, each)
+            self._call("gem_costmap_score_trajectories_device", pp, nt, T, ps, nv, int(flags),
+                       C.c_void_p(each.data_ptr()) if pose_costs and n else None, C.c_void_p(traj.data_ptr()) if nt else None)
+        else:
+            traj = np.zeros(nt, np.int32)
+            each = np.zeros(n, np.int32) if pose_costs else None
+            self._call("gem_costmap_score_trajectories", pp, nt, T, ps, nv, int(flags),
+                       each.ctypes.data_as(C.c_void_p) if pose_costs and n else None, traj.ctypes.data_as(C.c_void_p) if nt else None)
+        return (traj, each) if pose_costs else traj
 
 
 class RobotMotionMapUpdater:

@@ -132,7 +132,7 @@ void costmap_free(gem_handle* h)
     auto& c = h->costmap;
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& m : c.map) free_map(m);
-    for (Arena* a : {&c.small, &c.in, &c.win}) {
+    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

@@ -302,6 +302,7 @@ struct gem_handle {
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
         Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
         std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
+        Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping
     struct History {

@@ -16,22 +16,7 @@
 // order-preserving 64-bit keys under integer min.  Only vector stores and atomics write memory.
 #include "gem_costmap.hpp"
 
-#include <float.h>
-
 namespace gem {
-
-// Costmap2D::worldToMap with the contract's stricter failure: non-finite coordinates and quotients beyond int fail
-__device__ __forceinline__ bool cost_cell(const CostGeom& g, double wx, double wy, uint32_t& cell)
-{
-    if (!(fabs(wx) <= DBL_MAX && fabs(wy) <= DBL_MAX)) return false;
-    if (wx < g.ox || wy < g.oy) return false;
-    const double qx = (wx - g.ox) / g.res, qy = (wy - g.oy) / g.res;
-    if (!(qx < 2147483648.0 && qy < 2147483648.0)) return false;
-    const uint32_t mx = (uint32_t)(int)qx, my = (uint32_t)(int)qy;
-    if (!(mx < g.sx && my < g.sy)) return false;
-    cell = my * g.sx + mx;
-    return true;
-}
 
 // doubles as unsigned integers in the same order (-0 below +0)
 __device__ __forceinline__ unsigned long long cost_key(double v)

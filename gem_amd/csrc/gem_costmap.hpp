@@ -10,6 +10,7 @@
 #include "gem_local.hpp"
 
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <stdint.h>
 
 namespace gem {
@@ -25,6 +26,26 @@ struct CostGeom {
     double ox, oy, res;
     uint32_t sx, sy;
 };
+
+// Costmap2D::worldToMap with the contract's stricter failure: non-finite coordinates and quotients beyond int fail.  Shared by the
+// mark kernels, the footprint kernels (gem_footprint.hip) and the host side of gem_costmap_clear_footprint.
+__host__ __device__ __forceinline__ bool cost_cell_xy(const CostGeom& g, double wx, double wy, uint32_t& mx, uint32_t& my)
+{
+    if (!(__builtin_fabs(wx) <= DBL_MAX && __builtin_fabs(wy) <= DBL_MAX)) return false;
+    if (wx < g.ox || wy < g.oy) return false;
+    const double qx = (wx - g.ox) / g.res, qy = (wy - g.oy) / g.res;
+    if (!(qx < 2147483648.0 && qy < 2147483648.0)) return false;
+    mx = (uint32_t)(int)qx; my = (uint32_t)(int)qy;
+    return mx < g.sx && my < g.sy;
+}
+
+__host__ __device__ __forceinline__ bool cost_cell(const CostGeom& g, double wx, double wy, uint32_t& cell)
+{
+    uint32_t mx, my;
+    if (!cost_cell_xy(g, wx, wy, mx, my)) return false;
+    cell = my * g.sx + mx;
+    return true;
+}
 
 // what a mark launch accumulates into: a stamp per cell, 2 * (input index + 1) + lethal, 0 = untouched, resolved by integer max; and
 // four 64-bit words, the order-preserving keys of min px, min py, ~max px, ~max py over the accepted inputs, all reduced by integer

@@ -623,8 +623,19 @@ private:
 // A layer costmap on the device (gem_costmap_*): the updateBounds bodies of the reference's two costmap_2d plugins
 // (layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87) as marking passes, Costmap2D::updateOrigin as the rolling
 // step, the two updateCosts rules and a window read-back.  costmap_2d itself is restated in gem_hip.h, unverified against the
-// library.  Extra bounds, the footprint, enabled_ and the layered costmap stay with the caller, see INTEGRATION.md.
+// library.  Extra bounds, enabled_ and the layered costmap stay with the caller, see INTEGRATION.md.  The footprint calls
+// (gem_hip_footprint.h) clear the robot's outline out of a layer and answer base_local_planner's footprintCost in batches.
 // ---------------------------------------------------------------------------------------------
+// a pose as the footprint calls take it: the heading as its cosine and sine (the kernels hold no transcendental)
+struct FootprintPose : gem_footprint_pose {
+    FootprintPose() : gem_footprint_pose{0.0, 0.0, 1.0, 0.0} {}
+    FootprintPose(double x_, double y_, double cosTheta, double sinTheta) : gem_footprint_pose{x_, y_, cosTheta, sinTheta} {}
+    static FootprintPose fromYaw(double x_, double y_, double theta) { return FootprintPose(x_, y_, std::cos(theta), std::sin(theta)); }
+};
+static_assert(sizeof(FootprintPose) == sizeof(gem_footprint_pose), "an array of FootprintPose is an array of gem_footprint_pose");
+// a footprint specification: the polygon's vertices in the robot's frame, at most GEM_FOOTPRINT_MAX_VERTICES
+struct FootprintPoint { double x, y; };
+
 class Costmap {
 public:
     static constexpr unsigned char FREE_SPACE = 0, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
@@ -696,9 +707,45 @@ public:
         map_.check(gem_costmap_write(map_.handle(), id_, minI, minJ, maxI, maxJ, values.empty() ? nullptr : values.data(), w), "gem_costmap_write");
     }
 
+    // updateFootprint + setConvexPolygonCost(FREE_SPACE) of ObstacleLayer: every transformed vertex is touched into bounds, the
+    // polygon's cells become FREE_SPACE.  Only enqueued.  False (nothing written) when a vertex is off the map.
+    bool clearFootprint(const FootprintPose& pose, const std::vector<FootprintPoint>& spec, Bounds* bounds = nullptr)
+    {
+        int ok = 0;
+        map_.check(gem_costmap_clear_footprint(map_.handle(), id_, &pose, xy(spec), static_cast<int>(spec.size()), ptr(bounds), &ok),
+                   "gem_costmap_clear_footprint");
+        return ok != 0;
+    }
+    // CostmapModel::footprintCost of every pose: -3 off the map, -2 unknown, -1 lethal, else the largest cost on the outline
+    std::vector<int> footprintCost(const std::vector<FootprintPose>& poses, const std::vector<FootprintPoint>& spec, int flags = 0) const
+    {
+        std::vector<int> cost(poses.size());
+        map_.check(gem_costmap_footprint_cost(map_.handle(), id_, poses.empty() ? nullptr : poses.data(), static_cast<long long>(poses.size()),
+                                              xy(spec), static_cast<int>(spec.size()), flags, cost.empty() ? nullptr : cost.data()),
+                   "gem_costmap_footprint_cost");
+        return cost;
+    }
+    // trajectories of posesPerTrajectory consecutive poses: the first negative pose cost, else the maximum (GEM_FOOTPRINT_SUM: the
+    // sum), as ObstacleCostFunction::scoreTrajectory; poseCosts, if given, receives every pose's footprintCost
+    std::vector<int> scoreTrajectories(const std::vector<FootprintPose>& poses, int posesPerTrajectory, const std::vector<FootprintPoint>& spec,
+                                       int flags = 0, std::vector<int>* poseCosts = nullptr) const
+    {
+        if (posesPerTrajectory < 1 || poses.size() % static_cast<size_t>(posesPerTrajectory))
+            throw Error(GEM_ERR_INVALID, "Costmap::scoreTrajectories: the poses are not a whole number of trajectories");
+        std::vector<int> cost(poses.size() / static_cast<size_t>(posesPerTrajectory));
+        if (poseCosts) poseCosts->assign(poses.size(), 0);
+        map_.check(gem_costmap_score_trajectories(map_.handle(), id_, poses.empty() ? nullptr : poses.data(), static_cast<long long>(cost.size()),
+                                                  posesPerTrajectory, xy(spec), static_cast<int>(spec.size()), flags,
+                                                  poseCosts && !poseCosts->empty() ? poseCosts->data() : nullptr, cost.empty() ? nullptr : cost.data()),
+                   "gem_costmap_score_trajectories");
+        return cost;
+    }
+
 private:
     static_assert(sizeof(Bounds) == 4 * sizeof(double), "bounds are four packed doubles");
+    static_assert(sizeof(FootprintPoint) == 2 * sizeof(double), "a spec is packed pairs of doubles");
     static double* ptr(Bounds* b) { return b ? &b->min_x : nullptr; }
+    static const double* xy(const std::vector<FootprintPoint>& spec) { return spec.empty() ? nullptr : &spec.front().x; }
     ElevationMap& map_;
     int id_ = -1;
 };

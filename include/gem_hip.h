@@ -629,8 +629,9 @@ int  gem_global_count(gem_handle* h, int* out_submaps);
  *   gem_costmap_geometry           the configuration with the origin after rolling.
  * bounds = {min_x, min_y, max_x, max_y}, in / out, merged as touch() does; they compare as values, not bits (with std::min a tie
  * between -0 and +0 depends on the order).  With bounds NULL a mark only enqueues on the handle's stream and nothing waits.
- * Left with the caller: useExtraBounds, updateFootprint / setConvexPolygonCost (four footprint points and a polygon fill), enabled_,
- * the subscriptions and the layered costmap itself (master_grid.setCost from gem_costmap_read).  Every entry takes the handle's lock.
+ * Left with the caller: useExtraBounds, enabled_, the subscriptions and the layered costmap itself (master_grid.setCost from
+ * gem_costmap_read); updateFootprint / setConvexPolygonCost is gem_costmap_clear_footprint (gem_hip_footprint.h).  Every entry takes
+ * the handle's lock.
  * GEM_ERR_INVALID, nothing changed: a bad id; a zero size (or more than 2^30 cells), a resolution not finite and positive, a
  * non-finite origin or threshold; n < 0 or n above 2^31 - 2 (mark_global: the records of the call together); a window outside the
  * map; mark_grid_cloud or mark_visual without a capture; mark_global without an enabled stack or with an index out of range; an
@@ -730,6 +731,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 
 /* ---- the history cloud (visualCloud_): gem_history_*, gem_costmap_mark_history ------------------------------------------------ */
 #include "gem_hip_history.h"
+
+/* ---- footprints on the costmap: gem_costmap_clear_footprint, gem_costmap_footprint_cost*, gem_costmap_score_trajectories* ------- */
+#include "gem_hip_footprint.h"
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,12 @@
 //                    with scattered points) into a real ColorOcTree and compares the stream byte for byte; it settles the five points
 //                    include/gem_hip.h lists as not verified (prune on value only and the pruned node's colour, the host's exp, no
 //                    contraction in the blend, the uint8_t cast, the empty tree)
+//   foot gem_costmap_clear_footprint / gem_costmap_footprint_cost restate costmap_2d::transformFootprint (footprint.cpp),
+//                    Costmap2D::setConvexPolygonCost (polygonOutlineCells + convexFillCells over the line iterator) and
+//                    base_local_planner::CostmapModel::footprintCost (include/gem_hip_footprint.h; tests/footprint_ref.py restates the
+//                    same contract in numpy).  The row clears seeded poses of the launch files' rectangle and of a 16-gon out of a real
+//                    Costmap2D and scores seeded poses with a real CostmapModel on a noise grid, and compares every byte and every cost.
+//                    The poses' cosines and sines are this host's std::cos / std::sin, as transformFootprint's are
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -41,8 +47,8 @@
 //       -L/opt/ros/$ROS_DISTRO/lib -lgrid_map_core -lcostmap_2d -llayers -lroscpp -lrosconsole -ltf2_ros $(pkg-config --libs opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) -o ros_selfcheck && ./ros_selfcheck [seed]
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
-// there, against the library's public headers as documented, and has not been through a compiler; neither has the octo row
-// (add -loctomap -loctomath to the link line).
+// there, against the library's public headers as documented, and has not been through a compiler; neither have the octo row
+// (add -loctomap -loctomath to the link line) and the foot row (add -lbase_local_planner).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -76,6 +82,9 @@
 #include <costmap_2d/cost_values.h>
 #include <costmap_2d/costmap_2d.h>
 #include <costmap_2d/costmap_layer.h>
+#include <costmap_2d/footprint.h>
+#include <base_local_planner/costmap_model.h>
+#include <geometry_msgs/Point.h>
 #include <octomap/ColorOcTree.h>
 #include <sstream>
 
@@ -669,6 +678,69 @@ int check_cost(uint32_t seed)
     return 0;
 }
 
+// ---- foot ----------------------------------------------------------------------------------------------------------------------
+// Seeded poses over the map's box widened by a tenth (so vertices and centres fall off it), two footprints: setConvexPolygonCost on
+// a real Costmap2D against gem_costmap_clear_footprint, CostmapModel::footprintCost against gem_costmap_footprint_cost.
+int check_foot(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    const unsigned sx = 130, sy = 90;
+    const double res = 0.05, ox = -3.1, oy = 2.7;
+    costmap_2d::Costmap2D real(sx, sy, res, ox, oy, costmap_2d::NO_INFORMATION);
+    gem_costmap_config cc{};
+    cc.size_x = sx; cc.size_y = sy; cc.resolution = res; cc.origin_x = ox; cc.origin_y = oy; cc.default_value = costmap_2d::NO_INFORMATION;
+    int id = -1;
+    CHECK_GEM(gem_costmap_create(h, &cc, &id));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    std::vector<std::vector<double>> specs(2);
+    specs[0] = {-0.64, -0.40, -0.64, 0.40, 0.64, 0.40, 0.64, -0.40};    // costmap_common_params_local.yaml:8
+    for (int k = 0; k < 16; ++k) { specs[1].push_back(0.9 * std::cos(2 * M_PI * k / 16)); specs[1].push_back(0.9 * std::sin(2 * M_PI * k / 16)); }
+    for (const std::vector<double>& spec : specs) {
+        const int nv = (int)spec.size() / 2;
+        std::vector<geometry_msgs::Point> fp(nv), oriented;
+        for (int i = 0; i < nv; ++i) { fp[i].x = spec[2 * i]; fp[i].y = spec[2 * i + 1]; }
+        // the noise grid of the tests: 0 .. 252, 0.4 % lethal, 0.4 % unknown, a few inscribed
+        for (size_t i = 0; i < (size_t)sx * sy; ++i) {
+            const double v = u(rng);
+            real.getCharMap()[i] = v < 0.004 ? 254 : v < 0.008 ? 255 : v < 0.009 ? 253 : (unsigned char)(rng() % 253);
+        }
+        CHECK_GEM(gem_costmap_write(h, id, 0, 0, (int)sx, (int)sy, real.getCharMap(), sx));
+        base_local_planner::CostmapModel model(real);
+        const int n = 4000;
+        std::vector<gem_footprint_pose> poses(n);
+        std::vector<int> got(n);
+        std::vector<double> want(n);
+        for (int k = 0; k < n; ++k) {
+            const double x = ox + (u(rng) * 1.2 - 0.1) * sx * res, y = oy + (u(rng) * 1.2 - 0.1) * sy * res, th = (u(rng) * 2 - 1) * M_PI;
+            poses[k] = gem_footprint_pose{x, y, std::cos(th), std::sin(th)};
+            costmap_2d::transformFootprint(x, y, th, fp, oriented);
+            geometry_msgs::Point at; at.x = x; at.y = y;
+            want[k] = model.footprintCost(at, oriented, 0.0, 0.0);
+        }
+        CHECK_GEM(gem_costmap_footprint_cost(h, id, poses.data(), n, spec.data(), nv, 0, got.data()));
+        for (int k = 0; k < n; ++k) if ((double)got[k] != want[k]) report("foot: footprintCost", k, got[k], want[k]);
+        // clearing: updateFootprint's transform and touch, then setConvexPolygonCost
+        for (int k = 0; k < 200; ++k) {
+            oriented.resize(nv);
+            for (int i = 0; i < nv; ++i) {                                // transformFootprint's lines, from the pose's own cosine and sine
+                oriented[i].x = poses[k].x + (fp[i].x * poses[k].cos_th - fp[i].y * poses[k].sin_th);
+                oriented[i].y = poses[k].y + (fp[i].x * poses[k].sin_th + fp[i].y * poses[k].cos_th);
+            }
+            const bool want_ok = real.setConvexPolygonCost(oriented, costmap_2d::FREE_SPACE);
+            int ok = -1;
+            CHECK_GEM(gem_costmap_clear_footprint(h, id, &poses[k], spec.data(), nv, nullptr, &ok));
+            if ((ok != 0) != want_ok) report("foot: setConvexPolygonCost's return", k, ok, want_ok);
+            if (!same_costmap(h, id, real, "foot: setConvexPolygonCost")) break;
+        }
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -749,8 +821,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_sor(seed + 4u);
     if (rc == 0) rc = check_cost(seed + 5u);
     if (rc == 0) rc = check_octo(seed + 6u);
+    if (rc == 0) rc = check_foot(seed + 7u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all seven rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d and octomap (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / octomap does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all eight rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
     return 0;
 }
