@@ -71,6 +71,19 @@ template <int W> __device__ __forceinline__ uint32_t rec_load_cell(const uint4* 
     return reinterpret_cast<const uint32_t*>(rec)[(size_t)i * W + 2];
 }
 
+// k_frame's binning waves raise their issue priority (s_setprio) behind the issue of the load of their points.  Eight workgroups
+// share a CU and a SIMD issues for the highest level first; the binning blocks come last in block order, a binning wave is ~130
+// vector instructions and two memory round trips, and at the tiles' level it waited its turn behind tile waves most of which have a
+// microsecond of slack.  Measured (profiles/HISTORY.md, last section): a binning block's mean life 2.6 -> 2.0 us, the last one's end
+// 4.8 -> 3.8 us of a stamped launch, the C2 step 5.95 -> 5.75 us.  Levels for the tiles' waves by their record count were measured
+// as well: alone no gain, with this one inside the noise, left out.  (Only the order of the levels counts: any value above the
+// tiles' 0 is the same.)  The lean form only (bin_unit_lean): the same line in bin_unit cost the generic k_frame four more scalar
+// spills (10 -> 14).
+#ifndef GEM_FRAME_BIN_PRIO
+#define GEM_FRAME_BIN_PRIO 3
+#endif
+constexpr int kFrameBinPrio = GEM_FRAME_BIN_PRIO;                       // (build define: 0 = the binning waves at the tiles' level, for A/B builds)
+
 // one unit = 64 consecutive points, binned by one wave.
 // BUCKET (k_frame, one sweep, no colours): no descriptor words and no touched stamps.  The leader of each tile group reserves a range
 // of the tile's bucket with ONE returning atomic on bcount[tile] and the group's lanes store their records there, the point index
@@ -240,6 +253,7 @@ __device__ __forceinline__ void bin_unit_lean(const FrameLeanBin& a, int unit)
     if (unit >= a.B) return;                               // whole wave leaves together
     const uint32_t i = (uint32_t)unit * 64u + (uint32_t)lane_id();
     const float4 p = a.xyzi[i < a.n ? i : 0u];
+    if constexpr (kFrameBinPrio != 0) __builtin_amdgcn_s_setprio(kFrameBinPrio);     // (above the tiles' waves, behind the issue of the load)
     // the frame's constants arrive while the load of the points is in flight: one batch, no scalar load is waited for behind it
     FrameLeanBin f = a;
     GEM_PIN(f.keep_sentinel); GEM_PIN(f.tile_bits); GEM_PIN(f.tiles_per_row); GEM_PIN(f.filter_on); GEM_PIN_PTR(f.bkt); GEM_PIN_PTR(f.bcount);

@@ -35,6 +35,17 @@ n = lib.gem_debug_fuse_stamps(m._h, 0, buf.ctypes.data_as(C.c_void_p), ROWS)
 st = buf[:n].astype(np.int64)
 T = ((wl.length + 15) // 16) ** 2
 tiles, bins = st[:T], st[T:]
+# records per tile of the sweep the stamped launch fuses, from the CPU oracle's projection (the C2 map does not move: a tile's row of
+# stamps is its circular-buffer tile, which is its geographic one)
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent / "oracle"))
+import oracle
+oracle.build()
+_c = wl.clouds[n_sw - 2]
+_idx = np.asarray(oracle.OracleMap(wl.length, wl.resolution).process_points(wl.frames[n_sw - 2], _c[:, 0], _c[:, 1], _c[:, 2])["index"])
+_idx = _idx[_idx >= 0]
+_tpr = (wl.length + 15) // 16
+nrec = np.bincount(((_idx // wl.length) >> 4) * _tpr + ((_idx % wl.length) >> 4), minlength=T)[:T]
+nrec = nrec[tiles[:, 15] > 0]
 tiles = tiles[tiles[:, 15] > 0]; bins = bins[bins[:, 15] > 0]
 blk_t = tiles[:, 15] - 1; blk_b = bins[:, 15] - 1
 nst = (tiles[:, :12] > 0).sum(1)
@@ -68,6 +79,16 @@ if full.any():
     late = np.argsort(-te)[:5]
     for i in late:
         print(f"  last to end: block {blk_t[i]:5d} start {ts[i]:6.2f} us end {te[i]:6.2f} us total {dur[i]:6d} cycles ({dur[i] / max(1e-9, (te[i] - ts[i])) / 1000:.2f} GHz)")
+if full.any():
+    # the tiles the launch waits for: more than kFrameSpec = 256 records (a second, dependent DMA round trip)
+    SPEC, MID = 256, 64
+    print(f"weight classes (oracle): {int((nrec > SPEC).sum())} tiles above {SPEC} records, {int(((nrec > MID) & (nrec <= SPEC)).sum())} with {MID + 1}..{SPEC}, "
+          f"{int(((nrec > 0) & (nrec <= MID)).sum())} with 1..{MID}; largest {int(nrec.max())}")
+    for label, sel in ((f"tiles above {SPEC} records", full & (nrec > SPEC)), (f"tiles of at most {MID} records", full & (nrec > 0) & (nrec <= MID))):
+        if sel.any():
+            dh = np.diff(tiles[sel, :NS], axis=1)
+            print(f"{label}: {int(sel.sum())} | mean cycles per phase: {dict(zip(names, dh.mean(0).astype(int).tolist()))} | mean total {int(dur[sel].mean())} "
+                  f"| mean life {(te[sel] - ts[sel]).mean():.2f} us | last end {te[sel].max():.2f} us")
 print("tiles that left early (no record) or took another path:", int((nst < NS).sum()), "mean life", int(dur[nst < NS].mean()) if (nst < NS).any() else 0)
 if len(bins):
     print(f"binning blocks: mean life {(be - bs).mean():.2f} us, max {(be - bs).max():.2f} | first start {bs.min():.2f} us, last start {bs.max():.2f} us")
