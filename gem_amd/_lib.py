@@ -25,6 +25,8 @@ VOXEL_FIELD_NONE, VOXEL_FIELD_X, VOXEL_FIELD_Y, VOXEL_FIELD_Z, VOXEL_FIELD_INTEN
 DEPTH_U16, DEPTH_F32 = 0, 1
 FOOTPRINT_MAX_VERTICES = 32
 FOOTPRINT_INSCRIBED_LETHAL, FOOTPRINT_SUM = 1, 2
+COST_INSCRIBED_INFLATED_OBSTACLE = 253
+INFLATE_MAX_CELLS = 127
 COLOR_NONE, COLOR_BGR8, COLOR_RGB8 = range(3)
 
 
@@ -65,6 +67,11 @@ class CostmapConfig(C.Structure):
     """gem_costmap_config: a costmap's geometry and the value of a cell nothing has written."""
     _fields_ = [("size_x", C.c_uint), ("size_y", C.c_uint), ("resolution", c_double), ("origin_x", c_double), ("origin_y", c_double),
                 ("default_value", C.c_ubyte)]
+
+
+class InflationParams(C.Structure):
+    """gem_inflation_params: InflationLayer's parameters (cost_scaling_factor is the library's weight_)."""
+    _fields_ = [("inflation_radius", c_double), ("inscribed_radius", c_double), ("cost_scaling_factor", c_double), ("inflate_unknown", c_int)]
 
 
 class FootprintPose(C.Structure):
@@ -220,6 +227,12 @@ FOOTPRINT_SIGNATURES = {
     "gem_costmap_score_trajectories": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_int, POINTER(c_double), c_int, c_int, c_void_p, c_void_p]),
     "gem_costmap_score_trajectories_device": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_int, POINTER(c_double), c_int, c_int, c_void_p, c_void_p]),
 }
+# include/gem_hip_inflate.h (inflation on the costmap; gem_hip.h includes it)
+INFLATE_SIGNATURES = {
+    "gem_inflation_table": (c_int, [POINTER(InflationParams), c_double, c_void_p, POINTER(c_int)]),
+    "gem_costmap_inflate": (c_int, [c_void_p, c_int, POINTER(InflationParams), c_int, c_int, c_int, c_int]),
+    "gem_costmap_reset_window": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -245,7 +258,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **DEBUG_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

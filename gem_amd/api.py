@@ -1312,6 +1312,33 @@ class Costmap:
                        each.ctypes.data_as(C.c_void_p) if pose_costs and n else None, traj.ctypes.data_as(C.c_void_p) if nt else None)
         return (traj, each) if pose_costs else traj
 
+    # -- inflation (gem_hip_inflate.h) --------------------------------------------------------------------------------------------------
+    def inflate(self, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0, inflate_unknown: bool = False,
+                window=None) -> None:
+        """InflationLayer's costs around the 254 cells inside window = (min_i, min_j, max_i, max_j) widened by the cell radius (None:
+        the whole map), from the exact nearest lethal cell; the call only enqueues (the first one with new parameters uploads the table)."""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        p = _lib.InflationParams(float(inflation_radius), float(inscribed_radius), float(cost_scaling_factor), int(bool(inflate_unknown)))
+        self._call("gem_costmap_inflate", C.byref(p), *w)
+
+    def reset_window(self, x0: int, y0: int, xn: int, yn: int) -> None:
+        """Costmap2D::resetMap(x0, y0, xn, yn): rows y0 <= y < yn become default_value for x0 <= x < xn; only enqueued"""
+        self._call("gem_costmap_reset_window", int(x0), int(y0), int(xn), int(yn))
+
+
+def inflation_table(resolution: float, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0):
+    """(R, table): the cell radius and the R * R + 1 costs by squared cell distance that Costmap.inflate uses (gem_inflation_table;
+    host only, no device)."""
+    lib = _lib.load()
+    p = _lib.InflationParams(float(inflation_radius), float(inscribed_radius), float(cost_scaling_factor), 0)
+    r = C.c_int(-1)
+    if lib.gem_inflation_table(C.byref(p), float(resolution), None, C.byref(r)) != _lib.GEM_OK:
+        raise ValueError("inflation_table: a radius, factor or resolution that is not usable, or more than 127 cells")
+    table = np.zeros(r.value * r.value + 1, np.uint8)
+    if lib.gem_inflation_table(C.byref(p), float(resolution), table.ctypes.data_as(C.c_void_p), None) != _lib.GEM_OK:
+        raise ValueError("inflation_table")
+    return int(r.value), table
+
 
 class RobotMotionMapUpdater:
     """RobotMotionMapUpdater (RobotMotionMapUpdater.cpp:42-145): pose covariance -> scalar variance

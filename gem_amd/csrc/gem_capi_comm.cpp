@@ -138,8 +138,9 @@ int gather_layers_locked(gem_handle* h, int with_attributes)
     }
     ok = tp.group_end(h->gather_stream) && ok;
     if (!ok) return step_abort(h, fail(h, GEM_ERR_COMM, tp.err.c_str()));
-    GEM_HIP_STEP(h, hipEventRecord(h->ev_gathered[g], h->gather_stream));
+    // (the time stamp first: whoever has waited for ev_gathered, gem_synchronize among them, then finds the stamp complete as well)
     if (h->step_timed) GEM_HIP_STEP(h, hipEventRecord(h->ev_t[8], h->gather_stream));
+    GEM_HIP_STEP(h, hipEventRecord(h->ev_gathered[g], h->gather_stream));
     h->gathered_recorded[g] = true;
     h->gather_outstanding[g] = true;
     return GEM_OK;
@@ -415,8 +416,8 @@ int shard_finish_locked(gem_handle* h)
     }
     ok = tp.group_end(h->comm_stream) && ok;
     if (!ok) return step_abort(h, fail(h, GEM_ERR_COMM, tp.err.c_str()));
+    if (h->step_timed) GEM_HIP_STEP(h, hipEventRecord(h->ev_t[3], h->comm_stream));              // (in front of ev_exchanged, as ev_t[8] of ev_gathered)
     GEM_HIP_STEP(h, hipEventRecord(h->ev_exchanged, h->comm_stream));
-    if (h->step_timed) GEM_HIP_STEP(h, hipEventRecord(h->ev_t[3], h->comm_stream));
     GEM_HIP_STEP(h, hipStreamWaitEvent(h->stream, h->ev_exchanged, 0));
     const void* phv[kMaxRanks]; const void* pkey[kMaxRanks]; const void* prng[kMaxRanks];
     for (int s = 0; s < W; ++s) {

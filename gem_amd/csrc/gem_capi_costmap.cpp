@@ -116,7 +116,7 @@ int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const cha
 
 void free_map(Map& m)
 {
-    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps}) {
+    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -132,7 +132,7 @@ void costmap_free(gem_handle* h)
     auto& c = h->costmap;
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& m : c.map) free_map(m);
-    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj}) {
+    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

@@ -298,10 +298,14 @@ struct gem_handle {
             Arena grid[2];              // the byte grid (`act`) and the target of the next roll
             int act = 0;
             Arena stamps;               // a word per cell (padded to four): the verdict of a mark in flight, all-zero between calls
+            Arena infl_table;           // gem_costmap_inflate's cost table on the device, made for infl_key at this resolution
+            gem_inflation_params infl_key{};
+            bool infl_valid = false;
         } map[kMax];
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
         Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
         std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
+        Arena infl_bits, infl_flags;            // gem_costmap_inflate (gem_capi_inflate.cpp): the seed words of the widened window | a flag per block of them
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping

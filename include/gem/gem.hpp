@@ -635,10 +635,26 @@ struct FootprintPose : gem_footprint_pose {
 static_assert(sizeof(FootprintPose) == sizeof(gem_footprint_pose), "an array of FootprintPose is an array of gem_footprint_pose");
 // a footprint specification: the polygon's vertices in the robot's frame, at most GEM_FOOTPRINT_MAX_VERTICES
 struct FootprintPoint { double x, y; };
+// InflationLayer's parameters (gem_hip_inflate.h): inflation_radius, the robot's inscribed radius, cost_scaling_factor, inflate_unknown
+struct InflationParams : gem_inflation_params {
+    InflationParams() : gem_inflation_params{0.55, 0.0, 10.0, 0} {}
+    InflationParams(double inflationRadius, double inscribedRadius, double costScalingFactor = 10.0, bool inflateUnknown = false)
+        : gem_inflation_params{inflationRadius, inscribedRadius, costScalingFactor, inflateUnknown ? 1 : 0} {}
+    // cell_inflation_radius_ at this resolution and the costs by squared cell distance, [0 .. R * R] (host only)
+    std::vector<unsigned char> table(double resolution, int* cells = nullptr) const
+    {
+        int r = 0;
+        if (gem_inflation_table(this, resolution, nullptr, &r) != GEM_OK) throw Error(GEM_ERR_INVALID, "InflationParams::table: unusable parameters");
+        std::vector<unsigned char> t(static_cast<size_t>(r) * static_cast<size_t>(r) + 1);
+        gem_inflation_table(this, resolution, t.data(), nullptr);
+        if (cells) *cells = r;
+        return t;
+    }
+};
 
 class Costmap {
 public:
-    static constexpr unsigned char FREE_SPACE = 0, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
+    static constexpr unsigned char FREE_SPACE = 0, INSCRIBED_INFLATED_OBSTACLE = 253, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
     enum MergeMode { Overwrite = 0, Max = 1 };
     // a mark's bounds, in / out as updateBounds' four pointers
     struct Bounds { double min_x, min_y, max_x, max_y; };
@@ -740,6 +756,19 @@ public:
                    "gem_costmap_score_trajectories");
         return cost;
     }
+
+    // InflationLayer::updateCosts around the LETHAL_OBSTACLE cells inside [minI, maxI) x [minJ, maxJ) widened by the cell radius, from
+    // the exact nearest lethal cell (the library's brushfire can over-estimate a distance: gem_hip_inflate.h).  Only enqueued.
+    void inflate(const InflationParams& params, int minI, int minJ, int maxI, int maxJ)
+    { map_.check(gem_costmap_inflate(map_.handle(), id_, &params, minI, minJ, maxI, maxJ), "gem_costmap_inflate"); }
+    void inflate(const InflationParams& params)
+    {
+        const gem_costmap_config c = geometry();
+        inflate(params, 0, 0, static_cast<int>(c.size_x), static_cast<int>(c.size_y));
+    }
+    // Costmap2D::resetMap(x0, y0, xn, yn): what LayeredCostmap::updateMap does to the master before the layers write
+    void resetWindow(int x0, int y0, int xn, int yn)
+    { map_.check(gem_costmap_reset_window(map_.handle(), id_, x0, y0, xn, yn), "gem_costmap_reset_window"); }
 
 private:
     static_assert(sizeof(Bounds) == 4 * sizeof(double), "bounds are four packed doubles");

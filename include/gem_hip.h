@@ -625,7 +625,8 @@ int  gem_global_count(gem_handle* h, int* out_submaps);
  *                updateWithMax: it replaces the master cell if that is NO_INFORMATION or smaller.  Equal sizes.
  *   gem_costmap_read               the window's bytes, row j at out + (j - min_j) * row_stride (row_stride >= max_i - min_i).
  *   gem_costmap_write              the reverse: the window's cells from the caller's bytes (setCost over a window): what other
- *                layers of the caller's left in a master (inflation costs, a footprint) before a merge onto it.
+ *                layers of the caller's left in a master (a static map, say) before a merge onto it.  Inflation costs and the
+ *                footprint need no such round trip: gem_costmap_inflate (gem_hip_inflate.h), gem_costmap_clear_footprint.
  *   gem_costmap_geometry           the configuration with the origin after rolling.
  * bounds = {min_x, min_y, max_x, max_y}, in / out, merged as touch() does; they compare as values, not bits (with std::min a tie
  * between -0 and +0 depends on the order).  With bounds NULL a mark only enqueues on the handle's stream and nothing waits.
@@ -734,6 +735,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 
 /* ---- footprints on the costmap: gem_costmap_clear_footprint, gem_costmap_footprint_cost*, gem_costmap_score_trajectories* ------- */
 #include "gem_hip_footprint.h"
+
+/* ---- inflation on the costmap: gem_inflation_table, gem_costmap_inflate, gem_costmap_reset_window ------------------------------- */
+#include "gem_hip_inflate.h"
 
 #ifdef __cplusplus
 }
