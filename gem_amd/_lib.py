@@ -233,6 +233,17 @@ INFLATE_SIGNATURES = {
     "gem_costmap_inflate": (c_int, [c_void_p, c_int, POINTER(InflationParams), c_int, c_int, c_int, c_int]),
     "gem_costmap_reset_window": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int]),
 }
+# include/gem_hip_mapgrid.h (path and goal distance grids on the costmap; gem_hip.h includes it)
+MAPGRID_PATH, MAPGRID_GOAL = 1, 2
+MAPGRID_STOP_ON_FAILURE, MAPGRID_SUM = 1, 2
+MAPGRID_MAX_POINTS, MAPGRID_MAX_WORDS = 1 << 20, 4096
+MAPGRID_SIGNATURES = {
+    "gem_mapgrid_adjust_plan": (c_int, [POINTER(c_double), c_longlong, c_double, POINTER(c_double), c_longlong, POINTER(c_longlong)]),
+    "gem_costmap_mapgrid_prepare": (c_int, [c_void_p, c_int, POINTER(c_double), c_longlong, c_int]),
+    "gem_costmap_mapgrid_read": (c_int, [c_void_p, c_int, c_int, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "gem_costmap_mapgrid_score": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
+    "gem_costmap_mapgrid_score_device": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -258,7 +269,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **DEBUG_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

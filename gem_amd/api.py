@@ -1325,6 +1325,40 @@ class Costmap:
         """Costmap2D::resetMap(x0, y0, xn, yn): rows y0 <= y < yn become default_value for x0 <= x < xn; only enqueued"""
         self._call("gem_costmap_reset_window", int(x0), int(y0), int(xn), int(yn))
 
+    # -- path and goal distance grids (gem_hip_mapgrid.h) ---------------------------------------------------------------------------------
+    def prepare_map_grid(self, plan, which: int = _lib.MAPGRID_PATH | _lib.MAPGRID_GOAL) -> None:
+        """MapGrid::setTargetCells / setLocalGoal + computeTargetDistance from plan = [n, 2] world points (adjusted to the resolution
+        on the host) through the costmap's non-blocked cells as they are when the call runs on the stream; only enqueued."""
+        v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
+        self._call("gem_costmap_mapgrid_prepare", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]), int(which))
+
+    def read_map_grid(self, which: int):
+        """(distances int32 [size_y, size_x], started, (goal x, goal y)) of MAPGRID_PATH or MAPGRID_GOAL; the call waits."""
+        out = np.zeros((self.size_y, self.size_x), np.int32)
+        started, goal = C.c_int(-1), (C.c_int * 2)(-1, -1)
+        self._call("gem_costmap_mapgrid_read", int(which), out.ctypes.data_as(C.c_void_p), C.byref(started), goal)
+        return out, int(started.value), (int(goal[0]), int(goal[1]))
+
+    def score_map_grid(self, which: int, poses, poses_per_traj: int, xshift: float = 0.0, flags: int = 0):
+        """MapGridCostFunction::scoreTrajectory over trajectories of poses_per_traj consecutive poses each against the prepared grid:
+        -4 off the map, with MAPGRID_STOP_ON_FAILURE -3 / -2 on an obstacle / unreachable cell, else the last pose's distance
+        (MAPGRID_SUM: the sum).  int64 numpy for host poses (the call waits), an int64 device tensor, only enqueued, for a device tensor."""
+        keep, pp, n, dev = self._poses(poses)
+        T = int(poses_per_traj)
+        if T < 1 or n % T:
+            raise ValueError("the poses are not a whole number of trajectories")
+        nt = n // T
+        if dev:
+            import torch
+            out = torch.empty((nt,), dtype=torch.int64, device=poses.device)
+            self.map._hold(poses, out)
+            self._call("gem_costmap_mapgrid_score_device", int(which), pp, nt, T, float(xshift), int(flags), C.c_void_p(out.data_ptr()) if nt else None)
+            return out
+        out = np.zeros(nt, np.int64)
+        self._call("gem_costmap_mapgrid_score", int(which), pp, nt, T, float(xshift), int(flags), out.ctypes.data_as(C.c_void_p) if nt else None)
+        return out
+
+
 
 def inflation_table(resolution: float, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0):
     """(R, table): the cell radius and the R * R + 1 costs by squared cell distance that Costmap.inflate uses (gem_inflation_table;
@@ -1388,3 +1422,18 @@ class RobotMotionMapUpdater:
         u = self.compute(position, R_IB, covariance6x6, map_rotation)
         elevation_map.mapvar_update(u)                                  # RMU.cpp:81
         return u
+
+
+def adjust_plan(plan, resolution: float) -> np.ndarray:
+    """MapGrid::adjustPlanResolution of plan = [n, 2]: points inserted so that no two neighbours lie more than a resolution apart
+    (gem_mapgrid_adjust_plan; host only, no device)."""
+    lib = _lib.load()
+    v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
+    pv = v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None
+    n = C.c_longlong(-1)
+    if lib.gem_mapgrid_adjust_plan(pv, int(v.shape[0]), float(resolution), None, 0, C.byref(n)) != _lib.GEM_OK:
+        raise ValueError("adjust_plan: a coordinate or resolution that is not usable, or more than 2^20 points")
+    out = np.zeros((int(n.value), 2), np.float64)
+    if lib.gem_mapgrid_adjust_plan(pv, int(v.shape[0]), float(resolution), out.ctypes.data_as(C.POINTER(C.c_double)), int(n.value), None) != _lib.GEM_OK:
+        raise ValueError("adjust_plan")
+    return out

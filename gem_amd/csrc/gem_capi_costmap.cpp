@@ -111,12 +111,13 @@ int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const cha
                                 cell_ox, cell_oy, m.cfg.default_value));
     m.act = 1 - m.act;
     m.cfg.origin_x = ox; m.cfg.origin_y = oy;
+    m.gen = ++h->costmap.generation;                                    // the distance grids of gem_costmap_mapgrid_prepare are stale now
     return GEM_OK;
 }
 
 void free_map(Map& m)
 {
-    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table}) {
+    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_status}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -132,9 +133,14 @@ void costmap_free(gem_handle* h)
     auto& c = h->costmap;
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& m : c.map) free_map(m);
-    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags}) {
+    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (c.mg_pin[k]) hipHostFree(c.mg_pin[k]);
+        if (c.mg_ev[k]) hipEventDestroy(c.mg_ev[k]);
+        c.mg_pin[k] = nullptr; c.mg_pin_cap[k] = 0; c.mg_ev[k] = nullptr; c.mg_ev_pending[k] = false;
     }
 }
 
@@ -174,6 +180,7 @@ int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id
         return rc;
     }
     m.cfg = *cfg; m.act = 0;
+    m.gen = ++c.generation;
     GEM_HIP(h, hipMemsetAsync(m.stamps.p, 0, stamp_bytes, h->stream));
     GEM_HIP(h, launch_cost_fill(h->stream, grid_of(m), (uint32_t)cells, m.cfg.default_value));
     m.used = true;

@@ -301,11 +301,25 @@ struct gem_handle {
             Arena infl_table;           // gem_costmap_inflate's cost table on the device, made for infl_key at this resolution
             gem_inflation_params infl_key{};
             bool infl_valid = false;
+            Arena mg_dist[2];           // gem_costmap_mapgrid_prepare's grids (gem_capi_mapgrid.cpp): path | goal, an int per cell
+            Arena mg_status;            // per grid four ints: started, goal cell x, y, levels
+            unsigned long long gen = 0; // the costmap's generation: new at create and at every roll that moves it
+            unsigned long long mg_gen[2] = {0, 0};      // the generation each grid was prepared in (0: never)
         } map[kMax];
+        unsigned long long generation = 0;      // the last generation handed out
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
         Arena in, win;                  // a host cloud of gem_costmap_mark_points | the packed window of gem_costmap_read / _write
         std::vector<unsigned char> host_rows;   // that window on the host when the caller's row stride is wider
         Arena infl_bits, infl_flags;            // gem_costmap_inflate (gem_capi_inflate.cpp): the seed words of the widened window | a flag per block of them
+        // gem_costmap_mapgrid_* (gem_capi_mapgrid.cpp): the plan's cells in pinned host memory, two buffers taking turns, each with the
+        // event behind the launch that reads it | the host-array forms' poses and results | the adjusted plan on the host
+        void* mg_pin[2] = {nullptr, nullptr};
+        size_t mg_pin_cap[2] = {0, 0};
+        hipEvent_t mg_ev[2] = {nullptr, nullptr};
+        bool mg_ev_pending[2] = {false, false};
+        unsigned mg_turn = 0;
+        Arena mg_pose, mg_traj;
+        std::vector<double> mg_plan;
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping

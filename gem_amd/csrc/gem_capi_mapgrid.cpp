@@ -1,0 +1,236 @@
+// gem_capi_mapgrid.cpp -- the MapGrid entry points of include/gem_hip_mapgrid.h: adjustPlanResolution (host only), the path and goal
+// distance grids of a costmap and MapGridCostFunction::scoreTrajectory.  The kernels are in gem_mapgrid.hip.
+//
+// gem_costmap_mapgrid_prepare adjusts the plan and applies worldToMap on the host in plain C++ (it knows the geometry after rolling)
+// and only enqueues.  The cells travel in pinned host memory that the distance kernel reads over the link: two buffers take turns
+// (Costmaps::mg_pin), each guarded by an event recorded behind the launch that reads it, so a call waits at most for the launch two
+// prepares back and never for the stream's other work.  The grids and their status words live with the costmap (Map::mg_dist,
+// mg_status), the host-array forms of the scoring calls stage in Costmaps::mg_pose / mg_traj; all come from ensure() and only grow:
+// gem_debug_get("arena_allocations") counts them, and a second identical call allocates nothing.  A grid is valid while the
+// costmap's generation (new at create and at every roll that moves it) is the one it was prepared in.
+#include "gem_capi_internal.hpp"
+#include "gem_mapgrid.hpp"
+
+#include <cmath>
+#include <cstring>
+
+namespace {
+
+using Map = gem_handle::Costmaps::Map;
+constexpr long long kMaxPoses = 2147483646ll;                       // 2^31 - 2
+constexpr int kMaxPosesPerTraj = 1 << 20;
+constexpr int kKnownFlags = GEM_MAPGRID_STOP_ON_FAILURE | GEM_MAPGRID_SUM;
+constexpr int kBoth = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL;
+static_assert(kMapGridMaxWords == GEM_MAPGRID_MAX_WORDS, "the kernel's LDS limit is the header's");
+static_assert(sizeof(gem_footprint_pose) == sizeof(FootPose), "a pose is four packed doubles");
+
+CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
+unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
+
+int find(gem_handle* h, int id, const char* what, Map** out)
+{
+    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
+    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
+        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
+    *out = &h->costmap.map[id];
+    return GEM_OK;
+}
+
+bool fits(const Map& m) { return (unsigned long long)mapgrid_row_words(m.cfg.size_x) * m.cfg.size_y <= kMapGridMaxWords; }
+
+// MapGrid::adjustPlanResolution.  Returns the adjusted plan's point count and writes the first `cap` points to out (NULL: none);
+// -1: a coordinate or a step count that is not usable, or more than `limit` points.
+long long adjust_plan(const double* plan, long long n, double resolution, double* out, long long cap, long long limit)
+{
+    if (n == 0) return 0;
+    long long count = 0;
+    auto put = [&](double x, double y) {
+        if (out && count < cap) { out[2 * count] = x; out[2 * count + 1] = y; }
+        ++count;
+    };
+    for (long long i = 0; i < 2 * n; ++i) if (!std::isfinite(plan[i])) return -1;
+    double last_x = plan[0], last_y = plan[1];
+    put(last_x, last_y);
+    const double min_sq_resolution = resolution * resolution;
+    for (long long i = 1; i < n; ++i) {
+        const double loop_x = plan[2 * i], loop_y = plan[2 * i + 1];
+        const double sqdist = (loop_x - last_x) * (loop_x - last_x) + (loop_y - last_y) * (loop_y - last_y);
+        if (sqdist > min_sq_resolution) {
+            const double q = std::ceil(std::sqrt(sqdist) / resolution);
+            if (!(q < 2147483648.0)) return -1;                         // (also an overflowed sqdist)
+            const int steps = (int)q;
+            if (count + steps > limit) return -1;
+            const double deltax = (loop_x - last_x) / steps, deltay = (loop_y - last_y) / steps;
+            for (int j = 1; j < steps; ++j) put(last_x + j * deltax, last_y + j * deltay);
+        }
+        put(loop_x, loop_y);
+        if (count > limit) return -1;
+        last_x = loop_x; last_y = loop_y;
+    }
+    return count;
+}
+
+// exactly one grid -> its slot
+int slot_of(int which_one) { return which_one == GEM_MAPGRID_PATH ? 0 : (which_one == GEM_MAPGRID_GOAL ? 1 : -1); }
+
+int usable_grid(gem_handle* h, Map& m, int which_one, const char* what, int* slot)
+{
+    *slot = slot_of(which_one);
+    if (*slot < 0) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": which_one is GEM_MAPGRID_PATH or GEM_MAPGRID_GOAL").c_str());
+    if (!m.mg_gen[*slot]) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was never prepared").c_str());
+    if (m.mg_gen[*slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled").c_str());
+    return GEM_OK;
+}
+
+struct ScoreCall {
+    const char* what;
+    const gem_footprint_pose* poses;
+    long long n_traj;
+    int T;
+    long long* out;
+    bool on_device;
+};
+
+int score(gem_handle* h, int id, int which_one, const ScoreCall& c, double xshift, int flags)
+{
+    int rc, slot;
+    Map* m;
+    if ((rc = find(h, id, c.what, &m))) return rc;
+    if (c.T < 1 || c.T > kMaxPosesPerTraj) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": poses_per_traj outside 1 .. 2^20").c_str());
+    if (c.n_traj < 0 || c.n_traj > kMaxPoses / c.T) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": a negative count, or more than 2^31 - 2 poses").c_str());
+    if (flags & ~kKnownFlags) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": unknown flag bits").c_str());
+    if (!std::isfinite(xshift)) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": xshift not finite").c_str());
+    if ((rc = usable_grid(h, *m, which_one, c.what, &slot))) return rc;
+    if (c.n_traj > 0 && (!c.poses || !c.out)) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": a NULL array with a non-zero count").c_str());
+    if (c.n_traj == 0) return GEM_OK;
+
+    MapGridScoreArgs a{};
+    a.dist = static_cast<const int*>(m->mg_dist[slot].p);
+    a.n_traj = c.n_traj; a.T = c.T; a.xshift = xshift;
+    a.stop_on_failure = (flags & GEM_MAPGRID_STOP_ON_FAILURE) ? 1 : 0;
+    a.sum = (flags & GEM_MAPGRID_SUM) ? 1 : 0;
+    if (c.on_device) {
+        a.poses = reinterpret_cast<const FootPose*>(c.poses); a.out = c.out;
+        GEM_HIP(h, launch_mapgrid_score(h->stream, geom_of(*m), a));
+        return GEM_OK;
+    }
+    auto& cm = h->costmap;
+    const size_t n_poses = (size_t)c.n_traj * (size_t)c.T;
+    if ((rc = ensure(h, cm.mg_pose, n_poses * sizeof(FootPose))) || (rc = ensure(h, cm.mg_traj, (size_t)c.n_traj * sizeof(long long)))) return rc;
+    HostXfer up{const_cast<gem_footprint_pose*>(c.poses), cm.mg_pose.p, n_poses * sizeof(FootPose)};
+    if ((rc = upload_arrays(h, &up, 1))) return rc;
+    a.poses = static_cast<const FootPose*>(cm.mg_pose.p);
+    a.out = static_cast<long long*>(cm.mg_traj.p);
+    GEM_HIP(h, launch_mapgrid_score(h->stream, geom_of(*m), a));
+    HostXfer down{c.out, cm.mg_traj.p, (size_t)c.n_traj * sizeof(long long)};
+    return download_arrays(h, &down, 1, 0);
+}
+
+} // namespace
+
+#define MAPGRID_ENTRY(name)                                          \
+    ApiRange api_range(h, name);                                     \
+    if (!h) return GEM_ERR_INVALID;                                  \
+    std::lock_guard<std::mutex> lk(h->mu);                           \
+    hipSetDevice(h->device)
+
+extern "C" {
+
+int gem_mapgrid_adjust_plan(const double* plan_xy, long long n, double resolution, double* out_xy, long long cap, long long* out_n)
+{
+    if (n < 0 || (n > 0 && !plan_xy) || !std::isfinite(resolution) || !(resolution > 0.0) || (out_xy && cap < 0)) return GEM_ERR_INVALID;
+    const long long count = adjust_plan(plan_xy, n, resolution, out_xy, out_xy ? cap : 0, GEM_MAPGRID_MAX_POINTS);
+    if (count < 0) return GEM_ERR_INVALID;
+    if (out_n) *out_n = count;
+    return out_xy && cap < count ? GEM_ERR_INVALID : GEM_OK;
+}
+
+int gem_costmap_mapgrid_prepare(gem_handle* h, int id, const double* plan_xy, long long n, int which)
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_prepare");
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mapgrid_prepare", &m))) return rc;
+    if (!(which & kBoth) || (which & ~kBoth)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: which is a mask of GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL");
+    if (n < 0 || (n > 0 && !plan_xy)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: a negative count, or a NULL plan with a non-zero count");
+    if (!fits(*m)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS");
+    auto& cm = h->costmap;
+    const CostGeom g = geom_of(*m);
+    const long long count = adjust_plan(plan_xy, n, g.res, nullptr, 0, GEM_MAPGRID_MAX_POINTS);
+    if (count < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: a plan coordinate not finite, or an adjusted plan above GEM_MAPGRID_MAX_POINTS");
+    cm.mg_plan.resize((size_t)count * 2);
+    adjust_plan(plan_xy, n, g.res, cm.mg_plan.data(), count, GEM_MAPGRID_MAX_POINTS);
+
+    // the grids and status words; then this call's turn of the pinned cells
+    const size_t cells = (size_t)g.sx * g.sy;
+    for (int s = 0; s < 2; ++s)
+        if ((which & (1 << s)) && (rc = ensure(h, m->mg_dist[s], cells * sizeof(int)))) return rc;
+    if ((rc = ensure(h, m->mg_status, 2 * kMapGridStatusWords * sizeof(int)))) return rc;
+    const int turn = (int)(cm.mg_turn & 1u);
+    if (!cm.mg_ev[turn]) GEM_HIP(h, hipEventCreateWithFlags(&cm.mg_ev[turn], hipEventDisableTiming));
+    if (cm.mg_ev_pending[turn]) { GEM_HIP(h, hipEventSynchronize(cm.mg_ev[turn])); cm.mg_ev_pending[turn] = false; }
+    const size_t bytes = std::max<size_t>((size_t)count, 1) * sizeof(int);
+    if (bytes > cm.mg_pin_cap[turn]) {
+        if (cm.mg_pin[turn]) GEM_HIP(h, hipHostFree(cm.mg_pin[turn]));
+        cm.mg_pin[turn] = nullptr; cm.mg_pin_cap[turn] = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        GEM_HIP(h, hipHostMalloc(&cm.mg_pin[turn], want, hipHostMallocDefault));
+        cm.mg_pin_cap[turn] = want;
+    }
+    int* pin = static_cast<int*>(cm.mg_pin[turn]);
+    for (long long i = 0; i < count; ++i) {
+        uint32_t cell = 0u;
+        pin[i] = cost_cell(g, cm.mg_plan[2 * i], cm.mg_plan[2 * i + 1], cell) ? (int)cell : -1;
+    }
+    ++cm.mg_turn;
+
+    MapGridArgs a{};
+    a.grid = grid_of(*m); a.cells = pin; a.n = (int)count;
+    a.sx = g.sx; a.sy = g.sy; a.nw = mapgrid_row_words(g.sx);
+    int ng = 0;
+    for (int s = 0; s < 2; ++s) {
+        if (!(which & (1 << s))) continue;
+        a.dist[ng] = static_cast<int*>(m->mg_dist[s].p);
+        a.status[ng] = static_cast<int*>(m->mg_status.p) + s * kMapGridStatusWords;
+        a.goal[ng] = s;
+        ++ng;
+    }
+    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], ng == 2 ? a.dist[1] : nullptr, (uint32_t)cells, (int)cells + 1));
+    GEM_HIP(h, launch_mapgrid_distance(h->stream, a, ng));
+    GEM_HIP(h, hipEventRecord(cm.mg_ev[turn], h->stream));
+    cm.mg_ev_pending[turn] = true;
+    for (int s = 0; s < 2; ++s) if (which & (1 << s)) m->mg_gen[s] = m->gen;
+    return GEM_OK;
+}
+
+int gem_costmap_mapgrid_read(gem_handle* h, int id, int which_one, int* out, int* out_started, int out_goal_cell[2])
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_read");
+    int rc, slot;
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_mapgrid_read", &m))) return rc;
+    if ((rc = usable_grid(h, *m, which_one, "gem_costmap_mapgrid_read", &slot))) return rc;
+    int st[kMapGridStatusWords] = {};
+    HostXfer d[2] = {{st, static_cast<int*>(m->mg_status.p) + slot * kMapGridStatusWords, sizeof(st)},
+                     {out, m->mg_dist[slot].p, (size_t)m->cfg.size_x * m->cfg.size_y * sizeof(int)}};
+    if ((rc = download_arrays(h, d, out ? 2 : 1, 0))) return rc;
+    if (out_started) *out_started = st[kMapGridStarted];
+    if (out_goal_cell) { out_goal_cell[0] = st[kMapGridGoalX]; out_goal_cell[1] = st[kMapGridGoalY]; }
+    return GEM_OK;
+}
+
+int gem_costmap_mapgrid_score(gem_handle* h, int id, int which_one, const gem_footprint_pose* poses, long long n_traj, int poses_per_traj,
+                              double xshift, int flags, long long* out_traj)
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_score");
+    return score(h, id, which_one, ScoreCall{"gem_costmap_mapgrid_score", poses, n_traj, poses_per_traj, out_traj, false}, xshift, flags);
+}
+
+int gem_costmap_mapgrid_score_device(gem_handle* h, int id, int which_one, const gem_footprint_pose* d_poses, long long n_traj,
+                                     int poses_per_traj, double xshift, int flags, long long* d_out_traj)
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_score_device");
+    return score(h, id, which_one, ScoreCall{"gem_costmap_mapgrid_score_device", d_poses, n_traj, poses_per_traj, d_out_traj, true}, xshift, flags);
+}
+
+} // extern "C"

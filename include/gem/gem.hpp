@@ -624,7 +624,8 @@ private:
 // (layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87) as marking passes, Costmap2D::updateOrigin as the rolling
 // step, the two updateCosts rules and a window read-back.  costmap_2d itself is restated in gem_hip.h, unverified against the
 // library.  Extra bounds, enabled_ and the layered costmap stay with the caller, see INTEGRATION.md.  The footprint calls
-// (gem_hip_footprint.h) clear the robot's outline out of a layer and answer base_local_planner's footprintCost in batches.
+// (gem_hip_footprint.h) clear the robot's outline out of a layer and answer base_local_planner's footprintCost in batches; the MapGrid
+// calls (gem_hip_mapgrid.h) keep its path and goal distance grids and score trajectories against them.
 // ---------------------------------------------------------------------------------------------
 // a pose as the footprint calls take it: the heading as its cosine and sine (the kernels hold no transcendental)
 struct FootprintPose : gem_footprint_pose {
@@ -769,6 +770,53 @@ public:
     // Costmap2D::resetMap(x0, y0, xn, yn): what LayeredCostmap::updateMap does to the master before the layers write
     void resetWindow(int x0, int y0, int xn, int yn)
     { map_.check(gem_costmap_reset_window(map_.handle(), id_, x0, y0, xn, yn), "gem_costmap_reset_window"); }
+
+    // base_local_planner's MapGrid (gem_hip_mapgrid.h): the path and goal distance grids from a global plan through the cells that are
+    // not 253, 254 or 255, as the costmap is when the call runs on the stream.  Only enqueued.
+    enum MapGridWhich { PathGrid = GEM_MAPGRID_PATH, GoalGrid = GEM_MAPGRID_GOAL };
+    struct MapGrid {
+        std::vector<int> dist;          // size_y rows of size_x
+        bool started = false;           // a point of the plan was accepted
+        int goalX = -1, goalY = -1;     // the local goal's cell
+    };
+    // MapGrid::adjustPlanResolution (host only)
+    static std::vector<FootprintPoint> adjustPlan(const std::vector<FootprintPoint>& plan, double resolution)
+    {
+        long long n = 0;
+        if (gem_mapgrid_adjust_plan(xy(plan), static_cast<long long>(plan.size()), resolution, nullptr, 0, &n) != GEM_OK)
+            throw Error(GEM_ERR_INVALID, "Costmap::adjustPlan: an unusable coordinate or resolution, or more than 2^20 points");
+        std::vector<FootprintPoint> out(static_cast<size_t>(n));
+        if (n) gem_mapgrid_adjust_plan(xy(plan), static_cast<long long>(plan.size()), resolution, &out.front().x, n, nullptr);
+        return out;
+    }
+    void prepareMapGrid(const std::vector<FootprintPoint>& plan, int which = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL)
+    { map_.check(gem_costmap_mapgrid_prepare(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size()), which), "gem_costmap_mapgrid_prepare"); }
+    // waits
+    MapGrid mapGrid(MapGridWhich which) const
+    {
+        const gem_costmap_config c = geometry();
+        MapGrid g;
+        g.dist.assign(static_cast<size_t>(c.size_x) * c.size_y, 0);
+        int started = 0, goal[2] = {-1, -1};
+        map_.check(gem_costmap_mapgrid_read(map_.handle(), id_, which, g.dist.data(), &started, goal), "gem_costmap_mapgrid_read");
+        g.started = started != 0; g.goalX = goal[0]; g.goalY = goal[1];
+        return g;
+    }
+    // MapGridCostFunction::scoreTrajectory over trajectories of posesPerTrajectory consecutive poses: -4 off the map, with
+    // GEM_MAPGRID_STOP_ON_FAILURE -3 / -2 on an obstacle / unreachable cell, else the last pose's distance (GEM_MAPGRID_SUM: the sum).
+    // The poses' cos / sin are the host's (FootprintPose::fromYaw); xshift moves the scored point along the heading (goal_front,
+    // alignment); there is no yshift.
+    std::vector<long long> scoreMapGrid(MapGridWhich which, const std::vector<FootprintPose>& poses, int posesPerTrajectory, double xshift = 0.0,
+                                        int flags = 0) const
+    {
+        if (posesPerTrajectory < 1 || poses.size() % static_cast<size_t>(posesPerTrajectory))
+            throw Error(GEM_ERR_INVALID, "Costmap::scoreMapGrid: the poses are not a whole number of trajectories");
+        std::vector<long long> cost(poses.size() / static_cast<size_t>(posesPerTrajectory));
+        map_.check(gem_costmap_mapgrid_score(map_.handle(), id_, which, poses.empty() ? nullptr : poses.data(), static_cast<long long>(cost.size()),
+                                             posesPerTrajectory, xshift, flags, cost.empty() ? nullptr : cost.data()),
+                   "gem_costmap_mapgrid_score");
+        return cost;
+    }
 
 private:
     static_assert(sizeof(Bounds) == 4 * sizeof(double), "bounds are four packed doubles");

@@ -739,6 +739,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- inflation on the costmap: gem_inflation_table, gem_costmap_inflate, gem_costmap_reset_window ------------------------------- */
 #include "gem_hip_inflate.h"
 
+/* ---- path and goal distance grids on the costmap: gem_mapgrid_adjust_plan, gem_costmap_mapgrid_prepare / _read / _score* -------- */
+#include "gem_hip_mapgrid.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,12 @@
 //                    same contract in numpy).  The row clears seeded poses of the launch files' rectangle and of a 16-gon out of a real
 //                    Costmap2D and scores seeded poses with a real CostmapModel on a noise grid, and compares every byte and every cost.
 //                    The poses' cosines and sines are this host's std::cos / std::sin, as transformFootprint's are
+//   mapgrid gem_costmap_mapgrid_prepare / _read restate base_local_planner::MapGrid (map_grid.cpp: adjustPlanResolution, setTargetCells,
+//                    setLocalGoal, computeTargetDistance, updatePathCell; include/gem_hip_mapgrid.h; tests/mapgrid_ref.py restates the
+//                    same contract in numpy).  The row runs a real MapGrid's setTargetCells and setLocalGoal over seeded plans that
+//                    start off the map, cross noise grids with 253 / 254 / 255 cells and leave them again, and compares every
+//                    target_dist of both grids.  MapGridCostFunction::scoreTrajectory is not driven (it needs a Trajectory and the
+//                    planner's parameters): the scoring loop stays pinned on tests/mapgrid_ref.py alone
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -48,7 +54,7 @@
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
 // there, against the library's public headers as documented, and has not been through a compiler; neither have the octo row
-// (add -loctomap -loctomath to the link line) and the foot row (add -lbase_local_planner).
+// (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner) and the mapgrid row (the same library).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -84,6 +90,8 @@
 #include <costmap_2d/costmap_layer.h>
 #include <costmap_2d/footprint.h>
 #include <base_local_planner/costmap_model.h>
+#include <base_local_planner/map_grid.h>
+#include <geometry_msgs/PoseStamped.h>
 #include <geometry_msgs/Point.h>
 #include <octomap/ColorOcTree.h>
 #include <sstream>
@@ -741,6 +749,59 @@ int check_foot(uint32_t seed)
     return 0;
 }
 
+// ---- mapgrid -------------------------------------------------------------------------------------------------------------------
+// Seeded plans over noise grids: MapGrid::setTargetCells / setLocalGoal on a real Costmap2D against gem_costmap_mapgrid_prepare.
+int check_mapgrid(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    const unsigned sx = 130, sy = 90;
+    const double res = 0.05, ox = -3.1, oy = 2.7;
+    costmap_2d::Costmap2D real(sx, sy, res, ox, oy, costmap_2d::FREE_SPACE);
+    gem_costmap_config cc{};
+    cc.size_x = sx; cc.size_y = sy; cc.resolution = res; cc.origin_x = ox; cc.origin_y = oy; cc.default_value = costmap_2d::FREE_SPACE;
+    int id = -1;
+    CHECK_GEM(gem_costmap_create(h, &cc, &id));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    for (const double blocked : {0.0, 0.1, 0.3}) {
+        for (size_t i = 0; i < (size_t)sx * sy; ++i) {
+            const double v = u(rng);
+            real.getCharMap()[i] = v < blocked ? (unsigned char)(253 + rng() % 3) : (unsigned char)(rng() % 253);
+        }
+        CHECK_GEM(gem_costmap_write(h, id, 0, 0, (int)sx, (int)sy, real.getCharMap(), sx));
+        for (int k = 0; k < 20; ++k) {
+            // three to six points over the map's box widened by a tenth: a plan may start off the map, leave it and come back
+            std::vector<geometry_msgs::PoseStamped> plan(3 + rng() % 4);
+            std::vector<double> xy;
+            for (geometry_msgs::PoseStamped& p : plan) {
+                p.pose.position.x = ox + (u(rng) * 1.2 - 0.1) * sx * res; p.pose.position.y = oy + (u(rng) * 1.2 - 0.1) * sy * res;
+                p.pose.orientation.w = 1.0;
+                xy.push_back(p.pose.position.x); xy.push_back(p.pose.position.y);
+            }
+            base_local_planner::MapGrid path(sx, sy), goal(sx, sy);
+            path.resetPathDist(); goal.resetPathDist();
+            path.setTargetCells(real, plan);
+            goal.setLocalGoal(real, plan);
+            CHECK_GEM(gem_costmap_mapgrid_prepare(h, id, xy.data(), (long long)plan.size(), GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL));
+            std::vector<int> got((size_t)sx * sy);
+            for (int w = 0; w < 2; ++w) {
+                int started = -1, cell[2];
+                CHECK_GEM(gem_costmap_mapgrid_read(h, id, w ? GEM_MAPGRID_GOAL : GEM_MAPGRID_PATH, got.data(), &started, cell));
+                base_local_planner::MapGrid& lib = w ? goal : path;
+                long long differ = 0;
+                for (unsigned y = 0; y < sy; ++y)
+                    for (unsigned x = 0; x < sx; ++x) differ += (double)got[(size_t)y * sx + x] != lib(x, y).target_dist;
+                if (differ) report(w ? "mapgrid: setLocalGoal, cells that differ" : "mapgrid: setTargetCells, cells that differ", k, (double)differ, 0.0);
+            }
+        }
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -822,8 +883,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_cost(seed + 5u);
     if (rc == 0) rc = check_octo(seed + 6u);
     if (rc == 0) rc = check_foot(seed + 7u);
+    if (rc == 0) rc = check_mapgrid(seed + 8u);
     if (rc) return rc;
     if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all eight rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
+    std::printf("all nine rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
     return 0;
 }
