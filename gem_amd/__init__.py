@@ -5,7 +5,9 @@ this package holds its sources (csrc/), the in-tree build (build.py), the ctypes
 and a Python mirror of the reference's host interface for that path (api.py).
 """
 from .api import (POINT_DTYPE, Costmap, ElevationMap, Frame, GemError, RejectFilter, RobotMotionMapUpdater, SensorModel,  # noqa: F401
-                  SensorProcessor, VoxelStage, adjust_plan, inflation_table)
+                  SensorProcessor, VoxelStage, adjust_plan, external_critic, inflation_table, map_grid_critic, obstacle_critic,
+                  select_trajectory)
 
 __all__ = ["POINT_DTYPE", "Costmap", "ElevationMap", "Frame", "GemError", "RejectFilter", "RobotMotionMapUpdater", "SensorModel",
-           "SensorProcessor", "VoxelStage", "adjust_plan", "inflation_table"]
+           "SensorProcessor", "VoxelStage", "adjust_plan", "external_critic", "inflation_table", "map_grid_critic", "obstacle_critic",
+           "select_trajectory"]

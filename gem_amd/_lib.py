@@ -244,6 +244,29 @@ MAPGRID_SIGNATURES = {
     "gem_costmap_mapgrid_score": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
     "gem_costmap_mapgrid_score_device": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
 }
+# include/gem_hip_critics.h (the best trajectory: the critic list, the FRONT grid; gem_hip.h includes it)
+CRITIC_OBSTACLE, CRITIC_MAPGRID, CRITIC_EXTERNAL, CRITIC_MAX = 1, 2, 3, 8
+CRITIC_GRID_PATH, CRITIC_GRID_GOAL, CRITIC_GRID_FRONT = 1, 2, 4
+CRITIC_CENTRE_COST = 4
+
+
+class Critic(C.Structure):
+    _fields_ = [("kind", c_int), ("grid", c_int), ("flags", c_int), ("column", c_int), ("scale", c_double), ("xshift", c_double)]
+
+
+class BestTrajectory(C.Structure):
+    _fields_ = [("index", c_longlong), ("n_valid", c_longlong), ("cost", c_double), ("reserved", c_longlong)]
+
+
+_BEST_ARGS = [c_void_p, c_int, POINTER(Critic), c_int, c_void_p, c_void_p, c_longlong, c_int, POINTER(c_double), c_int, c_void_p, c_int,
+              c_void_p, c_void_p]
+CRITICS_SIGNATURES = {
+    "gem_costmap_mapgrid_prepare_front": (c_int, [c_void_p, c_int, POINTER(c_double), c_longlong]),
+    "gem_costmap_mapgrid_read_front": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_int), POINTER(c_int)]),
+    "gem_costmap_best_trajectory": (c_int, _BEST_ARGS),
+    "gem_costmap_best_trajectory_device": (c_int, _BEST_ARGS),
+    "gem_critics_select": (c_int, [POINTER(Critic), c_int, POINTER(c_double), c_longlong, POINTER(c_double), POINTER(BestTrajectory)]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -269,7 +292,8 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **DEBUG_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
+                               **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1358,6 +1358,64 @@ class Costmap:
         self._call("gem_costmap_mapgrid_score", int(which), pp, nt, T, float(xshift), int(flags), out.ctypes.data_as(C.c_void_p) if nt else None)
         return out
 
+    # -- the best trajectory (gem_hip_critics.h) ----------------------------------------------------------------------------------------
+    def prepare_map_grid_front(self, plan) -> None:
+        """The FRONT grid, which DWA's goal_front critic reads: the goal grid of `plan` (the caller's front plan, its last point already
+        moved forward) in a slot of its own; PATH and GOAL are not touched.  Only enqueued."""
+        v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
+        self._call("gem_costmap_mapgrid_prepare_front", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]))
+
+    def read_map_grid_front(self):
+        """(distances int32 [size_y, size_x], started, (goal x, goal y)) of the FRONT grid; the call waits."""
+        out = np.zeros((self.size_y, self.size_x), np.int32)
+        started, goal = C.c_int(-1), (C.c_int * 2)(-1, -1)
+        self._call("gem_costmap_mapgrid_read_front", out.ctypes.data_as(C.c_void_p), C.byref(started), goal)
+        return out, int(started.value), (int(goal[0]), int(goal[1]))
+
+    def best_trajectory(self, critics, poses, poses_per_traj: int, spec, ext=None, traj_len=None, totals: bool = False):
+        """SimpleScoredSamplingPlanner's scoreTrajectory + findBestTrajectory over trajectories of poses_per_traj pose slots each:
+        critics is the ordered list (obstacle_critic / map_grid_critic / external_critic), ext = [columns, n_traj] raw scores of the
+        external critics, traj_len = [n_traj] int32 poses each trajectory uses (None: all).  Host poses: (index, cost, n_valid), or
+        with totals (index, cost, n_valid, float64 totals); the call waits.  A device tensor of poses (ext and traj_len then device
+        tensors too): an int64 device tensor [4] = index, n_valid, the cost's bits (`.view(torch.float64)[2]`), 0 -- or with totals
+        (that, a float64 device tensor) -- only enqueued and held until the map is synchronised."""
+        keep, pp, n, dev = self._poses(poses)
+        T = int(poses_per_traj)
+        if T < 1 or n % T:
+            raise ValueError("the poses are not a whole number of trajectories")
+        nt = n // T
+        cs = (_lib.Critic * max(len(critics), 1))(*critics)
+        ks, ps, nv = self._spec(spec if spec is not None else [])
+        if dev:
+            import torch
+            for name, t, dt in (("ext", ext, torch.float64), ("traj_len", traj_len, torch.int32)):
+                if t is not None and not (_is_device_tensor(t) and t.dtype == dt and t.is_contiguous()):
+                    raise ValueError(f"with device poses {name} must be a contiguous device tensor of {dt}")
+            if ext is not None and (ext.dim() != 2 or ext.shape[1] != nt):
+                raise ValueError("ext must be [columns, n_traj]")
+            if traj_len is not None and traj_len.numel() != nt:
+                raise ValueError("traj_len must hold one int per trajectory")
+            best = torch.empty((4,), dtype=torch.int64, device=poses.device)
+            tot = torch.empty((nt,), dtype=torch.float64, device=poses.device) if totals else None
+            self.map._hold(poses, ext, traj_len, best, tot)
+            self._call("gem_costmap_best_trajectory_device", cs, len(critics), pp, C.c_void_p(traj_len.data_ptr()) if traj_len is not None and nt else None,
+                       nt, T, ps, nv, C.c_void_p(ext.data_ptr()) if ext is not None and ext.numel() else None, int(ext.shape[0]) if ext is not None else 0,
+                       C.c_void_p(tot.data_ptr()) if totals and nt else None, C.c_void_p(best.data_ptr()))
+            return (best, tot) if totals else best
+        e = None if ext is None else np.ascontiguousarray(ext, np.float64)
+        if e is not None and (e.ndim != 2 or e.shape[1] != nt):
+            raise ValueError("ext must be [columns, n_traj]")
+        ln = None if traj_len is None else np.ascontiguousarray(traj_len, np.int32).reshape(-1)
+        if ln is not None and ln.size != nt:
+            raise ValueError("traj_len must hold one int per trajectory")
+        best = _lib.BestTrajectory(-9, -9, -9.0, -9)
+        tot = np.zeros(nt, np.float64) if totals else None
+        self._call("gem_costmap_best_trajectory", cs, len(critics), pp, ln.ctypes.data_as(C.c_void_p) if ln is not None and nt else None, nt, T, ps, nv,
+                   e.ctypes.data_as(C.c_void_p) if e is not None and e.size else None, int(e.shape[0]) if e is not None else 0,
+                   tot.ctypes.data_as(C.c_void_p) if totals and nt else None, C.byref(best))
+        res = (int(best.index), float(best.cost), int(best.n_valid))
+        return res + (tot,) if totals else res
+
 
 
 def inflation_table(resolution: float, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0):
@@ -1437,3 +1495,35 @@ def adjust_plan(plan, resolution: float) -> np.ndarray:
     if lib.gem_mapgrid_adjust_plan(pv, int(v.shape[0]), float(resolution), out.ctypes.data_as(C.POINTER(C.c_double)), int(n.value), None) != _lib.GEM_OK:
         raise ValueError("adjust_plan")
     return out
+
+
+def obstacle_critic(scale: float, flags: int = 0) -> _lib.Critic:
+    """ObstacleCostFunction: flags of FOOTPRINT_INSCRIBED_LETHAL | FOOTPRINT_SUM | CRITIC_CENTRE_COST"""
+    return _lib.Critic(_lib.CRITIC_OBSTACLE, 0, int(flags), 0, float(scale), 0.0)
+
+
+def map_grid_critic(scale: float, grid: int, xshift: float = 0.0, flags: int = 0) -> _lib.Critic:
+    """MapGridCostFunction on CRITIC_GRID_PATH / _GOAL / _FRONT: flags of MAPGRID_STOP_ON_FAILURE | MAPGRID_SUM"""
+    return _lib.Critic(_lib.CRITIC_MAPGRID, int(grid), int(flags), 0, float(scale), float(xshift))
+
+
+def external_critic(scale: float, column: int) -> _lib.Critic:
+    """a critic the caller scored: row `column` of best_trajectory's ext"""
+    return _lib.Critic(_lib.CRITIC_EXTERNAL, 0, 0, int(column), float(scale), 0.0)
+
+
+def select_trajectory(critics, scores):
+    """The combination and the winner over scores the caller holds, scores = [n_critics, n_traj] (gem_critics_select; host only, no
+    device): (index, cost, n_valid, float64 totals)."""
+    lib = _lib.load()
+    cs = (_lib.Critic * max(len(critics), 1))(*critics)
+    s = np.ascontiguousarray(scores, np.float64)
+    if s.ndim != 2 or s.shape[0] != len(critics):
+        raise ValueError("scores must be [n_critics, n_traj]")
+    nt = int(s.shape[1])
+    tot = np.zeros(nt, np.float64)
+    best = _lib.BestTrajectory(-9, -9, -9.0, -9)
+    if lib.gem_critics_select(cs, len(critics), s.ctypes.data_as(C.POINTER(C.c_double)) if s.size else None, nt,
+                              tot.ctypes.data_as(C.POINTER(C.c_double)) if nt else None, C.byref(best)) != _lib.GEM_OK:
+        raise ValueError("select_trajectory: 1 .. 8 critics, every scale finite and not negative")
+    return int(best.index), float(best.cost), int(best.n_valid), tot

@@ -117,7 +117,7 @@ int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const cha
 
 void free_map(Map& m)
 {
-    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_status}) {
+    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -133,7 +133,8 @@ void costmap_free(gem_handle* h)
     auto& c = h->costmap;
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& m : c.map) free_map(m);
-    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj}) {
+    for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
+                     &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

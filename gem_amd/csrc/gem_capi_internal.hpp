@@ -301,10 +301,10 @@ struct gem_handle {
             Arena infl_table;           // gem_costmap_inflate's cost table on the device, made for infl_key at this resolution
             gem_inflation_params infl_key{};
             bool infl_valid = false;
-            Arena mg_dist[2];           // gem_costmap_mapgrid_prepare's grids (gem_capi_mapgrid.cpp): path | goal, an int per cell
+            Arena mg_dist[3];           // gem_costmap_mapgrid_prepare's / _prepare_front's grids (gem_capi_mapgrid.cpp): path | goal | front, an int per cell
             Arena mg_status;            // per grid four ints: started, goal cell x, y, levels
             unsigned long long gen = 0; // the costmap's generation: new at create and at every roll that moves it
-            unsigned long long mg_gen[2] = {0, 0};      // the generation each grid was prepared in (0: never)
+            unsigned long long mg_gen[3] = {0, 0, 0};   // the generation each grid was prepared in (0: never)
         } map[kMax];
         unsigned long long generation = 0;      // the last generation handed out
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
@@ -320,6 +320,9 @@ struct gem_handle {
         unsigned mg_turn = 0;
         Arena mg_pose, mg_traj;
         std::vector<double> mg_plan;
+        // gem_costmap_best_trajectory* (gem_capi_critics.cpp): the first pass's candidates | the host-array form's poses, lengths, external
+        // columns, totals and the 32-byte result
+        Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping

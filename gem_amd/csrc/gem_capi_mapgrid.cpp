@@ -8,6 +8,10 @@
 // mg_status), the host-array forms of the scoring calls stage in Costmaps::mg_pose / mg_traj; all come from ensure() and only grow:
 // gem_debug_get("arena_allocations") counts them, and a second identical call allocates nothing.  A grid is valid while the
 // costmap's generation (new at create and at every roll that moves it) is the one it was prepared in.
+//
+// A costmap has three grid slots: path, goal and front (the goal grid of DWA's front plan, include/gem_hip_critics.h).  prepare() and
+// read() below work on slots; the public `which` of the MapGrid calls still admits PATH | GOAL only, and the front slot is reached
+// through gem_costmap_mapgrid_prepare_front / _read_front and by gem_costmap_best_trajectory (gem_capi_critics.cpp).
 #include "gem_capi_internal.hpp"
 #include "gem_mapgrid.hpp"
 
@@ -20,7 +24,8 @@ using Map = gem_handle::Costmaps::Map;
 constexpr long long kMaxPoses = 2147483646ll;                       // 2^31 - 2
 constexpr int kMaxPosesPerTraj = 1 << 20;
 constexpr int kKnownFlags = GEM_MAPGRID_STOP_ON_FAILURE | GEM_MAPGRID_SUM;
-constexpr int kBoth = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL;
+constexpr int kBoth = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL;              // what the public `which` admits
+constexpr int kSlots = 3, kFrontSlot = 2;                           // path | goal | front (gem_hip_critics.h): the front grid has entries of its own
 static_assert(kMapGridMaxWords == GEM_MAPGRID_MAX_WORDS, "the kernel's LDS limit is the header's");
 static_assert(sizeof(gem_footprint_pose) == sizeof(FootPose), "a pose is four packed doubles");
 
@@ -73,13 +78,18 @@ long long adjust_plan(const double* plan, long long n, double resolution, double
 // exactly one grid -> its slot
 int slot_of(int which_one) { return which_one == GEM_MAPGRID_PATH ? 0 : (which_one == GEM_MAPGRID_GOAL ? 1 : -1); }
 
+int usable_slot(gem_handle* h, Map& m, int slot, const char* what)
+{
+    if (!m.mg_gen[slot]) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was never prepared").c_str());
+    if (m.mg_gen[slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled").c_str());
+    return GEM_OK;
+}
+
 int usable_grid(gem_handle* h, Map& m, int which_one, const char* what, int* slot)
 {
     *slot = slot_of(which_one);
     if (*slot < 0) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": which_one is GEM_MAPGRID_PATH or GEM_MAPGRID_GOAL").c_str());
-    if (!m.mg_gen[*slot]) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was never prepared").c_str());
-    if (m.mg_gen[*slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled").c_str());
-    return GEM_OK;
+    return usable_slot(h, m, *slot, what);
 }
 
 struct ScoreCall {
@@ -126,6 +136,79 @@ int score(gem_handle* h, int id, int which_one, const ScoreCall& c, double xshif
     return download_arrays(h, &down, 1, 0);
 }
 
+// gem_costmap_mapgrid_prepare and _prepare_front behind their own checks of `which`: `slots` is a mask of slots (bit 0 path | 1 goal |
+// 2 front), at most two of them: one launch
+int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots)
+{
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, what, &m))) return rc;
+    if (n < 0 || (n > 0 && !plan_xy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": a negative count, or a NULL plan with a non-zero count").c_str());
+    if (!fits(*m)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS").c_str());
+    auto& cm = h->costmap;
+    const CostGeom g = geom_of(*m);
+    const long long count = adjust_plan(plan_xy, n, g.res, nullptr, 0, GEM_MAPGRID_MAX_POINTS);
+    if (count < 0) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": a plan coordinate not finite, or an adjusted plan above GEM_MAPGRID_MAX_POINTS").c_str());
+    cm.mg_plan.resize((size_t)count * 2);
+    adjust_plan(plan_xy, n, g.res, cm.mg_plan.data(), count, GEM_MAPGRID_MAX_POINTS);
+
+    // the grids and status words; then this call's turn of the pinned cells
+    const size_t cells = (size_t)g.sx * g.sy;
+    for (int s = 0; s < kSlots; ++s)
+        if ((slots & (1 << s)) && (rc = ensure(h, m->mg_dist[s], cells * sizeof(int)))) return rc;
+    if ((rc = ensure(h, m->mg_status, kSlots * kMapGridStatusWords * sizeof(int)))) return rc;
+    const int turn = (int)(cm.mg_turn & 1u);
+    if (!cm.mg_ev[turn]) GEM_HIP(h, hipEventCreateWithFlags(&cm.mg_ev[turn], hipEventDisableTiming));
+    if (cm.mg_ev_pending[turn]) { GEM_HIP(h, hipEventSynchronize(cm.mg_ev[turn])); cm.mg_ev_pending[turn] = false; }
+    const size_t bytes = std::max<size_t>((size_t)count, 1) * sizeof(int);
+    if (bytes > cm.mg_pin_cap[turn]) {
+        if (cm.mg_pin[turn]) GEM_HIP(h, hipHostFree(cm.mg_pin[turn]));
+        cm.mg_pin[turn] = nullptr; cm.mg_pin_cap[turn] = 0;
+        const size_t want = bytes + bytes / 4 + 4096;
+        GEM_HIP(h, hipHostMalloc(&cm.mg_pin[turn], want, hipHostMallocDefault));
+        cm.mg_pin_cap[turn] = want;
+    }
+    int* pin = static_cast<int*>(cm.mg_pin[turn]);
+    for (long long i = 0; i < count; ++i) {
+        uint32_t cell = 0u;
+        pin[i] = cost_cell(g, cm.mg_plan[2 * i], cm.mg_plan[2 * i + 1], cell) ? (int)cell : -1;
+    }
+    ++cm.mg_turn;
+
+    MapGridArgs a{};
+    a.grid = grid_of(*m); a.cells = pin; a.n = (int)count;
+    a.sx = g.sx; a.sy = g.sy; a.nw = mapgrid_row_words(g.sx);
+    int ng = 0;
+    for (int s = 0; s < kSlots; ++s) {
+        if (!(slots & (1 << s))) continue;
+        a.dist[ng] = static_cast<int*>(m->mg_dist[s].p);
+        a.status[ng] = static_cast<int*>(m->mg_status.p) + s * kMapGridStatusWords;
+        a.goal[ng] = s != 0;                                             // the front grid is a goal grid of its own plan
+        ++ng;
+    }
+    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], ng == 2 ? a.dist[1] : nullptr, (uint32_t)cells, (int)cells + 1));
+    GEM_HIP(h, launch_mapgrid_distance(h->stream, a, ng));
+    GEM_HIP(h, hipEventRecord(cm.mg_ev[turn], h->stream));
+    cm.mg_ev_pending[turn] = true;
+    for (int s = 0; s < kSlots; ++s) if (slots & (1 << s)) m->mg_gen[s] = m->gen;
+    return GEM_OK;
+}
+
+int read(gem_handle* h, int id, const char* what, int slot, int* out, int* out_started, int out_goal_cell[2])
+{
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, what, &m))) return rc;
+    if ((rc = usable_slot(h, *m, slot, what))) return rc;
+    int st[kMapGridStatusWords] = {};
+    HostXfer d[2] = {{st, static_cast<int*>(m->mg_status.p) + slot * kMapGridStatusWords, sizeof(st)},
+                     {out, m->mg_dist[slot].p, (size_t)m->cfg.size_x * m->cfg.size_y * sizeof(int)}};
+    if ((rc = download_arrays(h, d, out ? 2 : 1, 0))) return rc;
+    if (out_started) *out_started = st[kMapGridStarted];
+    if (out_goal_cell) { out_goal_cell[0] = st[kMapGridGoalX]; out_goal_cell[1] = st[kMapGridGoalY]; }
+    return GEM_OK;
+}
+
 } // namespace
 
 #define MAPGRID_ENTRY(name)                                          \
@@ -152,55 +235,13 @@ int gem_costmap_mapgrid_prepare(gem_handle* h, int id, const double* plan_xy, lo
     Map* m;
     if ((rc = find(h, id, "gem_costmap_mapgrid_prepare", &m))) return rc;
     if (!(which & kBoth) || (which & ~kBoth)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: which is a mask of GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL");
-    if (n < 0 || (n > 0 && !plan_xy)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: a negative count, or a NULL plan with a non-zero count");
-    if (!fits(*m)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS");
-    auto& cm = h->costmap;
-    const CostGeom g = geom_of(*m);
-    const long long count = adjust_plan(plan_xy, n, g.res, nullptr, 0, GEM_MAPGRID_MAX_POINTS);
-    if (count < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: a plan coordinate not finite, or an adjusted plan above GEM_MAPGRID_MAX_POINTS");
-    cm.mg_plan.resize((size_t)count * 2);
-    adjust_plan(plan_xy, n, g.res, cm.mg_plan.data(), count, GEM_MAPGRID_MAX_POINTS);
+    return prepare(h, id, "gem_costmap_mapgrid_prepare", plan_xy, n, which);      // (the public bits are the slots' bits)
+}
 
-    // the grids and status words; then this call's turn of the pinned cells
-    const size_t cells = (size_t)g.sx * g.sy;
-    for (int s = 0; s < 2; ++s)
-        if ((which & (1 << s)) && (rc = ensure(h, m->mg_dist[s], cells * sizeof(int)))) return rc;
-    if ((rc = ensure(h, m->mg_status, 2 * kMapGridStatusWords * sizeof(int)))) return rc;
-    const int turn = (int)(cm.mg_turn & 1u);
-    if (!cm.mg_ev[turn]) GEM_HIP(h, hipEventCreateWithFlags(&cm.mg_ev[turn], hipEventDisableTiming));
-    if (cm.mg_ev_pending[turn]) { GEM_HIP(h, hipEventSynchronize(cm.mg_ev[turn])); cm.mg_ev_pending[turn] = false; }
-    const size_t bytes = std::max<size_t>((size_t)count, 1) * sizeof(int);
-    if (bytes > cm.mg_pin_cap[turn]) {
-        if (cm.mg_pin[turn]) GEM_HIP(h, hipHostFree(cm.mg_pin[turn]));
-        cm.mg_pin[turn] = nullptr; cm.mg_pin_cap[turn] = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        GEM_HIP(h, hipHostMalloc(&cm.mg_pin[turn], want, hipHostMallocDefault));
-        cm.mg_pin_cap[turn] = want;
-    }
-    int* pin = static_cast<int*>(cm.mg_pin[turn]);
-    for (long long i = 0; i < count; ++i) {
-        uint32_t cell = 0u;
-        pin[i] = cost_cell(g, cm.mg_plan[2 * i], cm.mg_plan[2 * i + 1], cell) ? (int)cell : -1;
-    }
-    ++cm.mg_turn;
-
-    MapGridArgs a{};
-    a.grid = grid_of(*m); a.cells = pin; a.n = (int)count;
-    a.sx = g.sx; a.sy = g.sy; a.nw = mapgrid_row_words(g.sx);
-    int ng = 0;
-    for (int s = 0; s < 2; ++s) {
-        if (!(which & (1 << s))) continue;
-        a.dist[ng] = static_cast<int*>(m->mg_dist[s].p);
-        a.status[ng] = static_cast<int*>(m->mg_status.p) + s * kMapGridStatusWords;
-        a.goal[ng] = s;
-        ++ng;
-    }
-    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], ng == 2 ? a.dist[1] : nullptr, (uint32_t)cells, (int)cells + 1));
-    GEM_HIP(h, launch_mapgrid_distance(h->stream, a, ng));
-    GEM_HIP(h, hipEventRecord(cm.mg_ev[turn], h->stream));
-    cm.mg_ev_pending[turn] = true;
-    for (int s = 0; s < 2; ++s) if (which & (1 << s)) m->mg_gen[s] = m->gen;
-    return GEM_OK;
+int gem_costmap_mapgrid_prepare_front(gem_handle* h, int id, const double* plan_xy, long long n)
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_prepare_front");
+    return prepare(h, id, "gem_costmap_mapgrid_prepare_front", plan_xy, n, 1 << kFrontSlot);
 }
 
 int gem_costmap_mapgrid_read(gem_handle* h, int id, int which_one, int* out, int* out_started, int out_goal_cell[2])
@@ -210,13 +251,13 @@ int gem_costmap_mapgrid_read(gem_handle* h, int id, int which_one, int* out, int
     Map* m;
     if ((rc = find(h, id, "gem_costmap_mapgrid_read", &m))) return rc;
     if ((rc = usable_grid(h, *m, which_one, "gem_costmap_mapgrid_read", &slot))) return rc;
-    int st[kMapGridStatusWords] = {};
-    HostXfer d[2] = {{st, static_cast<int*>(m->mg_status.p) + slot * kMapGridStatusWords, sizeof(st)},
-                     {out, m->mg_dist[slot].p, (size_t)m->cfg.size_x * m->cfg.size_y * sizeof(int)}};
-    if ((rc = download_arrays(h, d, out ? 2 : 1, 0))) return rc;
-    if (out_started) *out_started = st[kMapGridStarted];
-    if (out_goal_cell) { out_goal_cell[0] = st[kMapGridGoalX]; out_goal_cell[1] = st[kMapGridGoalY]; }
-    return GEM_OK;
+    return read(h, id, "gem_costmap_mapgrid_read", slot, out, out_started, out_goal_cell);
+}
+
+int gem_costmap_mapgrid_read_front(gem_handle* h, int id, int* out, int* out_started, int out_goal_cell[2])
+{
+    MAPGRID_ENTRY("gem_costmap_mapgrid_read_front");
+    return read(h, id, "gem_costmap_mapgrid_read_front", kFrontSlot, out, out_started, out_goal_cell);
 }
 
 int gem_costmap_mapgrid_score(gem_handle* h, int id, int which_one, const gem_footprint_pose* poses, long long n_traj, int poses_per_traj,

@@ -24,8 +24,9 @@
 // Scoring.  k_mapgrid_score: the lane-group scheme of gem_footprint.hip.  A group of G lanes owns whole trajectories; lane l takes
 // poses l, l + G, ...; a negative event carries its place in the sequential walk, pose << 2 | (answer + 4), and the group takes the
 // integer MIN of these keys: "the first negative event decides", whatever the timing.  Last is the last pose's d, Sum a 64-bit sum;
-// both are reduced by shuffles.
-#include "gem_mapgrid.hpp"
+// both are reduced by shuffles.  A pose's own part (shift, worldToMap, the cell's distance, its event) is mapgrid_pose_code of
+// gem_score_device.hpp, which k_critics (gem_critics.hip) shares.
+#include "gem_score_device.hpp"
 
 #include <mutex>
 
@@ -206,16 +207,8 @@ __global__ __launch_bounds__(kMapGridScoreThreads) void k_mapgrid_score(CostGeom
         long long sum = 0, last = 0;
         for (int p = l; p < a.T; p += G) {
             const FootPose P = a.poses[t * a.T + p];
-            double px = P.x, py = P.y;
-            if (a.xshift != 0.0) { px = P.x + a.xshift * P.c; py = P.y + a.xshift * P.s; }      // (-ffp-contract=off: no fma)
-            uint32_t cell = 0u;
-            int code = -1;
-            long long dd = 0;
-            if (!cost_cell(g, px, py, cell)) code = 0;                  // -4
-            else {
-                dd = a.dist[cell];
-                if (a.stop_on_failure) code = dd == OB ? 1 : (dd == UN ? 2 : -1);              // -3 | -2
-            }
+            long long dd;
+            const int code = mapgrid_pose_code(g, a.dist, P, a.xshift, a.stop_on_failure != 0, OB, UN, dd);
             if (code >= 0) {
                 const unsigned long long e = (unsigned long long)p << 2 | (unsigned long long)code;
                 key = e < key ? e : key;

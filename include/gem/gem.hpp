@@ -625,7 +625,8 @@ private:
 // step, the two updateCosts rules and a window read-back.  costmap_2d itself is restated in gem_hip.h, unverified against the
 // library.  Extra bounds, enabled_ and the layered costmap stay with the caller, see INTEGRATION.md.  The footprint calls
 // (gem_hip_footprint.h) clear the robot's outline out of a layer and answer base_local_planner's footprintCost in batches; the MapGrid
-// calls (gem_hip_mapgrid.h) keep its path and goal distance grids and score trajectories against them.
+// calls (gem_hip_mapgrid.h) keep its path and goal distance grids and score trajectories against them; bestTrajectory
+// (gem_hip_critics.h) combines the critics as SimpleScoredSamplingPlanner does and picks the winner.
 // ---------------------------------------------------------------------------------------------
 // a pose as the footprint calls take it: the heading as its cosine and sine (the kernels hold no transcendental)
 struct FootprintPose : gem_footprint_pose {
@@ -652,6 +653,43 @@ struct InflationParams : gem_inflation_params {
         return t;
     }
 };
+
+// a critic of the best-trajectory call (gem_hip_critics.h): its kind, what it reads and its scale, in the order the planner sums them
+struct Critic : gem_critic {
+    Critic() : gem_critic{GEM_CRITIC_EXTERNAL, 0, 0, 0, 0.0, 0.0} {}
+    // ObstacleCostFunction: flags of GEM_FOOTPRINT_INSCRIBED_LETHAL | GEM_FOOTPRINT_SUM | GEM_CRITIC_CENTRE_COST
+    static Critic obstacle(double scale, int flags = 0) { return make(GEM_CRITIC_OBSTACLE, 0, flags, 0, scale, 0.0); }
+    // MapGridCostFunction on GEM_CRITIC_GRID_PATH / _GOAL / _FRONT: flags of GEM_MAPGRID_STOP_ON_FAILURE | GEM_MAPGRID_SUM
+    static Critic mapGrid(double scale, int grid, double xshift = 0.0, int flags = 0) { return make(GEM_CRITIC_MAPGRID, grid, flags, 0, scale, xshift); }
+    // a critic the caller scored (oscillation, twirling, prefer-forward): column `column` of the ext array
+    static Critic external(double scale, int column) { return make(GEM_CRITIC_EXTERNAL, 0, 0, column, scale, 0.0); }
+private:
+    static Critic make(int kind, int grid, int flags, int column, double scale, double xshift)
+    {
+        Critic c;
+        c.kind = kind; c.grid = grid; c.flags = flags; c.column = column; c.scale = scale; c.xshift = xshift;
+        return c;
+    }
+};
+static_assert(sizeof(Critic) == sizeof(gem_critic), "an array of Critic is an array of gem_critic");
+// findBestTrajectory's answer: index -1 and cost -1.0 without a valid trajectory
+struct BestTrajectory : gem_best_trajectory {
+    BestTrajectory() : gem_best_trajectory{-1, 0, -1.0, 0} {}
+    bool valid() const { return index >= 0; }
+};
+static_assert(sizeof(BestTrajectory) == sizeof(gem_best_trajectory), "a BestTrajectory is a gem_best_trajectory");
+// The combination and the winner over scores the caller holds, scores[k * n + t] of critic k and trajectory t (host only, no device)
+inline BestTrajectory selectTrajectory(const std::vector<Critic>& critics, const std::vector<double>& scores, std::vector<double>* totals = nullptr)
+{
+    if (critics.empty() || scores.size() % critics.size()) throw Error(GEM_ERR_INVALID, "selectTrajectory: one score per critic and trajectory");
+    const long long n = static_cast<long long>(scores.size() / critics.size());
+    if (totals) totals->assign(static_cast<size_t>(n), 0.0);
+    BestTrajectory b;
+    if (gem_critics_select(critics.data(), static_cast<int>(critics.size()), scores.empty() ? nullptr : scores.data(), n,
+                           totals && n ? totals->data() : nullptr, &b) != GEM_OK)
+        throw Error(GEM_ERR_INVALID, "selectTrajectory: 1 .. 8 critics, every scale finite and not negative");
+    return b;
+}
 
 class Costmap {
 public:
@@ -816,6 +854,43 @@ public:
                                              posesPerTrajectory, xshift, flags, cost.empty() ? nullptr : cost.data()),
                    "gem_costmap_mapgrid_score");
         return cost;
+    }
+
+    // The FRONT grid (gem_hip_critics.h): the goal grid of the caller's front plan (its last point already moved forward) in a slot of
+    // its own, for DWA's goal_front critic; PATH and GOAL are not touched.  Only enqueued; mapGridFront waits.
+    void prepareMapGridFront(const std::vector<FootprintPoint>& plan)
+    { map_.check(gem_costmap_mapgrid_prepare_front(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size())), "gem_costmap_mapgrid_prepare_front"); }
+    MapGrid mapGridFront() const
+    {
+        const gem_costmap_config c = geometry();
+        MapGrid g;
+        g.dist.assign(static_cast<size_t>(c.size_x) * c.size_y, 0);
+        int started = 0, goal[2] = {-1, -1};
+        map_.check(gem_costmap_mapgrid_read_front(map_.handle(), id_, g.dist.data(), &started, goal), "gem_costmap_mapgrid_read_front");
+        g.started = started != 0; g.goalX = goal[0]; g.goalY = goal[1];
+        return g;
+    }
+    // SimpleScoredSamplingPlanner's scoreTrajectory + findBestTrajectory over trajectories of posesPerTrajectory pose slots: the critics
+    // in order, ext = the external critics' raw scores [columns][trajectories], trajLen (empty: all) the poses each trajectory uses.
+    // The smallest total among the valid trajectories wins, ties to the smallest index.  Waits.
+    BestTrajectory bestTrajectory(const std::vector<Critic>& critics, const std::vector<FootprintPose>& poses, int posesPerTrajectory,
+                                  const std::vector<FootprintPoint>& spec, const std::vector<double>& ext = {}, const std::vector<int>& trajLen = {},
+                                  std::vector<double>* totals = nullptr) const
+    {
+        if (posesPerTrajectory < 1 || poses.size() % static_cast<size_t>(posesPerTrajectory))
+            throw Error(GEM_ERR_INVALID, "Costmap::bestTrajectory: the poses are not a whole number of trajectories");
+        const size_t n = poses.size() / static_cast<size_t>(posesPerTrajectory);
+        if ((!trajLen.empty() && trajLen.size() != n) || (n ? ext.size() % n != 0 : !ext.empty()))
+            throw Error(GEM_ERR_INVALID, "Costmap::bestTrajectory: one length per trajectory, whole columns of external scores");
+        if (totals) totals->assign(n, 0.0);
+        BestTrajectory b;
+        map_.check(gem_costmap_best_trajectory(map_.handle(), id_, critics.empty() ? nullptr : critics.data(), static_cast<int>(critics.size()),
+                                               poses.empty() ? nullptr : poses.data(), trajLen.empty() ? nullptr : trajLen.data(),
+                                               static_cast<long long>(n), posesPerTrajectory, xy(spec), static_cast<int>(spec.size()),
+                                               ext.empty() ? nullptr : ext.data(), n ? static_cast<int>(ext.size() / n) : 0,
+                                               totals && n ? totals->data() : nullptr, &b),
+                   "gem_costmap_best_trajectory");
+        return b;
     }
 
 private:

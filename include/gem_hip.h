@@ -742,6 +742,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- path and goal distance grids on the costmap: gem_mapgrid_adjust_plan, gem_costmap_mapgrid_prepare / _read / _score* -------- */
 #include "gem_hip_mapgrid.h"
 
+/* ---- the best trajectory: gem_costmap_mapgrid_prepare_front / _read_front, gem_costmap_best_trajectory*, gem_critics_select ----- */
+#include "gem_hip_critics.h"
+
 #ifdef __cplusplus
 }
 #endif

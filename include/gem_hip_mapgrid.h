@@ -38,7 +38,8 @@
  *                the FIRST negative event in pose order decides, otherwise the aggregate.  (Product is NOT provided: it leaves the
  *                exact integers after a few poses.)  Results are long long.  Trajectory t owns poses [t * T, (t + 1) * T),
  *                T = poses_per_traj, as in gem_costmap_score_trajectories.
- * Combining the critics (obstacle, path_dist, goal_dist, goal_front, alignment) into one cost stays with the caller.
+ * Combining the critics (obstacle, path_dist, goal_dist, goal_front, alignment) into one cost and picking the winner is
+ * gem_costmap_best_trajectory of gem_hip_critics.h, which also keeps goal_front's own grid (FRONT); these calls know PATH and GOAL.
  *
  *   gem_mapgrid_adjust_plan   host only, no handle and no device: *out_n = the adjusted plan's point count, and with out_xy not
  *                NULL its points (cap = the pairs out_xy holds; fewer than *out_n: GEM_ERR_INVALID, *out_n still set).

@@ -40,6 +40,11 @@
 //                    start off the map, cross noise grids with 253 / 254 / 255 cells and leave them again, and compares every
 //                    target_dist of both grids.  MapGridCostFunction::scoreTrajectory is not driven (it needs a Trajectory and the
 //                    planner's parameters): the scoring loop stays pinned on tests/mapgrid_ref.py alone
+//   critics gem_critics_select restates base_local_planner::SimpleScoredSamplingPlanner (simple_scored_sampling_planner.cpp:
+//                    scoreTrajectory with its early exit, findBestTrajectory; include/gem_hip_critics.h; tests/critics_ref.py restates the
+//                    same contract in plain Python).  The row feeds a real planner seeded score tables through a table-driven
+//                    TrajectoryCostFunction and a generator that numbers its trajectories, and compares the winner's index and cost.
+//                    The critics' own scores are the foot and mapgrid rows'; ObstacleCostFunction and MapGridCostFunction are not driven
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -54,7 +59,8 @@
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
 // there, against the library's public headers as documented, and has not been through a compiler; neither have the octo row
-// (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner) and the mapgrid row (the same library).
+// (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner), the mapgrid row and the critics row (the
+// same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -91,6 +97,7 @@
 #include <costmap_2d/footprint.h>
 #include <base_local_planner/costmap_model.h>
 #include <base_local_planner/map_grid.h>
+#include <base_local_planner/simple_scored_sampling_planner.h>
 #include <geometry_msgs/PoseStamped.h>
 #include <geometry_msgs/Point.h>
 #include <octomap/ColorOcTree.h>
@@ -802,6 +809,55 @@ int check_mapgrid(uint32_t seed)
     return 0;
 }
 
+// ---- critics -------------------------------------------------------------------------------------------------------------------
+// Seeded score tables through a real SimpleScoredSamplingPlanner (its early exit included) against gem_critics_select.
+struct TableGenerator : base_local_planner::TrajectorySampleGenerator {
+    long long n = 0, next = 0;
+    bool hasMoreTrajectories() override { return next < n; }
+    bool nextTrajectory(base_local_planner::Trajectory& traj) override
+    {
+        traj.resetPoints();
+        traj.xv_ = (double)next++;                                       // the trajectory's number travels in its velocity sample
+        return true;
+    }
+};
+struct TableCost : base_local_planner::TrajectoryCostFunction {
+    const double* row = nullptr;
+    bool prepare() override { return true; }
+    double scoreTrajectory(base_local_planner::Trajectory& traj) override { return row[(long long)traj.xv_]; }
+};
+
+int check_critics(uint32_t seed)
+{
+    std::mt19937 rng(seed);
+    for (int k = 0; k < 400; ++k) {
+        const int nc = 1 + (int)(rng() % GEM_CRITIC_MAX);
+        const long long nt = k % 40 == 7 ? 0 : 1 + (long long)(rng() % 200);
+        std::vector<gem_critic> critics((size_t)nc);
+        std::vector<double> scores((size_t)nc * (size_t)nt);
+        for (int c = 0; c < nc; ++c) critics[(size_t)c] = gem_critic{GEM_CRITIC_EXTERNAL, 0, 0, c, (double)(rng() % 9) / 4.0, 0.0};
+        for (double& v : scores) v = rng() % 10 == 0 ? -(double)(1 + rng() % 7) : (double)(rng() % 12) / 4.0;      // quarters: exact sums, many ties
+        std::vector<TableCost> costs((size_t)nc);
+        std::vector<base_local_planner::TrajectoryCostFunction*> list;
+        for (int c = 0; c < nc; ++c) {
+            costs[(size_t)c].row = scores.data() + (size_t)c * (size_t)nt;
+            costs[(size_t)c].setScale(critics[(size_t)c].scale);
+            list.push_back(&costs[(size_t)c]);
+        }
+        TableGenerator gen;
+        gen.n = nt;
+        std::vector<base_local_planner::TrajectorySampleGenerator*> gens{&gen};
+        base_local_planner::SimpleScoredSamplingPlanner planner(gens, list);
+        base_local_planner::Trajectory best;
+        const bool found = planner.findBestTrajectory(best);
+        gem_best_trajectory got{};
+        CHECK_GEM(gem_critics_select(critics.data(), nc, scores.empty() ? nullptr : scores.data(), nt, nullptr, &got));
+        if (found != (got.index >= 0)) report("critics: a winner was found by one side only", k, (double)got.index, (double)found);
+        else if (found && ((long long)best.xv_ != got.index || best.cost_ != got.cost)) report("critics: the winner or its cost differs", k, got.cost, best.cost_);
+    }
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -884,8 +940,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_octo(seed + 6u);
     if (rc == 0) rc = check_foot(seed + 7u);
     if (rc == 0) rc = check_mapgrid(seed + 8u);
+    if (rc == 0) rc = check_critics(seed + 9u);
     if (rc) return rc;
     if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all nine rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
+    std::printf("all ten rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
     return 0;
 }
