@@ -267,6 +267,38 @@ CRITICS_SIGNATURES = {
     "gem_costmap_best_trajectory_device": (c_int, _BEST_ARGS),
     "gem_critics_select": (c_int, [POINTER(Critic), c_int, POINTER(c_double), c_longlong, POINTER(c_double), POINTER(BestTrajectory)]),
 }
+# include/gem_hip_trajgen.h (DWA's sampled trajectories: plan, host twin, generation on the device, dwa_best; gem_hip.h includes it)
+TRAJGEN_MAX_LIST = 256
+OSC_FORWARD_POS_ONLY, OSC_FORWARD_NEG_ONLY, OSC_STRAFE_POS_ONLY, OSC_STRAFE_NEG_ONLY, OSC_ROT_POS_ONLY, OSC_ROT_NEG_ONLY = 1, 2, 4, 8, 16, 32
+
+
+class TrajgenLimits(C.Structure):
+    _fields_ = [(n, c_double) for n in ("max_vel_x", "min_vel_x", "max_vel_y", "min_vel_y", "max_vel_theta", "min_vel_theta", "max_vel_trans",
+                                        "min_vel_trans", "acc_lim_x", "acc_lim_y", "acc_lim_theta")]
+
+
+class TrajgenConfig(C.Structure):
+    _fields_ = [("sim_time", c_double), ("sim_granularity", c_double), ("angular_sim_granularity", c_double), ("sim_period", c_double),
+                ("use_dwa", c_int), ("discretize_by_time", c_int), ("continued_acceleration", c_int), ("oscillation_flags", c_int),
+                ("vsamples", c_int * 3), ("reserved", c_int)]
+
+
+class DwaPlan(C.Structure):
+    _fields_ = [("limits", TrajgenLimits), ("config", TrajgenConfig), ("n_x", c_int), ("n_y", c_int), ("n_th", c_int), ("max_steps", c_int),
+                ("n_traj", c_longlong), ("samples", c_float * TRAJGEN_MAX_LIST)]
+
+
+_F3 = POINTER(c_float)
+_DWA_ARGS = [c_void_p, c_int, POINTER(Critic), c_int, POINTER(DwaPlan), _F3, _F3, c_int, POINTER(c_double), c_int, c_void_p, c_void_p]
+TRAJGEN_SIGNATURES = {
+    "gem_trajgen_plan": (c_int, [POINTER(TrajgenLimits), POINTER(TrajgenConfig), _F3, _F3, _F3, POINTER(DwaPlan)]),
+    "gem_trajgen_generate": (c_int, [POINTER(DwaPlan), _F3, _F3, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "gem_trajgen_velocity": (c_int, [POINTER(DwaPlan), _F3, c_longlong, _F3]),
+    "gem_trajgen_sincos": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p]),
+    "gem_trajgen_generate_device": (c_int, [c_void_p, POINTER(DwaPlan), _F3, _F3, c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "gem_costmap_dwa_best": (c_int, _DWA_ARGS),
+    "gem_costmap_dwa_best_device": (c_int, _DWA_ARGS),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -293,7 +325,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES,                                **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1416,6 +1416,34 @@ class Costmap:
         res = (int(best.index), float(best.cost), int(best.n_valid))
         return res + (tot,) if totals else res
 
+    # -- DWA's sampled trajectories (gem_hip_trajgen.h) ------------------------------------------------------------------------------
+    def dwa_best(self, critics, plan, pos, vel, poses_per_traj: int, spec, totals: bool = False, device: bool = False):
+        """SimpleTrajectoryGenerator's trajectories of `plan` (trajgen_plan) from the state pos = (x, y, theta), vel = (vx, vy, vtheta),
+        generated on the device into arenas of the handle, then best_trajectory over them: an external critic's column 0 / 1 is the
+        generated oscillation / twirling score.  Host form: (index, cost, n_valid), or with totals (index, cost, n_valid, float64
+        totals); the call waits.  device=True: an int64 device tensor [4] as best_trajectory's device form leaves it (with totals:
+        that and a float64 device tensor), only enqueued.  trajectory_velocity(plan, vel, index) is the winner's command."""
+        T = int(poses_per_traj)
+        nt = int(plan.n_traj)
+        cs = (_lib.Critic * max(len(critics), 1))(*critics)
+        ks, ps, nv = self._spec(spec if spec is not None else [])
+        p3, v3 = _float3(pos), _float3(vel)
+        if device:
+            import torch
+            dev = torch.device("cuda")
+            best = torch.empty((4,), dtype=torch.int64, device=dev)
+            tot = torch.empty((nt,), dtype=torch.float64, device=dev) if totals else None
+            self.map._hold(best, tot)
+            self._call("gem_costmap_dwa_best_device", cs, len(critics), C.byref(plan), p3, v3, T, ps, nv,
+                       C.c_void_p(tot.data_ptr()) if totals and nt else None, C.c_void_p(best.data_ptr()))
+            return (best, tot) if totals else best
+        best = _lib.BestTrajectory(-9, -9, -9.0, -9)
+        tot = np.zeros(nt, np.float64) if totals else None
+        self._call("gem_costmap_dwa_best", cs, len(critics), C.byref(plan), p3, v3, T, ps, nv,
+                   tot.ctypes.data_as(C.c_void_p) if totals and nt else None, C.byref(best))
+        res = (int(best.index), float(best.cost), int(best.n_valid))
+        return res + (tot,) if totals else res
+
 
 
 def inflation_table(resolution: float, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0):
@@ -1527,3 +1555,87 @@ def select_trajectory(critics, scores):
                               tot.ctypes.data_as(C.POINTER(C.c_double)) if nt else None, C.byref(best)) != _lib.GEM_OK:
         raise ValueError("select_trajectory: 1 .. 8 critics, every scale finite and not negative")
     return int(best.index), float(best.cost), int(best.n_valid), tot
+
+
+# ---- DWA's sampled trajectories (gem_hip_trajgen.h) ---------------------------------------------------------------------------------
+def _float3(v, n: int = 3):
+    a = [float(x) for x in np.asarray(v, np.float32).reshape(-1)]
+    if len(a) != n:
+        raise ValueError(f"expected {n} values")
+    return (C.c_float * n)(*a)
+
+
+TRAJGEN_LIMITS = ("max_vel_x", "min_vel_x", "max_vel_y", "min_vel_y", "max_vel_theta", "min_vel_theta", "max_vel_trans", "min_vel_trans",
+                  "acc_lim_x", "acc_lim_y", "acc_lim_theta")
+
+
+def trajgen_plan(limits: dict, config: dict, pos, vel, goal=(0.0, 0.0)) -> "_lib.DwaPlan":
+    """SimpleTrajectoryGenerator::initialise (gem_trajgen_plan; host only, no device): the velocity window and the three sample lists
+    for the state pos / vel.  limits: the eleven doubles of TRAJGEN_LIMITS; config: sim_time, sim_granularity, angular_sim_granularity,
+    sim_period, use_dwa, discretize_by_time, continued_acceleration, oscillation_flags, vsamples = (nx, ny, nth).  The plan's n_traj,
+    n_x / n_y / n_th, samples and max_steps (the poses_per_traj a call needs at least) can be read from it."""
+    lib = _lib.load()
+    L = _lib.TrajgenLimits(*[float(limits[k]) for k in TRAJGEN_LIMITS])
+    c = _lib.TrajgenConfig(float(config["sim_time"]), float(config["sim_granularity"]), float(config.get("angular_sim_granularity", 0.0)),
+                           float(config["sim_period"]), int(bool(config.get("use_dwa", True))), int(bool(config.get("discretize_by_time", False))),
+                           int(bool(config.get("continued_acceleration", False))), int(config.get("oscillation_flags", 0)),
+                           (C.c_int * 3)(*[int(v) for v in config["vsamples"]]), 0)
+    plan = _lib.DwaPlan()
+    if lib.gem_trajgen_plan(C.byref(L), C.byref(c), _float3(pos), _float3(vel), _float3(goal, 2), C.byref(plan)) != _lib.GEM_OK:
+        raise ValueError("trajgen_plan: a parameter that is not finite, a time or granularity <= 0, unknown oscillation bits, or lists "
+                         "of more than 256 values in sum")
+    return plan
+
+
+def plan_lists(plan):
+    """the plan's three float32 lists (x, y, theta)"""
+    a = np.ctypeslib.as_array(plan.samples).copy()
+    return a[:plan.n_x], a[plan.n_x:plan.n_x + plan.n_y], a[plan.n_x + plan.n_y:plan.n_x + plan.n_y + plan.n_th]
+
+
+def generate_trajectories(plan, pos, vel, poses_per_traj: int, elevation_map=None, fill=None):
+    """SimpleTrajectoryGenerator's trajectories of every sample of the plan: (poses float64 [n_traj * poses_per_traj, 4], traj_len int32
+    [n_traj], ext float64 [2, n_traj] = oscillation | twirling, velocities float32 [n_traj, 3]).  Slot t is the sample; a sample that is
+    not generated has length 0 and its pose slots, like the slots past a length, keep `fill` (None: zeros).  Without elevation_map the
+    host twin (gem_trajgen_generate) into numpy arrays; with one, the kernel into device tensors, only enqueued
+    (gem_trajgen_generate_device)."""
+    T, nt = int(poses_per_traj), int(plan.n_traj)
+    p3, v3 = _float3(pos), _float3(vel)
+    if elevation_map is not None:
+        import torch
+        m = elevation_map
+        dev = torch.device("cuda")
+        mk = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev) if fill is None else torch.full(shape, fill, dtype=dt, device=dev)
+        poses, lens, ext, vels = mk((max(nt * T, 0), 4), torch.float64), mk((nt,), torch.int32), mk((2, nt), torch.float64), mk((nt, 3), torch.float32)
+        m._hold(poses, lens, ext, vels)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+        m._check(m._lib.gem_trajgen_generate_device(m._h, C.byref(plan), p3, v3, ptr(poses), ptr(lens), ptr(ext), ptr(vels), T), "gem_trajgen_generate_device")
+        return poses, lens, ext, vels
+    lib = _lib.load()
+    mk = lambda shape, dt: np.zeros(shape, dt) if fill is None else np.full(shape, fill, dt)
+    poses, lens, ext, vels = mk((max(nt * T, 0), 4), np.float64), mk((nt,), np.int32), mk((2, nt), np.float64), mk((nt, 3), np.float32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    if lib.gem_trajgen_generate(C.byref(plan), p3, v3, ptr(poses), ptr(lens), ptr(ext), ptr(vels), T) != _lib.GEM_OK:
+        raise ValueError("generate_trajectories: a plan trajgen_plan did not make, a state that is not finite, poses_per_traj below the plan's "
+                         "max_steps or outside 1 .. 2^20, more than 2^31 - 2 pose slots, or |theta| beyond 64 pi")
+    return poses, lens, ext, vels
+
+
+def trajectory_velocity(plan, vel, index: int):
+    """(xv, yv, thetav) of sample `index` of the plan: the command of dwa_best's winner (gem_trajgen_velocity; host only)"""
+    lib = _lib.load()
+    out = (C.c_float * 3)()
+    if lib.gem_trajgen_velocity(C.byref(plan), _float3(vel), int(index), out) != _lib.GEM_OK:
+        raise ValueError("trajectory_velocity: an index outside the plan's samples, or a plan trajgen_plan did not make")
+    return float(out[0]), float(out[1]), float(out[2])
+
+
+def contract_sincos(angles):
+    """(sin, cos) of float64 angles by the contract's routine (gem_trajgen_sincos; host only): what the kernel and its twin evaluate"""
+    lib = _lib.load()
+    a = np.ascontiguousarray(angles, np.float64).reshape(-1)
+    s, c = np.zeros_like(a), np.zeros_like(a)
+    ptr = lambda v: v.ctypes.data_as(C.c_void_p) if v.size else None
+    if lib.gem_trajgen_sincos(ptr(a), int(a.size), ptr(s), ptr(c)) != _lib.GEM_OK:
+        raise ValueError("contract_sincos")
+    return s, c

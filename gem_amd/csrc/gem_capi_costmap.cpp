@@ -134,7 +134,8 @@ void costmap_free(gem_handle* h)
     if (h->stream) hipStreamSynchronize(h->stream);
     for (auto& m : c.map) free_map(m);
     for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
-                     &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best}) {
+                     &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best,
+                     &c.tg_pose, &c.tg_len, &c.tg_ext}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

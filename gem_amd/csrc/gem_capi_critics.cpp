@@ -1,6 +1,6 @@
 // gem_capi_critics.cpp -- the best-trajectory entry points of include/gem_hip_critics.h: gem_costmap_best_trajectory / _device and the
 // host-only gem_critics_select.  The kernels are in gem_critics.hip; the FRONT grid's entries are with the other grids in
-// gem_capi_mapgrid.cpp.
+// gem_capi_mapgrid.cpp.  critics_prepare -- the checks and the argument block -- is shared with gem_costmap_dwa_best (gem_capi_trajgen.cpp).
 //
 // Everything is checked on the host before anything is enqueued or written.  The critic list and the footprint spec travel in the
 // kernel arguments.  The first pass's candidates (Costmaps::cr_cand) and the host-array form's staging (cr_pose, cr_len, cr_ext,
@@ -45,26 +45,14 @@ double combine(const gem_critic* c, int n_critics, const double* scores, long lo
 
 bool scale_ok(double s) { return std::isfinite(s) && s >= 0.0; }
 
-struct Call {
-    const char* what;
-    const gem_critic* critics;
-    int n_critics;
-    const gem_footprint_pose* poses;
-    const int* traj_len;
-    long long n_traj;
-    int T;
-    const double* spec_xy;
-    int n_vertices;
-    const double* ext;
-    int n_ext;
-    double* out_total;
-    gem_best_trajectory* out_best;
-    bool on_device;
-};
+using Call = CriticsCall;
 
 int bad(gem_handle* h, const Call& c, const char* why) { return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": " + why).c_str()); }
 
-int best(gem_handle* h, int id, const Call& c)
+} // namespace
+
+// the checks of a best-trajectory call, the candidates' arena and the kernel's argument block with everything but the caller's arrays
+int gemi::critics_prepare(gem_handle* h, int id, const CriticsCall& c, CriticsArgs& a, FootSpec& spec, CostGeom& geom)
 {
     if (h->tp_x) return bad(h, c, "not on a handle with a communicator");
     if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used) return bad(h, c, "no such costmap");
@@ -74,10 +62,10 @@ int best(gem_handle* h, int id, const Call& c)
     if (c.n_traj < 0 || c.n_traj > kMaxPoses / c.T) return bad(h, c, "a negative count, or more than 2^31 - 2 poses");
     if (c.n_ext < 0) return bad(h, c, "a negative column count");
     if (!c.out_best) return bad(h, c, "out_best is NULL");
-    if (c.n_traj > 0 && !c.poses) return bad(h, c, "a NULL array with a non-zero count");
+    if (c.n_traj > 0 && !c.poses && !c.own_arrays) return bad(h, c, "a NULL array with a non-zero count");
 
-    CriticsArgs a{};
-    FootSpec spec{};
+    a = CriticsArgs{};
+    spec = FootSpec{};
     int obstacles = 0;
     for (int k = 0; k < c.n_critics; ++k) {
         const gem_critic& q = c.critics[k];
@@ -104,7 +92,7 @@ int best(gem_handle* h, int id, const Call& c)
         } else if (q.kind == GEM_CRITIC_EXTERNAL) {
             if (q.flags) return bad(h, c, "unknown flag bits of an EXTERNAL critic");
             if (q.column < 0 || q.column >= c.n_ext) return bad(h, c, "an EXTERNAL critic's column outside 0 .. n_ext_columns - 1");
-            if (c.n_traj > 0 && !c.ext) return bad(h, c, "a NULL array with a non-zero count");
+            if (c.n_traj > 0 && !c.ext && !c.own_arrays) return bad(h, c, "a NULL array with a non-zero count");
             d.column = q.column;
         } else {
             return bad(h, c, "an unknown kind of critic");
@@ -121,10 +109,24 @@ int best(gem_handle* h, int id, const Call& c)
     for (int s = 0; s < 3; ++s) a.dist[s] = static_cast<const int*>(m.mg_dist[s].p);
     a.cand = static_cast<CriticsCandidate*>(cm.cr_cand.p);
     a.n_traj = c.n_traj; a.T = c.T; a.n_critics = c.n_critics;
+    geom = geom_of(m);
+    return GEM_OK;
+}
+
+namespace {
+
+int best(gem_handle* h, int id, const Call& c)
+{
+    CriticsArgs a{};
+    FootSpec spec{};
+    CostGeom geom{};
+    int rc;
+    if ((rc = critics_prepare(h, id, c, a, spec, geom))) return rc;
+    auto& cm = h->costmap;
     if (c.on_device) {
         a.poses = reinterpret_cast<const FootPose*>(c.poses); a.traj_len = c.traj_len; a.ext = c.ext;
         a.out_total = c.out_total; a.out_best = reinterpret_cast<CriticsBest*>(c.out_best);
-        GEM_HIP(h, launch_critics(h->stream, geom_of(m), spec, a));
+        GEM_HIP(h, launch_critics(h->stream, geom, spec, a));
         return GEM_OK;
     }
     const size_t nt = (size_t)c.n_traj, pose_bytes = nt * (size_t)c.T * sizeof(FootPose);
@@ -143,7 +145,7 @@ int best(gem_handle* h, int id, const Call& c)
     a.ext = static_cast<const double*>(cm.cr_ext.p);
     a.out_total = c.out_total && nt ? static_cast<double*>(cm.cr_total.p) : nullptr;
     a.out_best = static_cast<CriticsBest*>(cm.cr_best.p);
-    GEM_HIP(h, launch_critics(h->stream, geom_of(m), spec, a));
+    GEM_HIP(h, launch_critics(h->stream, geom, spec, a));
     HostXfer down[2] = {{c.out_best, cm.cr_best.p, sizeof(CriticsBest)}, {c.out_total, cm.cr_total.p, nt * sizeof(double)}};
     return download_arrays(h, down, a.out_total ? 2 : 1, 0);
 }

@@ -31,6 +31,8 @@
 
 using namespace gem;
 
+namespace gem { struct CriticsArgs; struct FootSpec; struct CostGeom; }
+
 namespace gemi {
 
 extern thread_local std::string g_create_error;
@@ -323,6 +325,7 @@ struct gem_handle {
         // gem_costmap_best_trajectory* (gem_capi_critics.cpp): the first pass's candidates | the host-array form's poses, lengths, external
         // columns, totals and the 32-byte result
         Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
+        Arena tg_pose, tg_len, tg_ext;          // gem_costmap_dwa_best* (gem_capi_trajgen.cpp): the generated poses, lengths and the two external columns
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping
@@ -460,6 +463,27 @@ int history_check_room(gem_handle* h, long long n, const char* what);
 int history_reserve(gem_handle* h, long long extra);
 int history_append_device(gem_handle* h, const void* d_src, long long n);
 int history_blocks_culled(gem_handle* h, long long* out);      // the last gem_costmap_mark_history's count, downloaded
+// gem_capi_critics.cpp, for gem_costmap_dwa_best (gem_capi_trajgen.cpp): a best-trajectory call as its entry points describe it, and
+// its checks (GEM_ERR_INVALID, nothing enqueued), the candidates' arena and the kernel's argument block with everything but the
+// arrays.  own_arrays: poses, traj_len and ext are arenas of the handle that the caller binds afterwards (they may be NULL here).
+struct CriticsCall {
+    const char* what;
+    const gem_critic* critics;
+    int n_critics;
+    const gem_footprint_pose* poses;
+    const int* traj_len;
+    long long n_traj;
+    int T;
+    const double* spec_xy;
+    int n_vertices;
+    const double* ext;
+    int n_ext;
+    double* out_total;
+    gem_best_trajectory* out_best;
+    bool on_device;
+    bool own_arrays = false;
+};
+int critics_prepare(gem_handle* h, int id, const CriticsCall& c, gem::CriticsArgs& a, gem::FootSpec& spec, gem::CostGeom& geom);
 void costmap_free(gem_handle* h);               // gem_capi_costmap.cpp: every costmap of the handle and their shared arenas (gem_destroy)
 int voxel_reserve(gem_handle* h, long long max_points);   // gem_capi_voxel.cpp: the voxel arenas of a call of max_points points
 int settle(gem_handle* h);

@@ -691,6 +691,61 @@ inline BestTrajectory selectTrajectory(const std::vector<Critic>& critics, const
     return b;
 }
 
+// DWA's sampled trajectories (gem_hip_trajgen.h): SimpleTrajectoryGenerator's limits and configuration, the plan (the velocity window's
+// three sample lists), the host twin of the generating kernel, and the velocity of a sample.  The contract is restated there, unverified
+// against base_local_planner.
+struct TrajectoryLimits : gem_trajgen_limits {
+    TrajectoryLimits() : gem_trajgen_limits{0.55, 0.0, 0.1, -0.1, 1.0, 0.4, 0.55, 0.1, 2.5, 2.5, 3.2} {}      // dwa_local_planner's defaults
+};
+struct TrajectoryConfig : gem_trajgen_config {
+    TrajectoryConfig() : gem_trajgen_config{1.7, 0.025, 0.1, 0.05, 1, 0, 0, 0, {6, 1, 20}, 0} {}
+};
+struct TrajectoryState { float pos[3], vel[3]; };            // (x, y, theta) and (vx, vy, vtheta)
+struct TrajectoryPlan : gem_dwa_plan {
+    TrajectoryPlan() : gem_dwa_plan{} {}
+    // initialise: the window and the lists for this state; goal is read without use_dwa only
+    TrajectoryPlan(const TrajectoryLimits& limits, const TrajectoryConfig& config, const TrajectoryState& s, float goalX = 0.f, float goalY = 0.f)
+        : gem_dwa_plan{}
+    {
+        const float goal[2] = {goalX, goalY};
+        if (gem_trajgen_plan(&limits, &config, s.pos, s.vel, goal, this) != GEM_OK)
+            throw Error(GEM_ERR_INVALID, "TrajectoryPlan: a parameter that is not finite, a time or granularity <= 0, unknown oscillation bits, or lists of more than 256 values");
+    }
+    std::vector<float> list(int axis) const                  // 0: x, 1: y, 2: theta
+    {
+        const int at[4] = {0, n_x, n_x + n_y, n_x + n_y + n_th};
+        return std::vector<float>(samples + at[axis], samples + at[axis + 1]);
+    }
+    // (xv, yv, thetav) of a sample: the command of dwaBest's winner
+    std::array<float, 3> velocity(const TrajectoryState& s, long long index) const
+    {
+        std::array<float, 3> v{};
+        if (gem_trajgen_velocity(this, s.vel, index, v.data()) != GEM_OK) throw Error(GEM_ERR_INVALID, "TrajectoryPlan::velocity: no such sample");
+        return v;
+    }
+};
+static_assert(sizeof(TrajectoryPlan) == sizeof(gem_dwa_plan), "a TrajectoryPlan is a gem_dwa_plan");
+struct Trajectories {
+    int posesPerTrajectory = 0;
+    std::vector<FootprintPose> poses;                        // [trajectories * posesPerTrajectory]: slot t is sample t
+    std::vector<int> length;                                 // poses each trajectory uses; 0: not generated
+    std::vector<double> ext;                                 // [2][trajectories]: oscillation | twirling
+    std::vector<float> velocity;                             // [trajectories][3]: xv, yv, thetav
+};
+// generateTrajectory for every sample of the plan on the host (gem_trajgen_generate: the twin of the kernel); posesPerTrajectory 0: the
+// plan's max_steps
+inline Trajectories generateTrajectories(const TrajectoryPlan& plan, const TrajectoryState& s, int posesPerTrajectory = 0)
+{
+    Trajectories out;
+    out.posesPerTrajectory = posesPerTrajectory > 0 ? posesPerTrajectory : (plan.max_steps > 0 ? plan.max_steps : 1);
+    const size_t n = static_cast<size_t>(plan.n_traj > 0 ? plan.n_traj : 0);
+    out.poses.resize(n * static_cast<size_t>(out.posesPerTrajectory));
+    out.length.assign(n, 0); out.ext.assign(2 * n, 0.0); out.velocity.assign(3 * n, 0.f);
+    if (gem_trajgen_generate(&plan, s.pos, s.vel, out.poses.data(), out.length.data(), out.ext.data(), out.velocity.data(), out.posesPerTrajectory) != GEM_OK)
+        throw Error(GEM_ERR_INVALID, "generateTrajectories: a plan or state the call refuses, posesPerTrajectory below the plan's max_steps, or |theta| beyond 64 pi");
+    return out;
+}
+
 class Costmap {
 public:
     static constexpr unsigned char FREE_SPACE = 0, INSCRIBED_INFLATED_OBSTACLE = 253, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
@@ -890,6 +945,20 @@ public:
                                                ext.empty() ? nullptr : ext.data(), n ? static_cast<int>(ext.size() / n) : 0,
                                                totals && n ? totals->data() : nullptr, &b),
                    "gem_costmap_best_trajectory");
+        return b;
+    }
+    // The trajectories of the plan generated on the device (gem_hip_trajgen.h), then bestTrajectory over them: an external critic's
+    // column 0 / 1 is the generated oscillation / twirling score.  One call, three launches, 32 bytes back.  Waits.
+    BestTrajectory dwaBest(const std::vector<Critic>& critics, const TrajectoryPlan& plan, const TrajectoryState& s, int posesPerTrajectory,
+                           const std::vector<FootprintPoint>& spec, std::vector<double>* totals = nullptr) const
+    {
+        const size_t n = static_cast<size_t>(plan.n_traj > 0 ? plan.n_traj : 0);
+        if (totals) totals->assign(n, 0.0);
+        BestTrajectory b;
+        map_.check(gem_costmap_dwa_best(map_.handle(), id_, critics.empty() ? nullptr : critics.data(), static_cast<int>(critics.size()), &plan,
+                                        s.pos, s.vel, posesPerTrajectory, xy(spec), static_cast<int>(spec.size()),
+                                        totals && n ? totals->data() : nullptr, &b),
+                   "gem_costmap_dwa_best");
         return b;
     }
 

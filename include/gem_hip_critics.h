@@ -31,6 +31,7 @@
  *                the flags GEM_MAPGRID_STOP_ON_FAILURE | GEM_MAPGRID_SUM.  yshift and Product stay unprovided, as there.
  *       GEM_CRITIC_EXTERNAL   ext[column * n_traj + t]: the caller's raw score.  This is how the critics that read velocities only
  *                enter at their place in the order (oscillation first, twirling last, prefer-forward).  A negative value rejects.
+ *                (gem_hip_trajgen.h generates the trajectories and these two columns on the device: gem_costmap_dwa_best.)
  *                Fields a kind does not read (grid, column, xshift) are ignored; its flags are checked.
  *   combination  for trajectory t, every operation in double and rounded on its own:
  *                    total = 0.0

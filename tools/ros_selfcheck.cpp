@@ -45,6 +45,15 @@
 //                    same contract in plain Python).  The row feeds a real planner seeded score tables through a table-driven
 //                    TrajectoryCostFunction and a generator that numbers its trajectories, and compares the winner's index and cost.
 //                    The critics' own scores are the foot and mapgrid rows'; ObstacleCostFunction and MapGridCostFunction are not driven
+//   trajgen gem_trajgen_plan / gem_trajgen_generate restate base_local_planner::SimpleTrajectoryGenerator (simple_trajectory_generator.cpp:
+//                    initialise, generateTrajectory, computeNewVelocities; velocity_iterator.h; include/gem_hip_trajgen.h;
+//                    tests/trajgen_ref.py restates the same contract in plain Python).  The row drives a real generator over seeded
+//                    states with and without use_dwa, by time and by distance, and compares, sample by sample: whether it was
+//                    generated, the number of points, every (x, y, theta) as float bits -- x and y within num_steps ulps when the
+//                    cos overload the library picks is not the double one, which the row reports FIRST and on its own -- and
+//                    (xv, yv, thetav).  It also reports the deviation the header names: hypot against sqrt(x * x + y * y).
+//                    OscillationCostFunction and TwirlingCostFunction are not driven (they need the planner's state); their rules
+//                    are two lines each
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -59,8 +68,9 @@
 //
 // It cannot be compiled where the test suite runs (no ROS, grid_map, costmap_2d, OpenCV or PCL there); the cost row was written
 // there, against the library's public headers as documented, and has not been through a compiler; neither have the octo row
-// (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner), the mapgrid row and the critics row (the
-// same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes).
+// (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner), the mapgrid row, the critics row and the trajgen
+// row (the same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes, the
+// trajgen row base_local_planner/simple_trajectory_generator.h and base_local_planner/local_planner_limits.h).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -858,6 +868,75 @@ int check_critics(uint32_t seed)
     return 0;
 }
 
+// ---- trajgen -------------------------------------------------------------------------------------------------------------------
+// Seeded states through a real SimpleTrajectoryGenerator against gem_trajgen_plan / gem_trajgen_generate.  The contract promotes the
+// float argument of the library's unqualified cos(pos[2]) to double; if the installed library picked the float overload, theta and
+// the counts still agree and x / y drift by rounding: that case is told apart and reported as what it is.
+int check_trajgen(uint32_t seed)
+{
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    bool overload_reported = false;
+    for (int k = 0; k < 200; ++k) {
+        gem_trajgen_limits lim{0.3 + 0.5 * u(rng), k % 3 == 0 ? -0.2 : 0.0, 0.1 * (k % 2), -0.1 * (k % 2), 0.5 + u(rng), 0.4 * u(rng),
+                               k % 5 == 0 ? -1.0 : 0.4 + 0.5 * u(rng), k % 7 == 0 ? -1.0 : 0.1 * u(rng), 1.0 + 2.0 * u(rng), 1.0 + 2.0 * u(rng), 1.0 + 3.0 * u(rng)};
+        gem_trajgen_config cfg{1.0 + u(rng), 0.025 + 0.05 * u(rng), 0.05 + 0.1 * u(rng), 0.05 + 0.05 * u(rng), k % 4 != 0, (k / 4) % 2, k % 4 == 0, 0,
+                               {1 + (int)(rng() % 8), 1 + (int)(rng() % 3), 1 + (int)(rng() % 12)}, 0};
+        const float pos[3] = {(float)(10.0 * u(rng) - 5.0), (float)(10.0 * u(rng) - 5.0), (float)(6.28 * u(rng) - 3.14)};
+        const float vel[3] = {(float)(lim.max_vel_x * u(rng)), (float)(0.05 * (k % 2) * (u(rng) - 0.5)), (float)(u(rng) - 0.5)};
+        const float goal[2] = {pos[0] + (float)(3.0 * u(rng)), pos[1] + (float)(3.0 * u(rng) - 1.5)};
+        base_local_planner::LocalPlannerLimits limits;
+        limits.max_vel_x = lim.max_vel_x; limits.min_vel_x = lim.min_vel_x; limits.max_vel_y = lim.max_vel_y; limits.min_vel_y = lim.min_vel_y;
+        limits.max_vel_theta = lim.max_vel_theta; limits.min_vel_theta = lim.min_vel_theta;
+        limits.max_vel_trans = lim.max_vel_trans; limits.min_vel_trans = lim.min_vel_trans;
+        limits.acc_lim_x = lim.acc_lim_x; limits.acc_lim_y = lim.acc_lim_y; limits.acc_lim_theta = lim.acc_lim_theta;
+        base_local_planner::SimpleTrajectoryGenerator gen;
+        gen.setParameters(cfg.sim_time, cfg.sim_granularity, cfg.angular_sim_granularity, cfg.use_dwa != 0, cfg.sim_period);
+        gen.initialise(Eigen::Vector3f(pos[0], pos[1], pos[2]), Eigen::Vector3f(vel[0], vel[1], vel[2]), Eigen::Vector3f(goal[0], goal[1], 0.f), &limits,
+                       Eigen::Vector3f((float)cfg.vsamples[0], (float)cfg.vsamples[1], (float)cfg.vsamples[2]), cfg.discretize_by_time != 0);
+        gem_dwa_plan plan{};
+        CHECK_GEM(gem_trajgen_plan(&lim, &cfg, pos, vel, goal, &plan));
+        const int T = plan.max_steps > 0 ? plan.max_steps : 1;
+        std::vector<gem_footprint_pose> poses((size_t)plan.n_traj * (size_t)T);
+        std::vector<int> len((size_t)plan.n_traj);
+        std::vector<double> ext(2 * (size_t)plan.n_traj);
+        std::vector<float> v(3 * (size_t)plan.n_traj);
+        CHECK_GEM(gem_trajgen_generate(&plan, pos, vel, poses.data(), len.data(), ext.data(), v.data(), T));
+        long long t = 0;
+        while (gen.hasMoreTrajectories()) {
+            base_local_planner::Trajectory traj;
+            const bool generated = gen.nextTrajectory(traj);
+            if (t >= plan.n_traj) { report("trajgen: the library has more samples than the plan", k, (double)plan.n_traj, (double)t); break; }
+            if (generated != (len[(size_t)t] > 0)) { report("trajgen: a sample was generated by one side only", k, (double)len[(size_t)t], (double)generated); ++t; continue; }
+            if (generated) {
+                if ((int)traj.getPointsSize() != len[(size_t)t]) report("trajgen: num_steps differs (hypot against sqrt, or ceil)", k, (double)len[(size_t)t], (double)traj.getPointsSize());
+                else {
+                    if ((float)traj.xv_ != v[3 * (size_t)t] || (float)traj.yv_ != v[3 * (size_t)t + 1] || (float)traj.thetav_ != v[3 * (size_t)t + 2])
+                        report("trajgen: (xv, yv, thetav) differs", k, (double)v[3 * (size_t)t], traj.xv_);
+                    for (int i = 0; i < len[(size_t)t]; ++i) {
+                        double x, y, th;
+                        traj.getPoint((unsigned)i, x, y, th);
+                        const gem_footprint_pose& p = poses[(size_t)t * (size_t)T + (size_t)i];
+                        if ((float)x != (float)p.x || (float)y != (float)p.y) {
+                            const double ulp = std::ldexp(1.0, std::ilogb(std::fmax(std::fabs(x), std::fabs(p.x)) + 1e-30) - 23);
+                            const bool drift = std::fabs(x - p.x) <= len[(size_t)t] * ulp + 1e-12;
+                            if (drift && !overload_reported) {
+                                std::printf("trajgen: x / y agree within num_steps float ulps but not to the bit: the library's cos(pos[2]) is NOT the double overload on a double-promoted argument (or its libm differs from the contract's cosine by more than its 2^-53)\n");
+                                overload_reported = true;
+                                ++g_failures;
+                            } else if (!drift) report("trajgen: a pose differs", k, p.x, x);
+                            break;
+                        }
+                    }
+                }
+            }
+            ++t;
+        }
+        if (t != plan.n_traj) report("trajgen: the plan has more samples than the library", k, (double)plan.n_traj, (double)t);
+    }
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -941,8 +1020,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_foot(seed + 7u);
     if (rc == 0) rc = check_mapgrid(seed + 8u);
     if (rc == 0) rc = check_critics(seed + 9u);
+    if (rc == 0) rc = check_trajgen(seed + 10u);
     if (rc) return rc;
     if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all ten rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
+    std::printf("all eleven rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
     return 0;
 }
