@@ -462,7 +462,11 @@ constexpr bool kFrameSizedSort = GEM_FRAME_SIZED_SORT != 0;          // (build d
 #ifndef GEM_FRAME_RANK_ONE
 #define GEM_FRAME_RANK_ONE 1
 #endif
-constexpr bool kFrameRankOne = GEM_FRAME_RANK_ONE != 0;              // (build define: 0 = every tile ranks kFramePB / 256 slots per thread, for A/B builds)
+#ifndef GEM_FRAME_LIGHT
+#define GEM_FRAME_LIGHT 1
+#endif
+constexpr bool kFrameLight = GEM_FRAME_LIGHT != 0;                   // (build define: 0 = every tile takes the cell-centric path, for A/B builds)
+constexpr bool kFrameRankOne = GEM_FRAME_RANK_ONE != 0;             // (build define: 0 = every tile ranks kFramePB / 256 slots per thread, for A/B builds)
 constexpr int kFrameWG = 6;                         // workgroups per CU the register budget is set for
 // LDS: rank rows [256] x 8 u16 | generic lists head / tail [256][4] u16 (aliased), cell of a slot [PB] u16, next [PB] u16, stage [PB] x 16 B, misc
 constexpr size_t kFrameLds = 256 * 16 + kFramePB * 2 * 2 + kFramePB * 16 + 16;
@@ -1219,6 +1223,9 @@ __global__ __launch_bounds__(NT, fuse_list_waves(TS, NT, PB, ATTR, BATCH)) void 
 // (touched stamps, descriptor words, records).  A bucket holds records in the order the binning waves reserved them, so the
 // owner of a cell sorts its <= kRankMax records by point index (key = index << 10 | slot) instead of by slot.
 // One 16x16 tile of a single sweep, 256 threads, one cell per thread.
+//   LIGHT PATH (lean form, kFrameLight: at most 64 records in the tile, nothing queued for every cell): the count is branched on
+//     before any cell load; wave 0 alone, one lane per record of its own DMA, grouped by cell and ranked by point index across
+//     lanes -- see the path itself; an empty tile leaves there; a cell above kRankMax sends the workgroup on into the paths below;
 //   FAST PATH (at most kFramePB records in the tile and kRankMax per cell -- every tile of a C2 sweep): the records are in LDS
 //     after the first round trip (after a second one for tiles of more than kFrameSpec records), ranked per cell by an LDS atomic,
 //     and the owner sorts its <= 7 keys and runs the reference's recurrence (GPU:480-531) from registers;
@@ -1230,6 +1237,17 @@ __global__ __launch_bounds__(NT, fuse_list_waves(TS, NT, PB, ATTR, BATCH)) void 
 // has every word a tile reads before its chains are done in scalar registers when it calls this).
 // STAMPS: the cycle stamps of tools/frame_phases.py (a.dbg, thread 0) are compiled in -- the generic form and k_frame_stamped; the
 // lean production kernel carries none of it: no a.dbg, no stamp counter, no tid == 0 masks kept alive for them.
+// one step of the reference's recurrence (GPU:480-531) on a cell's registers; !live leaves them as they are
+template <bool LOWEST>
+__device__ __forceinline__ void frame_chain_step(float& ce, float& cs, float& lw, float h, float v, bool live, float mahal, float var_floor)
+{
+    float e2 = ce, s2 = cs;
+    (void)fuse_step(e2, s2, h, v, mahal, var_floor);
+    const bool fl = live && (!LOWEST || h != -1.0f);                     // GPU:482 (only LOWEST passes carry such records)
+    ce = fl ? e2 : ce; cs = fl ? s2 : cs;
+    if constexpr (LOWEST) { const float l2 = lowest_step(lw, h, v); lw = live ? l2 : lw; }
+}
+
 template <int FLAGS, bool STAMPS, class A>
 __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char* lds_raw)
 {
@@ -1255,6 +1273,11 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
     const int L = a.L;
     [[maybe_unused]] int dbg_k = 0;
 #define GEM_STAMP() do { if constexpr (STAMPS) { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + dbg_k++] = (unsigned long long)__builtin_readcyclecounter(); } } while (0)
+#define GEM_STAMP_END() do { if constexpr (STAMPS) { if (a.dbg && tid == 0) { \
+        a.dbg[(size_t)tile * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); \
+        a.dbg[(size_t)tile * 16 + 15] = (unsigned long long)block + 1ull; \
+        a.dbg[(size_t)tile * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      /* HW_REG_XCC_ID: the XCD's clock is its own */ \
+    } } } while (0)
     GEM_STAMP();                                                         // 0: start
     if constexpr (STAMPS) { if (a.dbg && tid == 0) a.dbg[(size_t)tile * 16 + 12] = (unsigned long long)__builtin_amdgcn_s_memrealtime(); }   // (100 MHz, one clock for the chip)
 
@@ -1267,6 +1290,88 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
         __builtin_amdgcn_global_load_lds(gsrc, ldst, 12, 0, 0);
     };
     dma((uint32_t)w * 64u);                                              // (inside the bucket whatever the count: kFrameSpec <= kFrameBucket)
+
+    // ---- LIGHT PATH (lean form): the count decides before any cell load is issued.  An empty tile leaves here; a tile of at
+    //      most 64 records is fused by wave 0 alone, one lane per RECORD instead of one thread per cell -- two thirds of a C2
+    //      sweep's tile workgroups hold 24 records in 21 of their 256 cells.  dense (queued increments, a dirty floor) touches
+    //      every cell and keeps the general path.
+    if constexpr (LEAN && kFrameLight) {
+        if (!a.dense && nrec <= 64u) {                                   // block-uniform; every branch on nrec, w and over below is wave-uniform
+            bool over = false;
+            if (nrec == 0) {
+                GEM_STAMP();
+            } else if (w != 0) {
+                __syncthreads();                                         // the one barrier of a light tile: waves 1-3 learn the verdict
+                over = __builtin_amdgcn_readfirstlane((int)misc[2]) != 0;
+            } else {
+                // all records of the tile are the 64 slots this wave's own DMA brought: its own vmcnt, no barrier
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                bool on = (uint32_t)lane < nrec;
+                const uint32_t z = stage[on ? lane : 0].z;
+                const uint32_t cell = z & 0xffu, idx = z >> 8;
+                const int row = row_base + (int)(cell >> TS), col = col_base + (int)(cell & (TE - 1));
+                on = on && row < a.row1 && row >= a.row0 && col < L;     // (the binning keeps no other record: a guard, not a case)
+                size_t g = 0, gl = 0;
+                if (on) {
+                    g = (size_t)row * L + col;
+                    if constexpr (LOWEST) {                              // (the geographic cell, as the general path computes it)
+                        int gr = row - a.start0, gc = col - a.start1;
+                        gr += gr < 0 ? L : 0; gc += gc < 0 ? L : 0;
+                        gl = (size_t)gr * L + gc;
+                    }
+                }
+                // the second round trip: the record's cell (off lanes read cell 0; duplicate addresses among lanes are fine)
+                float ce = a.elevation[g], cs = a.variance[g], lw = 0.0f;
+                if constexpr (LOWEST) lw = a.lowest[gl];
+                GEM_STAMP();                                             // 1: records arrived, cell loads issued
+                // ... and while those are in flight: the lanes of a cell, and the verdict (a cell above kRankMax: as before)
+                const uint64_t peers = wave_peers(on, cell, 2 * TS);
+                over = __ballot(__popcll(peers) > kRankMax) != 0;
+                if (lane == 0) misc[2] = over ? 1u : 0u;                 // (misc[0] / [1] are the general path's: it resets them unsynchronised)
+                __syncthreads();
+                if (!over) {                                             // wave-uniform
+                    GEM_STAMP();                                         // 2: grouped, verdict known
+                    // rank = peers with a smaller point index (the bucket is in reservation order); the group's lowest lane owns the cell
+                    uint32_t rank = 0;
+                    for (uint64_t m = peers & ~(1ull << lane); __ballot(m != 0) != 0; m &= m - 1) {      // wave-uniform: the largest group - 1 rounds
+                        const int j = m != 0 ? __ffsll((unsigned long long)m) - 1 : lane;
+                        const uint32_t other = (uint32_t)__builtin_amdgcn_ds_bpermute(j << 2, (int)idx);
+                        rank += (m != 0 && other < idx) ? 1u : 0u;
+                    }
+                    // the rank rows hand the records over in index order (written and read by this wave alone: LDS is in order per wave)
+                    if (on) rowp[cell * 8 + rank] = (uint16_t)lane;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    const bool owner = on && (peers & lanemask_lt()) == 0;
+                    const uint32_t n = owner ? (uint32_t)__popcll(peers) : 0u;
+                    const uint4 rw = *reinterpret_cast<const uint4*>(rowp + cell * 8);
+                    const uint32_t p[kRankMax] = {rw.x & 0xffffu, rw.x >> 16, rw.y & 0xffffu, rw.y >> 16, rw.z & 0xffffu, rw.z >> 16, rw.w & 0xffffu};
+                    GEM_STAMP();                                         // 3: ranked
+                    const float ce0 = ce, cs0 = cs;
+#pragma unroll
+                    for (int i = 0; i < kRankMax; ++i) {
+                        if (__ballot((uint32_t)i < n) == 0) break;       // wave-uniform
+                        const uint32_t sl = (uint32_t)i < n ? p[i] : 0u; // slot 0 is always a valid address
+                        frame_chain_step<LOWEST>(ce, cs, lw, __uint_as_float(stage[sl].x), __uint_as_float(stage[sl].y), (uint32_t)i < n, a.mahal, a.var_floor);
+                    }
+                    GEM_STAMP();                                         // 4: cells arrived, chains done
+                    if (cs < a.var_floor) cs = a.var_floor;
+                    if (owner) {
+                        if (__float_as_uint(ce) != __float_as_uint(ce0)) a.elevation[g] = ce;
+                        if (__float_as_uint(cs) != __float_as_uint(cs0)) a.variance[g] = cs;
+                        if constexpr (LOWEST) a.lowest[gl] = lw;         // (the general path rewrites the untouched cells with what it read)
+                    }
+                    if (lane == 0) a.bcount[tile] = 0u;                  // consumed (behind the barrier: every wave has its copy of the count)
+                    GEM_STAMP();                                         // 5: stores issued
+                    GEM_STAMP_END();
+                }
+            }
+            if (!over) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }    // (no LDS DMA outlives the workgroup)
+            // a cell of more than kRankMax records: all four waves go on into the general path, which ranks, overflows and reports
+            dbg_k = 1;
+        }
+    }
 
     const int c = tid;
     const int row = row_base + (c >> TS), col = col_base + (c & (TE - 1));
@@ -1333,13 +1438,7 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
         const uint4 rw = *reinterpret_cast<const uint4*>(rowp + tid * 8);
         const uint32_t n = rw.w >> 16;
         const uint32_t p[kRankMax] = {rw.x & 0xffffu, rw.x >> 16, rw.y & 0xffffu, rw.y >> 16, rw.z & 0xffffu, rw.z >> 16, rw.w & 0xffffu};
-        auto chain = [&](float h, float v, bool live) {                  // one step of the reference's recurrence (GPU:480-531)
-            float e2 = ce, s2 = cs;
-            (void)fuse_step(e2, s2, h, v, a.mahal, a.var_floor);
-            const bool fl = live && (!LOWEST || h != -1.0f);             // GPU:482 (only LOWEST passes carry such records)
-            ce = fl ? e2 : ce; cs = fl ? s2 : cs;
-            if constexpr (LOWEST) { const float l2 = lowest_step(lw, h, v); lw = live ? l2 : lw; }
-        };
+        auto chain = [&](float h, float v, bool live) { frame_chain_step<LOWEST>(ce, cs, lw, h, v, live, a.mahal, a.var_floor); };
         // N keys for a wave whose largest count is in [NMIN, min(N, kRankMax)]: entries at or beyond a lane's n stay ~0 and sort
         // behind its live keys, all of which are among the first N -- the order the full network gives
         auto owner = [&](auto size, auto least) {
@@ -1486,13 +1585,8 @@ __device__ __forceinline__ void frame_tile(const A& a, int block, unsigned char*
         }
     }
     GEM_STAMP();                                                         // 5: stores issued
-    if constexpr (STAMPS) {
-        if (a.dbg && tid == 0) {
-            a.dbg[(size_t)tile * 16 + 13] = (unsigned long long)__builtin_amdgcn_s_memrealtime();
-            a.dbg[(size_t)tile * 16 + 15] = (unsigned long long)block + 1ull;
-            a.dbg[(size_t)tile * 16 + 14] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20) + 1ull;      // HW_REG_XCC_ID: the XCD's clock is its own
-        }
-    }
+    GEM_STAMP_END();
+#undef GEM_STAMP_END
 #undef GEM_STAMP
 }
 

@@ -3,7 +3,7 @@
 previous sweep) and of every binning block (this sweep), put on a common clock per XCD (HW_REG_XCC_ID; the XCDs'
 counters are not synchronised, so every XCD's earliest stamp is its zero).
 
-    python tools/frame_phases.py [sweeps]
+    python tools/frame_phases.py [sweeps] [light=0]
 """
 import ctypes as C
 import sys
@@ -13,7 +13,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch
 from gem_amd import ElevationMap, synth, _lib
 
-n_sw = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+n_sw = next((int(a) for a in sys.argv[1:] if a.isdigit()), 8)
 wl = synth.config_c4(n_sweeps=n_sw)
 m = ElevationMap(wl.length, wl.resolution)
 lib = _lib.load()
@@ -84,10 +84,15 @@ if full.any():
     SPEC, MID = 256, 64
     print(f"weight classes (oracle): {int((nrec > SPEC).sum())} tiles above {SPEC} records, {int(((nrec > MID) & (nrec <= SPEC)).sum())} with {MID + 1}..{SPEC}, "
           f"{int(((nrec > 0) & (nrec <= MID)).sum())} with 1..{MID}; largest {int(nrec.max())}")
+    # a tile of at most MID records takes the light path (GEM_FRAME_LIGHT, the default; `light=0` as the last argument names the phases
+    # of a build without it): wave 0 alone, six stamps with their own meaning
+    light_names = ["count + own records, cell loads issued", "lanes grouped by cell, verdict, barrier", "ranks, rank rows", "cells arrived, chains", "stores"]
+    has_light = NS == 6 and "light=0" not in sys.argv[1:]
     for label, sel in ((f"tiles above {SPEC} records", full & (nrec > SPEC)), (f"tiles of at most {MID} records", full & (nrec > 0) & (nrec <= MID))):
         if sel.any():
             dh = np.diff(tiles[sel, :NS], axis=1)
-            print(f"{label}: {int(sel.sum())} | mean cycles per phase: {dict(zip(names, dh.mean(0).astype(int).tolist()))} | mean total {int(dur[sel].mean())} "
+            names_ = light_names if has_light and label.startswith("tiles of at most") else names
+            print(f"{label}{' (light path)' if names_ is light_names else ''}: {int(sel.sum())} | mean cycles per phase: {dict(zip(names_, dh.mean(0).astype(int).tolist()))} | mean total {int(dur[sel].mean())} "
                   f"| mean life {(te[sel] - ts[sel]).mean():.2f} us | last end {te[sel].max():.2f} us")
 print("tiles that left early (no record) or took another path:", int((nst < NS).sum()), "mean life", int(dur[nst < NS].mean()) if (nst < NS).any() else 0)
 if len(bins):
