@@ -16,7 +16,7 @@ CSRC = ROOT / "csrc"
 LIBDIR = ROOT / "lib"
 LIB = LIBDIR / "libgem_hip.so"
 
-SOURCES = [CSRC / "gem_kernels.hip", CSRC / "gem_sort.hip", CSRC / "gem_capi.cpp", CSRC / "gem_capi_core.cpp", CSRC / "gem_capi_pipeline.cpp", CSRC / "gem_capi_comm.cpp",
+SOURCES = [CSRC / "gem_kernels.hip", CSRC / "gem_frame_lean.hip", CSRC / "gem_sort.hip", CSRC / "gem_capi.cpp", CSRC / "gem_capi_core.cpp", CSRC / "gem_capi_pipeline.cpp", CSRC / "gem_capi_comm.cpp",
            CSRC / "gem_clean.hip", CSRC / "gem_capi_clean.cpp", CSRC / "gem_local.hip", CSRC / "gem_capi_local.cpp",
            CSRC / "gem_voxel.hip", CSRC / "gem_capi_voxel.cpp", CSRC / "gem_global.hip", CSRC / "gem_capi_global.cpp",
            CSRC / "gem_compose.hip", CSRC / "gem_capi_compose.cpp", CSRC / "gem_costmap.hip", CSRC / "gem_capi_costmap.cpp",
@@ -25,7 +25,7 @@ SOURCES = [CSRC / "gem_kernels.hip", CSRC / "gem_sort.hip", CSRC / "gem_capi.cpp
            CSRC / "gem_footprint.hip", CSRC / "gem_capi_footprint.cpp", CSRC / "gem_inflate.hip", CSRC / "gem_capi_inflate.cpp",
            CSRC / "gem_mapgrid.hip", CSRC / "gem_capi_mapgrid.cpp", CSRC / "gem_critics.hip", CSRC / "gem_capi_critics.cpp",
            CSRC / "gem_trajgen.hip", CSRC / "gem_capi_trajgen.cpp"]
-HEADERS = [CSRC / "gem_device.hpp", CSRC / "gem_kernels.hpp", CSRC / "gem_frame_lean.hpp", CSRC / "gem_frame_sort.hpp", CSRC / "gem_wave.hpp", CSRC / "gem_compact.hpp", CSRC / "gem_transport.hpp", CSRC / "gem_hostcopy.hpp", CSRC / "gem_capi_internal.hpp", CSRC / "gem_plan.hpp", CSRC / "gem_clean.hpp", CSRC / "gem_local.hpp", CSRC / "gem_voxel.hpp", CSRC / "gem_global.hpp", CSRC / "gem_compose.hpp", CSRC / "gem_costmap.hpp", CSRC / "gem_lsd.hpp", CSRC / "gem_octree.hpp", CSRC / "gem_depth.hpp", CSRC / "gem_history.hpp", CSRC / "gem_footprint.hpp", CSRC / "gem_inflate.hpp", CSRC / "gem_mapgrid.hpp", CSRC / "gem_score_device.hpp", CSRC / "gem_critics.hpp", CSRC / "gem_trajgen.hpp", CSRC / "gem_sincos.hpp",
+HEADERS = [CSRC / "gem_device.hpp", CSRC / "gem_kernels.hpp", CSRC / "gem_frame_lean.hpp", CSRC / "gem_frame_tile.hpp", CSRC / "gem_frame_sort.hpp", CSRC / "gem_wave.hpp", CSRC / "gem_compact.hpp", CSRC / "gem_transport.hpp", CSRC / "gem_hostcopy.hpp", CSRC / "gem_capi_internal.hpp", CSRC / "gem_plan.hpp", CSRC / "gem_clean.hpp", CSRC / "gem_local.hpp", CSRC / "gem_voxel.hpp", CSRC / "gem_global.hpp", CSRC / "gem_compose.hpp", CSRC / "gem_costmap.hpp", CSRC / "gem_lsd.hpp", CSRC / "gem_octree.hpp", CSRC / "gem_depth.hpp", CSRC / "gem_history.hpp", CSRC / "gem_footprint.hpp", CSRC / "gem_inflate.hpp", CSRC / "gem_mapgrid.hpp", CSRC / "gem_score_device.hpp", CSRC / "gem_critics.hpp", CSRC / "gem_trajgen.hpp", CSRC / "gem_sincos.hpp",
            ROOT.parent / "include" / "gem_hip_debug.h", ROOT.parent / "include" / "gem_hip.h", ROOT.parent / "include" / "gem_hip_history.h",
            ROOT.parent / "include" / "gem_hip_footprint.h", ROOT.parent / "include" / "gem_hip_inflate.h", ROOT.parent / "include" / "gem_hip_mapgrid.h",
            ROOT.parent / "include" / "gem_hip_critics.h", ROOT.parent / "include" / "gem_hip_trajgen.h"]
@@ -37,6 +37,23 @@ FLAGS = [
     "-Wno-unused-value", "-Wno-unused-result",
     *os.environ.get("GEM_BUILD_DEFINES", "").split(),          # build-time experiments (A/B builds on the GPU box), e.g. -DGEM_X=1
 ]
+
+# Flags of one source alone, behind FLAGS.  gem_frame_lean.hip: the leading scalar parameters of k_frame's lean form are preloaded
+# into user SGPRs (14 dwords, the hardware's limit); an -mllvm option acts on every kernel of a file, hence the file of its own.
+SOURCE_FLAGS = {
+    "gem_frame_lean.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
+}
+
+
+def compile_flags(src: Path, extra=()) -> list:
+    """The compile line's flags for `src`: FLAGS (GEM_BUILD_DEFINES among them), `extra`, then the source's own."""
+    return [f for f in FLAGS if f != "-shared"] + list(extra) + SOURCE_FLAGS.get(src.name, [])
+
+
+def flag_line(extra=()) -> str:
+    """What a rebuild of every object is keyed on: the common flags and every source's own."""
+    own = "".join(f" [{name}: {' '.join(fl)}]" for name, fl in sorted(SOURCE_FLAGS.items()))
+    return " ".join(compile_flags(Path("-"), extra)) + own
 
 
 def hipcc_path() -> str:
@@ -69,16 +86,15 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     objdir = LIBDIR / "obj"
     objdir.mkdir(exist_ok=True)
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cflags = [f for f in FLAGS if f != "-shared"]
     tag = objdir / ".flags"
-    flag_line = " ".join(cflags)
-    if not tag.exists() or tag.read_text() != flag_line:               # different flags (GEM_BUILD_DEFINES, GEM_DEBUG_BUILD): everything again
+    line = flag_line()
+    if not tag.exists() or tag.read_text() != line:                    # different flags (GEM_BUILD_DEFINES, GEM_DEBUG_BUILD, a source's own): everything again
         force = True
     jobs = []
     for src in SOURCES:
         obj = objdir / (src.stem + ".o")
         if force or _stale(obj, [src] + HEADERS):
-            cmd = [hipcc_path(), *cflags, "-c", str(src), "-o", str(obj)]
+            cmd = [hipcc_path(), *compile_flags(src), "-c", str(src), "-o", str(obj)]
             if verbose:
                 print(" ".join(cmd))
             jobs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
@@ -89,7 +105,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             errors.append(f"{src.name}: hipcc failed ({proc.returncode}):\n{out}")
     if errors:
         raise RuntimeError("\n".join(errors))
-    tag.write_text(flag_line)
+    tag.write_text(line)
     cmd = [hipcc_path(), "--offload-arch=gfx950", "-shared", "-fPIC", *[str(objdir / (s.stem + ".o")) for s in SOURCES], "-o", str(LIB),
            f"-L{rocm}/lib", "-lrccl", "-pthread", f"-Wl,-rpath,{rocm}/lib"]
     if verbose:
@@ -107,11 +123,10 @@ def build_variant(name: str, defines: str, verbose: bool = False) -> Path:
     objdir = out / "obj"
     objdir.mkdir(parents=True, exist_ok=True)
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cflags = [f for f in FLAGS if f != "-shared"] + defines.split()
     jobs = []
     for src in SOURCES:
         obj = objdir / (src.stem + ".o")
-        cmd = [hipcc_path(), *cflags, "-c", str(src), "-o", str(obj)]
+        cmd = [hipcc_path(), *compile_flags(src, defines.split()), "-c", str(src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd))
         jobs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

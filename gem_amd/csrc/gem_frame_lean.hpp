@@ -4,8 +4,9 @@
 // fast laser projection, no colours, one sweep) reads about a third, scattered over fifteen 64-byte lines -- the compiler fetched
 // them in dependent hops, each a scalar-cache round trip a wave waits out before its first vector load.  FrameLeanArgs holds
 // exactly what the lean kernel reads, once each: the tile half first (with the words both halves branch on at its head), the
-// binning half behind it, each one contiguous run.  launch_frame fills it from the FuseArgs / BinArgs it is handed
-// (frame_lean_args, a pure function), so nothing upstream of the launch knows about it.
+// binning half behind it, each one contiguous run.  launch_frame_lean fills it from the FuseArgs / BinArgs it is handed
+// (frame_lean_args, a pure function), so nothing upstream of the launch knows about it; the words a wave needs before its first
+// vector load are passed once more in front of it, as scalar parameters the hardware preloads (FrameLeanHead, below).
 // Everything here compiles for the host alone (tests/cpp/frame_lean_check.cpp).
 #pragma once
 
@@ -119,6 +120,33 @@ inline FrameLeanArgs frame_lean_args(const FuseArgs& fa, const BinArgs& ba)
     b.beam_a = fc.beam_a; b.beam_c = fc.beam_c; b.t2 = fc.t2;
     b.Js[0] = fc.Js[0]; b.Js[1] = fc.Js[1];
     return la;
+}
+
+// The HEAD of a lean launch: the words a wave needs before its first vector loads can leave -- the tile / binning branch, the
+// block -> tile map, the bucket and its count for a tile block; the cloud and its size for a binning block.  The lean kernels take
+// them as leading scalar parameters IN THIS ORDER, in front of the block (gem_frame_lean.hip), and that file is built with
+// kernel-argument preloading: the command processor writes the first kFrameHeadDwords dwords of the kernel arguments into user SGPRs
+// where a wave starts, so none of them is a scalar load the wave waits for.  The hardware preloads 14 dwords at most (16 user SGPRs,
+// two of them the kernel-argument pointer).  The kernels read these words from the parameters and never from the block.
+struct FrameLeanHead {
+    int       nf, T, tiles_per_row;
+    uint32_t  tile_div;
+    int       center_tr, center_tc;
+    const uint32_t* bkt; uint32_t* bcount;             // the tile half's (the pass being fused)
+    const float4* xyzi; int B; uint32_t n;             // the binning half's
+};
+constexpr int kFrameHeadDwords = (int)(sizeof(FrameLeanHead) / 4);
+static_assert(sizeof(FrameLeanHead) == 56 && kFrameHeadDwords <= 14, "the head of a lean launch: no padding, at most the 14 dwords the hardware preloads");
+
+// the head of a filled block (launch_frame_lean): copies
+inline FrameLeanHead frame_lean_head(const FrameLeanArgs& la)
+{
+    FrameLeanHead h{};
+    h.nf = la.t.nf; h.T = la.t.T; h.tiles_per_row = la.t.tiles_per_row; h.tile_div = la.t.tile_div;
+    h.center_tr = la.t.center_tr; h.center_tc = la.t.center_tc;
+    h.bkt = la.t.bkt; h.bcount = la.t.bcount;
+    h.xyzi = la.b.xyzi; h.B = la.b.B; h.n = la.b.n;
+    return h;
 }
 
 } // namespace gem

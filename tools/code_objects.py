@@ -3,6 +3,7 @@
 
 The host library carries one clang offload bundle per translation unit in its .hip_fatbin section; every bundle holds an AMDGPU ELF whose
 NT_AMDGPU_METADATA note (msgpack) lists, per kernel: VGPR / SGPR counts, spill counts, scratch (.private_segment_fixed_size), LDS.
+The kernel descriptors (<kernel>.kd) give the dwords of kernel arguments preloaded into user SGPRs ("preload": k_frame's lean form).
 
     python tools/code_objects.py [path/to/libgem_hip.so] [--spills]       # table of every kernel (or only those that spill / use scratch)
 """
@@ -76,11 +77,39 @@ def kernels_of(elf):
                     yield k
 
 
+def preload_lengths(elf):
+    """{kernel name: dwords of kernel arguments the command processor preloads into user SGPRs}, from the kernel descriptors:
+    symbol <kernel>.kd, 64 bytes; bytes 58-59 = KERNARG_PRELOAD, the length in dwords in bits 0-6 (the offset in bits 7-15)."""
+    assert elf[:4] == b"\x7fELF" and elf[4] == 2 and elf[5] == 1, "not a little-endian ELF64"
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, _ = struct.unpack_from("<HHH", elf, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQII", elf, shoff + i * shentsize) for i in range(shnum)]   # name, type, flags, addr, offset, size, link, info
+    out = {}
+    for _n, typ, _f, _a, off, size, link, _i in secs:
+        if typ not in (2, 11):            # SHT_SYMTAB, SHT_DYNSYM
+            continue
+        stroff = secs[link][4]
+        for p in range(off, off + size, 24):
+            st_name, _info, _other, shndx, value, st_size = struct.unpack_from("<IBBHQQ", elf, p)
+            e = elf.index(b"\0", stroff + st_name)
+            name = elf[stroff + st_name:e].decode()
+            if not name.endswith(".kd") or st_size != 64 or not 0 < shndx < shnum:
+                continue
+            _sn, _st, _sf, saddr, soff, ssize, _sl, _si = secs[shndx]
+            at = soff + (value - saddr)
+            assert soff <= at and at + 64 <= soff + ssize, name
+            word, = struct.unpack_from("<H", elf, at + 58)
+            out[name[:-3]] = word & 0x7f
+    return out
+
+
 def all_kernels(lib_path):
     out = []
     for triple, elf in code_objects(lib_path):
+        preload = preload_lengths(elf)
         for k in kernels_of(elf):
             out.append({
+                "preload": preload[k[".name"]],
                 "name": k[".name"], "vgpr": k.get(".vgpr_count", -1), "agpr": k.get(".agpr_count", 0), "sgpr": k.get(".sgpr_count", -1),
                 "vgpr_spill": k.get(".vgpr_spill_count", 0), "sgpr_spill": k.get(".sgpr_spill_count", 0),
                 "scratch": k.get(".private_segment_fixed_size", 0), "lds": k.get(".group_segment_fixed_size", 0),
@@ -108,7 +137,7 @@ def main():
     for k, nm in sorted(zip(ks, pretty), key=lambda t: t[1]):
         if only and not (k["vgpr_spill"] or k["sgpr_spill"] or k["scratch"]):
             continue
-        print(f"{nm[:110]:110s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} sgpr {k['sgpr']:3d} spill v{k['vgpr_spill']:3d} s{k['sgpr_spill']:3d} scratch {k['scratch']:4d} lds {k['lds']:6d}")
+        print(f"{nm[:110]:110s} vgpr {k['vgpr']:3d} agpr {k['agpr']:3d} sgpr {k['sgpr']:3d} spill v{k['vgpr_spill']:3d} s{k['sgpr_spill']:3d} scratch {k['scratch']:4d} lds {k['lds']:6d} preload {k['preload']:2d}")
 
 
 if __name__ == "__main__":

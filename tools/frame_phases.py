@@ -2,6 +2,9 @@
 """Profiling aid: the time line of ONE k_frame launch of the C2 stream -- cycle stamps of thread 0 of every tile workgroup (fuse of the
 previous sweep) and of every binning block (this sweep), put on a common clock per XCD (HW_REG_XCC_ID; the XCDs'
 counters are not synchronised, so every XCD's earliest stamp is its zero).
+The lean form's start stamps (tiles and binning blocks) are taken into registers where the wave starts and stored once the stamp
+buffer's pointer has arrived (it is not among the preloaded head words), so a block's first phase and its life include the scalar
+fetch of its arguments; the generic form's start stamp is stored through that pointer, behind the fetch.
 
     python tools/frame_phases.py [sweeps] [light=0]
 """
