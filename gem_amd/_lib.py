@@ -299,6 +299,24 @@ TRAJGEN_SIGNATURES = {
     "gem_costmap_dwa_best": (c_int, _DWA_ARGS),
     "gem_costmap_dwa_best_device": (c_int, _DWA_ARGS),
 }
+# include/gem_hip_navplan.h (the global plan on the costmap: weighted potential and grid path; gem_hip.h includes it)
+NAV_OUTLINE, NAV_UNREACHED = 1, 0x7FFFFFFF
+
+
+class NavplanStatus(C.Structure):
+    _fields_ = [("found", c_int), ("n_path", c_int), ("rounds", c_int), ("chunks", c_int), ("goal_potential", c_int),
+                ("start_cell", c_int * 2), ("goal_cell", c_int * 2)]
+
+
+NAVPLAN_SIGNATURES = {
+    "gem_navplan_weights": (c_int, [c_int, c_double, c_int, c_int, POINTER(c_int)]),
+    "gem_navplan_host": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int), POINTER(c_int), c_void_p, c_void_p, c_longlong,
+                                 POINTER(NavplanStatus)]),
+    "gem_costmap_navplan": (c_int, [c_void_p, c_int, POINTER(c_double), POINTER(c_double), POINTER(c_int), c_int, c_void_p, c_longlong,
+                                    POINTER(NavplanStatus)]),
+    "gem_costmap_navplan_status": (c_int, [c_void_p, c_int, POINTER(NavplanStatus)]),
+    "gem_costmap_navplan_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_longlong]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -325,7 +343,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES,                                **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1358,6 +1358,40 @@ class Costmap:
         self._call("gem_costmap_mapgrid_score", int(which), pp, nt, T, float(xshift), int(flags), out.ctypes.data_as(C.c_void_p) if nt else None)
         return out
 
+    # -- the global plan (gem_hip_navplan.h) -------------------------------------------------------------------------------------------
+    def nav_plan(self, start, goal, weights=None, outline: bool = True):
+        """global_planner's makePlan in its order-free configuration (Dijkstra, the non-quadratic potential, the grid path) from the
+        world points start to goal over the costmap's bytes as they are when the call runs on the stream; weights = int32 [256] by cost
+        byte, 0 = impassable (None: nav_weights()).  The call waits.  Returns (path float64 [n, 2] of cell centres from start to goal,
+        status dict: found, n_path, rounds, chunks, goal_potential, start_cell, goal_cell)."""
+        w = np.ascontiguousarray(nav_weights() if weights is None else weights, np.int32)
+        if w.shape != (256,):
+            raise ValueError("weights must be int32 [256]")
+        s, g = (C.c_double * 2)(*[float(v) for v in start]), (C.c_double * 2)(*[float(v) for v in goal])
+        st = _lib.NavplanStatus()
+        self._call("gem_costmap_navplan", s, g, w.ctypes.data_as(C.POINTER(C.c_int)), _lib.NAV_OUTLINE if outline else 0, None, 0, C.byref(st))
+        cells = np.zeros(int(st.n_path), np.int32)
+        if cells.size:
+            self._call("gem_costmap_navplan_read", None, cells.ctypes.data_as(C.c_void_p), int(cells.size))
+        geo = self.geometry()                                           # cell centres, in double, as the C entry computes them
+        path = np.stack([geo["origin_x"] + ((cells % self.size_x).astype(np.float64) + 0.5) * geo["resolution"],
+                         geo["origin_y"] + ((cells // self.size_x).astype(np.float64) + 0.5) * geo["resolution"]], axis=1).reshape(-1, 2)
+        return path, _nav_status(st)
+
+    def nav_status(self) -> dict:
+        """The status of the costmap's last plan (gem_costmap_navplan_status), whoever made it; nothing is enqueued."""
+        st = _lib.NavplanStatus()
+        self._call("gem_costmap_navplan_status", C.byref(st))
+        return _nav_status(st)
+
+    def read_potential(self):
+        """(potential int32 [size_y, size_x], path cells int32 [n] as y * size_x + x) of the costmap's last plan; the call waits."""
+        n = self.nav_status()["n_path"]
+        pot = np.zeros((self.size_y, self.size_x), np.int32)
+        cells = np.zeros(n, np.int32)
+        self._call("gem_costmap_navplan_read", pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p) if n else None, n)
+        return pot, cells
+
     # -- the best trajectory (gem_hip_critics.h) ----------------------------------------------------------------------------------------
     def prepare_map_grid_front(self, plan) -> None:
         """The FRONT grid, which DWA's goal_front critic reads: the goal grid of `plan` (the caller's front plan, its last point already
@@ -1523,6 +1557,42 @@ def adjust_plan(plan, resolution: float) -> np.ndarray:
     if lib.gem_mapgrid_adjust_plan(pv, int(v.shape[0]), float(resolution), out.ctypes.data_as(C.POINTER(C.c_double)), int(n.value), None) != _lib.GEM_OK:
         raise ValueError("adjust_plan")
     return out
+
+
+def nav_weights(neutral_cost: int = 50, cost_factor: float = 3.0, lethal_cost: int = 253, allow_unknown: bool = True) -> np.ndarray:
+    """The weight table of Costmap.nav_plan as Expander::getCost gives it: int32 [256] by cost byte, 0 = impassable
+    (gem_navplan_weights; host only, no device).  A factor under which a traversable cost is not a whole number is refused."""
+    out = np.zeros(256, np.int32)
+    if _lib.load().gem_navplan_weights(int(neutral_cost), float(cost_factor), int(lethal_cost), int(bool(allow_unknown)),
+                                       out.ctypes.data_as(C.POINTER(C.c_int))) != _lib.GEM_OK:
+        raise ValueError("nav_weights: parameters out of range, or a traversable cost that is not a positive whole number")
+    return out
+
+
+def _nav_status(st) -> dict:
+    return {"found": int(st.found), "n_path": int(st.n_path), "rounds": int(st.rounds), "chunks": int(st.chunks),
+            "goal_potential": int(st.goal_potential), "start_cell": (int(st.start_cell[0]), int(st.start_cell[1])),
+            "goal_cell": (int(st.goal_cell[0]), int(st.goal_cell[1]))}
+
+
+def nav_plan_host(grid, start_cell, goal_cell, weights=None, outline: bool = True):
+    """The host twin of Costmap.nav_plan (gem_navplan_host; no device): grid = uint8 [size_y, size_x], start_cell and goal_cell (x, y).
+    Returns (potential int32 [size_y, size_x], path cells int32 [n] as y * size_x + x, status dict)."""
+    g = np.ascontiguousarray(grid, np.uint8)
+    if g.ndim != 2 or not g.size:
+        raise ValueError("grid must be uint8 [size_y, size_x]")
+    w = np.ascontiguousarray(nav_weights() if weights is None else weights, np.int32)
+    if w.shape != (256,):
+        raise ValueError("weights must be int32 [256]")
+    sy, sx = g.shape
+    pot = np.zeros((sy, sx), np.int32)
+    cells = np.empty(sx * sy, np.int32)
+    st = _lib.NavplanStatus()
+    s, e = (C.c_int * 2)(*[int(v) for v in start_cell]), (C.c_int * 2)(*[int(v) for v in goal_cell])
+    if _lib.load().gem_navplan_host(g.ctypes.data_as(C.c_void_p), sx, sy, w.ctypes.data_as(C.POINTER(C.c_int)), _lib.NAV_OUTLINE if outline else 0,
+                                    s, e, pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), int(cells.size), C.byref(st)) != _lib.GEM_OK:
+        raise ValueError("nav_plan_host: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1")
+    return pot, cells[:st.n_path].copy(), _nav_status(st)
 
 
 def obstacle_critic(scale: float, flags: int = 0) -> _lib.Critic:

@@ -307,6 +307,12 @@ struct gem_handle {
             Arena mg_status;            // per grid four ints: started, goal cell x, y, levels
             unsigned long long gen = 0; // the costmap's generation: new at create and at every roll that moves it
             unsigned long long mg_gen[3] = {0, 0, 0};   // the generation each grid was prepared in (0: never)
+            // gem_costmap_navplan (gem_capi_navplan.cpp): the potential, an int per cell | the tiles' two active maps | the path, an int
+            // per cell, written from the end | the status words
+            Arena nav_pot, nav_act, nav_path, nav_status;
+            unsigned long long nav_gen = 0;             // the generation the last plan ran in (0: never)
+            int nav_n_path = 0;                         // its path's cells
+            gem_navplan_status nav_last{};              // ... and its status (gem_costmap_navplan_status)
         } map[kMax];
         unsigned long long generation = 0;      // the last generation handed out
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
@@ -322,6 +328,11 @@ struct gem_handle {
         unsigned mg_turn = 0;
         Arena mg_pose, mg_traj;
         std::vector<double> mg_plan;
+        // gem_costmap_navplan: the weight table on the device | pinned host memory, the table a call hands over and the status words its
+        // kernels answer with (the call waits, so one block serves every costmap) | the path's cells on the host
+        Arena nav_w;
+        void* nav_pin = nullptr;
+        std::vector<int> nav_cells;
         // gem_costmap_best_trajectory* (gem_capi_critics.cpp): the first pass's candidates | the host-array form's poses, lengths, external
         // columns, totals and the 32-byte result
         Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
@@ -338,6 +349,7 @@ struct gem_handle {
         long long box_cap = 0;          // blocks the table has room for
         Arena small;                    // device words: workgroups the last gem_costmap_mark_history culled
     } history;
+    int  nav_chunk = 0;                 // debug knob "nav_chunk": rounds gem_costmap_navplan enqueues per host round trip (0 = tiles_x + tiles_y)
     bool history_cull = true;           // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
     // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)
     struct Octree {

@@ -1,0 +1,268 @@
+// gem_capi_navplan.cpp -- the global-plan entry points of include/gem_hip_navplan.h: the weight table and the host twin (host only),
+// gem_costmap_navplan and its read-back.  The kernels are in gem_navplan.hip, the path routine in gem_navpath.hpp.
+//
+// gem_costmap_navplan maps start and goal with worldToMap on the host (it knows the geometry after rolling), hands the weight table
+// over in pinned host memory and enqueues: init, then CHUNKS of rounds, each chunk closed by k_nav_finish, which answers through the
+// pinned status words: "a tile is still marked", or the walked path.  The round count depends on the data, so the host loops: a chunk
+// of tiles_x + tiles_y rounds (gem_debug_set "nav_chunk" sets another length), a wait, a look at the converged word, the next chunk
+// while it is not set.  A round behind convergence finds no active tile and costs one empty launch.  The total is bounded by the cell
+// count, as Bellman-Ford's is: after round r every cell whose cheapest path crosses at most r tile seams holds its final value (its
+// tile ran behind the round that settled the edge cell the path last entered through, and a tile's round ends at its local fixed
+// point), a path has at most `cells` cells, and one more round finds nothing to mark.  The bound is in the loop's condition.
+// The potential, the active maps, the path and the status live with the costmap (Map::nav_*), the device table and the pinned block
+// with the handle's costmaps; all come from ensure() and only grow, so a second identical call allocates nothing.
+#include "gem_capi_internal.hpp"
+#include "gem_costmap.hpp"
+#include "gem_navplan.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <queue>
+#include <utility>
+
+namespace {
+
+using Map = gem_handle::Costmaps::Map;
+static_assert(kNavUnreached == GEM_NAV_UNREACHED, "the kernels' constant is the header's");
+constexpr long long kNavLimit = 2147483647ll;                       // 2^31 - 1
+constexpr size_t kNavPinBytes = (256 + kNavStatusWords) * sizeof(int);
+
+CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
+unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
+
+int find(gem_handle* h, int id, const char* what, Map** out)
+{
+    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
+    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
+        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
+    *out = &h->costmap.map[id];
+    return GEM_OK;
+}
+
+// a table the contract admits for this many cells: no negative weight, cells * max(w) below 2^31 - 1
+bool weights_ok(const int* w, long long cells)
+{
+    long long top = 0;
+    for (int c = 0; c < 256; ++c) {
+        if (w[c] < 0) return false;
+        top = std::max<long long>(top, w[c]);
+    }
+    return cells >= 1 && cells < kNavLimit && cells * top < kNavLimit;
+}
+
+void empty_status(gem_navplan_status* st)
+{
+    *st = gem_navplan_status{};
+    st->goal_potential = GEM_NAV_UNREACHED;
+    st->start_cell[0] = st->start_cell[1] = st->goal_cell[0] = st->goal_cell[1] = -1;
+}
+
+// the contract's potential by a binary-heap Dijkstra: the minimum over 4-connected paths is what the heap settles, whatever the order
+void host_potential(const unsigned char* grid, int sx, int sy, const int* w, bool outline, int start, int* pot)
+{
+    const long long cells = (long long)sx * sy;
+    std::fill(pot, pot + cells, GEM_NAV_UNREACHED);
+    if (start < 0) return;
+    auto weight = [&](int x, int y) {
+        if (outline && (x == 0 || y == 0 || x == sx - 1 || y == sy - 1)) return 0;
+        return w[grid[(size_t)y * sx + x]];
+    };
+    using Item = std::pair<int, int>;                                   // potential, cell
+    std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+    pot[start] = 0;
+    heap.push({0, start});
+    const int dx[4] = {-1, 1, 0, 0}, dy[4] = {0, 0, -1, 1};
+    while (!heap.empty()) {
+        const Item it = heap.top();
+        heap.pop();
+        if (it.first != pot[it.second]) continue;                       // an entry a smaller one overtook
+        const int cx = it.second % sx, cy = it.second / sx;
+        for (int k = 0; k < 4; ++k) {
+            const int x = cx + dx[k], y = cy + dy[k];
+            if (x < 0 || y < 0 || x >= sx || y >= sy) continue;
+            const int n = y * sx + x, wn = n == start ? 0 : weight(x, y);
+            if (wn <= 0) continue;
+            const int cand = it.first + wn;                             // below 2^31 - 1: cells * max(w) is
+            if (cand < pot[n]) { pot[n] = cand; heap.push({cand, n}); }
+        }
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int gem_navplan_weights(int neutral_cost, double cost_factor, int lethal_cost, int allow_unknown, int out[256])
+{
+    if (!out || !std::isfinite(cost_factor) || lethal_cost < 1 || lethal_cost > 256 || neutral_cost < 0 || neutral_cost > 255) return GEM_ERR_INVALID;
+    const float factor = (float)cost_factor, neutral = (float)neutral_cost;
+    int table[256];
+    for (int c = 0; c < 256; ++c) {
+        table[c] = 0;
+        if (!(c < lethal_cost - 1 || (allow_unknown && c == 255))) continue;
+        const float prod = (float)c * factor;
+        const float v = prod + neutral;                                 // (two float32 operations, each rounded on its own)
+        if (!(v == v)) return GEM_ERR_INVALID;
+        if (v >= (float)lethal_cost) { table[c] = lethal_cost - 1; }
+        else {
+            if (!(v > 0.0f) || v != std::floor(v)) return GEM_ERR_INVALID;      // the integer contract
+            table[c] = (int)v;
+        }
+        if (table[c] <= 0) return GEM_ERR_INVALID;
+    }
+    std::copy(table, table + 256, out);
+    return GEM_OK;
+}
+
+int gem_navplan_host(const unsigned char* grid, int size_x, int size_y, const int* w, int flags, const int start_cell[2], const int goal_cell[2],
+                     int* pot, int* path_cells, long long cap, gem_navplan_status* status)
+{
+    if (!grid || !w || !start_cell || !goal_cell || !status || size_x < 1 || size_y < 1 || (flags & ~GEM_NAV_OUTLINE) || (path_cells && cap < 0))
+        return GEM_ERR_INVALID;
+    const long long cells = (long long)size_x * size_y;
+    if (!weights_ok(w, cells)) return GEM_ERR_INVALID;
+    auto cell_of = [&](const int c[2]) { return c[0] >= 0 && c[1] >= 0 && c[0] < size_x && c[1] < size_y ? c[1] * size_x + c[0] : -1; };
+    const int start = cell_of(start_cell), goal = cell_of(goal_cell);
+    empty_status(status);
+    if (start >= 0) { status->start_cell[0] = start_cell[0]; status->start_cell[1] = start_cell[1]; }
+    if (goal >= 0) { status->goal_cell[0] = goal_cell[0]; status->goal_cell[1] = goal_cell[1]; }
+    std::vector<int> own;
+    if (!pot) { own.resize((size_t)cells); pot = own.data(); }
+    host_potential(grid, size_x, size_y, w, (flags & GEM_NAV_OUTLINE) != 0, start, pot);
+    if (goal >= 0) status->goal_potential = pot[goal];
+    if (start < 0 || goal < 0 || pot[goal] == GEM_NAV_UNREACHED) return GEM_OK;
+    const long long n = nav_grid_path(pot, size_x, size_y, start, goal, nullptr, 0);
+    status->found = 1;
+    status->n_path = (int)n;
+    if (!path_cells) return GEM_OK;
+    if (cap < n) return GEM_ERR_INVALID;
+    nav_grid_path(pot, size_x, size_y, start, goal, path_cells, n);
+    std::reverse(path_cells, path_cells + n);
+    return GEM_OK;
+}
+
+#define NAVPLAN_ENTRY(name)                                          \
+    ApiRange api_range(h, name);                                     \
+    if (!h) return GEM_ERR_INVALID;                                  \
+    std::lock_guard<std::mutex> lk(h->mu);                           \
+    hipSetDevice(h->device)
+
+int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const double goal_xy[2], const int* w, int flags, double* out_xy,
+                        long long cap, gem_navplan_status* st)
+{
+    NAVPLAN_ENTRY("gem_costmap_navplan");
+    const char* what = "gem_costmap_navplan";
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, what, &m))) return rc;
+    if (!start_xy || !goal_xy || !w || !st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a NULL start, goal, weight table or status");
+    if (flags & ~GEM_NAV_OUTLINE) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: unknown flag bits");
+    if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative capacity");
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(start_xy[k]) || !std::isfinite(goal_xy[k])) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a coordinate not finite");
+    const CostGeom g = geom_of(*m);
+    const long long cells = (long long)g.sx * g.sy;
+    if (!weights_ok(w, cells)) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1");
+
+    auto& cm = h->costmap;
+    NavArgs a{};
+    a.sx = (int)g.sx; a.sy = (int)g.sy; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
+    const size_t nt = (size_t)a.ntx * a.nty;
+    if ((rc = ensure(h, m->nav_pot, (size_t)cells * sizeof(int))) || (rc = ensure(h, m->nav_path, (size_t)cells * sizeof(int))) ||
+        (rc = ensure(h, m->nav_act, 2 * nt * sizeof(int))) || (rc = ensure(h, m->nav_status, kNavStatusWords * sizeof(int))) ||
+        (rc = ensure(h, cm.nav_w, 256 * sizeof(int)))) return rc;
+    if (!cm.nav_pin) GEM_HIP(h, hipHostMalloc(&cm.nav_pin, kNavPinBytes, hipHostMallocDefault));
+    int* pin = static_cast<int*>(cm.nav_pin);
+    volatile int* pin_status = pin + 256;
+    std::copy(w, w + 256, pin);
+    for (int i = 0; i < kNavStatusWords; ++i) pin_status[i] = 0;
+
+    empty_status(st);
+    uint32_t cell = 0u;
+    a.start = cost_cell(g, start_xy[0], start_xy[1], cell) ? (int)cell : -1;
+    a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
+    if (a.start >= 0) { st->start_cell[0] = a.start % a.sx; st->start_cell[1] = a.start / a.sx; }
+    if (a.goal >= 0) { st->goal_cell[0] = a.goal % a.sx; st->goal_cell[1] = a.goal / a.sx; }
+    a.grid = grid_of(*m);
+    a.w = static_cast<int*>(cm.nav_w.p);
+    a.pot = static_cast<int*>(m->nav_pot.p); a.act = static_cast<int*>(m->nav_act.p);
+    a.path = static_cast<int*>(m->nav_path.p); a.status = static_cast<int*>(m->nav_status.p);
+    a.pin = pin;
+    a.outline = (flags & GEM_NAV_OUTLINE) ? 1 : 0;
+
+    m->nav_gen = 0;                                                     // (a failure below leaves no plan to read)
+    m->nav_n_path = 0;
+    GEM_HIP(h, launch_nav_init(h->stream, a));
+    const long long chunk = h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty;
+    long long rounds = 0;
+    int chunks = 0;
+    bool converged = false;
+    const long long max_rounds = cells + 2;                             // (fits a.round: a costmap has at most 2^30 cells)
+    while (!converged && rounds < max_rounds) {                         // (bounded by the cell count: see the head comment)
+        const long long n_rounds = std::min(chunk, max_rounds - rounds);   // (the last chunk is cut at the bound)
+        for (long long r = 0; r < n_rounds; ++r, ++rounds) {
+            a.round = (int)rounds;
+            GEM_HIP(h, launch_nav_round(h->stream, a));
+        }
+        a.round = (int)rounds;
+        GEM_HIP(h, launch_nav_finish(h->stream, a));
+        GEM_HIP(h, hipStreamSynchronize(h->stream));
+        ++chunks;
+        converged = pin_status[kNavConverged] != 0;
+    }
+    if (!converged) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan: the potential did not converge within its bound");
+    st->found = pin_status[kNavFound];
+    st->n_path = pin_status[kNavNPath];
+    st->rounds = pin_status[kNavRounds];
+    st->chunks = chunks;
+    st->goal_potential = pin_status[kNavGoalPot];
+    m->nav_gen = m->gen;
+    m->nav_n_path = st->n_path;
+    m->nav_last = *st;
+    const long long n = st->n_path;
+    cm.nav_cells.resize((size_t)n);
+    if (n > 0) {
+        HostXfer d{cm.nav_cells.data(), a.path + (cells - n), (size_t)n * sizeof(int)};
+        if ((rc = download_arrays(h, &d, 1, 0))) return rc;
+    }
+    if (!out_xy) return GEM_OK;
+    for (long long i = 0; i < std::min(n, cap); ++i) {
+        const int c = cm.nav_cells[(size_t)i];
+        out_xy[2 * i] = g.ox + ((double)(c % a.sx) + 0.5) * g.res;
+        out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
+    }
+    return cap < n ? fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: the path has more points than out_xy holds") : GEM_OK;
+}
+
+int gem_costmap_navplan_status(gem_handle* h, int id, gem_navplan_status* st)
+{
+    NAVPLAN_ENTRY("gem_costmap_navplan_status");
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_navplan_status", &m))) return rc;
+    if (!st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: a NULL status");
+    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: no plan was made");
+    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: the plan was made before the costmap last rolled");
+    *st = m->nav_last;
+    return GEM_OK;
+}
+
+int gem_costmap_navplan_read(gem_handle* h, int id, int* out_pot, int* out_path_cells, long long cap)
+{
+    NAVPLAN_ENTRY("gem_costmap_navplan_read");
+    const char* what = "gem_costmap_navplan_read";
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, what, &m))) return rc;
+    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: no plan was made");
+    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: the plan was made before the costmap last rolled");
+    const long long n = m->nav_n_path, cells = (long long)m->cfg.size_x * m->cfg.size_y;
+    if (out_path_cells && cap < n) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: the path has more cells than out_path_cells holds");
+    HostXfer d[2];
+    int k = 0;
+    if (out_pot) d[k++] = HostXfer{out_pot, m->nav_pot.p, (size_t)cells * sizeof(int)};
+    if (out_path_cells && n > 0) d[k++] = HostXfer{out_path_cells, static_cast<int*>(m->nav_path.p) + (cells - n), (size_t)n * sizeof(int)};
+    return k ? download_arrays(h, d, k, 0) : GEM_OK;
+}
+
+} // extern "C"

@@ -746,6 +746,23 @@ inline Trajectories generateTrajectories(const TrajectoryPlan& plan, const Traje
     return out;
 }
 
+// A global plan (gem_hip_navplan.h): global_planner's makePlan in its order-free configuration -- Dijkstra, the non-quadratic
+// potential, the grid path -- restated from memory and unverified against the library.  The weight table is indexed by the cost
+// byte, 0 = impassable.
+struct NavPlan {
+    bool found = false;
+    std::vector<FootprintPoint> path;                        // cell centres from the start to the goal, both included
+    gem_navplan_status status{};
+    // Expander::getCost as a table (host only); a factor under which a traversable cost is not a whole number is refused
+    static std::vector<int> weights(int neutralCost = 50, double costFactor = 3.0, int lethalCost = 253, bool allowUnknown = true)
+    {
+        std::vector<int> w(256, 0);
+        if (gem_navplan_weights(neutralCost, costFactor, lethalCost, allowUnknown ? 1 : 0, w.data()) != GEM_OK)
+            throw Error(GEM_ERR_INVALID, "NavPlan::weights: parameters out of range, or a traversable cost that is not a positive whole number");
+        return w;
+    }
+};
+
 class Costmap {
 public:
     static constexpr unsigned char FREE_SPACE = 0, INSCRIBED_INFLATED_OBSTACLE = 253, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
@@ -925,6 +942,35 @@ public:
         g.started = started != 0; g.goalX = goal[0]; g.goalY = goal[1];
         return g;
     }
+    // The global plan from the world point start to goal over the costmap's bytes as they are when the call runs on the stream
+    // (gem_hip_navplan.h); weights empty: NavPlan::weights().  Waits.  potential() reads the last plan's potential back, size_y rows of
+    // size_x, GEM_NAV_UNREACHED where the search did not come.
+    NavPlan navPlan(const FootprintPoint& start, const FootprintPoint& goal, const std::vector<int>& weights = {}, bool outline = true)
+    {
+        const std::vector<int> w = weights.empty() ? NavPlan::weights() : weights;
+        if (w.size() != 256) throw Error(GEM_ERR_INVALID, "Costmap::navPlan: the weight table has 256 entries");
+        NavPlan p;
+        const int flags = outline ? GEM_NAV_OUTLINE : 0;
+        map_.check(gem_costmap_navplan(map_.handle(), id_, &start.x, &goal.x, w.data(), flags, nullptr, 0, &p.status), "gem_costmap_navplan");
+        p.found = p.status.found != 0;
+        std::vector<int> cells(static_cast<size_t>(p.status.n_path));
+        map_.check(gem_costmap_navplan_read(map_.handle(), id_, nullptr, cells.empty() ? nullptr : cells.data(), static_cast<long long>(cells.size())),
+                   "gem_costmap_navplan_read");
+        const gem_costmap_config c = geometry();
+        p.path.reserve(cells.size());
+        for (int cell : cells)                                // cell centres, in double, as the C entry computes them
+            p.path.push_back(FootprintPoint{c.origin_x + (static_cast<double>(cell % static_cast<int>(c.size_x)) + 0.5) * c.resolution,
+                                            c.origin_y + (static_cast<double>(cell / static_cast<int>(c.size_x)) + 0.5) * c.resolution});
+        return p;
+    }
+    std::vector<int> potential() const
+    {
+        const gem_costmap_config c = geometry();
+        std::vector<int> pot(static_cast<size_t>(c.size_x) * c.size_y, 0);
+        map_.check(gem_costmap_navplan_read(map_.handle(), id_, pot.data(), nullptr, 0), "gem_costmap_navplan_read");
+        return pot;
+    }
+
     // SimpleScoredSamplingPlanner's scoreTrajectory + findBestTrajectory over trajectories of posesPerTrajectory pose slots: the critics
     // in order, ext = the external critics' raw scores [columns][trajectories], trajLen (empty: all) the poses each trajectory uses.
     // The smallest total among the valid trajectories wins, ties to the smallest index.  Waits.

@@ -54,6 +54,14 @@
 //                    (xv, yv, thetav).  It also reports the deviation the header names: hypot against sqrt(x * x + y * y).
 //                    OscillationCostFunction and TwirlingCostFunction are not driven (they need the planner's state); their rules
 //                    are two lines each
+//   navplan gem_costmap_navplan / _read restate global_planner (GlobalPlanner::makePlan with use_dijkstra, use_quadratic = false,
+//                    use_grid_path: DijkstraExpansion::calculatePotentials over PotentialCalculator, Expander::getCost through
+//                    gem_navplan_weights, GridPath::getPath; include/gem_hip_navplan.h, restated FROM MEMORY; tests/navplan_ref.py
+//                    restates the same contract in numpy / plain Python).  The row drives the library's expansion and path objects
+//                    over seeded noise grids whose rim it closes itself (outlineMap) and compares the goal's potential, the
+//                    potential of every cell the library settled below the goal's (the library leaves at the goal, the device
+//                    converges everywhere) and the path cell by cell.  convert_offset_ is makePlan's and is not driven.  It
+//                    cannot be run where the test suite runs and has not been through a compiler
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -70,7 +78,9 @@
 // there, against the library's public headers as documented, and has not been through a compiler; neither have the octo row
 // (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner), the mapgrid row, the critics row and the trajgen
 // row (the same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes, the
-// trajgen row base_local_planner/simple_trajectory_generator.h and base_local_planner/local_planner_limits.h).
+// trajgen row base_local_planner/simple_trajectory_generator.h and base_local_planner/local_planner_limits.h).  The navplan row has not
+// been through a compiler either; it is the one row of another package, global_planner: add -lglobal_planner to the link line (its
+// three headers are among the includes below).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -108,6 +118,9 @@
 #include <base_local_planner/costmap_model.h>
 #include <base_local_planner/map_grid.h>
 #include <base_local_planner/simple_scored_sampling_planner.h>
+#include <global_planner/dijkstra.h>
+#include <global_planner/grid_path.h>
+#include <global_planner/potential_calculator.h>
 #include <geometry_msgs/PoseStamped.h>
 #include <geometry_msgs/Point.h>
 #include <octomap/ColorOcTree.h>
@@ -937,6 +950,67 @@ int check_trajgen(uint32_t seed)
     return 0;
 }
 
+// ---- navplan -------------------------------------------------------------------------------------------------------------------
+// Seeded noise grids through a real DijkstraExpansion + PotentialCalculator + GridPath against gem_costmap_navplan.  Written against
+// the package's public headers as recalled; not compiled where the test suite runs.
+int check_navplan(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    const int sx = 130, sy = 90;
+    const double res = 0.2, ox = -3.1, oy = 2.7;
+    gem_costmap_config cc{};
+    cc.size_x = sx; cc.size_y = sy; cc.resolution = res; cc.origin_x = ox; cc.origin_y = oy; cc.default_value = costmap_2d::FREE_SPACE;
+    int id = -1;
+    CHECK_GEM(gem_costmap_create(h, &cc, &id));
+    int w[256];
+    CHECK_GEM(gem_navplan_weights(50, 3.0, 253, 1, w));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    std::vector<unsigned char> grid((size_t)sx * sy), outlined;
+    for (const double noise : {0.0, 0.2, 0.3}) {
+        for (unsigned char& b : grid) b = u(rng) < noise ? (unsigned char)(rng() % 256) : (unsigned char)0;
+        CHECK_GEM(gem_costmap_write(h, id, 0, 0, sx, sy, grid.data(), sx));
+        outlined = grid;                                                  // GlobalPlanner::outlineMap writes 254 into the rim; the device does not
+        for (int x = 0; x < sx; ++x) outlined[x] = outlined[(size_t)(sy - 1) * sx + x] = costmap_2d::LETHAL_OBSTACLE;
+        for (int y = 0; y < sy; ++y) outlined[(size_t)y * sx] = outlined[(size_t)y * sx + sx - 1] = costmap_2d::LETHAL_OBSTACLE;
+        for (int k = 0; k < 10; ++k) {
+            const int s[2] = {1 + (int)(rng() % (sx - 2)), 1 + (int)(rng() % (sy - 2))}, e[2] = {1 + (int)(rng() % (sx - 2)), 1 + (int)(rng() % (sy - 2))};
+            global_planner::PotentialCalculator calc(sx, sy);
+            global_planner::DijkstraExpansion expansion(&calc, sx, sy);
+            expansion.setPreciseStart(false);
+            expansion.setLethalCost(253); expansion.setNeutralCost(50); expansion.setFactor(3.0); expansion.setHasUnknown(true);
+            std::vector<float> lib_pot((size_t)sx * sy);
+            const bool lib_found = expansion.calculatePotentials(outlined.data(), s[0], s[1], e[0], e[1], sx * sy * 2, lib_pot.data());
+            std::vector<std::pair<float, float>> lib_path;
+            global_planner::GridPath walker(&calc);
+            if (lib_found) walker.getPath(lib_pot.data(), s[0], s[1], e[0], e[1], lib_path);
+            const double sxy[2] = {ox + (s[0] + 0.5) * res, oy + (s[1] + 0.5) * res}, exy[2] = {ox + (e[0] + 0.5) * res, oy + (e[1] + 0.5) * res};
+            gem_navplan_status st{};
+            CHECK_GEM(gem_costmap_navplan(h, id, sxy, exy, w, GEM_NAV_OUTLINE, nullptr, 0, &st));
+            std::vector<int> pot((size_t)sx * sy), cells((size_t)st.n_path);
+            CHECK_GEM(gem_costmap_navplan_read(h, id, pot.data(), cells.empty() ? nullptr : cells.data(), (long long)cells.size()));
+            if ((st.found != 0) != lib_found) { report("navplan: found differs", k, (double)st.found, (double)lib_found); continue; }
+            if (!lib_found) continue;
+            const float goal_pot = lib_pot[(size_t)e[1] * sx + e[0]];
+            if ((double)goal_pot != (double)st.goal_potential) report("navplan: the goal's potential differs", k, (double)st.goal_potential, goal_pot);
+            long long differ = 0;                                         // the cells the library settled before it left at the goal
+            for (size_t i = 0; i < pot.size(); ++i) differ += lib_pot[i] < goal_pot && (double)lib_pot[i] != (double)pot[i];
+            if (differ) report("navplan: potentials below the goal's that differ", k, (double)differ, 0.0);
+            // the library's path runs goal -> start before makePlan reverses it; the device's runs start -> goal
+            if (lib_path.size() != cells.size()) { report("navplan: the path's length differs", k, (double)cells.size(), (double)lib_path.size()); continue; }
+            for (size_t i = 0; i < cells.size(); ++i) {
+                const std::pair<float, float>& p = lib_path[lib_path.size() - 1 - i];
+                if ((int)p.first != cells[i] % sx || (int)p.second != cells[i] / sx) { report("navplan: a path cell differs", k, (double)cells[i], p.second * sx + p.first); break; }
+            }
+        }
+    }
+    gem_destroy(h);
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -1021,8 +1095,9 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_mapgrid(seed + 8u);
     if (rc == 0) rc = check_critics(seed + 9u);
     if (rc == 0) rc = check_trajgen(seed + 10u);
+    if (rc == 0) rc = check_navplan(seed + 11u);
     if (rc) return rc;
-    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all eleven rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner and octomap (seed %u)\n", seed);
+    if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / global_planner / octomap does NOT match this installation\n", g_failures); return 1; }
+    std::printf("all twelve rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner, global_planner and octomap (seed %u)\n", seed);
     return 0;
 }
