@@ -317,6 +317,30 @@ NAVPLAN_SIGNATURES = {
     "gem_costmap_navplan_status": (c_int, [c_void_p, c_int, POINTER(NavplanStatus)]),
     "gem_costmap_navplan_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_longlong]),
 }
+# include/gem_hip_frontier.h (frontier search on the costmap: components, travel cost, one winner; gem_hip.h includes it)
+
+
+class FrontierParams(C.Structure):
+    _fields_ = [("min_frontier_size", c_double), ("potential_scale", c_double), ("gain_scale", c_double)]
+
+
+class Frontier(C.Structure):
+    _fields_ = [("root", c_int), ("size", c_int), ("sum_x", c_longlong), ("sum_y", c_longlong), ("access_potential", c_int),
+                ("access_cell", c_int), ("cost", c_double)]
+
+
+class FrontierStatus(C.Structure):
+    _fields_ = [("n_cells", c_int), ("n_frontiers", c_int), ("n_kept", c_int), ("best", c_int), ("rounds", c_int), ("chunks", c_int),
+                ("best_frontier", Frontier)]
+
+
+FRONTIER_SIGNATURES = {
+    "gem_frontiers_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, POINTER(FrontierParams), c_void_p, c_void_p, c_longlong,
+                                   POINTER(FrontierStatus)]),
+    "gem_costmap_frontiers": (c_int, [c_void_p, c_int, POINTER(FrontierParams), POINTER(FrontierStatus)]),
+    "gem_costmap_frontiers_read": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
+    "gem_costmap_navplan_goal": (c_int, [c_void_p, c_int, POINTER(c_double), c_void_p, c_longlong, POINTER(NavplanStatus)]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -343,7 +367,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

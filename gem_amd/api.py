@@ -1392,6 +1392,44 @@ class Costmap:
         self._call("gem_costmap_navplan_read", pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p) if n else None, n)
         return pot, cells
 
+    # -- frontier search (gem_hip_frontier.h) --------------------------------------------------------------------------------------------
+    def frontiers(self, min_frontier_size: float = 0.0, potential_scale: float = 1.0, gain_scale: float = 1.0) -> dict:
+        """The frontiers of the costmap's bytes against the potential of its last plan (gem_costmap_frontiers): 8-connected components
+        of the unknown cells that have a known, reached 4-neighbour; cost = potential_scale * access potential - gain_scale * size *
+        resolution; the kept frontier of least cost wins.  The call waits.  Returns the status dict: n_cells, n_frontiers, n_kept, best
+        (index into the kept list, -1 without one), rounds, chunks, best_frontier (a frontier dict with its centroid, or None)."""
+        p = _lib.FrontierParams(float(min_frontier_size), float(potential_scale), float(gain_scale))
+        st = _lib.FrontierStatus()
+        self._call("gem_costmap_frontiers", C.byref(p), C.byref(st))
+        return _frontier_status(st, self.geometry())
+
+    def read_frontiers(self):
+        """(kept frontiers: a list of dicts in ascending root order, labels int32 [size_y, size_x]: the root of the cell's frontier, -1
+        for a cell that is no frontier cell) of the costmap's last search; the call waits."""
+        labels = np.zeros((self.size_y, self.size_x), np.int32)
+        self._call("gem_costmap_frontiers_read", None, 0, labels.ctypes.data_as(C.c_void_p))
+        n = int((labels.reshape(-1) == np.arange(labels.size, dtype=np.int64)).sum())       # the roots: the kept list has no more records
+        rec = (_lib.Frontier * max(n, 1))()
+        for r in rec:
+            r.root = -1                                                 # (what the read leaves alone: behind the kept list)
+        self._call("gem_costmap_frontiers_read", rec, n, None)
+        geo = self.geometry()
+        return [_frontier(r, geo) for r in rec if r.root >= 0], labels
+
+    def nav_plan_to(self, goal):
+        """The grid path from the last plan's start to another goal on the last plan's potential, which stays as it is
+        (gem_costmap_navplan_goal): one walk, no second search.  Returns (path, status) as nav_plan does."""
+        g = (C.c_double * 2)(*[float(v) for v in goal])
+        st = _lib.NavplanStatus()
+        self._call("gem_costmap_navplan_goal", g, None, 0, C.byref(st))
+        cells = np.zeros(int(st.n_path), np.int32)
+        if cells.size:
+            self._call("gem_costmap_navplan_read", None, cells.ctypes.data_as(C.c_void_p), int(cells.size))
+        geo = self.geometry()                                           # cell centres, in double, as the C entry computes them
+        path = np.stack([geo["origin_x"] + ((cells % self.size_x).astype(np.float64) + 0.5) * geo["resolution"],
+                         geo["origin_y"] + ((cells // self.size_x).astype(np.float64) + 0.5) * geo["resolution"]], axis=1).reshape(-1, 2)
+        return path, _nav_status(st)
+
     # -- the best trajectory (gem_hip_critics.h) ----------------------------------------------------------------------------------------
     def prepare_map_grid_front(self, plan) -> None:
         """The FRONT grid, which DWA's goal_front critic reads: the goal grid of `plan` (the caller's front plan, its last point already
@@ -1593,6 +1631,41 @@ def nav_plan_host(grid, start_cell, goal_cell, weights=None, outline: bool = Tru
                                     s, e, pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), int(cells.size), C.byref(st)) != _lib.GEM_OK:
         raise ValueError("nav_plan_host: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1")
     return pot, cells[:st.n_path].copy(), _nav_status(st)
+
+
+def _frontier(f, geo) -> dict:
+    """a gem_frontier as a dict; the centroid is origin + (sum / size + 0.5) * resolution, in double, as the C++ facade computes it"""
+    res = float(geo["resolution"])
+    return {"root": int(f.root), "size": int(f.size), "sum_x": int(f.sum_x), "sum_y": int(f.sum_y), "access_potential": int(f.access_potential),
+            "access_cell": int(f.access_cell), "cost": float(f.cost),
+            "centroid": (float(geo["origin_x"]) + (float(f.sum_x) / float(f.size) + 0.5) * res,
+                         float(geo["origin_y"]) + (float(f.sum_y) / float(f.size) + 0.5) * res)}
+
+
+def _frontier_status(st, geo) -> dict:
+    return {"n_cells": int(st.n_cells), "n_frontiers": int(st.n_frontiers), "n_kept": int(st.n_kept), "best": int(st.best),
+            "rounds": int(st.rounds), "chunks": int(st.chunks), "best_frontier": _frontier(st.best_frontier, geo) if st.best >= 0 else None}
+
+
+def frontiers_host(grid, pot, resolution: float, min_frontier_size: float = 0.0, potential_scale: float = 1.0, gain_scale: float = 1.0,
+                   origin=(0.0, 0.0)):
+    """The host twin of Costmap.frontiers (gem_frontiers_host; no device): grid = uint8 [size_y, size_x], pot = int32 of the same shape,
+    a plan's potential.  Returns (kept frontiers: a list of dicts in ascending root order, labels int32 [size_y, size_x], status dict)."""
+    g = np.ascontiguousarray(grid, np.uint8)
+    p = np.ascontiguousarray(pot, np.int32)
+    if g.ndim != 2 or not g.size or p.shape != g.shape:
+        raise ValueError("grid must be uint8 [size_y, size_x] and pot int32 of the same shape")
+    sy, sx = g.shape
+    prm = _lib.FrontierParams(float(min_frontier_size), float(potential_scale), float(gain_scale))
+    labels = np.zeros((sy, sx), np.int32)
+    cap = ((sx + 1) // 2) * ((sy + 1) // 2)                             # components of a map: never two in a 2 x 2 block
+    rec = (_lib.Frontier * cap)()
+    st = _lib.FrontierStatus()
+    if _lib.load().gem_frontiers_host(g.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p), sx, sy, float(resolution), C.byref(prm),
+                                      labels.ctypes.data_as(C.c_void_p), rec, cap, C.byref(st)) != _lib.GEM_OK:
+        raise ValueError("frontiers_host: a resolution or parameter that is not finite, is negative or is above 1e100")
+    geo = {"origin_x": origin[0], "origin_y": origin[1], "resolution": resolution}
+    return [_frontier(rec[i], geo) for i in range(st.n_kept)], labels, _frontier_status(st, geo)
 
 
 def obstacle_critic(scale: float, flags: int = 0) -> _lib.Critic:

@@ -118,7 +118,8 @@ int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const cha
 void free_map(Map& m)
 {
     for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status,
-                     &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status}) {
+                     &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status,
+                     &m.fr_label, &m.fr_index, &m.fr_act, &m.fr_rec, &m.fr_out, &m.fr_words}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -136,12 +137,14 @@ void costmap_free(gem_handle* h)
     for (auto& m : c.map) free_map(m);
     for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
                      &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best,
-                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w}) {
+                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
     if (c.nav_pin) hipHostFree(c.nav_pin);
     c.nav_pin = nullptr;
+    if (c.fr_pin) hipHostFree(c.fr_pin);
+    c.fr_pin = nullptr;
     for (int k = 0; k < 2; ++k) {
         if (c.mg_pin[k]) hipHostFree(c.mg_pin[k]);
         if (c.mg_ev[k]) hipEventDestroy(c.mg_ev[k]);

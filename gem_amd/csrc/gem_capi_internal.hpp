@@ -313,6 +313,12 @@ struct gem_handle {
             unsigned long long nav_gen = 0;             // the generation the last plan ran in (0: never)
             int nav_n_path = 0;                         // its path's cells
             gem_navplan_status nav_last{};              // ... and its status (gem_costmap_navplan_status)
+            // gem_costmap_frontiers (gem_capi_frontier.cpp): the labels, an int per cell | each root's list index at the root's cell,
+            // an int per cell, never cleared | the tiles' two active maps | the records, field by field, one per possible component |
+            // the kept list (gem_frontier) | the device words
+            Arena fr_label, fr_index, fr_act, fr_rec, fr_out, fr_words;
+            unsigned long long fr_gen = 0;              // the generation the last search ran in (0: never, or a plan was made since)
+            int fr_n_kept = 0;                          // its kept list's length
         } map[kMax];
         unsigned long long generation = 0;      // the last generation handed out
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
@@ -333,6 +339,10 @@ struct gem_handle {
         Arena nav_w;
         void* nav_pin = nullptr;
         std::vector<int> nav_cells;
+        // gem_costmap_frontiers: the compaction's block counts and total | pinned host memory its kernels answer through (the call
+        // waits, so one block serves every costmap)
+        Arena fr_blocks;
+        void* fr_pin = nullptr;
         // gem_costmap_best_trajectory* (gem_capi_critics.cpp): the first pass's candidates | the host-array form's poses, lengths, external
         // columns, totals and the 32-byte result
         Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
@@ -350,7 +360,8 @@ struct gem_handle {
         Arena small;                    // device words: workgroups the last gem_costmap_mark_history culled
     } history;
     int  nav_chunk = 0;                 // debug knob "nav_chunk": rounds gem_costmap_navplan enqueues per host round trip (0 = tiles_x + tiles_y)
-    bool history_cull = true;           // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
+    int  front_chunk = 0;               // debug knob "front_chunk": label rounds gem_costmap_frontiers enqueues per host round trip (0 = tiles_x + tiles_y)
+    bool history_cull = true;          // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
     // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)
     struct Octree {
         static constexpr int kSlots = 4;

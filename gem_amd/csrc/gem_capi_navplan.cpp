@@ -192,6 +192,7 @@ int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const d
 
     m->nav_gen = 0;                                                     // (a failure below leaves no plan to read)
     m->nav_n_path = 0;
+    m->fr_gen = 0;                                                      // (a frontier search carries the plan it was made from)
     GEM_HIP(h, launch_nav_init(h->stream, a));
     const long long chunk = h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty;
     long long rounds = 0;
@@ -232,6 +233,67 @@ int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const d
         out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
     }
     return cap < n ? fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: the path has more points than out_xy holds") : GEM_OK;
+}
+
+// Another goal on the last plan's potential (include/gem_hip_frontier.h): one launch of k_nav_finish.  After convergence both active
+// maps are clear, so the kernel reports "converged" and walks; the potential is read, never written.
+int gem_costmap_navplan_goal(gem_handle* h, int id, const double goal_xy[2], double* out_xy, long long cap, gem_navplan_status* st)
+{
+    NAVPLAN_ENTRY("gem_costmap_navplan_goal");
+    int rc;
+    Map* m;
+    if ((rc = find(h, id, "gem_costmap_navplan_goal", &m))) return rc;
+    if (!goal_xy || !st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a NULL goal or status");
+    if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a negative capacity");
+    if (!std::isfinite(goal_xy[0]) || !std::isfinite(goal_xy[1])) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a coordinate not finite");
+    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: no plan was made");
+    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: the plan was made before the costmap last rolled");
+    auto& cm = h->costmap;
+    const CostGeom g = geom_of(*m);
+    const long long cells = (long long)g.sx * g.sy;
+    NavArgs a{};
+    a.sx = (int)g.sx; a.sy = (int)g.sy; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
+    int* pin = static_cast<int*>(cm.nav_pin);                           // (a plan was made on this handle: the arenas and the block exist)
+    volatile int* pin_status = pin + 256;
+    for (int i = 0; i < kNavStatusWords; ++i) pin_status[i] = 0;
+    *st = m->nav_last;
+    uint32_t cell = 0u;
+    a.start = st->start_cell[0] >= 0 ? st->start_cell[1] * a.sx + st->start_cell[0] : -1;
+    a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
+    st->goal_cell[0] = a.goal >= 0 ? a.goal % a.sx : -1;
+    st->goal_cell[1] = a.goal >= 0 ? a.goal / a.sx : -1;
+    a.grid = grid_of(*m);
+    a.w = static_cast<int*>(cm.nav_w.p);
+    a.pot = static_cast<int*>(m->nav_pot.p); a.act = static_cast<int*>(m->nav_act.p);
+    a.path = static_cast<int*>(m->nav_path.p); a.status = static_cast<int*>(m->nav_status.p);
+    a.pin = pin;
+    a.round = 0;                                                        // (either map: both are clear)
+    const unsigned long long plan_gen = m->nav_gen;
+    m->nav_gen = 0;                                                     // (a failure below leaves no path to read)
+    m->nav_n_path = 0;
+    GEM_HIP(h, launch_nav_finish(h->stream, a));
+    GEM_HIP(h, hipStreamSynchronize(h->stream));
+    if (!pin_status[kNavConverged]) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan_goal: a tile of the last plan is still marked");
+    st->found = pin_status[kNavFound];
+    st->n_path = pin_status[kNavNPath];
+    st->chunks = 1;
+    st->goal_potential = pin_status[kNavGoalPot];
+    m->nav_gen = plan_gen;
+    m->nav_n_path = st->n_path;
+    m->nav_last = *st;
+    const long long n = st->n_path;
+    cm.nav_cells.resize((size_t)n);
+    if (n > 0) {
+        HostXfer d{cm.nav_cells.data(), a.path + (cells - n), (size_t)n * sizeof(int)};
+        if ((rc = download_arrays(h, &d, 1, 0))) return rc;
+    }
+    if (!out_xy) return GEM_OK;
+    for (long long i = 0; i < std::min(n, cap); ++i) {
+        const int c = cm.nav_cells[(size_t)i];
+        out_xy[2 * i] = g.ox + ((double)(c % a.sx) + 0.5) * g.res;
+        out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
+    }
+    return cap < n ? fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: the path has more points than out_xy holds") : GEM_OK;
 }
 
 int gem_costmap_navplan_status(gem_handle* h, int id, gem_navplan_status* st)

@@ -763,6 +763,25 @@ struct NavPlan {
     }
 };
 
+// A frontier (gem_hip_frontier.h): an 8-connected component of the unknown cells that have a known 4-neighbour the last plan reached;
+// in the manner of explore_lite's FrontierSearch, restated from memory and unverified against the library.
+struct Frontier {
+    gem_frontier record{};
+    double originX = 0.0, originY = 0.0, resolution = 0.0;   // the costmap's geometry when the search ran
+    // the mean of its cells' centres: origin + ((double)sum / (double)size + 0.5) * resolution
+    FootprintPoint centroid() const
+    {
+        return FootprintPoint{originX + (static_cast<double>(record.sum_x) / static_cast<double>(record.size) + 0.5) * resolution,
+                              originY + (static_cast<double>(record.sum_y) / static_cast<double>(record.size) + 0.5) * resolution};
+    }
+};
+
+struct FrontierSearch {
+    gem_frontier_status status{};
+    bool found = false;                                      // a frontier was kept
+    Frontier best;                                           // the kept frontier of least cost, when found
+};
+
 class Costmap {
 public:
     static constexpr unsigned char FREE_SPACE = 0, INSCRIBED_INFLATED_OBSTACLE = 253, LETHAL_OBSTACLE = 254, NO_INFORMATION = 255;
@@ -970,6 +989,49 @@ public:
         map_.check(gem_costmap_navplan_read(map_.handle(), id_, pot.data(), nullptr, 0), "gem_costmap_navplan_read");
         return pot;
     }
+    // The path from the last plan's start to another goal on the last plan's potential, which stays as it is (gem_hip_frontier.h): one
+    // walk, no second search.  Waits.
+    NavPlan navPlanTo(const FootprintPoint& goal)
+    {
+        NavPlan p;
+        map_.check(gem_costmap_navplan_goal(map_.handle(), id_, &goal.x, nullptr, 0, &p.status), "gem_costmap_navplan_goal");
+        p.found = p.status.found != 0;
+        std::vector<int> cells(static_cast<size_t>(p.status.n_path));
+        map_.check(gem_costmap_navplan_read(map_.handle(), id_, nullptr, cells.empty() ? nullptr : cells.data(), static_cast<long long>(cells.size())),
+                   "gem_costmap_navplan_read");
+        const gem_costmap_config c = geometry();
+        p.path.reserve(cells.size());
+        for (int cell : cells)
+            p.path.push_back(FootprintPoint{c.origin_x + (static_cast<double>(cell % static_cast<int>(c.size_x)) + 0.5) * c.resolution,
+                                            c.origin_y + (static_cast<double>(cell / static_cast<int>(c.size_x)) + 0.5) * c.resolution});
+        return p;
+    }
+    // Frontier search over the costmap's bytes and the potential of its last plan (gem_hip_frontier.h).  Waits.  readFrontiers() reads
+    // the last search's kept frontiers back in ascending root order and, with labels, the label grid (a cell's root, -1 for a cell
+    // that is no frontier cell).
+    FrontierSearch frontiers(double minFrontierSize = 0.0, double potentialScale = 1.0, double gainScale = 1.0)
+    {
+        const gem_frontier_params prm{minFrontierSize, potentialScale, gainScale};
+        FrontierSearch s;
+        map_.check(gem_costmap_frontiers(map_.handle(), id_, &prm, &s.status), "gem_costmap_frontiers");
+        lastKept_ = s.status.n_kept;
+        s.found = s.status.best >= 0;
+        if (s.found) s.best = frontierOf(s.status.best_frontier);
+        return s;
+    }
+    std::vector<Frontier> readFrontiers(std::vector<int>* labels = nullptr) const
+    {
+        const gem_costmap_config c = geometry();
+        if (labels) labels->assign(static_cast<size_t>(c.size_x) * c.size_y, 0);
+        std::vector<gem_frontier> rec(static_cast<size_t>(lastKept_));
+        map_.check(gem_costmap_frontiers_read(map_.handle(), id_, rec.empty() ? nullptr : rec.data(), static_cast<long long>(rec.size()),
+                                              labels ? labels->data() : nullptr),
+                   "gem_costmap_frontiers_read");
+        std::vector<Frontier> out;
+        out.reserve(rec.size());
+        for (const gem_frontier& r : rec) out.push_back(frontierOf(r));
+        return out;
+    }
 
     // SimpleScoredSamplingPlanner's scoreTrajectory + findBestTrajectory over trajectories of posesPerTrajectory pose slots: the critics
     // in order, ext = the external critics' raw scores [columns][trajectories], trajLen (empty: all) the poses each trajectory uses.
@@ -1013,8 +1075,16 @@ private:
     static_assert(sizeof(FootprintPoint) == 2 * sizeof(double), "a spec is packed pairs of doubles");
     static double* ptr(Bounds* b) { return b ? &b->min_x : nullptr; }
     static const double* xy(const std::vector<FootprintPoint>& spec) { return spec.empty() ? nullptr : &spec.front().x; }
+    Frontier frontierOf(const gem_frontier& r) const
+    {
+        const gem_costmap_config c = geometry();
+        Frontier f;
+        f.record = r; f.originX = c.origin_x; f.originY = c.origin_y; f.resolution = c.resolution;
+        return f;
+    }
     ElevationMap& map_;
     int id_ = -1;
+    int lastKept_ = 0;                                       // the kept list's length of the last frontiers() of this object
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -751,6 +751,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- the global plan: gem_navplan_weights, gem_navplan_host, gem_costmap_navplan / _status / _read -------------------------------- */
 #include "gem_hip_navplan.h"
 
+/* ---- frontier search: gem_frontiers_host, gem_costmap_frontiers / _read, gem_costmap_navplan_goal --------------------------------- */
+#include "gem_hip_frontier.h"
+
 #ifdef __cplusplus
 }
 #endif
