@@ -9,8 +9,7 @@
 // A mark is its mark launches followed by one resolve launch on the handle's stream; the inputs that already live on the device
 // (the capture, the submap stack) are read where they are, a capture's record count from its device word.  Every device buffer comes
 // from ensure(), so gem_debug_get("arena_allocations") counts it.
-#include "gem_capi_internal.hpp"
-#include "gem_costmap.hpp"
+#include "gem_costmap_host.hpp"
 
 #include <algorithm>
 
@@ -19,31 +18,14 @@ namespace {
 constexpr size_t kRec = sizeof(LocalRecord);
 constexpr long long kMaxInputs = 2147483646ll;                      // 2^31 - 2: the stamp 2 * (i + 1) + 1 fits 32 bits
 constexpr long long kMaxCells = 1ll << 30;
-using Map = gem_handle::Costmaps::Map;
 
 unsigned long long* acc_words(gem_handle* h) { return static_cast<unsigned long long*>(h->costmap.small.p); }
-unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
-uint32_t cells_of(const Map& m) { return m.cfg.size_x * m.cfg.size_y; }
-CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
-CostAccum accum_of(gem_handle* h, Map& m) { return CostAccum{static_cast<uint32_t*>(m.stamps.p), acc_words(h)}; }
+CostAccum accum_of(gem_handle* h, CostMap& m) { return CostAccum{static_cast<uint32_t*>(m.stamps.p), acc_words(h)}; }
 
-int usable(gem_handle* h, const char* what)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    return GEM_OK;
-}
+int invalid(gem_handle* h, const char* what, const char* reason) { return fail(h, GEM_ERR_INVALID, (std::string(what) + ": " + reason).c_str()); }
+int usable(gem_handle* h, const char* what) { return h->tp_x ? invalid(h, what, "not on a handle with a communicator") : GEM_OK; }
 
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    const int rc = usable(h, what);
-    if (rc) return rc;
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
-
-bool window_ok(const Map& m, int min_i, int min_j, int max_i, int max_j)
+bool window_ok(const CostMap& m, int min_i, int min_j, int max_i, int max_j)
 {
     return min_i >= 0 && min_j >= 0 && min_i <= max_i && min_j <= max_j && (long long)max_i <= (long long)m.cfg.size_x &&
            (long long)max_j <= (long long)m.cfg.size_y;
@@ -51,7 +33,7 @@ bool window_ok(const Map& m, int min_i, int min_j, int max_i, int max_j)
 
 // the resolve pass behind a mark's launches, then the caller's bounds merged with the touched ones: touch() of costmap_layer.cpp,
 // *min = std::min(p, *min) and *max = std::max(p, *max) over the accepted inputs
-int finish_mark(gem_handle* h, Map& m, double bounds[4])
+int finish_mark(gem_handle* h, CostMap& m, double bounds[4])
 {
     unsigned long long* acc = acc_words(h);
     GEM_HIP(h, launch_cost_resolve(h->stream, cells_of(m), static_cast<uint32_t*>(m.stamps.p), grid_of(m), acc, acc + 4));
@@ -68,7 +50,7 @@ int finish_mark(gem_handle* h, Map& m, double bounds[4])
     return GEM_OK;
 }
 
-int mark_records(gem_handle* h, Map& m, const LocalRecord* d_rec, long long n, double thresh, double bounds[4])
+int mark_records(gem_handle* h, CostMap& m, const LocalRecord* d_rec, long long n, double thresh, double bounds[4])
 {
     if (n > 0) {
         CostPointsArgs a{d_rec, nullptr, (uint32_t)n, 0u, thresh};
@@ -97,7 +79,7 @@ bool capture_of(gem_handle* h, CostVisualArgs* v)
 }
 
 // Costmap2D::updateOrigin (costmap_2d.cpp), restated in include/gem_hip.h
-int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const char* what)
+int update_origin(gem_handle* h, CostMap& m, double new_ox, double new_oy, const char* what)
 {
     if (!std::isfinite(new_ox) || !std::isfinite(new_oy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": origin not finite").c_str());
     const double qx = (new_ox - m.cfg.origin_x) / m.cfg.resolution, qy = (new_oy - m.cfg.origin_y) / m.cfg.resolution;
@@ -115,7 +97,7 @@ int update_origin(gem_handle* h, Map& m, double new_ox, double new_oy, const cha
     return GEM_OK;
 }
 
-void free_map(Map& m)
+void free_map(CostMap& m)
 {
     for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status,
                      &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status,
@@ -123,12 +105,34 @@ void free_map(Map& m)
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
-    m = Map{};
+    m = CostMap{};
 }
 
 } // namespace
 
 namespace gemi {
+
+int costmap_find(gem_handle* h, int id, const char* what, CostMap** out)
+{
+    if (const int rc = usable(h, what)) return rc;
+    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used) return invalid(h, what, "no such costmap");
+    *out = &h->costmap.map[id];
+    return GEM_OK;
+}
+
+int costmap_plan_fresh(gem_handle* h, const CostMap& m, const char* what)
+{
+    if (!m.nav_gen) return invalid(h, what, "no plan was made");
+    if (m.nav_gen != m.gen) return invalid(h, what, "the plan was made before the costmap last rolled");
+    return GEM_OK;
+}
+
+int costmap_search_fresh(gem_handle* h, const CostMap& m, const char* what)
+{
+    if (!m.fr_gen) return invalid(h, what, "no search was made, or a plan was made since");
+    if (m.fr_gen != m.gen) return invalid(h, what, "the search was made before the costmap last rolled");
+    return GEM_OK;
+}
 
 void costmap_free(gem_handle* h)
 {
@@ -154,19 +158,12 @@ void costmap_free(gem_handle* h)
 
 } // namespace gemi
 
-#define COSTMAP_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device);                                         \
-    int rc;                                                          \
-    (void)rc
-
 extern "C" {
 
 int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id)
 {
-    COSTMAP_ENTRY("gem_costmap_create");
+    GEM_ENTRY("gem_costmap_create");
+    int rc;
     if ((rc = usable(h, "gem_costmap_create"))) return rc;
     if (!cfg || !out_id) return fail(h, GEM_ERR_INVALID, "gem_costmap_create: null argument");
     if (cfg->size_x == 0 || cfg->size_y == 0 || (long long)cfg->size_x * cfg->size_y > kMaxCells)
@@ -177,7 +174,7 @@ int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id
     int id = 0;
     while (id < gem_handle::Costmaps::kMax && c.map[id].used) ++id;
     if (id == gem_handle::Costmaps::kMax) return fail(h, GEM_ERR_INVALID, "gem_costmap_create: every costmap of the handle is in use");
-    Map& m = c.map[id];
+    CostMap& m = c.map[id];
     const size_t cells = (size_t)cfg->size_x * cfg->size_y, stamp_bytes = (cells + 3) / 4 * 16;
     if (!c.small.p) {
         if ((rc = ensure(h, c.small, 64))) return rc;
@@ -198,9 +195,10 @@ int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id
 
 int gem_costmap_destroy(gem_handle* h, int id)
 {
-    COSTMAP_ENTRY("gem_costmap_destroy");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_destroy", &m))) return rc;
+    GEM_ENTRY("gem_costmap_destroy");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_destroy", &m))) return rc;
     GEM_HIP(h, hipStreamSynchronize(h->stream));
     free_map(*m);
     return GEM_OK;
@@ -208,9 +206,10 @@ int gem_costmap_destroy(gem_handle* h, int id)
 
 int gem_costmap_geometry(gem_handle* h, int id, gem_costmap_config* out)
 {
-    COSTMAP_ENTRY("gem_costmap_geometry");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_geometry", &m))) return rc;
+    GEM_ENTRY("gem_costmap_geometry");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_geometry", &m))) return rc;
     if (!out) return fail(h, GEM_ERR_INVALID, "gem_costmap_geometry: null argument");
     *out = m->cfg;
     return GEM_OK;
@@ -218,26 +217,29 @@ int gem_costmap_geometry(gem_handle* h, int id, gem_costmap_config* out)
 
 int gem_costmap_reset(gem_handle* h, int id)
 {
-    COSTMAP_ENTRY("gem_costmap_reset");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_reset", &m))) return rc;
+    GEM_ENTRY("gem_costmap_reset");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_reset", &m))) return rc;
     GEM_HIP(h, launch_cost_fill(h->stream, grid_of(*m), cells_of(*m), m->cfg.default_value));
     return GEM_OK;
 }
 
 int gem_costmap_update_origin(gem_handle* h, int id, double new_origin_x, double new_origin_y)
 {
-    COSTMAP_ENTRY("gem_costmap_update_origin");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_update_origin", &m))) return rc;
+    GEM_ENTRY("gem_costmap_update_origin");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_update_origin", &m))) return rc;
     return update_origin(h, *m, new_origin_x, new_origin_y, "gem_costmap_update_origin");
 }
 
 int gem_costmap_roll_to(gem_handle* h, int id, double robot_x, double robot_y)
 {
-    COSTMAP_ENTRY("gem_costmap_roll_to");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_roll_to", &m))) return rc;
+    GEM_ENTRY("gem_costmap_roll_to");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_roll_to", &m))) return rc;
     // getSizeInMetersX() = (size_x - 1 + 0.5) * resolution (costmap_2d.cpp)
     const double mx = (m->cfg.size_x - 1 + 0.5) * m->cfg.resolution, my = (m->cfg.size_y - 1 + 0.5) * m->cfg.resolution;
     return update_origin(h, *m, robot_x - mx / 2, robot_y - my / 2, "gem_costmap_roll_to");
@@ -245,9 +247,10 @@ int gem_costmap_roll_to(gem_handle* h, int id, double robot_x, double robot_y)
 
 int gem_costmap_mark_points(gem_handle* h, int id, const void* points, long long n, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_points");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_points", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_points");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_points", &m))) return rc;
     if ((rc = check_cloud(h, "gem_costmap_mark_points", points, n, travers_thresh))) return rc;
     if (n > 0) {
         if ((rc = ensure(h, h->costmap.in, (size_t)n * kRec))) return rc;
@@ -259,18 +262,20 @@ int gem_costmap_mark_points(gem_handle* h, int id, const void* points, long long
 
 int gem_costmap_mark_points_device(gem_handle* h, int id, const void* d_points, long long n, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_points_device");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_points_device", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_points_device");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_points_device", &m))) return rc;
     if ((rc = check_cloud(h, "gem_costmap_mark_points_device", d_points, n, travers_thresh))) return rc;
     return mark_records(h, *m, static_cast<const LocalRecord*>(d_points), n, travers_thresh, bounds);
 }
 
 int gem_costmap_mark_grid_cloud(gem_handle* h, int id, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_grid_cloud");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_grid_cloud", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_grid_cloud");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_grid_cloud", &m))) return rc;
     if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_grid_cloud: travers_thresh not finite");
     CostVisualArgs cap{};
     if (!capture_of(h, &cap)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_grid_cloud: the local map is not enabled or has no capture");
@@ -281,9 +286,10 @@ int gem_costmap_mark_grid_cloud(gem_handle* h, int id, double travers_thresh, do
 
 int gem_costmap_mark_global(gem_handle* h, int id, int index, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_global");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_global", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_global");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_global", &m))) return rc;
     if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: travers_thresh not finite");
     auto& g = h->global;
     if (!g.enabled) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_global: the submap stack is not enabled (gem_global_enable)");
@@ -306,9 +312,10 @@ int gem_costmap_mark_global(gem_handle* h, int id, int index, double travers_thr
 // PointMapLayer over the history cloud where it lies (gem_hip_history.h): one launch, a workgroup per block of the box table
 int gem_costmap_mark_history(gem_handle* h, int id, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_history");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_history", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_history");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_history", &m))) return rc;
     if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_history: travers_thresh not finite");
     auto& hs = h->history;
     if (!hs.enabled) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_history: the history is not enabled (gem_history_enable)");
@@ -325,9 +332,10 @@ int gem_costmap_mark_history(gem_handle* h, int id, double travers_thresh, doubl
 
 int gem_costmap_mark_visual(gem_handle* h, int id, double travers_thresh, double bounds[4])
 {
-    COSTMAP_ENTRY("gem_costmap_mark_visual");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mark_visual", &m))) return rc;
+    GEM_ENTRY("gem_costmap_mark_visual");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mark_visual", &m))) return rc;
     if (!std::isfinite(travers_thresh)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_visual: travers_thresh not finite");
     CostVisualArgs a{};
     if (!capture_of(h, &a)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mark_visual: the local map is not enabled or has no capture");
@@ -338,9 +346,10 @@ int gem_costmap_mark_visual(gem_handle* h, int id, double travers_thresh, double
 
 int gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_j, int max_i, int max_j, int mode)
 {
-    COSTMAP_ENTRY("gem_costmap_merge");
-    Map *m, *master;
-    if ((rc = find(h, id, "gem_costmap_merge", &m)) || (rc = find(h, master_id, "gem_costmap_merge", &master))) return rc;
+    GEM_ENTRY("gem_costmap_merge");
+    int rc;
+    CostMap *m, *master;
+    if ((rc = costmap_find(h, id, "gem_costmap_merge", &m)) || (rc = costmap_find(h, master_id, "gem_costmap_merge", &master))) return rc;
     if (m->cfg.size_x != master->cfg.size_x || m->cfg.size_y != master->cfg.size_y)
         return fail(h, GEM_ERR_INVALID, "gem_costmap_merge: the two costmaps differ in size");
     if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_merge: window outside the map");
@@ -352,9 +361,10 @@ int gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_j
 
 int gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, unsigned char* out, size_t row_stride)
 {
-    COSTMAP_ENTRY("gem_costmap_read");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_read", &m))) return rc;
+    GEM_ENTRY("gem_costmap_read");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_read", &m))) return rc;
     if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_read: window outside the map");
     const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
     if (!w || !rows) return GEM_OK;
@@ -381,9 +391,10 @@ int gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int
 
 int gem_costmap_write(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, const unsigned char* in, size_t row_stride)
 {
-    COSTMAP_ENTRY("gem_costmap_write");
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_write", &m))) return rc;
+    GEM_ENTRY("gem_costmap_write");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_write", &m))) return rc;
     if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_write: window outside the map");
     const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
     if (!w || !rows) return GEM_OK;

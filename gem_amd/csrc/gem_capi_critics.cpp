@@ -6,7 +6,7 @@
 // kernel arguments.  The first pass's candidates (Costmaps::cr_cand) and the host-array form's staging (cr_pose, cr_len, cr_ext,
 // cr_total, cr_best) come from ensure() and only grow: gem_debug_get("arena_allocations") counts them, and a second identical call
 // allocates nothing.
-#include "gem_capi_internal.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_critics.hpp"
 
 #include <cmath>
@@ -14,7 +14,6 @@
 
 namespace {
 
-using Map = gem_handle::Costmaps::Map;
 constexpr long long kMaxPoses = 2147483646ll;                       // 2^31 - 2
 constexpr int kMaxPosesPerTraj = 1 << 20;
 constexpr int kObstacleFlags = GEM_FOOTPRINT_INSCRIBED_LETHAL | GEM_FOOTPRINT_SUM | GEM_CRITIC_CENTRE_COST;
@@ -26,8 +25,6 @@ static_assert(kCriticsMax == GEM_CRITIC_MAX && kCriticObstacle == GEM_CRITIC_OBS
 static_assert(GEM_CRITIC_GRID_PATH == GEM_MAPGRID_PATH && GEM_CRITIC_GRID_GOAL == GEM_MAPGRID_GOAL, "the first two grids are the MapGrid calls'");
 static_assert(GEM_FOOTPRINT_INSCRIBED_LETHAL == 1 && GEM_FOOTPRINT_SUM == 2 && GEM_MAPGRID_STOP_ON_FAILURE == 1 && GEM_MAPGRID_SUM == 2,
               "k_critics tests these bits");
-
-CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
 
 // the combination of one trajectory over the scores the caller holds: SimpleScoredSamplingPlanner::scoreTrajectory without its early exit
 double combine(const gem_critic* c, int n_critics, const double* scores, long long n_traj, long long t)
@@ -54,9 +51,10 @@ int bad(gem_handle* h, const Call& c, const char* why) { return fail(h, GEM_ERR_
 // the checks of a best-trajectory call, the candidates' arena and the kernel's argument block with everything but the caller's arrays
 int gemi::critics_prepare(gem_handle* h, int id, const CriticsCall& c, CriticsArgs& a, FootSpec& spec, CostGeom& geom)
 {
-    if (h->tp_x) return bad(h, c, "not on a handle with a communicator");
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used) return bad(h, c, "no such costmap");
-    Map& m = h->costmap.map[id];
+    int rc;
+    CostMap* found;
+    if ((rc = costmap_find(h, id, c.what, &found))) return rc;
+    CostMap& m = *found;
     if (c.n_critics < 1 || c.n_critics > GEM_CRITIC_MAX || !c.critics) return bad(h, c, "1 .. GEM_CRITIC_MAX critics, and not NULL");
     if (c.T < 1 || c.T > kMaxPosesPerTraj) return bad(h, c, "poses_per_traj outside 1 .. 2^20");
     if (c.n_traj < 0 || c.n_traj > kMaxPoses / c.T) return bad(h, c, "a negative count, or more than 2^31 - 2 poses");
@@ -102,10 +100,9 @@ int gemi::critics_prepare(gem_handle* h, int id, const CriticsCall& c, CriticsAr
         for (long long t = 0; t < c.n_traj; ++t)
             if (c.traj_len[t] < 1 || c.traj_len[t] > c.T) return bad(h, c, "a length outside 1 .. poses_per_traj");
 
-    int rc;
     auto& cm = h->costmap;
     if ((rc = ensure(h, cm.cr_cand, (size_t)kCriticsMaxBlocks * sizeof(CriticsCandidate)))) return rc;
-    a.grid = static_cast<const unsigned char*>(m.grid[m.act].p);
+    a.grid = grid_of(m);
     for (int s = 0; s < 3; ++s) a.dist[s] = static_cast<const int*>(m.mg_dist[s].p);
     a.cand = static_cast<CriticsCandidate*>(cm.cr_cand.p);
     a.n_traj = c.n_traj; a.T = c.T; a.n_critics = c.n_critics;
@@ -152,19 +149,13 @@ int best(gem_handle* h, int id, const Call& c)
 
 } // namespace
 
-#define CRITICS_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 extern "C" {
 
 int gem_costmap_best_trajectory(gem_handle* h, int id, const gem_critic* critics, int n_critics, const gem_footprint_pose* poses,
                                 const int* traj_len, long long n_traj, int poses_per_traj, const double* spec_xy, int n_vertices,
                                 const double* ext, int n_ext_columns, double* out_total, gem_best_trajectory* out_best)
 {
-    CRITICS_ENTRY("gem_costmap_best_trajectory");
+    GEM_ENTRY("gem_costmap_best_trajectory");
     return best(h, id, Call{"gem_costmap_best_trajectory", critics, n_critics, poses, traj_len, n_traj, poses_per_traj, spec_xy, n_vertices,
                             ext, n_ext_columns, out_total, out_best, false});
 }
@@ -173,7 +164,7 @@ int gem_costmap_best_trajectory_device(gem_handle* h, int id, const gem_critic* 
                                        const int* d_traj_len, long long n_traj, int poses_per_traj, const double* spec_xy, int n_vertices,
                                        const double* d_ext, int n_ext_columns, double* d_out_total, gem_best_trajectory* d_out_best)
 {
-    CRITICS_ENTRY("gem_costmap_best_trajectory_device");
+    GEM_ENTRY("gem_costmap_best_trajectory_device");
     return best(h, id, Call{"gem_costmap_best_trajectory_device", critics, n_critics, d_poses, d_traj_len, n_traj, poses_per_traj, spec_xy,
                             n_vertices, d_ext, n_ext_columns, d_out_total, d_out_best, true});
 }

@@ -6,29 +6,16 @@
 // bounds, the vertex cells and `ok` on the host in plain C++ (it knows the geometry after rolling) and only enqueues the fill.  The
 // host-array forms of the scoring calls stage their poses and results in Costmaps::fp_pose / fp_cost / fp_traj, which come from
 // ensure(): gem_debug_get("arena_allocations") counts them, and a loop that has reached its sizes allocates nothing.
-#include "gem_capi_internal.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_footprint.hpp"
 
 namespace {
 
-using Map = gem_handle::Costmaps::Map;
 constexpr long long kMaxPoses = 2147483646ll;                       // 2^31 - 2
 constexpr int kMaxPosesPerTraj = 1 << 20;
 constexpr int kKnownFlags = GEM_FOOTPRINT_INSCRIBED_LETHAL | GEM_FOOTPRINT_SUM;
 static_assert(sizeof(gem_footprint_pose) == 32 && sizeof(FootPose) == 32, "a pose is four packed doubles");
 static_assert(kFootMaxVertices == GEM_FOOTPRINT_MAX_VERTICES, "the kernels' vertex limit is the header's");
-
-CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
-unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
-
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
 
 int check_spec(gem_handle* h, const char* what, const double* spec_xy, int n_vertices, FootSpec* out)
 {
@@ -56,8 +43,8 @@ struct ScoreCall {
 int score(gem_handle* h, int id, const ScoreCall& c, const double* spec_xy, int n_vertices, int flags)
 {
     int rc;
-    Map* m;
-    if ((rc = find(h, id, c.what, &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, c.what, &m))) return rc;
     if (c.T < 1 || c.T > kMaxPosesPerTraj) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": poses_per_traj outside 1 .. 2^20").c_str());
     if (c.n_traj < 0 || c.n_traj > kMaxPoses / c.T) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": a negative count, or more than 2^31 - 2 poses").c_str());
     if (flags & ~kKnownFlags) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": unknown flag bits").c_str());
@@ -91,21 +78,15 @@ int score(gem_handle* h, int id, const ScoreCall& c, const double* spec_xy, int 
 
 } // namespace
 
-#define FOOTPRINT_ENTRY(name)                                        \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 extern "C" {
 
 int gem_costmap_clear_footprint(gem_handle* h, int id, const gem_footprint_pose* pose, const double* spec_xy, int n_vertices,
                                 double bounds[4], int* out_ok)
 {
-    FOOTPRINT_ENTRY("gem_costmap_clear_footprint");
+    GEM_ENTRY("gem_costmap_clear_footprint");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_clear_footprint", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_clear_footprint", &m))) return rc;
     FootSpec spec;
     if ((rc = check_spec(h, "gem_costmap_clear_footprint", spec_xy, n_vertices, &spec))) return rc;
     if (!pose || !std::isfinite(pose->x) || !std::isfinite(pose->y) || !std::isfinite(pose->cos_th) || !std::isfinite(pose->sin_th))
@@ -138,21 +119,21 @@ int gem_costmap_clear_footprint(gem_handle* h, int id, const gem_footprint_pose*
 int gem_costmap_footprint_cost(gem_handle* h, int id, const gem_footprint_pose* poses, long long n, const double* spec_xy,
                                int n_vertices, int flags, int* out_cost)
 {
-    FOOTPRINT_ENTRY("gem_costmap_footprint_cost");
+    GEM_ENTRY("gem_costmap_footprint_cost");
     return score(h, id, ScoreCall{"gem_costmap_footprint_cost", poses, n, 1, nullptr, out_cost, false}, spec_xy, n_vertices, flags);
 }
 
 int gem_costmap_footprint_cost_device(gem_handle* h, int id, const gem_footprint_pose* d_poses, long long n, const double* spec_xy,
                                       int n_vertices, int flags, int* d_out_cost)
 {
-    FOOTPRINT_ENTRY("gem_costmap_footprint_cost_device");
+    GEM_ENTRY("gem_costmap_footprint_cost_device");
     return score(h, id, ScoreCall{"gem_costmap_footprint_cost_device", d_poses, n, 1, nullptr, d_out_cost, true}, spec_xy, n_vertices, flags);
 }
 
 int gem_costmap_score_trajectories(gem_handle* h, int id, const gem_footprint_pose* poses, long long n_traj, int poses_per_traj,
                                    const double* spec_xy, int n_vertices, int flags, int* out_pose_cost, int* out_traj_cost)
 {
-    FOOTPRINT_ENTRY("gem_costmap_score_trajectories");
+    GEM_ENTRY("gem_costmap_score_trajectories");
     return score(h, id, ScoreCall{"gem_costmap_score_trajectories", poses, n_traj, poses_per_traj, out_pose_cost, out_traj_cost, false},
                  spec_xy, n_vertices, flags);
 }
@@ -160,7 +141,7 @@ int gem_costmap_score_trajectories(gem_handle* h, int id, const gem_footprint_po
 int gem_costmap_score_trajectories_device(gem_handle* h, int id, const gem_footprint_pose* d_poses, long long n_traj, int poses_per_traj,
                                           const double* spec_xy, int n_vertices, int flags, int* d_out_pose_cost, int* d_out_traj_cost)
 {
-    FOOTPRINT_ENTRY("gem_costmap_score_trajectories_device");
+    GEM_ENTRY("gem_costmap_score_trajectories_device");
     return score(h, id, ScoreCall{"gem_costmap_score_trajectories_device", d_poses, n_traj, poses_per_traj, d_out_pose_cost, d_out_traj_cost, true},
                  spec_xy, n_vertices, flags);
 }

@@ -2,33 +2,21 @@
 // gem_costmap_frontiers and its read-back.  The kernels are in gem_frontier.hip; gem_costmap_navplan_goal is in gem_capi_navplan.cpp.
 //
 // gem_costmap_frontiers enqueues: the classification, then CHUNKS of label rounds, each chunk closed by k_front_check, which answers
-// through pinned words: "a tile is still marked" or not.  The round count depends on the data, so the host loops as for the potential:
-// a chunk of tiles_x + tiles_y rounds (gem_debug_set "front_chunk" sets another length), a wait, a look at the converged word, the next
-// chunk while it is not set.  The total is bounded by the cell count: after round r every cell whose chain to its component's smallest
-// cell crosses at most r tile seams holds its final label, a chain has at most `cells` cells, and one more round finds nothing to mark.
-// The bound is in the loop's condition.  Behind the last chunk the reduction is enqueued, and one more wait brings the status.
+// through pinned words: "a tile is still marked" or not.  The host loop and its bound are run_tile_rounds' (gem_rounds.hpp), as for the
+// potential; a chunk is tiles_x + tiles_y rounds (gem_debug_set "front_chunk" sets another length).  Behind the last chunk the
+// reduction is enqueued, and one more wait brings the status.
 // The labels, the index scratch, the active maps, the records and the kept list live with the costmap (Map::fr_*), the compaction's
 // block counts and the pinned block with the handle's costmaps; all come from ensure() and only grow.
-#include "gem_capi_internal.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_compact.hpp"
 #include "gem_frontier.hpp"
+#include "gem_rounds.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 namespace {
-
-using Map = gem_handle::Costmaps::Map;
-
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
 
 // finite, not negative, at most 1e100: no product of the cost overflows and no NaN can arise
 bool params_ok(const gem_frontier_params* p)
@@ -136,22 +124,15 @@ int gem_frontiers_host(const unsigned char* grid, const int* pot, int size_x, in
     return GEM_OK;
 }
 
-#define FRONTIER_ENTRY(name)                                         \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 int gem_costmap_frontiers(gem_handle* h, int id, const gem_frontier_params* params, gem_frontier_status* status)
 {
-    FRONTIER_ENTRY("gem_costmap_frontiers");
+    GEM_ENTRY("gem_costmap_frontiers");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_frontiers", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_frontiers", &m))) return rc;
     if (!params || !status) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers: NULL params or status");
     if (!params_ok(params)) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers: a parameter that is not finite, is negative or is above 1e100");
-    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers: no plan was made");
-    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers: the plan was made before the costmap last rolled");
+    if ((rc = costmap_plan_fresh(h, *m, "gem_costmap_frontiers"))) return rc;
 
     auto& cm = h->costmap;
     FrontArgs a{};
@@ -170,7 +151,7 @@ int gem_costmap_frontiers(gem_handle* h, int id, const gem_frontier_params* para
     volatile FrontPin* pin = static_cast<FrontPin*>(cm.fr_pin);
     pin->converged = 0; pin->rounds = 0;
 
-    a.grid = static_cast<unsigned char*>(m->grid[m->act].p);
+    a.grid = grid_of(*m);
     a.pot = static_cast<int*>(m->nav_pot.p);
     a.label = static_cast<int*>(m->fr_label.p); a.index = static_cast<int*>(m->fr_index.p);
     a.act = static_cast<int*>(m->fr_act.p); a.words = static_cast<int*>(m->fr_words.p);
@@ -188,28 +169,28 @@ int gem_costmap_frontiers(gem_handle* h, int id, const gem_frontier_params* para
     GEM_HIP(h, hipMemsetAsync(a.act, 0, 2 * nt * sizeof(int), h->stream));
     GEM_HIP(h, hipMemsetAsync(a.words, 0, kFrontWords * sizeof(int), h->stream));
     GEM_HIP(h, launch_front_classify(h->stream, a));
-    const long long chunk = h->front_chunk > 0 ? h->front_chunk : (long long)a.ntx + a.nty;
-    long long rounds = 0;
-    int chunks = 0;
-    bool converged = false;
-    const long long max_rounds = cells + 2;                             // (fits a.round: a costmap has at most 2^30 cells)
-    while (!converged && rounds < max_rounds) {                         // (bounded by the cell count: see the head comment)
-        const long long n_rounds = std::min(chunk, max_rounds - rounds);   // (the last chunk is cut at the bound)
-        for (long long r = 0; r < n_rounds; ++r, ++rounds) {
-            a.round = (int)rounds;
+    RoundsResult rr;
+    rc = run_tile_rounds(
+        cells, h->front_chunk > 0 ? h->front_chunk : (long long)a.ntx + a.nty,
+        [&](int round) -> int {
+            a.round = round;
             GEM_HIP(h, launch_front_round(h->stream, a));
-        }
-        a.round = (int)rounds;
-        GEM_HIP(h, launch_front_check(h->stream, a));
-        GEM_HIP(h, hipStreamSynchronize(h->stream));
-        ++chunks;
-        converged = pin->converged != 0;
-    }
-    if (!converged) return fail(h, GEM_ERR_HIP, "gem_costmap_frontiers: the labels did not converge within their bound");
+            return GEM_OK;
+        },
+        [&](int round, bool& converged) -> int {
+            a.round = round;
+            GEM_HIP(h, launch_front_check(h->stream, a));
+            GEM_HIP(h, hipStreamSynchronize(h->stream));
+            converged = pin->converged != 0;
+            return GEM_OK;
+        },
+        rr);
+    if (rc) return rc;
+    if (!rr.converged) return fail(h, GEM_ERR_HIP, "gem_costmap_frontiers: the labels did not converge within their bound");
     GEM_HIP(h, launch_front_reduce(h->stream, a, static_cast<uint32_t*>(cm.fr_blocks.p)));
     GEM_HIP(h, hipStreamSynchronize(h->stream));
     *status = const_cast<const FrontPin*>(static_cast<FrontPin*>(cm.fr_pin))->status;
-    status->chunks = chunks;
+    status->chunks = rr.chunks;
     if (status->best < 0) status->best_frontier = empty_frontier();
     m->fr_gen = m->gen;
     m->fr_n_kept = status->n_kept;
@@ -218,12 +199,11 @@ int gem_costmap_frontiers(gem_handle* h, int id, const gem_frontier_params* para
 
 int gem_costmap_frontiers_read(gem_handle* h, int id, gem_frontier* out, long long cap, int* out_labels)
 {
-    FRONTIER_ENTRY("gem_costmap_frontiers_read");
+    GEM_ENTRY("gem_costmap_frontiers_read");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_frontiers_read", &m))) return rc;
-    if (!m->fr_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers_read: no search was made, or a plan was made since");
-    if (m->fr_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers_read: the search was made before the costmap last rolled");
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_frontiers_read", &m))) return rc;
+    if ((rc = costmap_search_fresh(h, *m, "gem_costmap_frontiers_read"))) return rc;
     const long long n = m->fr_n_kept, cells = (long long)m->cfg.size_x * m->cfg.size_y;
     if (out && cap < n) return fail(h, GEM_ERR_INVALID, "gem_costmap_frontiers_read: the list has more records than out holds");
     HostXfer d[2];

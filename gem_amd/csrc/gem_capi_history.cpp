@@ -110,19 +110,12 @@ int history_blocks_culled(gem_handle* h, long long* out)
 
 } // namespace gemi
 
-#define HISTORY_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device);                                         \
-    int rc;                                                          \
-    (void)rc
-
 extern "C" {
 
 int gem_history_enable(gem_handle* h, long long capacity)
 {
-    HISTORY_ENTRY("gem_history_enable");
+    GEM_ENTRY("gem_history_enable");
+    int rc;
     if (capacity < 0 || capacity > kMaxInputs) return fail(h, GEM_ERR_INVALID, "gem_history_enable: capacity out of range");
     if (h->tp_x) return fail(h, GEM_ERR_INVALID, "gem_history_enable: not on a handle with a communicator");
     if (capacity == 0) { history_free(h); return GEM_OK; }
@@ -139,7 +132,8 @@ int gem_history_enable(gem_handle* h, long long capacity)
 
 int gem_history_append(gem_handle* h, const void* points, long long n)
 {
-    HISTORY_ENTRY("gem_history_append");
+    GEM_ENTRY("gem_history_append");
+    int rc;
     if ((rc = usable(h, "gem_history_append"))) return rc;
     if (n < 0 || (n > 0 && !points)) return fail(h, GEM_ERR_INVALID, "gem_history_append: bad cloud");
     if ((rc = history_check_room(h, n, "gem_history_append"))) return rc;
@@ -155,7 +149,8 @@ int gem_history_append(gem_handle* h, const void* points, long long n)
 
 int gem_history_append_device(gem_handle* h, const void* d_points, long long n)
 {
-    HISTORY_ENTRY("gem_history_append_device");
+    GEM_ENTRY("gem_history_append_device");
+    int rc;
     if ((rc = usable(h, "gem_history_append_device"))) return rc;
     if (n < 0 || (n > 0 && !d_points)) return fail(h, GEM_ERR_INVALID, "gem_history_append_device: bad cloud");
     if ((rc = history_check_room(h, n, "gem_history_append_device"))) return rc;
@@ -166,7 +161,8 @@ int gem_history_append_device(gem_handle* h, const void* d_points, long long n)
 
 int gem_history_reset_from_global(gem_handle* h)
 {
-    HISTORY_ENTRY("gem_history_reset_from_global");
+    GEM_ENTRY("gem_history_reset_from_global");
+    int rc;
     if ((rc = usable(h, "gem_history_reset_from_global"))) return rc;
     const auto& g = h->global;
     if (!g.enabled) return fail(h, GEM_ERR_INVALID, "gem_history_reset_from_global: the submap stack is not enabled (gem_global_enable)");
@@ -189,7 +185,8 @@ int gem_history_reset_from_global(gem_handle* h)
 
 int gem_history_clear(gem_handle* h)
 {
-    HISTORY_ENTRY("gem_history_clear");
+    GEM_ENTRY("gem_history_clear");
+    int rc;
     if ((rc = usable(h, "gem_history_clear"))) return rc;
     h->history.len = 0;
     return GEM_OK;
@@ -197,7 +194,8 @@ int gem_history_clear(gem_handle* h)
 
 int gem_history_size(gem_handle* h, long long* out_count)
 {
-    HISTORY_ENTRY("gem_history_size");
+    GEM_ENTRY("gem_history_size");
+    int rc;
     if (!out_count) return fail(h, GEM_ERR_INVALID, "gem_history_size: null argument");
     if ((rc = usable(h, "gem_history_size"))) return rc;
     *out_count = h->history.len;
@@ -206,7 +204,8 @@ int gem_history_size(gem_handle* h, long long* out_count)
 
 int gem_history_export(gem_handle* h, int with_grid_cloud, void* points, long long max_points, long long* out_count)
 {
-    HISTORY_ENTRY("gem_history_export");
+    GEM_ENTRY("gem_history_export");
+    int rc;
     if ((rc = usable(h, "gem_history_export"))) return rc;
     auto& hs = h->history;
     uint32_t n_grid = 0;

@@ -7,7 +7,7 @@
 // call live in Costmaps::infl_bits / infl_flags, which come from ensure() and only grow, so a loop that has reached its window
 // allocates nothing (gem_debug_get("arena_allocations") counts).  gem_costmap_inflate enqueues two launches and waits for nothing,
 // except in the call that uploads a new table.
-#include "gem_capi_internal.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_inflate.hpp"
 
 #include <cmath>
@@ -15,21 +15,9 @@
 
 namespace {
 
-using Map = gem_handle::Costmaps::Map;
 static_assert(kInflateMaxCells == GEM_INFLATE_MAX_CELLS, "the kernels' radius limit is the header's");
 
-unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
-
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
-
-bool window_ok(const Map& m, int x0, int y0, int xn, int yn)
+bool window_ok(const CostMap& m, int x0, int y0, int xn, int yn)
 {
     return x0 >= 0 && y0 >= 0 && x0 <= xn && y0 <= yn && (long long)xn <= (long long)m.cfg.size_x && (long long)yn <= (long long)m.cfg.size_y;
 }
@@ -70,12 +58,6 @@ bool same_key(const gem_inflation_params& a, const gem_inflation_params& b)
 
 } // namespace
 
-#define INFLATE_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 extern "C" {
 
 int gem_inflation_table(const gem_inflation_params* params, double resolution, unsigned char* out_table, int* out_cells)
@@ -89,10 +71,10 @@ int gem_inflation_table(const gem_inflation_params* params, double resolution, u
 
 int gem_costmap_inflate(gem_handle* h, int id, const gem_inflation_params* params, int min_i, int min_j, int max_i, int max_j)
 {
-    INFLATE_ENTRY("gem_costmap_inflate");
+    GEM_ENTRY("gem_costmap_inflate");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_inflate", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_inflate", &m))) return rc;
     unsigned R;
     if (!inflation_cells(params, m->cfg.resolution, &R))
         return fail(h, GEM_ERR_INVALID, "gem_costmap_inflate: NULL parameters, a radius or factor not finite or negative, or more than 127 cells");
@@ -120,10 +102,10 @@ int gem_costmap_inflate(gem_handle* h, int id, const gem_inflation_params* param
 
 int gem_costmap_reset_window(gem_handle* h, int id, int x0, int y0, int xn, int yn)
 {
-    INFLATE_ENTRY("gem_costmap_reset_window");
+    GEM_ENTRY("gem_costmap_reset_window");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_reset_window", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_reset_window", &m))) return rc;
     if (!window_ok(*m, x0, y0, xn, yn)) return fail(h, GEM_ERR_INVALID, "gem_costmap_reset_window: window outside the map");
     GEM_HIP(h, launch_inflate_reset(h->stream, grid_of(*m), m->cfg.size_x, InflateBox{(uint32_t)x0, (uint32_t)y0, (uint32_t)xn, (uint32_t)yn},
                                     m->cfg.default_value));

@@ -7,6 +7,9 @@
 //                          gem_reserve: the same plans for the extremal passes inside its bounds
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
+//   gem_costmap_host.hpp   the costmap family's shared host pieces (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
+//                          _navplan / _frontier .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
+//   gem_rounds.hpp         the host loop of the tiled fixed-point kernels (plan, frontier labels): chunks of rounds up to the bound (pure C++)
 #pragma once
 
 #include "../../include/gem_hip.h"
@@ -402,6 +405,14 @@ struct ApiRange {
 
 #define GEM_HIP(h, call)                                                        \
     do { hipError_t _e = (call); if (_e != hipSuccess) return fail(h, GEM_ERR_HIP, #call, _e); } while (0)
+
+// The prelude of an entry point that takes the handle's lock for the whole call: the optional roctx range, the NULL handle, the lock,
+// the handle's device.  Nothing else belongs here; an entry point that needs an `rc` declares it.
+#define GEM_ENTRY(name)                                                         \
+    ApiRange api_range(h, name);                                                \
+    if (!h) return GEM_ERR_INVALID;                                             \
+    std::lock_guard<std::mutex> lk(h->mu);                                      \
+    hipSetDevice(h->device)
 
 // ... inside a multi-rank step, between its collectives: a rank that fails there takes the communicators down with it, so that the
 // peers' pending receives fail instead of waiting for it (step_abort)

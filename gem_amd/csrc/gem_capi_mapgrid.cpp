@@ -12,7 +12,7 @@
 // A costmap has three grid slots: path, goal and front (the goal grid of DWA's front plan, include/gem_hip_critics.h).  prepare() and
 // read() below work on slots; the public `which` of the MapGrid calls still admits PATH | GOAL only, and the front slot is reached
 // through gem_costmap_mapgrid_prepare_front / _read_front and by gem_costmap_best_trajectory (gem_capi_critics.cpp).
-#include "gem_capi_internal.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_mapgrid.hpp"
 
 #include <cmath>
@@ -20,7 +20,6 @@
 
 namespace {
 
-using Map = gem_handle::Costmaps::Map;
 constexpr long long kMaxPoses = 2147483646ll;                       // 2^31 - 2
 constexpr int kMaxPosesPerTraj = 1 << 20;
 constexpr int kKnownFlags = GEM_MAPGRID_STOP_ON_FAILURE | GEM_MAPGRID_SUM;
@@ -29,19 +28,7 @@ constexpr int kSlots = 3, kFrontSlot = 2;                           // path | go
 static_assert(kMapGridMaxWords == GEM_MAPGRID_MAX_WORDS, "the kernel's LDS limit is the header's");
 static_assert(sizeof(gem_footprint_pose) == sizeof(FootPose), "a pose is four packed doubles");
 
-CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
-unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
-
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
-
-bool fits(const Map& m) { return (unsigned long long)mapgrid_row_words(m.cfg.size_x) * m.cfg.size_y <= kMapGridMaxWords; }
+bool fits(const CostMap& m) { return (unsigned long long)mapgrid_row_words(m.cfg.size_x) * m.cfg.size_y <= kMapGridMaxWords; }
 
 // MapGrid::adjustPlanResolution.  Returns the adjusted plan's point count and writes the first `cap` points to out (NULL: none);
 // -1: a coordinate or a step count that is not usable, or more than `limit` points.
@@ -78,14 +65,14 @@ long long adjust_plan(const double* plan, long long n, double resolution, double
 // exactly one grid -> its slot
 int slot_of(int which_one) { return which_one == GEM_MAPGRID_PATH ? 0 : (which_one == GEM_MAPGRID_GOAL ? 1 : -1); }
 
-int usable_slot(gem_handle* h, Map& m, int slot, const char* what)
+int usable_slot(gem_handle* h, CostMap& m, int slot, const char* what)
 {
     if (!m.mg_gen[slot]) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was never prepared").c_str());
     if (m.mg_gen[slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled").c_str());
     return GEM_OK;
 }
 
-int usable_grid(gem_handle* h, Map& m, int which_one, const char* what, int* slot)
+int usable_grid(gem_handle* h, CostMap& m, int which_one, const char* what, int* slot)
 {
     *slot = slot_of(which_one);
     if (*slot < 0) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": which_one is GEM_MAPGRID_PATH or GEM_MAPGRID_GOAL").c_str());
@@ -104,8 +91,8 @@ struct ScoreCall {
 int score(gem_handle* h, int id, int which_one, const ScoreCall& c, double xshift, int flags)
 {
     int rc, slot;
-    Map* m;
-    if ((rc = find(h, id, c.what, &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, c.what, &m))) return rc;
     if (c.T < 1 || c.T > kMaxPosesPerTraj) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": poses_per_traj outside 1 .. 2^20").c_str());
     if (c.n_traj < 0 || c.n_traj > kMaxPoses / c.T) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": a negative count, or more than 2^31 - 2 poses").c_str());
     if (flags & ~kKnownFlags) return fail(h, GEM_ERR_INVALID, (std::string(c.what) + ": unknown flag bits").c_str());
@@ -141,8 +128,8 @@ int score(gem_handle* h, int id, int which_one, const ScoreCall& c, double xshif
 int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots)
 {
     int rc;
-    Map* m;
-    if ((rc = find(h, id, what, &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
     if (n < 0 || (n > 0 && !plan_xy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": a negative count, or a NULL plan with a non-zero count").c_str());
     if (!fits(*m)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS").c_str());
     auto& cm = h->costmap;
@@ -197,8 +184,8 @@ int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long
 int read(gem_handle* h, int id, const char* what, int slot, int* out, int* out_started, int out_goal_cell[2])
 {
     int rc;
-    Map* m;
-    if ((rc = find(h, id, what, &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
     if ((rc = usable_slot(h, *m, slot, what))) return rc;
     int st[kMapGridStatusWords] = {};
     HostXfer d[2] = {{st, static_cast<int*>(m->mg_status.p) + slot * kMapGridStatusWords, sizeof(st)},
@@ -210,12 +197,6 @@ int read(gem_handle* h, int id, const char* what, int slot, int* out, int* out_s
 }
 
 } // namespace
-
-#define MAPGRID_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
 
 extern "C" {
 
@@ -230,47 +211,47 @@ int gem_mapgrid_adjust_plan(const double* plan_xy, long long n, double resolutio
 
 int gem_costmap_mapgrid_prepare(gem_handle* h, int id, const double* plan_xy, long long n, int which)
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_prepare");
+    GEM_ENTRY("gem_costmap_mapgrid_prepare");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mapgrid_prepare", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mapgrid_prepare", &m))) return rc;
     if (!(which & kBoth) || (which & ~kBoth)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare: which is a mask of GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL");
     return prepare(h, id, "gem_costmap_mapgrid_prepare", plan_xy, n, which);      // (the public bits are the slots' bits)
 }
 
 int gem_costmap_mapgrid_prepare_front(gem_handle* h, int id, const double* plan_xy, long long n)
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_prepare_front");
+    GEM_ENTRY("gem_costmap_mapgrid_prepare_front");
     return prepare(h, id, "gem_costmap_mapgrid_prepare_front", plan_xy, n, 1 << kFrontSlot);
 }
 
 int gem_costmap_mapgrid_read(gem_handle* h, int id, int which_one, int* out, int* out_started, int out_goal_cell[2])
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_read");
+    GEM_ENTRY("gem_costmap_mapgrid_read");
     int rc, slot;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_mapgrid_read", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mapgrid_read", &m))) return rc;
     if ((rc = usable_grid(h, *m, which_one, "gem_costmap_mapgrid_read", &slot))) return rc;
     return read(h, id, "gem_costmap_mapgrid_read", slot, out, out_started, out_goal_cell);
 }
 
 int gem_costmap_mapgrid_read_front(gem_handle* h, int id, int* out, int* out_started, int out_goal_cell[2])
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_read_front");
+    GEM_ENTRY("gem_costmap_mapgrid_read_front");
     return read(h, id, "gem_costmap_mapgrid_read_front", kFrontSlot, out, out_started, out_goal_cell);
 }
 
 int gem_costmap_mapgrid_score(gem_handle* h, int id, int which_one, const gem_footprint_pose* poses, long long n_traj, int poses_per_traj,
                               double xshift, int flags, long long* out_traj)
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_score");
+    GEM_ENTRY("gem_costmap_mapgrid_score");
     return score(h, id, which_one, ScoreCall{"gem_costmap_mapgrid_score", poses, n_traj, poses_per_traj, out_traj, false}, xshift, flags);
 }
 
 int gem_costmap_mapgrid_score_device(gem_handle* h, int id, int which_one, const gem_footprint_pose* d_poses, long long n_traj,
                                      int poses_per_traj, double xshift, int flags, long long* d_out_traj)
 {
-    MAPGRID_ENTRY("gem_costmap_mapgrid_score_device");
+    GEM_ENTRY("gem_costmap_mapgrid_score_device");
     return score(h, id, which_one, ScoreCall{"gem_costmap_mapgrid_score_device", d_poses, n_traj, poses_per_traj, d_out_traj, true}, xshift, flags);
 }
 

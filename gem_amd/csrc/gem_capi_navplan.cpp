@@ -3,17 +3,13 @@
 //
 // gem_costmap_navplan maps start and goal with worldToMap on the host (it knows the geometry after rolling), hands the weight table
 // over in pinned host memory and enqueues: init, then CHUNKS of rounds, each chunk closed by k_nav_finish, which answers through the
-// pinned status words: "a tile is still marked", or the walked path.  The round count depends on the data, so the host loops: a chunk
-// of tiles_x + tiles_y rounds (gem_debug_set "nav_chunk" sets another length), a wait, a look at the converged word, the next chunk
-// while it is not set.  A round behind convergence finds no active tile and costs one empty launch.  The total is bounded by the cell
-// count, as Bellman-Ford's is: after round r every cell whose cheapest path crosses at most r tile seams holds its final value (its
-// tile ran behind the round that settled the edge cell the path last entered through, and a tile's round ends at its local fixed
-// point), a path has at most `cells` cells, and one more round finds nothing to mark.  The bound is in the loop's condition.
+// pinned status words: "a tile is still marked", or the walked path.  The host loop and its bound are run_tile_rounds' (gem_rounds.hpp);
+// a chunk is tiles_x + tiles_y rounds (gem_debug_set "nav_chunk" sets another length).
 // The potential, the active maps, the path and the status live with the costmap (Map::nav_*), the device table and the pinned block
 // with the handle's costmaps; all come from ensure() and only grow, so a second identical call allocates nothing.
-#include "gem_capi_internal.hpp"
-#include "gem_costmap.hpp"
+#include "gem_costmap_host.hpp"
 #include "gem_navplan.hpp"
+#include "gem_rounds.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -22,22 +18,9 @@
 
 namespace {
 
-using Map = gem_handle::Costmaps::Map;
 static_assert(kNavUnreached == GEM_NAV_UNREACHED, "the kernels' constant is the header's");
 constexpr long long kNavLimit = 2147483647ll;                       // 2^31 - 1
 constexpr size_t kNavPinBytes = (256 + kNavStatusWords) * sizeof(int);
-
-CostGeom geom_of(const Map& m) { return CostGeom{m.cfg.origin_x, m.cfg.origin_y, m.cfg.resolution, m.cfg.size_x, m.cfg.size_y}; }
-unsigned char* grid_of(Map& m) { return static_cast<unsigned char*>(m.grid[m.act].p); }
-
-int find(gem_handle* h, int id, const char* what, Map** out)
-{
-    if (h->tp_x) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": not on a handle with a communicator").c_str());
-    if (id < 0 || id >= gem_handle::Costmaps::kMax || !h->costmap.map[id].used)
-        return fail(h, GEM_ERR_INVALID, (std::string(what) + ": no such costmap").c_str());
-    *out = &h->costmap.map[id];
-    return GEM_OK;
-}
 
 // a table the contract admits for this many cells: no negative weight, cells * max(w) below 2^31 - 1
 bool weights_ok(const int* w, long long cells)
@@ -86,6 +69,52 @@ void host_potential(const unsigned char* grid, int sx, int sy, const int* w, boo
             if (cand < pot[n]) { pot[n] = cand; heap.push({cand, n}); }
         }
     }
+}
+
+// the kernels' argument block bound to a costmap whose arenas and pinned block exist: sizes, tiles, grid, arenas, pin (its status
+// words cleared); start, goal, outline and round are the caller's
+NavArgs bind_args(gem_handle* h, CostMap& m)
+{
+    auto& cm = h->costmap;
+    NavArgs a{};
+    a.sx = (int)m.cfg.size_x; a.sy = (int)m.cfg.size_y; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
+    a.grid = grid_of(m);
+    a.w = static_cast<int*>(cm.nav_w.p);
+    a.pot = static_cast<int*>(m.nav_pot.p); a.act = static_cast<int*>(m.nav_act.p);
+    a.path = static_cast<int*>(m.nav_path.p); a.status = static_cast<int*>(m.nav_status.p);
+    a.pin = static_cast<int*>(cm.nav_pin);
+    volatile int* pin_status = a.pin + 256;
+    for (int i = 0; i < kNavStatusWords; ++i) pin_status[i] = 0;
+    return a;
+}
+
+// behind the wait for k_nav_finish: its answer out of the pinned words into *st (rounds and chunks are the caller's), the plan on
+// record in generation `gen`, the path downloaded and its cells' centres in out_xy
+int finish_plan(gem_handle* h, CostMap& m, const NavArgs& a, unsigned long long gen, const char* what, gem_navplan_status* st, double* out_xy,
+                long long cap)
+{
+    auto& cm = h->costmap;
+    const volatile int* pin_status = a.pin + 256;
+    st->found = pin_status[kNavFound];
+    st->n_path = pin_status[kNavNPath];
+    st->goal_potential = pin_status[kNavGoalPot];
+    m.nav_gen = gen;
+    m.nav_n_path = st->n_path;
+    m.nav_last = *st;
+    const long long n = st->n_path, cells = (long long)a.sx * a.sy;
+    cm.nav_cells.resize((size_t)n);
+    if (n > 0) {
+        HostXfer d{cm.nav_cells.data(), a.path + (cells - n), (size_t)n * sizeof(int)};
+        if (const int rc = download_arrays(h, &d, 1, 0)) return rc;
+    }
+    if (!out_xy) return GEM_OK;
+    const CostGeom g = geom_of(m);
+    for (long long i = 0; i < std::min(n, cap); ++i) {
+        const int c = cm.nav_cells[(size_t)i];
+        out_xy[2 * i] = g.ox + ((double)(c % a.sx) + 0.5) * g.res;
+        out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
+    }
+    return cap < n ? fail(h, GEM_ERR_INVALID, (std::string(what) + ": the path has more points than out_xy holds").c_str()) : GEM_OK;
 }
 
 } // namespace
@@ -141,20 +170,14 @@ int gem_navplan_host(const unsigned char* grid, int size_x, int size_y, const in
     return GEM_OK;
 }
 
-#define NAVPLAN_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const double goal_xy[2], const int* w, int flags, double* out_xy,
                         long long cap, gem_navplan_status* st)
 {
-    NAVPLAN_ENTRY("gem_costmap_navplan");
+    GEM_ENTRY("gem_costmap_navplan");
     const char* what = "gem_costmap_navplan";
     int rc;
-    Map* m;
-    if ((rc = find(h, id, what, &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
     if (!start_xy || !goal_xy || !w || !st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a NULL start, goal, weight table or status");
     if (flags & ~GEM_NAV_OUTLINE) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: unknown flag bits");
     if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative capacity");
@@ -165,17 +188,13 @@ int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const d
     if (!weights_ok(w, cells)) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1");
 
     auto& cm = h->costmap;
-    NavArgs a{};
-    a.sx = (int)g.sx; a.sy = (int)g.sy; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
-    const size_t nt = (size_t)a.ntx * a.nty;
+    const size_t nt = (size_t)nav_tiles((int)g.sx) * nav_tiles((int)g.sy);
     if ((rc = ensure(h, m->nav_pot, (size_t)cells * sizeof(int))) || (rc = ensure(h, m->nav_path, (size_t)cells * sizeof(int))) ||
         (rc = ensure(h, m->nav_act, 2 * nt * sizeof(int))) || (rc = ensure(h, m->nav_status, kNavStatusWords * sizeof(int))) ||
         (rc = ensure(h, cm.nav_w, 256 * sizeof(int)))) return rc;
     if (!cm.nav_pin) GEM_HIP(h, hipHostMalloc(&cm.nav_pin, kNavPinBytes, hipHostMallocDefault));
-    int* pin = static_cast<int*>(cm.nav_pin);
-    volatile int* pin_status = pin + 256;
-    std::copy(w, w + 256, pin);
-    for (int i = 0; i < kNavStatusWords; ++i) pin_status[i] = 0;
+    NavArgs a = bind_args(h, *m);
+    std::copy(w, w + 256, a.pin);
 
     empty_status(st);
     uint32_t cell = 0u;
@@ -183,141 +202,88 @@ int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const d
     a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
     if (a.start >= 0) { st->start_cell[0] = a.start % a.sx; st->start_cell[1] = a.start / a.sx; }
     if (a.goal >= 0) { st->goal_cell[0] = a.goal % a.sx; st->goal_cell[1] = a.goal / a.sx; }
-    a.grid = grid_of(*m);
-    a.w = static_cast<int*>(cm.nav_w.p);
-    a.pot = static_cast<int*>(m->nav_pot.p); a.act = static_cast<int*>(m->nav_act.p);
-    a.path = static_cast<int*>(m->nav_path.p); a.status = static_cast<int*>(m->nav_status.p);
-    a.pin = pin;
     a.outline = (flags & GEM_NAV_OUTLINE) ? 1 : 0;
 
     m->nav_gen = 0;                                                     // (a failure below leaves no plan to read)
     m->nav_n_path = 0;
     m->fr_gen = 0;                                                      // (a frontier search carries the plan it was made from)
     GEM_HIP(h, launch_nav_init(h->stream, a));
-    const long long chunk = h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty;
-    long long rounds = 0;
-    int chunks = 0;
-    bool converged = false;
-    const long long max_rounds = cells + 2;                             // (fits a.round: a costmap has at most 2^30 cells)
-    while (!converged && rounds < max_rounds) {                         // (bounded by the cell count: see the head comment)
-        const long long n_rounds = std::min(chunk, max_rounds - rounds);   // (the last chunk is cut at the bound)
-        for (long long r = 0; r < n_rounds; ++r, ++rounds) {
-            a.round = (int)rounds;
+    const volatile int* pin_status = a.pin + 256;
+    RoundsResult rr;
+    rc = run_tile_rounds(
+        cells, h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty,
+        [&](int round) -> int {
+            a.round = round;
             GEM_HIP(h, launch_nav_round(h->stream, a));
-        }
-        a.round = (int)rounds;
-        GEM_HIP(h, launch_nav_finish(h->stream, a));
-        GEM_HIP(h, hipStreamSynchronize(h->stream));
-        ++chunks;
-        converged = pin_status[kNavConverged] != 0;
-    }
-    if (!converged) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan: the potential did not converge within its bound");
-    st->found = pin_status[kNavFound];
-    st->n_path = pin_status[kNavNPath];
+            return GEM_OK;
+        },
+        [&](int round, bool& converged) -> int {
+            a.round = round;
+            GEM_HIP(h, launch_nav_finish(h->stream, a));
+            GEM_HIP(h, hipStreamSynchronize(h->stream));
+            converged = pin_status[kNavConverged] != 0;
+            return GEM_OK;
+        },
+        rr);
+    if (rc) return rc;
+    if (!rr.converged) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan: the potential did not converge within its bound");
     st->rounds = pin_status[kNavRounds];
-    st->chunks = chunks;
-    st->goal_potential = pin_status[kNavGoalPot];
-    m->nav_gen = m->gen;
-    m->nav_n_path = st->n_path;
-    m->nav_last = *st;
-    const long long n = st->n_path;
-    cm.nav_cells.resize((size_t)n);
-    if (n > 0) {
-        HostXfer d{cm.nav_cells.data(), a.path + (cells - n), (size_t)n * sizeof(int)};
-        if ((rc = download_arrays(h, &d, 1, 0))) return rc;
-    }
-    if (!out_xy) return GEM_OK;
-    for (long long i = 0; i < std::min(n, cap); ++i) {
-        const int c = cm.nav_cells[(size_t)i];
-        out_xy[2 * i] = g.ox + ((double)(c % a.sx) + 0.5) * g.res;
-        out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
-    }
-    return cap < n ? fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: the path has more points than out_xy holds") : GEM_OK;
+    st->chunks = rr.chunks;
+    return finish_plan(h, *m, a, m->gen, what, st, out_xy, cap);
 }
 
 // Another goal on the last plan's potential (include/gem_hip_frontier.h): one launch of k_nav_finish.  After convergence both active
 // maps are clear, so the kernel reports "converged" and walks; the potential is read, never written.
 int gem_costmap_navplan_goal(gem_handle* h, int id, const double goal_xy[2], double* out_xy, long long cap, gem_navplan_status* st)
 {
-    NAVPLAN_ENTRY("gem_costmap_navplan_goal");
+    GEM_ENTRY("gem_costmap_navplan_goal");
+    const char* what = "gem_costmap_navplan_goal";
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_navplan_goal", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
     if (!goal_xy || !st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a NULL goal or status");
     if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a negative capacity");
     if (!std::isfinite(goal_xy[0]) || !std::isfinite(goal_xy[1])) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: a coordinate not finite");
-    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: no plan was made");
-    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: the plan was made before the costmap last rolled");
-    auto& cm = h->costmap;
-    const CostGeom g = geom_of(*m);
-    const long long cells = (long long)g.sx * g.sy;
-    NavArgs a{};
-    a.sx = (int)g.sx; a.sy = (int)g.sy; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
-    int* pin = static_cast<int*>(cm.nav_pin);                           // (a plan was made on this handle: the arenas and the block exist)
-    volatile int* pin_status = pin + 256;
-    for (int i = 0; i < kNavStatusWords; ++i) pin_status[i] = 0;
-    *st = m->nav_last;
+    if ((rc = costmap_plan_fresh(h, *m, what))) return rc;
+    NavArgs a = bind_args(h, *m);                                       // (a plan was made on this handle: the arenas and the block exist)
+    *st = m->nav_last;                                                  // (rounds are the plan's)
     uint32_t cell = 0u;
     a.start = st->start_cell[0] >= 0 ? st->start_cell[1] * a.sx + st->start_cell[0] : -1;
-    a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
+    a.goal = cost_cell(geom_of(*m), goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
     st->goal_cell[0] = a.goal >= 0 ? a.goal % a.sx : -1;
     st->goal_cell[1] = a.goal >= 0 ? a.goal / a.sx : -1;
-    a.grid = grid_of(*m);
-    a.w = static_cast<int*>(cm.nav_w.p);
-    a.pot = static_cast<int*>(m->nav_pot.p); a.act = static_cast<int*>(m->nav_act.p);
-    a.path = static_cast<int*>(m->nav_path.p); a.status = static_cast<int*>(m->nav_status.p);
-    a.pin = pin;
     a.round = 0;                                                        // (either map: both are clear)
     const unsigned long long plan_gen = m->nav_gen;
     m->nav_gen = 0;                                                     // (a failure below leaves no path to read)
     m->nav_n_path = 0;
     GEM_HIP(h, launch_nav_finish(h->stream, a));
     GEM_HIP(h, hipStreamSynchronize(h->stream));
+    const volatile int* pin_status = a.pin + 256;
     if (!pin_status[kNavConverged]) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan_goal: a tile of the last plan is still marked");
-    st->found = pin_status[kNavFound];
-    st->n_path = pin_status[kNavNPath];
     st->chunks = 1;
-    st->goal_potential = pin_status[kNavGoalPot];
-    m->nav_gen = plan_gen;
-    m->nav_n_path = st->n_path;
-    m->nav_last = *st;
-    const long long n = st->n_path;
-    cm.nav_cells.resize((size_t)n);
-    if (n > 0) {
-        HostXfer d{cm.nav_cells.data(), a.path + (cells - n), (size_t)n * sizeof(int)};
-        if ((rc = download_arrays(h, &d, 1, 0))) return rc;
-    }
-    if (!out_xy) return GEM_OK;
-    for (long long i = 0; i < std::min(n, cap); ++i) {
-        const int c = cm.nav_cells[(size_t)i];
-        out_xy[2 * i] = g.ox + ((double)(c % a.sx) + 0.5) * g.res;
-        out_xy[2 * i + 1] = g.oy + ((double)(c / a.sx) + 0.5) * g.res;
-    }
-    return cap < n ? fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_goal: the path has more points than out_xy holds") : GEM_OK;
+    return finish_plan(h, *m, a, plan_gen, what, st, out_xy, cap);
 }
 
 int gem_costmap_navplan_status(gem_handle* h, int id, gem_navplan_status* st)
 {
-    NAVPLAN_ENTRY("gem_costmap_navplan_status");
+    GEM_ENTRY("gem_costmap_navplan_status");
     int rc;
-    Map* m;
-    if ((rc = find(h, id, "gem_costmap_navplan_status", &m))) return rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_navplan_status", &m))) return rc;
     if (!st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: a NULL status");
-    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: no plan was made");
-    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_status: the plan was made before the costmap last rolled");
+    if ((rc = costmap_plan_fresh(h, *m, "gem_costmap_navplan_status"))) return rc;
     *st = m->nav_last;
     return GEM_OK;
 }
 
 int gem_costmap_navplan_read(gem_handle* h, int id, int* out_pot, int* out_path_cells, long long cap)
 {
-    NAVPLAN_ENTRY("gem_costmap_navplan_read");
+    GEM_ENTRY("gem_costmap_navplan_read");
     const char* what = "gem_costmap_navplan_read";
     int rc;
-    Map* m;
-    if ((rc = find(h, id, what, &m))) return rc;
-    if (!m->nav_gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: no plan was made");
-    if (m->nav_gen != m->gen) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: the plan was made before the costmap last rolled");
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
+    if ((rc = costmap_plan_fresh(h, *m, what))) return rc;
     const long long n = m->nav_n_path, cells = (long long)m->cfg.size_x * m->cfg.size_y;
     if (out_path_cells && cap < n) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan_read: the path has more cells than out_path_cells holds");
     HostXfer d[2];

@@ -293,18 +293,12 @@ void octree_free(gem_handle* h)
 
 } // namespace gemi
 
-#define OCTREE_ENTRY(name)                          \
-    ApiRange api_range(h, name);                    \
-    if (!h) return GEM_ERR_INVALID;                 \
-    std::lock_guard<std::mutex> lk(h->mu);          \
-    hipSetDevice(h->device);                        \
-    int rc
-
 extern "C" {
 
 int gem_octree_build(gem_handle* h, int slot, const gem_octree_params* params, const void* points, long long n, gem_octree_stats* stats)
 {
-    OCTREE_ENTRY("gem_octree_build");
+    GEM_ENTRY("gem_octree_build");
+    int rc;
     Tables t;
     if ((rc = check_common(h, slot, "gem_octree_build")) || (rc = check_cloud(h, "gem_octree_build", points, n))) return rc;
     if (!make_tables(params, t)) return fail(h, GEM_ERR_INVALID, "gem_octree_build: parameters (resolution, prob_hit, clamps)");
@@ -318,7 +312,8 @@ int gem_octree_build(gem_handle* h, int slot, const gem_octree_params* params, c
 
 int gem_octree_build_device(gem_handle* h, int slot, const gem_octree_params* params, const void* d_points, long long n, gem_octree_stats* stats)
 {
-    OCTREE_ENTRY("gem_octree_build_device");
+    GEM_ENTRY("gem_octree_build_device");
+    int rc;
     Tables t;
     if ((rc = check_common(h, slot, "gem_octree_build_device")) || (rc = check_cloud(h, "gem_octree_build_device", d_points, n))) return rc;
     if (!make_tables(params, t)) return fail(h, GEM_ERR_INVALID, "gem_octree_build_device: parameters (resolution, prob_hit, clamps)");
@@ -328,7 +323,8 @@ int gem_octree_build_device(gem_handle* h, int slot, const gem_octree_params* pa
 int gem_local_compose_octrees(gem_handle* h, const gem_compose_params* p, const gem_octree_params* road_params,
                               const gem_octree_params* obstacle_params, int out_counts[3], double* out_threshold, gem_octree_stats stats[2])
 {
-    OCTREE_ENTRY("gem_local_compose_octrees");
+    GEM_ENTRY("gem_local_compose_octrees");
+    int rc;
     Tables tr, to;
     if ((rc = compose_check(h, p, "gem_local_compose_octrees"))) return rc;
     if (!make_tables(road_params, tr) || !make_tables(obstacle_params, to))
@@ -347,7 +343,8 @@ int gem_local_compose_octrees(gem_handle* h, const gem_compose_params* p, const 
 
 int gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_t* out_bytes)
 {
-    OCTREE_ENTRY("gem_octree_read");
+    GEM_ENTRY("gem_octree_read");
+    int rc;
     if ((rc = check_common(h, slot, "gem_octree_read"))) return rc;
     const auto& sl = h->octree.slot[slot];
     const size_t bytes = (size_t)sl.bytes;

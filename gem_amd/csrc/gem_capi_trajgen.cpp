@@ -65,12 +65,6 @@ int dwa_best(gem_handle* h, int id, const char* what, const gem_critic* critics,
 
 } // namespace
 
-#define TRAJGEN_ENTRY(name)                                          \
-    ApiRange api_range(h, name);                                     \
-    if (!h) return GEM_ERR_INVALID;                                  \
-    std::lock_guard<std::mutex> lk(h->mu);                           \
-    hipSetDevice(h->device)
-
 extern "C" {
 
 int gem_trajgen_plan(const gem_trajgen_limits* limits, const gem_trajgen_config* config, const float pos[3], const float vel[3],
@@ -100,7 +94,7 @@ int gem_trajgen_sincos(const double* angles, long long n, double* out_sin, doubl
 int gem_trajgen_generate_device(gem_handle* h, const gem_dwa_plan* plan, const float pos[3], const float vel[3], gem_footprint_pose* d_poses,
                                 int* d_traj_len, double* d_ext, float* d_vel, int poses_per_traj)
 {
-    TRAJGEN_ENTRY("gem_trajgen_generate_device");
+    GEM_ENTRY("gem_trajgen_generate_device");
     if (h->tp_x) return fail(h, GEM_ERR_INVALID, "gem_trajgen_generate_device: not on a handle with a communicator");
     if (!trajgen_call_ok(plan, pos, vel, poses_per_traj))
         return fail(h, GEM_ERR_INVALID, "gem_trajgen_generate_device: a plan gem_trajgen_plan did not make, a start state that is not finite, poses_per_traj "
@@ -116,7 +110,7 @@ int gem_costmap_dwa_best(gem_handle* h, int id, const gem_critic* critics, int n
                          const float vel[3], int poses_per_traj, const double* spec_xy, int n_vertices, double* out_total,
                          gem_best_trajectory* out_best)
 {
-    TRAJGEN_ENTRY("gem_costmap_dwa_best");
+    GEM_ENTRY("gem_costmap_dwa_best");
     return dwa_best(h, id, "gem_costmap_dwa_best", critics, n_critics, plan, pos, vel, poses_per_traj, spec_xy, n_vertices, out_total, out_best, false);
 }
 
@@ -124,7 +118,7 @@ int gem_costmap_dwa_best_device(gem_handle* h, int id, const gem_critic* critics
                                 const float vel[3], int poses_per_traj, const double* spec_xy, int n_vertices, double* d_out_total,
                                 gem_best_trajectory* d_out_best)
 {
-    TRAJGEN_ENTRY("gem_costmap_dwa_best_device");
+    GEM_ENTRY("gem_costmap_dwa_best_device");
     return dwa_best(h, id, "gem_costmap_dwa_best_device", critics, n_critics, plan, pos, vel, poses_per_traj, spec_xy, n_vertices, d_out_total,
                     d_out_best, true);
 }

@@ -80,6 +80,18 @@ def test_the_copy_thread_pool_moves_every_byte(tmp_path):
     assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout + run.stderr
 
 
+def test_the_round_driver_stops_at_its_bound(tmp_path):
+    """gem_amd/csrc/gem_rounds.hpp on its own (tests/cpp/rounds_check.cpp): the host loop of gem_costmap_navplan and gem_costmap_frontiers
+    with counting lambdas -- rounds and closes in order, the chunk count, the bound of cells + 2 rounds and the cut of the last chunk
+    at it (which no converging kernel reaches), and a lambda's non-zero return stopping the loop at once."""
+    exe = tmp_path / "rounds_check"
+    res = subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-Werror", str(ROOT / "tests" / "cpp" / "rounds_check.cpp"), "-o", str(exe)],
+                         capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0 and run.stdout.strip() == "ok", run.stdout + run.stderr
+
+
 def test_gem_reserve_covers_the_plan_of_every_pass_inside_its_bounds(tmp_path):
     """gem_amd/csrc/gem_plan.hpp on its own (tests/cpp/plan_cover.cpp): over map sizes, sorted forms, pass counts, chunks, thresholds,
     rings, bounds and colours, every buffer of every pass drawn from inside the bounds is no larger than what gem_reserve's bound
