@@ -2,14 +2,14 @@
 // to a record, one winner.  The contract is restated in include/gem_hip_frontier.h.  Integer code only, except the pick's cost.
 //
 // Labelling is a connected-component problem above one workgroup (a global costmap is 1000 x 1000 cells), so it takes the form of
-// gem_navplan.hip: the labels live in global memory and are relaxed TILE BY TILE, a launch per round:
+// gem_navplan.hip: the labels live in global memory and are relaxed tile by tile, a launch per round.  The protocol -- active maps,
+// load, store, marks, and why a tile may read old halo values -- is gem_tile_round.hpp's; this file's own part:
 //   k_front_classify  one pass over the cells: the byte, the four neighbours' bytes and potentials.  label[c] = c for a frontier cell,
 //                     kFrontNone (2^31 - 1) otherwise; every tile that holds a frontier cell is marked in round 0's active map; the
 //                     frontier cells are counted, one atomic per wave and trip at most.
-//   k_front_round     one workgroup -- one wave -- per tile of 64 x 64 cells.  A tile that is not marked in this round's active map
-//                     leaves at once.  An active tile clears its mark, loads its labels and a one-cell halo WITH the four corner cells
-//                     (connectivity is 8: 66 x 66) into LDS, rows in batches whose loads are all in flight together, and relaxes to the
-//                     tile's LOCAL fixed point: every frontier cell takes the minimum of its own label and its eight neighbours',
+//   k_front_round     an active tile loads its labels and a one-cell halo WITH the four corner cells (connectivity is 8: 66 x 66),
+//                     leaves if it holds no frontier cell (nothing can change), and relaxes to the tile's LOCAL fixed point:
+//                     every frontier cell takes the minimum of its own label and its eight neighbours',
 //                     cells that are no frontier cells stay kFrontNone and carry nothing.  Lane t runs a running minimum along row t
 //                     from the left halo to the right and back, then along column t down and up, then along the two wrapped
 //                     diagonals through (0, t) -- the minimum resets at a cell that is no frontier cell.  A line's 64 cells are held
@@ -18,30 +18,18 @@
 //                     tools/bench_frontier.py: a step that waits for its own load and branches round its store, with one diagonal
 //                     step per pass, took 12.2 ms where this form takes 5.6 ms); a pass extends the reach of a component's smallest
 //                     label along every in-tile chain
-//                     by at least one cell, a chain has at most 4096 cells, hence the loop's bound (stated in its condition).  Then it
-//                     stores the cells that changed and marks, in the NEXT round's map, each of the up to EIGHT neighbour tiles whose
-//                     facing edge or corner cell changed.
+//                     by at least one cell, a chain has at most 4096 cells, hence the loop's bound (stated in its condition).  Each of
+//                     the up to EIGHT neighbour tiles is marked whose facing edge or corner cell changed.
 //   k_front_check     one wave behind a chunk of rounds: "a tile is still marked" goes to the pinned words and the host enqueues
 //                     another chunk, or the reduction.
-// The active maps are double-buffered: round r reads map r & 1 and writes marks (plain stores of 1) into map (r + 1) & 1; a tile is
-// the only one that clears its own word.  The labelling has converged when a round marks nothing.
-//
-// Why stale halo reads are safe.  Inside a launch a tile may read a neighbour's edge while the neighbour rewrites it; nothing orders
-// the two, and nothing needs to:
-//   1. labels only fall: every store writes a value below the one the same workgroup loaded from that cell, and a cell is written by
-//      its own tile's workgroup alone (and by k_front_classify before the first round);
-//   2. every stored label is the linear index of a cell of the SAME component (induction: a cell's own index is one, and a label
-//      taken from an 8-neighbour that is a frontier cell is one -- the halo's included), so no label ever lies BELOW the component's
-//      smallest cell, and a tile that works from old halo values computes labels that are too large at worst.  The same holds inside
-//      a tile's LDS: a lane may read a neighbour row's cell before or after its owner lowers it, both are labels of the component, and
-//      a pass that changes nothing has read no cell that was written in it, so it has seen the fixed point itself;
-//   3. an aligned 32-bit load sees the old or the new value of a cell, never a mixture;
-//   4. a tile whose neighbour's facing edge or corner cell changed in round r is marked by that neighbour and runs in round r + 1,
-//      behind the kernel boundary that makes round r's stores visible to every CU.  So whatever a tile missed it sees one round later.
-// At the fixed point no edge changes, no tile is marked, and label[c] = min(label[c], min8(label)) holds for every frontier cell with
+// Why its values are valid ones (point 2 there): every stored label is the linear index of a cell of the SAME component (induction: a
+// cell's own index is one, and a label taken from an 8-neighbour that is a frontier cell is one -- the halo's included), so no label
+// ever lies BELOW the component's smallest cell.  The same holds inside a tile's LDS: a lane may read a neighbour row's cell before or
+// after its owner lowers it, both are labels of the component, and a pass that changes nothing has read no cell that was written in
+// it, so it has seen the fixed point itself.  That fixed point is label[c] = min(label[c], min8(label)) for every frontier cell with
 // the true halo: two 8-adjacent frontier cells carry the same label, so a component carries one label, which is at most its smallest
-// cell's own index (that cell started with it, and labels only fall) and by 2. not below it: every frontier cell carries its
-// component's smallest cell.
+// cell's own index (that cell started with it, and labels only fall) and not below it: every frontier cell carries its component's
+// smallest cell.
 //
 // The reduction needs no order either.  The roots (label[c] == c) go through the stable count / scan / scatter of gem_compact.hpp into
 // a dense list in ascending cell order; the scatter writes each root's list index at the root's cell of a cells-sized scratch (only
@@ -53,10 +41,9 @@
 // computes cost and kept flag per record, compacts the kept records in order, takes the minimum of (cost, root) and writes the winner
 // and the counts to the pinned status.
 //
-// No workgroup waits for another one: there is no spin-wait, no grid-wide barrier, no cooperative launch and no residency
-// requirement; every loop is bounded by a count stated in its condition.  Global memory is touched by vector loads, stores and
-// vector atomics only.  status.rounds is the last round that found an active tile, plus one; it depends on timing (point 4 above),
-// nothing else does.
+// As in the rounds, no workgroup waits for another one here, every loop is bounded by a count stated in its condition, and global
+// memory is touched by vector loads, stores and vector atomics only.  status.rounds is the protocol's round counter: it depends on
+// timing, nothing else does.
 #include "gem_frontier.hpp"
 
 #include "gem_compact.hpp"
@@ -65,16 +52,10 @@
 
 namespace gem {
 
-static_assert(kNavTile == 64, "a tile's row and column are a wave wide");
-static_assert((kNavTile + 2) % kFrontLoadBatch == 0, "the load phase takes the tile's rows and its two halo rows in whole batches");
-static_assert(kFrontStride % 2 == 1, "an odd LDS stride: a wave's lanes on rows t hit different banks");
 static_assert(kFrontNone == kNavUnreached, "one 'nothing' for labels and potentials");
 static_assert(sizeof(gem_frontier) == 40, "the record of the header");
 
 constexpr unsigned long long kFrontNoKey = ~0ull;
-
-// A word another launch wrote, read with a vector load (see gem_navplan.hip).
-__device__ __forceinline__ int front_load_word(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // the access key of cell (x, y): the smallest (potential << 32) | cell over its doors, kFrontNoKey without one.  The four neighbours'
 // loads are unconditional at clamped addresses, the selects afterwards: one memory round trip.
@@ -204,64 +185,11 @@ __global__ __launch_bounds__(64) void k_front_round(FrontArgs a)
 {
     __shared__ int s_lab[(kNavTile + 2) * kFrontStride];                // [row + 1][column + 1] with the halo
     __shared__ int s_old[kNavTile * kNavTile];                          // the labels as they were loaded
-    const int nt = a.ntx * a.nty, tile = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (tile >= nt) return;
-    int* act_cur = a.act + (a.round & 1) * nt;
-    int* act_next = a.act + ((a.round + 1) & 1) * nt;
-    if (front_load_word(act_cur + tile) == 0) return;                   // (uniform: the whole wave read the same word)
-    if (lane == 0) {
-        act_cur[tile] = 0;                                              // read: cleared by its own tile
-        atomicMax(&a.words[kFrontRounds], a.round + 1);
-    }
-    const int ty = tile / a.ntx, tx = tile - ty * a.ntx;
-    const int x0 = tx * kNavTile, y0 = ty * kNavTile;
-
-    // ---- load: rows -1 .. 64 of the tile's columns, the two halo columns and the four corners.  Every load of a batch is issued
-    //      before the first of them is used -- unconditional loads at clamped addresses, the selects afterwards.
-    bool has = false;
-    {
-        const int gx = x0 + lane, hy = y0 + lane;
-        int halo[2], corner;
-        bool halo_in[2], corner_in;
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int hx = side ? x0 + kNavTile : x0 - 1;
-            halo_in[side] = hy < a.sy && hx >= 0 && hx < a.sx;
-            halo[side] = a.label[halo_in[side] ? (size_t)hy * (size_t)a.sx + (size_t)hx : (size_t)0];
-        }
-        const int cside = lane & 1, cbottom = (lane >> 1) & 1;          // lanes 0 .. 3 take a corner each, the others repeat them
-        {
-            const int cx = cside ? x0 + kNavTile : x0 - 1, cy = cbottom ? y0 + kNavTile : y0 - 1;
-            corner_in = cx >= 0 && cx < a.sx && cy >= 0 && cy < a.sy;
-            corner = a.label[corner_in ? (size_t)cy * (size_t)a.sx + (size_t)cx : (size_t)0];
-        }
-#pragma unroll 1
-        for (int r0 = 0; r0 < kNavTile + 2; r0 += kFrontLoadBatch) {
-            int l[kFrontLoadBatch];
-#pragma unroll
-            for (int j = 0; j < kFrontLoadBatch; ++j) {
-                const int gy = y0 + r0 + j - 1;
-                const bool in = gy >= 0 && gy < a.sy && gx < a.sx;
-                l[j] = a.label[in ? (size_t)gy * (size_t)a.sx + (size_t)gx : (size_t)0];
-            }
-#pragma unroll
-            for (int j = 0; j < kFrontLoadBatch; ++j) {
-                const int r = r0 + j, gy = y0 + r - 1;
-                const bool in = gy >= 0 && gy < a.sy && gx < a.sx;
-                const int lv = in ? l[j] : kFrontNone;
-                s_lab[r * kFrontStride + lane + 1] = lv;
-                if (r >= 1 && r <= kNavTile) {
-                    s_old[(r - 1) * kNavTile + lane] = lv;              // what memory holds: the store phase compares with it
-                    has |= lv != kFrontNone;
-                }
-            }
-        }
-#pragma unroll
-        for (int side = 0; side < 2; ++side)
-            s_lab[(lane + 1) * kFrontStride + (side ? kNavTile + 1 : 0)] = halo_in[side] ? halo[side] : kFrontNone;
-        if (lane < 4) s_lab[(cbottom ? kNavTile + 1 : 0) * kFrontStride + (cside ? kNavTile + 1 : 0)] = corner_in ? corner : kFrontNone;
-    }
-    if (!__any(has)) return;                                            // (uniform) no frontier cell here: nothing can change
+    const int lane = (int)threadIdx.x;
+    TileRound t;
+    if (!tile_round_enter(a.act, a.round, a.ntx, a.nty, &a.words[kFrontRounds], t)) return;   // (uniform)
+    TileNoExtra none;
+    if (!tile_load<kFrontStride, true>(a.label, a.sx, a.sy, t, kFrontNone, s_lab, s_old, none)) return;   // (uniform) no frontier cell here
     __syncthreads();
 
     // ---- relax to the tile's fixed point
@@ -283,48 +211,14 @@ __global__ __launch_bounds__(64) void k_front_round(FrontArgs a)
     }
     if (!any_change) return;                                            // (uniform)
 
-    // ---- store what changed; which edges and corners did.  The old values are the LDS copy of the load phase: only this workgroup
-    //      writes these cells, so memory still holds them and nothing is read again.
-    int edges = 0;                                                      // 1 top | 2 bottom | 4 left | 8 right | 16 .. 128 the corners
-    {
-        const int gx = x0 + lane;
-#pragma unroll 8
-        for (int r = 0; r < kNavTile; ++r) {
-            const int gy = y0 + r;
-            const int old = s_old[r * kNavTile + lane], now = s_lab[(r + 1) * kFrontStride + lane + 1];
-            if (gy < a.sy && gx < a.sx && now != old) {
-                a.label[(size_t)gy * (size_t)a.sx + (size_t)gx] = now;
-                const bool t = r == 0, b = r == kNavTile - 1, l = lane == 0, rt = lane == kNavTile - 1;
-                edges |= (t ? 1 : 0) | (b ? 2 : 0) | (l ? 4 : 0) | (rt ? 8 : 0) | (t && l ? 16 : 0) | (t && rt ? 32 : 0) | (b && l ? 64 : 0) |
-                         (b && rt ? 128 : 0);
-            }
-        }
-    }
-    int all = 0;
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) all |= __any(edges & (1 << bit)) ? (1 << bit) : 0;
-    if (lane == 0) {
-        const bool up = ty > 0, down = ty + 1 < a.nty, lft = tx > 0, rgt = tx + 1 < a.ntx;
-        if ((all & 1) && up) act_next[tile - a.ntx] = 1;
-        if ((all & 2) && down) act_next[tile + a.ntx] = 1;
-        if ((all & 4) && lft) act_next[tile - 1] = 1;
-        if ((all & 8) && rgt) act_next[tile + 1] = 1;
-        if ((all & 16) && up && lft) act_next[tile - a.ntx - 1] = 1;
-        if ((all & 32) && up && rgt) act_next[tile - a.ntx + 1] = 1;
-        if ((all & 64) && down && lft) act_next[tile + a.ntx - 1] = 1;
-        if ((all & 128) && down && rgt) act_next[tile + a.ntx + 1] = 1;
-    }
+    tile_store_and_mark<kFrontStride, true>(a.label, a.sx, a.sy, a.ntx, a.nty, t, s_lab, s_old);
 }
 
 __global__ __launch_bounds__(64) void k_front_check(FrontArgs a)
 {
-    const int nt = a.ntx * a.nty, lane = (int)threadIdx.x;
-    const int* act = a.act + (a.round & 1) * nt;                        // the map the next round would read
-    bool marked = false;
-    for (int i = lane; i < nt; i += 64) marked |= act[i] != 0;          // (bounded by the tile count)
-    const int rounds = front_load_word(a.words + kFrontRounds);
-    const bool any = __any(marked);
-    if (lane == 0) { a.pin->rounds = rounds; a.pin->converged = any ? 0 : 1; }
+    const bool any = tiles_still_marked(a.act, a.round, a.ntx * a.nty); // in the map the next round would read
+    const int rounds = tile_load_word(a.words + kFrontRounds);
+    if (threadIdx.x == 0) { a.pin->rounds = rounds; a.pin->converged = any ? 0 : 1; }
 }
 
 // ---- the reduction ---------------------------------------------------------------------------------------------------------------------
@@ -367,7 +261,7 @@ __device__ __forceinline__ unsigned long long wave_min64(unsigned long long v)
 __global__ __launch_bounds__(256) void k_front_accumulate(FrontArgs a, const uint32_t* n_roots_p)
 {
     const uint32_t cells = (uint32_t)a.sx * (uint32_t)a.sy;
-    const uint32_t n_roots = (uint32_t)front_load_word(reinterpret_cast<const int*>(n_roots_p));
+    const uint32_t n_roots = (uint32_t)tile_load_word(reinterpret_cast<const int*>(n_roots_p));
     for (uint32_t base = blockIdx.x * 256u; base < cells; base += gridDim.x * 256u) {   // (workgroup-uniform; bounded by the cell count)
         const uint32_t i = base + threadIdx.x;
         const int l = i < cells ? a.label[i] : kFrontNone;
@@ -434,7 +328,7 @@ __global__ __launch_bounds__(kFrontPickThreads) void k_front_pick(FrontArgs a, c
     __shared__ uint32_t s_scan[16];
     __shared__ double s_cost[NW];
     __shared__ int s_root[NW], s_idx[NW], s_rec[NW];
-    const uint32_t n_all = (uint32_t)front_load_word(reinterpret_cast<const int*>(n_roots_p));
+    const uint32_t n_all = (uint32_t)tile_load_word(reinterpret_cast<const int*>(n_roots_p));
     const int n = (int)(n_all < cap ? n_all : cap);
     uint32_t carry = 0;
     FrontBest best{0.0, -1, -1, -1};
@@ -465,11 +359,11 @@ __global__ __launch_bounds__(kFrontPickThreads) void k_front_pick(FrontArgs a, c
     if (threadIdx.x == 0) {
         for (int i = 1; i < NW; ++i) best = front_better(best, FrontBest{s_cost[i], s_root[i], s_idx[i], s_rec[i]});   // (bounded by the waves)
         gem_frontier_status* st = &a.pin->status;                       // (field by field: no copy of the struct on a stack)
-        st->n_cells = front_load_word(a.words + kFrontCells);
+        st->n_cells = tile_load_word(a.words + kFrontCells);
         st->n_frontiers = n;
         st->n_kept = (int)carry;
         st->best = best.idx;
-        st->rounds = front_load_word(a.words + kFrontRounds);
+        st->rounds = tile_load_word(a.words + kFrontRounds);
         st->chunks = 0;
         bool kept;
         const gem_frontier f = front_record(a, best.root >= 0 ? best.rec : 0, kept);      // (record 0 of the arena: readable, not used)

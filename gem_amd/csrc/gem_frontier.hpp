@@ -18,7 +18,6 @@ namespace gem {
 
 constexpr int kFrontNone = 0x7fffffff;                              // the label of a cell that is no frontier cell
 constexpr int kFrontStride = kNavTile + 3;                          // LDS row of the labels with its two halo cells, odd
-constexpr int kFrontLoadBatch = 22;                                 // rows of a tile with its two halo rows (66) loaded together
 constexpr int kFrontPickThreads = 1024;
 
 // device words | their pinned host copy

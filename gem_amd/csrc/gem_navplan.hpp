@@ -8,6 +8,7 @@
 #pragma once
 
 #include "gem_navpath.hpp"
+#include "gem_tile_round.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -15,10 +16,8 @@
 
 namespace gem {
 
-constexpr int kNavTile = 64;                                        // a tile is 64 x 64 cells, one wave: lane t owns row t, then column t
 constexpr int kNavPotStride = kNavTile + 3;                         // LDS row of the potentials with its two halo cells, odd
 constexpr int kNavWStride = kNavTile + 1;
-constexpr int kNavLoadBatch = 22;                                   // rows of a tile (with its two halo rows: 66) whose loads are in flight together
 constexpr unsigned kNavBlockedWeight = 0x80000000u;                 // an impassable cell's weight in LDS: v + it is above every potential
 
 // status words, on the device and in their pinned host copy
@@ -37,8 +36,6 @@ struct NavArgs {
     int outline;
     int round;                          // the round of this launch (finish: the next one)
 };
-
-inline int nav_tiles(int n) { return (n + kNavTile - 1) / kNavTile; }
 
 hipError_t launch_nav_init(hipStream_t st, const NavArgs& a);
 hipError_t launch_nav_round(hipStream_t st, const NavArgs& a);

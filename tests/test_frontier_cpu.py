@@ -90,6 +90,38 @@ def diagonal_scene(anti):
     return g, (1, 1)
 
 
+def climbing_scene(left):
+    """130 x 130: one frontier whose smallest cell lies in an UPPER tile and whose label, having run down across an edge and along
+    row 64, reaches another upper tile only by CLIMBING through that tile's corner: from (63, 64) up to (64, 63) into tile (1, 0), the
+    root 660 in tile (0, 0); or, `left`, from (64, 64) up to (63, 63) into tile (0, 0), the root 750 in tile (1, 0).  (diagonal_scene's
+    smallest cell lies in an upper tile too, so there a label crosses the corner downwards only.)"""
+    g = np.zeros((130, 130), np.uint8)
+    if not left:
+        g[5:71, 10] = 255
+        g[64, 10:64] = 255
+        g[63, 64:80] = 255
+    else:
+        g[5:65, 100] = 255
+        g[64, 64:101] = 255
+        g[63, 50:64] = 255
+    g.setflags(write=False)
+    return g, (1, 1)
+
+
+CLIMBING = {False: (660, 135), True: (750, 110)}                         # left: the frontier's root and its cells
+
+
+def climbing_expected(left):
+    """(grid, start, pot, fref.search) of climbing_scene, with what the scene claims asserted"""
+    g, start = climbing_scene(left)
+    pot = potential(g, start)
+    want = fref.search(g, pot, RES)
+    four = fref.labels_flood(want["mask"], fref.N4)
+    assert want["n_frontiers"] == 1 and len(np.unique(four[want["mask"]])) == 2      # 4-connectivity would not pass
+    assert (want["all"][0]["root"], want["all"][0]["size"]) == CLIMBING[left]
+    return g, start, pot, want
+
+
 def serpentine_scene(n=130):
     """a one-cell-wide serpentine of unknown cells through known free space: rows y = 1, 3, 5, ... span x = 1 .. n - 2 and are joined
     at alternating ends"""
@@ -286,6 +318,11 @@ def test_host_twin_special_scenes_and_the_pick(lib):
         rc, lab, rec, st = host_search(lib, g, pot)
         assert rc == 0
         same_as_ref(fref.search(g, pot, RES), lab, rec, st, name)
+    for left in (False, True):
+        g, start, pot, want = climbing_expected(left)
+        rc, lab, rec, st = host_search(lib, g, pot)
+        assert rc == 0
+        same_as_ref(want, lab, rec, st, f"climbing, left {left}")
     g, start = pick_scene()
     pot = potential(g, start)
     winners = {}

@@ -32,7 +32,7 @@ import frontier_ref as fref  # noqa: E402
 import inflate_ref as iref  # noqa: E402
 import navplan_ref as nref  # noqa: E402
 from test_costmap_gpu import lattice_cloud  # noqa: E402
-from test_frontier_cpu import (PICK_PARAMS, RES, SCENES, build_frontier_check, check_pick_winners, diagonal_scene, expected, far_root_scene,  # noqa: E402
+from test_frontier_cpu import (PICK_PARAMS, RES, SCENES, build_frontier_check, check_pick_winners, climbing_expected, diagonal_scene, expected, far_root_scene,  # noqa: E402
                                frontier_struct, pick_scene, potential, ragged_scene, serpentine_scene, weights_known_only)
 from test_navplan_cpu import GEOMETRIES, default_weights, special_cases  # noqa: E402
 
@@ -128,6 +128,19 @@ def test_link_across_the_corner_of_four_tiles(emap, anti):
     try:
         plan_from(dev, start)
         same_search(emap, dev, want, (0.0, 1.0, 1.0), f"diagonal, anti {anti}")
+    finally:
+        dev.close()
+
+
+@pytest.mark.parametrize("left", [False, True])
+def test_label_climbs_through_a_tile_corner(emap, left):
+    """a lower tile's top-right (`left`: top-left) corner cell changes and nothing else that faces the tile above it diagonally: that
+    tile is reached by the corner mark alone, upwards"""
+    g, start, _pot, want = climbing_expected(left)
+    dev = device_copy(emap, g)
+    try:
+        plan_from(dev, start)
+        same_search(emap, dev, want, (0.0, 1.0, 1.0), f"climbing, left {left}")
     finally:
         dev.close()
 

@@ -16,7 +16,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import navplan_ref as ref  # noqa: E402
 
-GEOMETRIES = {"64x64": (64, 64), "65x65": (65, 65), "130x90": (130, 90), "65x3": (65, 3), "1x200": (1, 200), "200x1": (200, 1)}   # size_x, size_y
+GEOMETRIES = {"64x64": (64, 64), "65x65": (65, 65), "130x90": (130, 90), "129x129": (129, 129), "65x3": (65, 3), "1x200": (1, 200), "200x1": (200, 1)}   # size_x, size_y
 KINDS = ["empty", "noise", "wall", "blocked"]
 INV = -1                                                                 # GEM_ERR_INVALID
 
