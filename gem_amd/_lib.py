@@ -341,6 +341,21 @@ FRONTIER_SIGNATURES = {
     "gem_costmap_frontiers_read": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
     "gem_costmap_navplan_goal": (c_int, [c_void_p, c_int, POINTER(c_double), c_void_p, c_longlong, POINTER(NavplanStatus)]),
 }
+# include/gem_hip_obstacle.h (ObstacleLayer on the costmap: ray-traced clearing and marking; gem_hip.h includes it)
+OBS_MARKING, OBS_CLEARING, OBS_MAX = 1, 2, 8
+
+
+class Observation(C.Structure):
+    """gem_observation: one observation of an ObservationBuffer -- its cloud, the sensor's origin, the two ranges, the height window."""
+    _fields_ = [("points", c_void_p), ("n", c_longlong), ("point_step", C.c_uint), ("flags", C.c_uint), ("origin", c_double * 3),
+                ("obstacle_range", c_double), ("raytrace_range", c_double), ("min_obstacle_height", c_double), ("max_obstacle_height", c_double)]
+
+
+OBSTACLE_SIGNATURES = {
+    "gem_costmap_observe": (c_int, [c_void_p, c_int, POINTER(Observation), c_int, c_double, POINTER(c_double)]),
+    "gem_costmap_observe_device": (c_int, [c_void_p, c_int, POINTER(Observation), c_int, c_double, POINTER(c_double)]),
+    "gem_obstacle_host": (c_int, [c_void_p, POINTER(CostmapConfig), POINTER(Observation), c_int, c_double, POINTER(c_double)]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -367,7 +382,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

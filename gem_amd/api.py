@@ -1312,6 +1312,19 @@ class Costmap:
                        each.ctypes.data_as(C.c_void_p) if pose_costs and n else None, traj.ctypes.data_as(C.c_void_p) if nt else None)
         return (traj, each) if pose_costs else traj
 
+    # -- ObstacleLayer (gem_hip_obstacle.h) ---------------------------------------------------------------------------------------------
+    def observe(self, observations, layer_max_obstacle_height: float = 2.0, bounds=None):
+        """ObstacleLayer::updateBounds over `observations`: the rays of every clearing observation free the cells they cross, then the
+        records of every marking one become lethal.  An observation is a dict: points (a host array, float32 [n, k >= 3] or records
+        whose first three floats are x, y, z such as POINT_DTYPE; or a contiguous device tensor, float32 [n, k >= 3] or uint8 [n,
+        4 m >= 12]), origin (x, y, z), and optionally obstacle_range (2.5), raytrace_range (3.0), min_obstacle_height (0.0),
+        max_obstacle_height (2.0), marking (True), clearing (True): costmap_2d's defaults.  All host or all device; device tensors are
+        held until the map is synchronised.  With bounds=None the call only enqueues; else the merged bounds come back."""
+        obs, keep, on_device = _observations(observations)
+        if on_device:
+            self.map._hold(*keep)
+        return self._mark("gem_costmap_observe_device" if on_device else "gem_costmap_observe", bounds, obs, len(keep), float(layer_max_obstacle_height))
+
     # -- inflation (gem_hip_inflate.h) --------------------------------------------------------------------------------------------------
     def inflate(self, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0, inflate_unknown: bool = False,
                 window=None) -> None:
@@ -1666,6 +1679,58 @@ def frontiers_host(grid, pot, resolution: float, min_frontier_size: float = 0.0,
         raise ValueError("frontiers_host: a resolution or parameter that is not finite, is negative or is above 1e100")
     geo = {"origin_x": origin[0], "origin_y": origin[1], "resolution": resolution}
     return [_frontier(rec[i], geo) for i in range(st.n_kept)], labels, _frontier_status(st, geo)
+
+
+def _observations(observations):
+    """a list of observation dicts (Costmap.observe) -> (gem_observation array, the arrays it points into, whether they are device tensors)"""
+    observations = list(observations)
+    obs = (_lib.Observation * max(len(observations), 1))()
+    keep, kinds = [], set()
+    for k, o in enumerate(observations):
+        pts = o["points"]
+        if _is_device_tensor(pts):
+            import torch
+            if not pts.is_contiguous() or pts.dim() != 2 or pts.dtype not in (torch.float32, torch.uint8):
+                raise ValueError("device points must be a contiguous float32 [n, k] or uint8 [n, bytes] tensor")
+            n, step, ptr = int(pts.shape[0]), int(pts.shape[1]) * pts.element_size(), pts.data_ptr()
+            kinds.add(True)
+        else:
+            pts = np.asarray(pts)
+            if pts.dtype.fields is None:
+                pts = np.ascontiguousarray(pts, np.float32)
+                if pts.ndim != 2:
+                    raise ValueError("host points must be float32 [n, k >= 3] or an array of records that begin with float x, y, z")
+                n, step = int(pts.shape[0]), int(pts.shape[1]) * 4
+            else:
+                pts = np.ascontiguousarray(pts).reshape(-1)
+                n, step = int(pts.shape[0]), int(pts.dtype.itemsize)
+            ptr = pts.ctypes.data
+            kinds.add(False)
+        if step < 12 or step % 4:
+            raise ValueError("a record is at least 12 bytes and a multiple of 4 long")
+        keep.append(pts)
+        flags = (_lib.OBS_MARKING if o.get("marking", True) else 0) | (_lib.OBS_CLEARING if o.get("clearing", True) else 0)
+        obs[k] = _lib.Observation(ptr if n else None, n, step, flags, (C.c_double * 3)(*[float(v) for v in o["origin"]]),
+                                  float(o.get("obstacle_range", 2.5)), float(o.get("raytrace_range", 3.0)),
+                                  float(o.get("min_obstacle_height", 0.0)), float(o.get("max_obstacle_height", 2.0)))
+    if len(kinds) > 1:
+        raise ValueError("the observations of one call are all host arrays or all device tensors")
+    return obs, keep, kinds == {True}
+
+
+def obstacle_host(grid, resolution: float, origin, observations, layer_max_obstacle_height: float = 2.0, bounds=None):
+    """The host twin of Costmap.observe (gem_obstacle_host; no device) on grid = uint8 [size_y, size_x], which is changed in place.
+    Returns the merged bounds (None stays None)."""
+    if not (isinstance(grid, np.ndarray) and grid.dtype == np.uint8 and grid.ndim == 2 and grid.flags.c_contiguous and grid.flags.writeable):
+        raise ValueError("grid must be a writeable contiguous uint8 [size_y, size_x] array")
+    obs, keep, on_device = _observations(observations)
+    if on_device:
+        raise ValueError("obstacle_host takes host arrays")
+    cfg = _lib.CostmapConfig(grid.shape[1], grid.shape[0], float(resolution), float(origin[0]), float(origin[1]), 0)
+    b = Costmap._bounds(bounds)
+    if _lib.load().gem_obstacle_host(grid.ctypes.data_as(C.c_void_p), C.byref(cfg), obs, len(keep), float(layer_max_obstacle_height), b) != _lib.GEM_OK:
+        raise ValueError("obstacle_host: an argument the contract of gem_hip_obstacle.h refuses")
+    return None if b is None else list(b)
 
 
 def obstacle_critic(scale: float, flags: int = 0) -> _lib.Critic:

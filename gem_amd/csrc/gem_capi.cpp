@@ -960,6 +960,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "fast_laser")         h->fast_laser = value != 0;
     else if (k == "sort_form")          { if (value < 0 || value > 2) return fail(h, GEM_ERR_INVALID, "sort_form: 0 (by pass), 1 (cell-sorted), 2 (block-sorted)"); h->sort_form = (int)value; }
     else if (k == "history_cull")       { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "history_cull: 0 or 1"); h->history_cull = value != 0; }
+    else if (k == "obstacle_direct")    { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "obstacle_direct: 0 or 1"); h->obstacle_direct = value != 0; }
     else if (k == "nav_chunk")          { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "nav_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->nav_chunk = (int)value; }
     else if (k == "front_chunk")        { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "front_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->front_chunk = (int)value; }
     else return fail(h, GEM_ERR_INVALID, "gem_debug_set: unknown key");
@@ -988,6 +989,7 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "frame_form_seen") *out = h->form_seen ? (long long)*static_cast<volatile const uint32_t*>(h->form_seen) : 0;
     else if (k == "walks_left") *out = h->walks_left;
     else if (k == "history_cull") *out = h->history_cull ? 1 : 0;
+    else if (k == "obstacle_direct") *out = h->obstacle_direct ? 1 : 0;
     else if (k == "nav_chunk") *out = h->nav_chunk;
     else if (k == "front_chunk") *out = h->front_chunk;
     else if (k == "history_blocks") *out = h->history.enabled ? cost_mark_blocks(h->history.len) : 0;

@@ -123,14 +123,14 @@ int costmap_find(gem_handle* h, int id, const char* what, CostMap** out)
 int costmap_plan_fresh(gem_handle* h, const CostMap& m, const char* what)
 {
     if (!m.nav_gen) return invalid(h, what, "no plan was made");
-    if (m.nav_gen != m.gen) return invalid(h, what, "the plan was made before the costmap last rolled");
+    if (m.nav_gen != m.gen) return invalid(h, what, "the plan was made before the costmap last rolled or was observed");
     return GEM_OK;
 }
 
 int costmap_search_fresh(gem_handle* h, const CostMap& m, const char* what)
 {
     if (!m.fr_gen) return invalid(h, what, "no search was made, or a plan was made since");
-    if (m.fr_gen != m.gen) return invalid(h, what, "the search was made before the costmap last rolled");
+    if (m.fr_gen != m.gen) return invalid(h, what, "the search was made before the costmap last rolled or was observed");
     return GEM_OK;
 }
 
@@ -141,7 +141,7 @@ void costmap_free(gem_handle* h)
     for (auto& m : c.map) free_map(m);
     for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
                      &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best,
-                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks}) {
+                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks, &c.ob_bits, &c.ob_rays, &c.ob_cnt}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

@@ -85,7 +85,7 @@ int gemi::critics_prepare(gem_handle* h, int id, const CriticsCall& c, CriticsAr
             if (slot < 0) return bad(h, c, "a MAPGRID critic's grid is GEM_CRITIC_GRID_PATH, _GOAL or _FRONT");
             if (!std::isfinite(q.xshift)) return bad(h, c, "xshift not finite");
             if (!m.mg_gen[slot]) return bad(h, c, "a critic's grid was never prepared");
-            if (m.mg_gen[slot] != m.gen) return bad(h, c, "a critic's grid was prepared before the costmap last rolled");
+            if (m.mg_gen[slot] != m.gen) return bad(h, c, "a critic's grid was prepared before the costmap last rolled or was observed");
             d.grid = slot; d.xshift = q.xshift;
         } else if (q.kind == GEM_CRITIC_EXTERNAL) {
             if (q.flags) return bad(h, c, "unknown flag bits of an EXTERNAL critic");

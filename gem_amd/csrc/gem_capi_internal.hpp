@@ -8,7 +8,7 @@
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
 //   gem_costmap_host.hpp   the costmap family's shared host pieces (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
-//                          _navplan / _frontier .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
+//                          _navplan / _frontier / _obstacle .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
 //   gem_rounds.hpp         the host loop of the tiled fixed-point kernels (plan, frontier labels): chunks of rounds up to the bound (pure C++)
 #pragma once
 
@@ -308,7 +308,7 @@ struct gem_handle {
             bool infl_valid = false;
             Arena mg_dist[3];           // gem_costmap_mapgrid_prepare's / _prepare_front's grids (gem_capi_mapgrid.cpp): path | goal | front, an int per cell
             Arena mg_status;            // per grid four ints: started, goal cell x, y, levels
-            unsigned long long gen = 0; // the costmap's generation: new at create and at every roll that moves it
+            unsigned long long gen = 0; // the costmap's generation: new at create, at every roll that moves it and at every gem_costmap_observe*
             unsigned long long mg_gen[3] = {0, 0, 0};   // the generation each grid was prepared in (0: never)
             // gem_costmap_navplan (gem_capi_navplan.cpp): the potential, an int per cell | the tiles' two active maps | the path, an int
             // per cell, written from the end | the status words
@@ -350,6 +350,9 @@ struct gem_handle {
         // columns, totals and the 32-byte result
         Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
         Arena tg_pose, tg_len, tg_ext;          // gem_costmap_dwa_best* (gem_capi_trajgen.cpp): the generated poses, lengths and the two external columns
+        // gem_costmap_observe* (gem_capi_obstacle.cpp): the end-cell and mark bitmaps, all-zero between calls | the ray list | the
+        // compaction's block counts and total
+        Arena ob_bits, ob_rays, ob_cnt;
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping
@@ -364,6 +367,7 @@ struct gem_handle {
     } history;
     int  nav_chunk = 0;                 // debug knob "nav_chunk": rounds gem_costmap_navplan enqueues per host round trip (0 = tiles_x + tiles_y)
     int  front_chunk = 0;               // debug knob "front_chunk": label rounds gem_costmap_frontiers enqueues per host round trip (0 = tiles_x + tiles_y)
+    bool obstacle_direct = true;       // debug knob "obstacle_direct": gem_costmap_observe* walks a ray per accepted record (the default: measured faster) or one per distinct end cell
     bool history_cull = true;          // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
     // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)
     struct Octree {

@@ -68,7 +68,7 @@ int slot_of(int which_one) { return which_one == GEM_MAPGRID_PATH ? 0 : (which_o
 int usable_slot(gem_handle* h, CostMap& m, int slot, const char* what)
 {
     if (!m.mg_gen[slot]) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was never prepared").c_str());
-    if (m.mg_gen[slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled").c_str());
+    if (m.mg_gen[slot] != m.gen) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": the grid was prepared before the costmap last rolled or was observed").c_str());
     return GEM_OK;
 }
 

@@ -18,13 +18,6 @@
 
 namespace gem {
 
-// doubles as unsigned integers in the same order (-0 below +0)
-__device__ __forceinline__ unsigned long long cost_key(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | (1ull << 63));
-}
-
 struct CostInput {
     double px, py;
     bool lethal;

@@ -69,7 +69,14 @@ struct CostVisualArgs {
     double thresh;
 };
 
-// the host side of CostAccum::acc (gem_costmap.hip's cost_key): false when the word is all-ones
+// doubles as unsigned integers in the same order (-0 below +0): the keys of CostAccum::acc (the mark kernels, gem_obstacle.hip)
+__device__ __forceinline__ unsigned long long cost_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | (1ull << 63));
+}
+
+// the host side of CostAccum::acc (cost_key): false when the word is all-ones
 inline bool cost_key_decode(unsigned long long k, bool inverted, double* out)
 {
     if (k == ~0ull) return false;

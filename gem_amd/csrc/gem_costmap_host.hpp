@@ -1,5 +1,5 @@
 // gem_costmap_host.hpp -- what the costmap family's translation units (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
-// _navplan / _frontier .cpp) share on the host: the lookup of a costmap by id, its geometry and grid, and the staleness checks of a plan
+// _navplan / _frontier / _obstacle .cpp) share on the host: the lookup of a costmap by id, its geometry and grid, and the staleness checks of a plan
 // and of a frontier search.  Host only; the functions are defined in gem_capi_costmap.cpp.
 #pragma once
 

@@ -16,6 +16,7 @@
 //   ElevationMapping::updateGlobalMap and globalMap_ (GlobalMap)   src/ElevationMapping.cpp:630-687, 773-905
 //   pcl::VoxelGrid of the launch files' nodelets (VoxelGrid)       filter.launch, filter_kitti.launch
 //   PointMapLayer / ElevationMapLayer ::updateBounds, ::updateCosts (Costmap)   layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87
+//   costmap_2d::ObstacleLayer::updateBounds, which ElevationMapLayer derives from (Costmap::observe)   layers/src/elevationMap_layer.cpp:16
 #pragma once
 
 #include "../gem_hip.h"
@@ -654,6 +655,21 @@ struct InflationParams : gem_inflation_params {
     }
 };
 
+// one observation of an ObservationBuffer as ObstacleLayer::updateBounds reads it (gem_hip_obstacle.h): the cloud in the global frame,
+// the sensor's origin, the two ranges and the buffer's height window, with costmap_2d's defaults
+struct Observation : gem_observation {
+    Observation() : gem_observation{nullptr, 0, 12u, GEM_OBS_MARKING | GEM_OBS_CLEARING, {0.0, 0.0, 0.0}, 2.5, 3.0, 0.0, 2.0} {}
+    // `cloud` must outlive the call that takes the observation
+    Observation(const std::vector<PointXYZRGBICT>& cloud, double originX, double originY, double originZ, bool marking = true, bool clearing = true)
+        : Observation()
+    {
+        points = cloud.empty() ? nullptr : cloud.data(); n = static_cast<long long>(cloud.size()); point_step = sizeof(PointXYZRGBICT);
+        flags = (marking ? GEM_OBS_MARKING : 0u) | (clearing ? GEM_OBS_CLEARING : 0u);
+        origin[0] = originX; origin[1] = originY; origin[2] = originZ;
+    }
+};
+static_assert(sizeof(Observation) == sizeof(gem_observation), "an array of Observation is an array of gem_observation");
+
 // a critic of the best-trajectory call (gem_hip_critics.h): its kind, what it reads and its scale, in the order the planner sums them
 struct Critic : gem_critic {
     Critic() : gem_critic{GEM_CRITIC_EXTERNAL, 0, 0, 0, 0.0, 0.0} {}
@@ -861,6 +877,14 @@ public:
         map_.check(gem_costmap_clear_footprint(map_.handle(), id_, &pose, xy(spec), static_cast<int>(spec.size()), ptr(bounds), &ok),
                    "gem_costmap_clear_footprint");
         return ok != 0;
+    }
+    // ObstacleLayer::updateBounds over the observations (gem_hip_obstacle.h): every clearing observation's rays free the cells they cross,
+    // then every marking observation's records become LETHAL_OBSTACLE.  bounds nullptr: only enqueued.  Plans, searches and distance
+    // grids made before it are stale afterwards.
+    void observe(const std::vector<Observation>& observations, double layerMaxObstacleHeight = 2.0, Bounds* bounds = nullptr)
+    {
+        map_.check(gem_costmap_observe(map_.handle(), id_, observations.empty() ? nullptr : observations.data(), static_cast<int>(observations.size()),
+                                       layerMaxObstacleHeight, ptr(bounds)), "gem_costmap_observe");
     }
     // CostmapModel::footprintCost of every pose: -3 off the map, -2 unknown, -1 lethal, else the largest cost on the outline
     std::vector<int> footprintCost(const std::vector<FootprintPose>& poses, const std::vector<FootprintPoint>& spec, int flags = 0) const

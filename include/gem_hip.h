@@ -754,6 +754,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- frontier search: gem_frontiers_host, gem_costmap_frontiers / _read, gem_costmap_navplan_goal --------------------------------- */
 #include "gem_hip_frontier.h"
 
+/* ---- ObstacleLayer: gem_costmap_observe / _observe_device, gem_obstacle_host ------------------------------------------------------- */
+#include "gem_hip_obstacle.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,7 +51,11 @@ extern "C" {
  *       "nav_chunk" (rounds of the tiled potential that gem_costmap_navplan enqueues between two reads of its converged word: 0, the
  *       default = tiles_x + tiles_y, or 1 .. 2^20; a small value makes a test take the second chunk.  The plan is the same either way),
  *       "front_chunk" (the same for the label rounds of gem_costmap_frontiers: 0, the default = tiles_x + tiles_y, or 1 .. 2^20.  The
- *       search is the same either way).
+ *       search is the same either way),
+ *       "obstacle_direct" (0/1, default 1: gem_costmap_observe* walks one ray per accepted record, the direct form; 0 = one ray per
+ *       DISTINCT end cell of an observation, from a bitmap of end cells compacted into a list.  The direct form is the default because
+ *       it measured faster on all three workloads of tools/bench_obstacle.py (profiles/obstacle_c2.txt); the end-cell form stays as
+ *       the form to measure against and as a second path for the parity tests.  The grid and the bounds are the same either way).
  *       Returns GEM_ERR_INVALID for an unknown key or a value out of range. */
 int gem_debug_set(gem_handle* h, const char* key, long long value);
 
@@ -67,7 +71,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            "frame_lean_launches", "frame_generic_launches" (launches of k_frame's lean / generic form so far: k_frame itself, the first
  *            frame's binning, the fuse-only launch at a synchronisation), "frame_form_seen" (the word of pinned host memory a tile's slow
  *            path sets: 1 = the host's choice is the generic form from now on),
- *            "nav_chunk" (the knob), "front_chunk" (the knob), "history_cull" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
+ *            "nav_chunk" (the knob), "front_chunk" (the knob), "history_cull" (the knob), "obstacle_direct" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
  *            gem_costmap_mark_history) and "history_blocks_culled" (those of them the LAST gem_costmap_mark_history culled: a device word,
  *            downloaded by this call, which waits for the stream; 0 with "history_cull" 0),
  *            "step_pending" (1: the second half of a gem_add_sharded_device step is still to come),

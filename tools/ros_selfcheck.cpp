@@ -62,6 +62,17 @@
 //                    potential of every cell the library settled below the goal's (the library leaves at the goal, the device
 //                    converges everywhere) and the path cell by cell.  convert_offset_ is makePlan's and is not driven.  It
 //                    cannot be run where the test suite runs and has not been through a compiler
+//   obs  gem_costmap_observe restates costmap_2d::ObstacleLayer::updateBounds (obstacle_layer.cpp: raytraceFreespace with its four
+//                    clips, updateRaytraceBounds, the marking loop), Costmap2D::raytraceLine / bresenham2D / cellDistance
+//                    (costmap_2d.h) and the height window of ObservationBuffer::bufferCloud (include/gem_hip_obstacle.h;
+//                    tests/obstacle_ref.py restates the same contract in numpy).  The row drives a real ObstacleLayer that was never
+//                    initialised through ROS: its map is sized by hand, rolling and footprint clearing are off, and the observations
+//                    are handed over by addStaticObservation, so updateBounds runs its own clearing and marking loops over seeded
+//                    clouds that leave the map on every side, from sensors on and off the map, at two raytrace ranges.  Every byte
+//                    and the four bounds are compared.  The height window is applied by the row while it builds the PointCloud2 (the
+//                    buffer needs TF).  It also reports the deviations the header names: hypot against sqrt(x * x + y * y), in the
+//                    integer form of raytraceLine and the double form of updateRaytraceBounds.  It cannot be compiled where the test
+//                    suite runs and has not been through a compiler
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
@@ -80,7 +91,8 @@
 // row (the same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes, the
 // trajgen row base_local_planner/simple_trajectory_generator.h and base_local_planner/local_planner_limits.h).  The navplan row has not
 // been through a compiler either; it is the one row of another package, global_planner: add -lglobal_planner to the link line (its
-// three headers are among the includes below).
+// three headers are among the includes below).  The obs row has not been through a compiler either (costmap_2d's obstacle_layer.h
+// pulls in tf2_ros, message_filters and laser_geometry: add -llaser_geometry -lmessage_filters to the link line).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
 // The sor row filters a point type of its own (SorPoint), which PCL's precompiled libraries do not hold.  The define is file-wide, so
@@ -115,6 +127,10 @@
 #include <costmap_2d/costmap_2d.h>
 #include <costmap_2d/costmap_layer.h>
 #include <costmap_2d/footprint.h>
+#include <costmap_2d/obstacle_layer.h>
+#include <costmap_2d/observation.h>
+#include <sensor_msgs/PointCloud2.h>
+#include <sensor_msgs/point_cloud2_iterator.h>
 #include <base_local_planner/costmap_model.h>
 #include <base_local_planner/map_grid.h>
 #include <base_local_planner/simple_scored_sampling_planner.h>
@@ -779,6 +795,81 @@ int check_foot(uint32_t seed)
     return 0;
 }
 
+// ---- obs -----------------------------------------------------------------------------------------------------------------------
+// A real ObstacleLayer without ROS around it: the map sized by hand, everything updateBounds would ask a LayeredCostmap for switched off.
+struct ObstacleProbe : costmap_2d::ObstacleLayer {
+    ObstacleProbe(unsigned sx, unsigned sy, double res, double ox, double oy, double max_height)
+    {
+        resizeMap(sx, sy, res, ox, oy);
+        default_value_ = costmap_2d::NO_INFORMATION;
+        rolling_window_ = false; footprint_clearing_enabled_ = false; enabled_ = true; current_ = true;
+        max_obstacle_height_ = max_height;
+        combination_method_ = 1;
+    }
+};
+
+int check_obs(uint32_t seed)
+{
+    gem_map_config cfg{};
+    cfg.length = 32; cfg.resolution = 0.05f; cfg.mahalanobis_threshold = 5.0f; cfg.variance_floor = 1e-4f; cfg.obstacle_threshold = 0.5f; cfg.device = -1;
+    gem_handle* h = nullptr;
+    CHECK_GEM(gem_create(&cfg, &h));
+    const unsigned sx = 130, sy = 90;
+    const double res = 0.05, ox = -3.1, oy = 2.7, w = sx * res, hgt = sy * res, layer_max = 1.5, lo = 0.0, hi = 2.0;
+    gem_costmap_config cc{};
+    cc.size_x = sx; cc.size_y = sy; cc.resolution = res; cc.origin_x = ox; cc.origin_y = oy; cc.default_value = costmap_2d::NO_INFORMATION;
+    int id = -1;
+    CHECK_GEM(gem_costmap_create(h, &cc, &id));
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    const double sensors[4][2] = {{ox + 0.37 * w, oy + 0.61 * hgt}, {ox + 0.3 * res, oy + 0.6 * res}, {ox + 20 * res, oy + 31 * res}, {ox - 0.05 * w, oy + 0.5 * hgt}};
+    long long hypot_int = 0, hypot_double = 0;
+    for (int k = 0; k < 8; ++k) {
+        ObstacleProbe real(sx, sy, res, ox, oy, layer_max);
+        for (size_t i = 0; i < (size_t)sx * sy; ++i) real.getCharMap()[i] = (unsigned char)(rng() % 253);
+        CHECK_GEM(gem_costmap_write(h, id, 0, 0, (int)sx, (int)sy, real.getCharMap(), sx));
+        const double sx0 = sensors[k % 4][0], sy0 = sensors[k % 4][1], sz0 = 0.8, raytrace = (k < 4 ? 0.4 : 2.0) * w, obstacle = 0.35 * w;
+        const int n = 4000;
+        std::vector<float> xyz;                                            // what the call reads: every record, the window applied by the library's twin below
+        for (int i = 0; i < n; ++i) {
+            xyz.push_back((float)(ox + (u(rng) * 1.6 - 0.3) * w)); xyz.push_back((float)(oy + (u(rng) * 1.6 - 0.3) * hgt)); xyz.push_back((float)(u(rng) * 3.0 - 0.5));
+            if (i % 211 == 0) xyz[xyz.size() - 3] = (float)sx0;              // a == 0
+            if (i % 223 == 0) xyz[xyz.size() - 2] = (float)sy0;              // b == 0
+        }
+        // ObservationBuffer::bufferCloud's height window, then the cloud as the buffer would hold it
+        sensor_msgs::PointCloud2 cloud;
+        sensor_msgs::PointCloud2Modifier mod(cloud);
+        mod.setPointCloud2FieldsByString(1, "xyz");
+        std::vector<int> kept;
+        for (int i = 0; i < n; ++i) if ((double)xyz[3 * i + 2] <= hi && (double)xyz[3 * i + 2] >= lo) kept.push_back(i);
+        mod.resize(kept.size());
+        sensor_msgs::PointCloud2Iterator<float> ix(cloud, "x"), iy(cloud, "y"), iz(cloud, "z");
+        for (int i : kept) { *ix = xyz[3 * i]; *iy = xyz[3 * i + 1]; *iz = xyz[3 * i + 2]; ++ix; ++iy; ++iz; }
+        geometry_msgs::Point origin; origin.x = sx0; origin.y = sy0; origin.z = sz0;
+        costmap_2d::Observation seen(origin, cloud, obstacle, raytrace);
+        real.addStaticObservation(seen, true, true);
+        double want[4] = {1e30, 1e30, -1e30, -1e30}, got[4] = {1e30, 1e30, -1e30, -1e30};
+        real.updateBounds(0.0, 0.0, 0.0, &want[0], &want[1], &want[2], &want[3]);
+        gem_observation o{};
+        o.points = xyz.data(); o.n = n; o.point_step = 12; o.flags = GEM_OBS_MARKING | GEM_OBS_CLEARING;
+        o.origin[0] = sx0; o.origin[1] = sy0; o.origin[2] = sz0; o.obstacle_range = obstacle; o.raytrace_range = raytrace;
+        o.min_obstacle_height = lo; o.max_obstacle_height = hi;
+        CHECK_GEM(gem_costmap_observe(h, id, &o, 1, layer_max, got));
+        for (int b = 0; b < 4; ++b) if (got[b] != want[b]) report("obs: touch bounds", b, got[b], want[b]);
+        if (!same_costmap(h, id, real, "obs: ObstacleLayer::updateBounds")) break;
+        // the named deviations, counted: hypot against sqrt(x * x + y * y)
+        for (int dx = -129; dx <= 129; dx += 1 + k) for (int dy = -89; dy <= 89; ++dy)
+            hypot_int += std::hypot((double)dx, (double)dy) != std::sqrt((double)(dx * dx + dy * dy));
+        for (int i = 0; i < n; ++i) {
+            const double ddx = (double)xyz[3 * i] - sx0, ddy = (double)xyz[3 * i + 1] - sy0;
+            hypot_double += std::hypot(ddx, ddy) != std::sqrt(ddx * ddx + ddy * ddy);
+        }
+    }
+    std::printf("obs: hypot differs from sqrt(x * x + y * y) for %lld integer and %lld double arguments of those tried\n", hypot_int, hypot_double);
+    gem_destroy(h);
+    return 0;
+}
+
 // ---- mapgrid -------------------------------------------------------------------------------------------------------------------
 // Seeded plans over noise grids: MapGrid::setTargetCells / setLocalGoal on a real Costmap2D against gem_costmap_mapgrid_prepare.
 int check_mapgrid(uint32_t seed)
@@ -1096,6 +1187,7 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_critics(seed + 9u);
     if (rc == 0) rc = check_trajgen(seed + 10u);
     if (rc == 0) rc = check_navplan(seed + 11u);
+    if (rc == 0) rc = check_obs(seed + 12u);
     if (rc) return rc;
     if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / global_planner / octomap does NOT match this installation\n", g_failures); return 1; }
     std::printf("all twelve rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner, global_planner and octomap (seed %u)\n", seed);
