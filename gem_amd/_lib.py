@@ -356,6 +356,24 @@ OBSTACLE_SIGNATURES = {
     "gem_costmap_observe_device": (c_int, [c_void_p, c_int, POINTER(Observation), c_int, c_double, POINTER(c_double)]),
     "gem_obstacle_host": (c_int, [c_void_p, POINTER(CostmapConfig), POINTER(Observation), c_int, c_double, POINTER(c_double)]),
 }
+# include/gem_hip_voxlayer.h (VoxelLayer on the costmap: a voxel column per cell, 3-D ray clearing and marking; gem_hip.h includes it)
+
+
+class VoxelConfig(C.Structure):
+    """gem_voxel_config: the third axis of a costmap with voxels attached and the layer's two thresholds."""
+    _fields_ = [("size_z", C.c_uint), ("z_resolution", c_double), ("origin_z", c_double), ("unknown_threshold", C.c_uint), ("mark_threshold", C.c_uint)]
+
+
+VOXLAYER_SIGNATURES = {
+    "gem_costmap_voxels_create": (c_int, [c_void_p, c_int, POINTER(VoxelConfig)]),
+    "gem_costmap_voxels_destroy": (c_int, [c_void_p, c_int]),
+    "gem_costmap_voxels_read": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
+    "gem_costmap_voxels_write": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, C.c_size_t]),
+    "gem_costmap_voxel_observe": (c_int, [c_void_p, c_int, POINTER(Observation), c_int, c_double, POINTER(c_double)]),
+    "gem_costmap_voxel_observe_device": (c_int, [c_void_p, c_int, POINTER(Observation), c_int, c_double, POINTER(c_double)]),
+    "gem_voxlayer_host": (c_int, [c_void_p, c_void_p, POINTER(CostmapConfig), POINTER(VoxelConfig), POINTER(Observation), c_int, c_double,
+                                  POINTER(c_double)]),
+}
 # include/gem_hip_debug.h (tuning knobs / profiling aids, not part of the drop-in surface)
 DEBUG_SIGNATURES = {
     "gem_debug_set": (c_int, [c_void_p, c_char_p, c_longlong]),
@@ -382,7 +400,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1325,6 +1325,43 @@ class Costmap:
             self.map._hold(*keep)
         return self._mark("gem_costmap_observe_device" if on_device else "gem_costmap_observe", bounds, obs, len(keep), float(layer_max_obstacle_height))
 
+    # -- VoxelLayer (gem_hip_voxlayer.h) -------------------------------------------------------------------------------------------------
+    def attach_voxels(self, size_z: int = 10, z_resolution: float = 0.2, origin_z: float = 0.0, unknown_threshold: int = 15,
+                      mark_threshold: int = 0) -> None:
+        """A voxel grid on this costmap (gem_costmap_voxels_create), every column unknown: size_z in 1 .. 16 voxels of z_resolution from
+        origin_z upwards, and VoxelLayer's two thresholds with costmap_2d's defaults.  reset, update_origin and roll_to then move the
+        columns with the bytes."""
+        cfg = _lib.VoxelConfig(int(size_z), float(z_resolution), float(origin_z), int(unknown_threshold), int(mark_threshold))
+        self._call("gem_costmap_voxels_create", C.byref(cfg))
+
+    def detach_voxels(self) -> None:
+        self._call("gem_costmap_voxels_destroy")
+
+    def read_voxels(self, window=None) -> np.ndarray:
+        """The window's voxel columns as uint32 [rows, width] (None: the whole map): bit z "not known free", bit 16 + z "marked"."""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        out = np.zeros((max(w[3] - w[1], 0), max(w[2] - w[0], 0)), np.uint32)
+        self._call("gem_costmap_voxels_read", *w, out.ctypes.data_as(C.c_void_p) if out.size else None, out.shape[1])
+        return out
+
+    def write_voxels(self, columns, window=None) -> None:
+        """The window's voxel columns from a uint32 [rows, width] array (None: the whole map)."""
+        w = (0, 0, self.size_x, self.size_y) if window is None else tuple(int(v) for v in window)
+        v = np.ascontiguousarray(columns, np.uint32)
+        if v.shape != (w[3] - w[1], w[2] - w[0]):
+            raise ValueError(f"expected a {(w[3] - w[1], w[2] - w[0])} array, got {v.shape}")
+        self._call("gem_costmap_voxels_write", *w, v.ctypes.data_as(C.c_void_p) if v.size else None, max(w[2] - w[0], 0))
+
+    def voxel_observe(self, observations, layer_max_obstacle_height: float = 2.0, bounds=None):
+        """VoxelLayer::updateBounds over `observations` (dicts as for observe) on a costmap with voxels attached: the 3-D rays of
+        every clearing observation clear the voxels they cross, then the records of every marking one mark theirs; a cell becomes
+        free, unknown or lethal by its column's bit counts.  With bounds=None the call only enqueues; else the merged bounds come back."""
+        obs, keep, on_device = _observations(observations)
+        if on_device:
+            self.map._hold(*keep)
+        return self._mark("gem_costmap_voxel_observe_device" if on_device else "gem_costmap_voxel_observe", bounds, obs, len(keep),
+                          float(layer_max_obstacle_height))
+
     # -- inflation (gem_hip_inflate.h) --------------------------------------------------------------------------------------------------
     def inflate(self, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0, inflate_unknown: bool = False,
                 window=None) -> None:
@@ -1730,6 +1767,27 @@ def obstacle_host(grid, resolution: float, origin, observations, layer_max_obsta
     b = Costmap._bounds(bounds)
     if _lib.load().gem_obstacle_host(grid.ctypes.data_as(C.c_void_p), C.byref(cfg), obs, len(keep), float(layer_max_obstacle_height), b) != _lib.GEM_OK:
         raise ValueError("obstacle_host: an argument the contract of gem_hip_obstacle.h refuses")
+    return None if b is None else list(b)
+
+
+def voxlayer_host(grid, columns, resolution: float, origin, voxels, observations, layer_max_obstacle_height: float = 2.0, bounds=None):
+    """The host twin of Costmap.voxel_observe (gem_voxlayer_host; no device) on grid = uint8 [size_y, size_x] and columns = uint32
+    [size_y, size_x], both changed in place.  voxels = (size_z, z_resolution, origin_z, unknown_threshold, mark_threshold).  Returns
+    the merged bounds (None stays None)."""
+    for a, t in ((grid, np.uint8), (columns, np.uint32)):
+        if not (isinstance(a, np.ndarray) and a.dtype == t and a.ndim == 2 and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("grid must be a writeable contiguous uint8 [size_y, size_x] array, columns a uint32 one")
+    if grid.shape != columns.shape:
+        raise ValueError("grid and columns differ in shape")
+    obs, keep, on_device = _observations(observations)
+    if on_device:
+        raise ValueError("voxlayer_host takes host arrays")
+    cfg = _lib.CostmapConfig(grid.shape[1], grid.shape[0], float(resolution), float(origin[0]), float(origin[1]), 0)
+    vox = _lib.VoxelConfig(int(voxels[0]), float(voxels[1]), float(voxels[2]), int(voxels[3]), int(voxels[4]))
+    b = Costmap._bounds(bounds)
+    if _lib.load().gem_voxlayer_host(grid.ctypes.data_as(C.c_void_p), columns.ctypes.data_as(C.c_void_p), C.byref(cfg), C.byref(vox), obs, len(keep),
+                                     float(layer_max_obstacle_height), b) != _lib.GEM_OK:
+        raise ValueError("voxlayer_host: an argument the contract of gem_hip_voxlayer.h refuses")
     return None if b is None else list(b)
 
 

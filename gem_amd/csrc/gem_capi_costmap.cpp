@@ -2,7 +2,8 @@
 // reference's layers/, with the pieces of costmap_2d they call restated there).  The kernels are in gem_costmap.hip.
 //
 // State (gem_handle::Costmaps):
-//   a costmap      two byte grids (a roll writes the other one and they swap) and a stamp word per cell, all-zero between calls
+//   a costmap      two byte grids (a roll writes the other one and they swap) and a stamp word per cell, all-zero between calls;
+//                  with voxels attached (gem_capi_voxlayer.cpp) two grids of 32-bit columns that reset and roll with the bytes
 //   small          the bounds words of a mark (four accumulated by the mark kernels, four published by the resolve pass)
 //   in, win        a host cloud of gem_costmap_mark_points on the device | the packed window of gem_costmap_read / _write
 // gem_costmap_mark_history reads the history cloud (gem_handle::History, gem_capi_history.cpp) and its box table where they lie.
@@ -10,6 +11,7 @@
 // (the capture, the submap stack) are read where they are, a capture's record count from its device word.  Every device buffer comes
 // from ensure(), so gem_debug_get("arena_allocations") counts it.
 #include "gem_costmap_host.hpp"
+#include "gem_voxlayer.hpp"
 
 #include <algorithm>
 
@@ -92,6 +94,10 @@ int update_origin(gem_handle* h, CostMap& m, double new_ox, double new_oy, const
     GEM_HIP(h, launch_cost_roll(h->stream, grid_of(m), static_cast<unsigned char*>(m.grid[1 - m.act].p), m.cfg.size_x, m.cfg.size_y,
                                 cell_ox, cell_oy, m.cfg.default_value));
     m.act = 1 - m.act;
+    if (m.has_vox) {                                                    // VoxelLayer::updateOrigin: the columns move with the bytes
+        GEM_HIP(h, launch_vox_roll(h->stream, columns_of(m), static_cast<uint32_t*>(m.vox[1 - m.vox_act].p), m.cfg.size_x, m.cfg.size_y, cell_ox, cell_oy));
+        m.vox_act = 1 - m.vox_act;
+    }
     m.cfg.origin_x = ox; m.cfg.origin_y = oy;
     m.gen = ++h->costmap.generation;                                    // the distance grids of gem_costmap_mapgrid_prepare are stale now
     return GEM_OK;
@@ -101,7 +107,7 @@ void free_map(CostMap& m)
 {
     for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status,
                      &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status,
-                     &m.fr_label, &m.fr_index, &m.fr_act, &m.fr_rec, &m.fr_out, &m.fr_words}) {
+                     &m.fr_label, &m.fr_index, &m.fr_act, &m.fr_rec, &m.fr_out, &m.fr_words, &m.vox[0], &m.vox[1]}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -141,7 +147,7 @@ void costmap_free(gem_handle* h)
     for (auto& m : c.map) free_map(m);
     for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
                      &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best,
-                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks, &c.ob_bits, &c.ob_rays, &c.ob_cnt}) {
+                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks, &c.ob_bits, &c.ob_rays, &c.ob_cnt, &c.vx_marks, &c.vx_touched, &c.vx_rays}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }
@@ -222,6 +228,7 @@ int gem_costmap_reset(gem_handle* h, int id)
     CostMap* m;
     if ((rc = costmap_find(h, id, "gem_costmap_reset", &m))) return rc;
     GEM_HIP(h, launch_cost_fill(h->stream, grid_of(*m), cells_of(*m), m->cfg.default_value));
+    if (m->has_vox) GEM_HIP(h, launch_vox_fill(h->stream, columns_of(*m), cells_of(*m)));      // VoxelLayer::resetMaps
     return GEM_OK;
 }
 

@@ -8,7 +8,7 @@
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
 //   gem_costmap_host.hpp   the costmap family's shared host pieces (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
-//                          _navplan / _frontier / _obstacle .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
+//                          _navplan / _frontier / _obstacle / _voxlayer .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
 //   gem_rounds.hpp         the host loop of the tiled fixed-point kernels (plan, frontier labels): chunks of rounds up to the bound (pure C++)
 #pragma once
 
@@ -322,6 +322,12 @@ struct gem_handle {
             Arena fr_label, fr_index, fr_act, fr_rec, fr_out, fr_words;
             unsigned long long fr_gen = 0;              // the generation the last search ran in (0: never, or a plan was made since)
             int fr_n_kept = 0;                          // its kept list's length
+            // gem_costmap_voxels_create (gem_capi_voxlayer.cpp): a 32-bit voxel column per cell (`vox_act`) and the target of the next
+            // roll, as the byte grids
+            bool has_vox = false;
+            gem_voxel_config vox_cfg{};
+            Arena vox[2];
+            int vox_act = 0;
         } map[kMax];
         unsigned long long generation = 0;      // the last generation handed out
         Arena small;                    // device words (64-bit): the bounds keys a mark accumulates [4] | the ones its resolve pass published [4]
@@ -353,6 +359,9 @@ struct gem_handle {
         // gem_costmap_observe* (gem_capi_obstacle.cpp): the end-cell and mark bitmaps, all-zero between calls | the ray list | the
         // compaction's block counts and total
         Arena ob_bits, ob_rays, ob_cnt;
+        // gem_costmap_voxel_observe* (gem_capi_voxlayer.cpp): the new-marks word and the touched byte per cell, all-zero between calls |
+        // the ray list, 64 bits per record
+        Arena vx_marks, vx_touched, vx_rays;
         Arena fp_pose, fp_cost, fp_traj;        // the host-array forms of gem_costmap_footprint_cost / _score_trajectories (gem_capi_footprint.cpp): poses | pose costs | trajectory costs
     } costmap;
     // the history cloud (gem_history_*, gem_capi_history.cpp; the box table's kernel in gem_history.hip): visualCloud_ of ElevationMapping

@@ -20,8 +20,10 @@ constexpr long long kMaxCells = 1ll << 30;
 static_assert(sizeof(gem_observation) == 80, "gem_observation is 80 bytes");
 static_assert(kObsMax == GEM_OBS_MAX && kObsMarking == GEM_OBS_MARKING && kObsClearing == GEM_OBS_CLEARING, "the kernels' constants are the header's");
 
+} // namespace
+
 // the checks of the header's last paragraph that do not need a handle: NULL, or the reason
-const char* check_observations(const gem_observation* obs, int n_obs, double layer_max_h)
+const char* gemi::check_observations(const gem_observation* obs, int n_obs, double layer_max_h)
 {
     if (n_obs < 0 || n_obs > GEM_OBS_MAX || (n_obs > 0 && !obs)) return "0 .. 8 observations, and not NULL";
     if (std::isnan(layer_max_h)) return "layer_max_obstacle_height is NaN";
@@ -38,6 +40,8 @@ const char* check_observations(const gem_observation* obs, int n_obs, double lay
     }
     return nullptr;
 }
+
+namespace {
 
 // the host's part of an observation: the origin's cell, the map's far edges, the cell range
 ObsParams params_of(const CostGeom& g, const gem_observation& o, const void* points, double layer_max_h)

@@ -17,6 +17,7 @@
 //   pcl::VoxelGrid of the launch files' nodelets (VoxelGrid)       filter.launch, filter_kitti.launch
 //   PointMapLayer / ElevationMapLayer ::updateBounds, ::updateCosts (Costmap)   layers/src/pointMap_layer.cpp:45-100, elevationMap_layer.cpp:42-87
 //   costmap_2d::ObstacleLayer::updateBounds, which ElevationMapLayer derives from (Costmap::observe)   layers/src/elevationMap_layer.cpp:16
+//   costmap_2d::VoxelLayer::updateBounds, the plugin for a 3-D sensor (Costmap::attachVoxels / voxelObserve)
 #pragma once
 
 #include "../gem_hip.h"
@@ -670,6 +671,13 @@ struct Observation : gem_observation {
 };
 static_assert(sizeof(Observation) == sizeof(gem_observation), "an array of Observation is an array of gem_observation");
 
+// the voxel grid of a VoxelLayer (gem_hip_voxlayer.h) with costmap_2d's defaults: ten voxels of 0.2 m from z = 0, unknown_threshold 15,
+// mark_threshold 0
+struct VoxelConfig : gem_voxel_config {
+    VoxelConfig(unsigned sizeZ = 10, double zResolution = 0.2, double originZ = 0.0, unsigned unknownThreshold = 15, unsigned markThreshold = 0)
+        : gem_voxel_config{sizeZ, zResolution, originZ, unknownThreshold, markThreshold} {}
+};
+
 // a critic of the best-trajectory call (gem_hip_critics.h): its kind, what it reads and its scale, in the order the planner sums them
 struct Critic : gem_critic {
     Critic() : gem_critic{GEM_CRITIC_EXTERNAL, 0, 0, 0, 0.0, 0.0} {}
@@ -885,6 +893,32 @@ public:
     {
         map_.check(gem_costmap_observe(map_.handle(), id_, observations.empty() ? nullptr : observations.data(), static_cast<int>(observations.size()),
                                        layerMaxObstacleHeight, ptr(bounds)), "gem_costmap_observe");
+    }
+    // VoxelLayer (gem_hip_voxlayer.h): a voxel column per cell, every voxel unknown; resetMaps, updateOrigin and rollTo then move the
+    // columns with the bytes
+    void attachVoxels(const VoxelConfig& config = VoxelConfig())
+    { map_.check(gem_costmap_voxels_create(map_.handle(), id_, &config), "gem_costmap_voxels_create"); }
+    // VoxelLayer::updateBounds over the observations: 3-D rays clear the voxels they cross, then the records mark theirs; a cell becomes
+    // FREE_SPACE, NO_INFORMATION or LETHAL_OBSTACLE by its column's bit counts.  bounds nullptr: only enqueued.  Plans, searches and
+    // distance grids made before it are stale afterwards.
+    void voxelObserve(const std::vector<Observation>& observations, double layerMaxObstacleHeight = 2.0, Bounds* bounds = nullptr)
+    {
+        map_.check(gem_costmap_voxel_observe(map_.handle(), id_, observations.empty() ? nullptr : observations.data(), static_cast<int>(observations.size()),
+                                             layerMaxObstacleHeight, ptr(bounds)), "gem_costmap_voxel_observe");
+    }
+    // the window's columns, row-major, (maxI - minI) per row: bit z "not known free", bit 16 + z "marked"
+    std::vector<unsigned> readVoxels(int minI, int minJ, int maxI, int maxJ) const
+    {
+        const size_t w = maxI > minI ? static_cast<size_t>(maxI - minI) : 0, rows = maxJ > minJ ? static_cast<size_t>(maxJ - minJ) : 0;
+        std::vector<unsigned> v(w * rows);
+        map_.check(gem_costmap_voxels_read(map_.handle(), id_, minI, minJ, maxI, maxJ, v.empty() ? nullptr : v.data(), w), "gem_costmap_voxels_read");
+        return v;
+    }
+    void writeVoxels(int minI, int minJ, int maxI, int maxJ, const std::vector<unsigned>& columns)
+    {
+        const size_t w = maxI > minI ? static_cast<size_t>(maxI - minI) : 0, rows = maxJ > minJ ? static_cast<size_t>(maxJ - minJ) : 0;
+        if (columns.size() != w * rows) throw Error(GEM_ERR_INVALID, "Costmap::writeVoxels: one column per cell of the window");
+        map_.check(gem_costmap_voxels_write(map_.handle(), id_, minI, minJ, maxI, maxJ, columns.empty() ? nullptr : columns.data(), w), "gem_costmap_voxels_write");
     }
     // CostmapModel::footprintCost of every pose: -3 off the map, -2 unknown, -1 lethal, else the largest cost on the outline
     std::vector<int> footprintCost(const std::vector<FootprintPose>& poses, const std::vector<FootprintPoint>& spec, int flags = 0) const

@@ -757,6 +757,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- ObstacleLayer: gem_costmap_observe / _observe_device, gem_obstacle_host ------------------------------------------------------- */
 #include "gem_hip_obstacle.h"
 
+/* ---- VoxelLayer: gem_costmap_voxels_*, gem_costmap_voxel_observe / _observe_device, gem_voxlayer_host ------------------------------ */
+#include "gem_hip_voxlayer.h"
+
 #ifdef __cplusplus
 }
 #endif

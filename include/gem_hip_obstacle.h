@@ -55,7 +55,7 @@
  *                    of the square root, the double one may differ from hypot in the last place.
  *   NOT PROVIDED     obstacle_min_range / raytrace_min_range (later releases), the buffers' time-keeping (observation_keep_time,
  *                    expected_update_rate) and TF -- the caller hands over the observations that are current, in the global frame --,
- *                    footprint clearing (gem_costmap_clear_footprint is that), and VoxelLayer.
+ *                    footprint clearing (gem_costmap_clear_footprint is that).  VoxelLayer is gem_hip_voxlayer.h.
  *
  * gem_costmap_observe takes `points` in host memory, gem_costmap_observe_device in device memory, untouched until gem_synchronize as
  * for gem_add_device.  gem_obstacle_host is the host twin: the same statement in plain C++ on a caller's grid (row-major, size_y rows

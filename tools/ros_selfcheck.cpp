@@ -73,12 +73,25 @@
 //                    buffer needs TF).  It also reports the deviations the header names: hypot against sqrt(x * x + y * y), in the
 //                    integer form of raytraceLine and the double form of updateRaytraceBounds.  It cannot be compiled where the test
 //                    suite runs and has not been through a compiler
+//   voxel gem_costmap_voxel_observe restates costmap_2d::VoxelLayer::updateBounds (voxel_layer.cpp: raytraceFreespace with the
+//                    2 * resolution shortening, its ceiling / floor clip and four edge clips, the marking loop, resetMaps,
+//                    updateOrigin) and voxel_grid::VoxelGrid (voxel_grid.h: markVoxelInMap, clearVoxelLineInMap, raytraceLine,
+//                    bresenham3D, bitsBelowThreshold), from memory (include/gem_hip_voxlayer.h; tests/voxlayer_ref.py restates the same
+//                    contract in numpy, literally and as a set function).  THIS ROW IS TEXT ONLY: no code below drives it yet.  What
+//                    it has to do, in the obs row's manner: a real VoxelLayer sized by hand (matchSize builds its voxel_grid_),
+//                    rolling, footprint clearing and both publishers off, unknown_threshold_ / mark_threshold_ / z_resolution_ /
+//                    origin_z_ / size_z_ set directly, the observations handed over by addStaticObservation; compare every byte of
+//                    the costmap, every column of getVoxelGrid().getData() and the four bounds after updateBounds, with
+//                    mark_threshold 0 (where the bounds must be equal) and 2 (where the header's named departure allows the device's
+//                    to contain the library's).  It settles the header's open points: the popcount <= threshold reading of
+//                    bitsBelowThreshold, no touch of the sensor, getSizeInMetersX for map_end, the 2 * resolution shortening, and
+//                    sqrt against hypot
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
 // MI355X with libgem_hip.so): it drives the real libraries through the same loops the reference runs and compares every output of the
 // HIP path bit for bit.  Exit code 0 = every row pinned on the real third-party code; non-zero = first difference printed.
-// The voxel row is bit for bit in the output order, the count and every voxel of one or two points; in voxels of three or more points
+// The vox row is bit for bit in the output order, the count and every voxel of one or two points; in voxels of three or more points
 // it allows a few ulps, because PCL's std::sort is not stable and may sum such a voxel in another order than input order.
 //
 //   g++ -std=c++17 -O1 tools/ros_selfcheck.cpp -Iinclude -I/opt/ros/$ROS_DISTRO/include $(pkg-config --cflags eigen3 opencv4 pcl_filters-1.8 pcl_kdtree-1.8 pcl_search-1.8) \
