@@ -253,7 +253,8 @@ void gem_destroy(gem_handle* h)
     if (h->form_seen) hipHostFree(h->form_seen);
     for (auto& b : h->pb) {
         for (Arena* a : {&b.rec, &b.srt, &b.seg, &b.flag, &b.gflag, &b.tables, &b.s_hv1, &b.s_hv2, &b.s_key1, &b.s_key2, &b.s_src1, &b.s_src2,
-                         &b.s_cnt1, &b.s_cnt2, &b.s_misc, &b.s_ranges, &b.s_shard, &b.s_blkcnt}) if (a->p) hipFree(a->p);
+                         &b.s_cnt1, &b.s_cnt2, &b.s_misc, &b.s_ranges, &b.s_shard, &b.s_blkcnt,
+                         &b.bkt, &b.bcnt, &b.spill, &b.fctl}) if (a->p) hipFree(a->p);      // (k_frame's arenas: four sets on a handle that has paired)
         if (b.host_tables) hipHostFree(b.host_tables);
         if (b.tables_done) hipEventDestroy(b.tables_done);
         if (b.bin_done) hipEventDestroy(b.bin_done);
@@ -290,6 +291,7 @@ int gem_wait_event(gem_handle* h, void* hip_event)
     std::lock_guard<std::mutex> lk(h->mu);
     hipSetDevice(h->device);
     hipEvent_t ev = static_cast<hipEvent_t>(hip_event);
+    { const int rcp = frame_unpair(h); if (rcp) return rcp; }         // (a held sweep belongs in front of the wait: its call came first)
     GEM_HIP(h, hipStreamWaitEvent(h->stream, ev, 0));
     if (h->bin_stream) GEM_HIP(h, hipStreamWaitEvent(h->bin_stream, ev, 0));
     if (h->bin_stream2) GEM_HIP(h, hipStreamWaitEvent(h->bin_stream2, ev, 0));
@@ -572,6 +574,7 @@ int gem_mapvar_update(gem_handle* h, float var_update)
     std::lock_guard<std::mutex> lk(h->mu);
     hipSetDevice(h->device);
     { const int rcs = shard_finish_locked(h); if (rcs) return rcs; }       // (the increment belongs behind a pending step's walk)
+    { const int rcp = frame_unpair(h); if (rcp) return rcp; }              // (a held sweep is enqueued first: the stream is no longer one nobody touches in between)
     return queue_increment(h, var_update);
 }
 
@@ -866,7 +869,9 @@ int gem_set_timing(gem_handle* h, int enabled)
     if (!h) return GEM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     hipSetDevice(h->device);
-    { const int rcd = settle(h); if (rcd) return rcd; }
+    // (everything put off is settled but k_frame's stream of sweeps: a sweep that is deferred or held is timed, or not, by the launch
+    //  that carries it, so switching the time stamps neither flushes nor unpairs)
+    { int rcd = shard_finish_locked(h); if (!rcd) rcd = flush_walk(h); if (!rcd) rcd = wait_gather(h); if (rcd) return rcd; }
     h->timing = enabled != 0;
     h->step_timed = h->timing && h->tp_x != nullptr && h->nranks > 1;
     return GEM_OK;
@@ -918,6 +923,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "dense_min")          { if (value < 0 || value > 0xffffffffll) return fail(h, GEM_ERR_INVALID, "dense_min: 0 .. 2^32 - 1"); h->dense_min = (unsigned)value; }
     else if (k == "dbg_sweep")          h->dbg_sweep = (int)value;
     else if (k == "dbg_frame")          h->dbg_frame = value != 0;
+    else if (k == "frame_pair")         { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "frame_pair: 0 (one launch per sweep) or 1 (two, for a stream nobody reads in between)"); h->frame_pair = value != 0; }
     else if (k == "frame_lean")         { if (value < 0 || value > 2) return fail(h, GEM_ERR_INVALID, "frame_lean: 0 (generic), 1 (lean) or 2 (the host picks)"); h->frame_lean = (int)value; }   // (settle above flushed the deferred pass)
     else if (k == "overlap")            h->overlap = value != 0;
     else if (k == "overlap_min_points") { if (value < 0) return fail(h, GEM_ERR_INVALID, "overlap_min_points: >= 0"); h->overlap_min_points = value; h->sort_overlap_min_points = value; }
@@ -986,6 +992,9 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "walks_unwaited") *out = h->walks_unwaited;
     else if (k == "frame_lean_launches") *out = h->frame_lean_launches;
     else if (k == "frame_generic_launches") *out = h->frame_generic_launches;
+    else if (k == "frame_pairs") *out = h->frame_pairs;
+    else if (k == "frame_held_flushed") *out = h->frame_held_flushed;
+    else if (k == "frame_pair") *out = h->frame_pair ? 1 : 0;
     else if (k == "frame_form_seen") *out = h->form_seen ? (long long)*static_cast<volatile const uint32_t*>(h->form_seen) : 0;
     else if (k == "walks_left") *out = h->walks_left;
     else if (k == "history_cull") *out = h->history_cull ? 1 : 0;

@@ -398,6 +398,7 @@ void fold_events(gem_handle* h)
             if (ep.kind == 0)      { h->stats.ms_bin += ms; h->stats.launches_bin++; }
             else if (ep.kind == 1) { h->stats.ms_fuse += ms; h->stats.launches_fuse++; }
             else if (ep.kind == 2) { h->stats.ms_frame += ms; h->stats.launches_frame++; }
+            else if (ep.kind == 10) { h->stats.ms_frame += ms; h->stats.launches_frame += 2; }    // (a pair: launches_frame counts SWEEPS, ms_frame / launches_frame stays the time per sweep)
             else if (ep.kind == 9) { h->stats.ms_walk += ms; h->stats.launches_walk++; }
             else                   { h->stats.ms_sort[ep.kind - 3] += ms; if (ep.kind == 3) h->stats.launches_sort++; }
         }
@@ -409,29 +410,84 @@ void fold_events(gem_handle* h)
 
 // The form of the next k_frame launch (gem_handle::form_seen): lean only if the pass it fuses was binned lean (`fused_lean`; true where
 // there is nothing to fuse), the frame it bins takes the fast laser projection -- the only one the lean form carries (`bin_fast`; true
-// where there is nothing to bin) -- and no tile has reported the slow path yet: a plain load of the pinned word.  Counts the launch.
-bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast)
+// where there is nothing to bin) -- and no tile has reported the slow path yet: a plain load of the pinned word.  Counts the launch:
+// `sweeps` is the larger number of sweeps in either half, so a launch that carries a pair counts as the two it stands for.
+bool frame_would_lean(const gem_handle* h)
 {
     const bool seen = h->form_seen && *static_cast<volatile const uint32_t*>(h->form_seen) != 0u;
-    const bool lean = fused_lean && bin_fast && (h->frame_lean == 1 || (h->frame_lean == 2 && !seen));
-    ++(lean ? h->frame_lean_launches : h->frame_generic_launches);
+    return h->frame_lean == 1 || (h->frame_lean == 2 && !seen);
+}
+bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast, int sweeps)
+{
+    const bool lean = fused_lean && bin_fast && frame_would_lean(h);
+    (lean ? h->frame_lean_launches : h->frame_generic_launches) += sweeps;
     return lean;
 }
 
-// the fuse of the newest frame, if it is still pending (see gem_handle::deferred)
+int frame_launch(gem_handle* h, gem_handle::FrameSweep* const* bins, int nb)
+{
+    const int nf = h->fstate.deferred;
+    if (nf + nb == 0) return GEM_OK;
+    bool fused_lean = true, bin_fast = true;
+    for (int i = 0; i < nf; ++i) fused_lean = fused_lean && h->deferred[i].lean_binned;
+    for (int i = 0; i < nb; ++i) bin_fast = bin_fast && bins[i]->ba.frame0.fast_laser != 0 && !bins[i]->ba.rgb;
+    const int attr = nb ? bins[0]->attr : h->deferred[0].attr;
+    const int most = nf > nb ? nf : nb;
+    const bool lean = frame_launch_lean(h, fused_lean, bin_fast, most);
+    for (int i = 0; i < nb; ++i) { bins[i]->ba.lean = lean ? 1 : 0; bins[i]->lean_binned = lean; }
+    // (event pairs by what the launch holds: 0 binning only, 1 fuse only, 2 k_frame, 10 k_frame with two sweeps in a half)
+    const gem::FuseArgs no_fuse{};
+    const gem::BinArgs no_bin{};
+    if (most == 1) {
+        Timed t(h, nb == 0 ? 1 : nf == 0 ? 0 : 2);
+        GEM_HIP(h, launch_frame(h->stream, nf ? h->deferred[0].fa : no_fuse, nb ? bins[0]->ba : no_bin, attr, lean, t.events()));
+    } else if (lean && attr == 0) {
+        const gem::FuseArgs* fp[2] = {&h->deferred[0].fa, &h->deferred[1].fa};
+        const gem::BinArgs* bp[2] = {nb > 0 ? &bins[0]->ba : nullptr, nb > 1 ? &bins[1]->ba : nullptr};
+        Timed t(h, nb == 0 ? 1 : nf == 0 ? 0 : 10);
+        GEM_HIP(h, launch_frame_pair(h->stream, fp, nf, bp, nb, t.events()));
+        ++h->frame_pairs;
+    } else {
+        // a tile reported the slow path between the hold and the launch (or the form is forced): the single generic launches instead
+        for (int i = 0; i < most; ++i) {
+            Timed t(h, i >= nb ? 1 : i >= nf ? 0 : 2);
+            GEM_HIP(h, launch_frame(h->stream, i < nf ? h->deferred[i].fa : no_fuse, i < nb ? bins[i]->ba : no_bin, attr, false, t.events()));
+        }
+    }
+    for (int i = 0; i < nb; ++i) h->deferred[i] = *bins[i];            // (the callers' sweeps are the held one and a local: never a deferred one)
+    h->fstate.deferred = nb;
+    return GEM_OK;
+}
+
+// Everything k_frame's stream of sweeps has put off (gem_handle::deferred, held; the plan: frame_pair_step): a held sweep is binned
+// beside the fuse of the sweeps before it, then the fuse-only launch of whatever is deferred -- a pair too.  The ONE place: every
+// entry point that observes or modifies the map comes through here (settle, flush_local, the pipelines).
 int flush_deferred(gem_handle* h)
 {
-    if (!h->deferred.valid) return GEM_OK;
-    h->deferred.valid = false;
+    if (!h->fstate.held && !h->fstate.deferred) { h->fstate.streak = 0; return GEM_OK; }
     h->main_reads_pb = true;
-    if (h->dbg_frame) h->deferred.fa.dbg = nullptr;            // (the stamps of the last k_frame stay readable: this flush is not the launch being profiled)
-    Timed t(h, 1);
-    // A deferred list is one k_frame would have fused beside the next sweep's binning (16x16 tiles, one sweep, no attributes):
-    // the same kernel without a binning half -- six workgroups per CU hold every tile of a 600^2 map at once, k_fuse_list's four
-    // take two tile lifetimes (10.0-10.4 us against ~6.5 for the C2 sweep; this launch ends every synchronised run of sweeps)
-    gem::BinArgs no_bin{};
-    const bool lean = frame_launch_lean(h, h->deferred.lean_binned, true);
-    GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, no_bin, h->deferred.attr, lean, t.events()));
+    gem::FramePairState s = h->fstate;
+    const gem::FramePairPlan plan = gem::frame_pair_step(s, gem::kFrameFlush);
+    if (plan.held_flushed) ++h->frame_held_flushed;
+    for (int k = 0; k < plan.n; ++k) {
+        // (the stamps of the last k_frame stay readable: this flush is not the launch being profiled)
+        for (int i = 0; h->dbg_frame && i < h->fstate.deferred; ++i) h->deferred[i].fa.dbg = nullptr;
+        // A deferred list is one k_frame would have fused beside the next sweep's binning (16x16 tiles, one sweep, no attributes):
+        // the same kernel without a binning half -- six workgroups per CU hold every tile of a 600^2 map at once, k_fuse_list's four
+        // take two tile lifetimes (10.0-10.4 us against ~6.5 for the C2 sweep; this launch ends every synchronised run of sweeps)
+        gem_handle::FrameSweep* bins[1] = {&h->held};
+        const int rc = frame_launch(h, bins, plan.launch[k].bin);
+        h->fstate.held = false;
+        if (rc) { h->fstate = gem::FramePairState{}; return rc; }
+    }
+    h->fstate = s;
+    return GEM_OK;
+}
+
+int frame_unpair(gem_handle* h)
+{
+    if (h->fstate.held || h->fstate.deferred == 2) return flush_deferred(h);
+    h->fstate.streak = 0;
     return GEM_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/gem_hip.h"
 #include "../../include/gem_hip_debug.h"
 #include "gem_kernels.hpp"
+#include "gem_frame_pair.hpp"
 #include "gem_plan.hpp"
 #include "gem_hostcopy.hpp"
 #include "gem_transport.hpp"
@@ -105,7 +106,15 @@ struct gem_handle {
     // A stream of single device-resident sweeps runs as ONE launch per frame: k_frame fuses the previous
     // frame's records next to the binning of the new cloud.  The fuse of the newest frame is therefore
     // deferred until the next gem_add_device -- or until anything observes or modifies the map.
-    struct Deferred { bool valid = false; FuseArgs fa{}; int ts = 0, attr = 0; bool lean_binned = false; } deferred;   // lean_binned: its binning ran with BinArgs::lean
+    // A stream nobody reads in between goes one step further (gem_frame_pair.hpp): every other call is HELD -- accepted, its
+    // arguments built, nothing enqueued -- and the call behind it launches one grid for both sweeps, so up to two sweeps are
+    // deferred and one held.  Each of them owns one of the four pass buffer sets (`set`; a launch bins into sets none of them holds).
+    // fstate.deferred of `deferred` are live, oldest first; `held` is live while fstate.held.  flush_deferred settles all of it.
+    struct FrameSweep { FuseArgs fa{}; BinArgs ba{}; int ts = 0, attr = 0, set = 0; bool lean_binned = false; };   // lean_binned: its binning ran with BinArgs::lean
+    FrameSweep deferred[2], held;
+    gem::FramePairState fstate;
+    bool frame_pair = true;             // debug knob "frame_pair": 0 = one launch per sweep, as before
+    long long frame_pairs = 0, frame_held_flushed = 0;   // launches that carried two sweeps; held sweeps settled by a flush (gem_debug_get)
     // k_frame has two forms (gem_kernels.hip): the generic one, which switches a buffer set to the descriptor form on the device, and
     // a lean one that carries the bucket form only.  The HOST picks per launch: lean while the word `form_seen` -- pinned host memory
     // that frame_tile's slow path stores 1 into -- reads zero and the pass to fuse was binned lean; generic for good after that.  The
@@ -487,7 +496,13 @@ struct Timed {
 
 void fold_events(gem_handle* h);
 int flush_deferred(gem_handle* h);
-bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast);   // the host's pick of k_frame's form for the next launch (gem_handle::form_seen)
+bool frame_would_lean(const gem_handle* h);                              // ... the knob and the pinned word alone: what a launch of lean-binned, fast-laser sweeps would pick now
+bool frame_launch_lean(gem_handle* h, bool fused_lean, bool bin_fast, int sweeps = 1);   // the host's pick of k_frame's form for the next launch (gem_handle::form_seen)
+// One k_frame launch: fuses every deferred sweep of the handle, oldest first, beside the binning of bins[0 .. nb), which are the
+// deferred ones behind it (nb == 0: the fuse-only launch).  Two sweeps in either half: the pair kernel, or -- the launch is not
+// lean -- the single generic launches it stands for.
+int frame_launch(gem_handle* h, gem_handle::FrameSweep* const* bins, int nb);
+int frame_unpair(gem_handle* h);                                        // a call that may not share a launch: a held sweep or a deferred pair is settled first
 int flush_walk(gem_handle* h);
 int flush_local(gem_handle* h);
 int wait_gather(gem_handle* h);

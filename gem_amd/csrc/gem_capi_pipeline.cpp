@@ -410,6 +410,7 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
 
     if (B == 0) {
         // Fuse with zero points still runs the floor pass (gpu_process.cu:533-534)
+        { const int rcd = frame_unpair(h); if (rcd) return rcd; }      // (not a call a held sweep may wait behind)
         if (batched && in.var_updates)
             for (int s = 0; s < in.n_sweeps; ++s) {
                 if (h->n_pending == kMaxPending) { int rc = flush_pending(h, true); if (rc) return rc; }
@@ -432,7 +433,27 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
     const bool defer = h->defer && in.device_input && in.src == 0 && !batched && (attr & 3) == 0 && ts == 4 && !overlap &&
                        !h->counting && (!h->dbg_on || h->dbg_frame);
     if (!defer) { const int rcd = flush_deferred(h); if (rcd) return rcd; }
-    gem_handle::PassBuffers& pb = h->pb[(overlap || defer) ? (h->pass++ & 1u) : 0u];
+    // ... and one launch per TWO sweeps once nobody has read in between for a while (gem_frame_pair.hpp): a call may be held or share a
+    // launch when that launch is going to be the lean one, the cloud is the caller's own buffer (an arena or a staging half of the
+    // handle is refilled by the next call, before a held sweep would have been binned) and the stream is the handle's own (on a
+    // caller-provided stream the work is on that stream when the call returns).  Everything else takes the single form, behind a
+    // held sweep or a deferred pair if there is one.
+    gem::FrameConst frame0{};
+    if (!batched) fill_frame(h, in.src == 0 ? in.params : nullptr, frame0);
+    bool pairable = defer && h->frame_pair && attr == 0 && in.caller_device && h->stream == h->own_stream && in.n > 0 && !h->dbg_on && !h->counting &&
+                    frame0.fast_laser != 0 && !in.rgb && frame_would_lean(h);
+    for (int i = 0; pairable && i < h->fstate.deferred; ++i) pairable = h->deferred[i].lean_binned && h->deferred[i].attr == 0;
+    if (defer && !pairable) { const int rcd = frame_unpair(h); if (rcd) return rcd; }
+    // the deferred and the held sweeps own a buffer set each: this pass takes the first of the four that is free (a stream of singles
+    // alternates between the first two, as it always did; the other two are allocated by the first pair, or by gem_reserve)
+    unsigned set = 0;
+    if (defer) {
+        unsigned used = 0;
+        for (int i = 0; i < h->fstate.deferred; ++i) used |= 1u << h->deferred[i].set;
+        if (h->fstate.held) used |= 1u << h->held.set;
+        while (used & (1u << set)) ++set;
+    } else if (overlap) set = h->pass++ & 1u;
+    gem_handle::PassBuffers& pb = h->pb[set];
     hipStream_t sbin = overlap ? h->bin_stream : h->stream;
     int rc;
     if ((rc = switch_to_bin_streams(h, overlap))) return rc;
@@ -468,7 +489,7 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
         fa.sweep_unit0 = ba.sweep_unit0;
         fa.var_updates = in.var_updates ? reinterpret_cast<const float*>(d + tab.o_var) : nullptr;
     } else {
-        fill_frame(h, in.src == 0 ? in.params : nullptr, ba.frame0);
+        ba.frame0 = frame0;
     }
     ba.n_sweeps = in.n_sweeps; ba.n = in.n;
     ba.xyzi = in.xyzi; ba.rgb = in.rgb; ba.orig = in.orig;
@@ -513,13 +534,24 @@ int run_pipeline(gem_handle* h, const PassInput& in0)
         ba.bkt = static_cast<uint32_t*>(pb.bkt.p); ba.bcount = static_cast<uint32_t*>(pb.bcnt.p); ba.spill = static_cast<uint4*>(pb.spill.p);
         ba.ctl = static_cast<uint32_t*>(pb.fctl.p);
         fa.bkt = ba.bkt; fa.bcount = ba.bcount; fa.spill = ba.spill; fa.ctl = ba.ctl; fa.form_seen = h->form_seen;
-        if (h->deferred.valid && h->deferred.attr != attr) { const int rcd = flush_deferred(h); if (rcd) return rcd; }   // (cannot happen: toggling the tracking flushes)
-        // the host's pick of k_frame's form: the launch is lean as a whole -- its fuse half AND the binning of this pass -- or generic
-        const bool lean = frame_launch_lean(h, !h->deferred.valid || h->deferred.lean_binned, ba.frame0.fast_laser != 0 && !ba.rgb);
-        ba.lean = lean ? 1 : 0;
-        if (h->deferred.valid) { Timed t(h, 2); GEM_HIP(h, launch_frame(h->stream, h->deferred.fa, ba, attr, lean, t.events())); }
-        else                   { Timed t(h, 0); GEM_HIP(h, launch_frame(h->stream, FuseArgs{}, ba, attr, lean, t.events())); }   // (no tile blocks: binning only)
-        h->deferred.fa = fa; h->deferred.ts = ts; h->deferred.attr = attr; h->deferred.valid = true; h->deferred.lean_binned = lean;
+        if (h->fstate.deferred && h->deferred[0].attr != attr) { const int rcd = flush_deferred(h); if (rcd) return rcd; }   // (cannot happen: toggling the tracking flushes)
+        // hold, or launch: the plan is frame_pair_step's (a flush the event asks for has been made above: frame_unpair).  The host's
+        // pick of k_frame's form is frame_launch's: the launch is lean as a whole -- its fuse half AND the binning -- or generic
+        gem_handle::FrameSweep sw;
+        sw.fa = fa; sw.ba = ba; sw.ts = ts; sw.attr = attr; sw.set = (int)set;
+        const gem::FramePairPlan fp = gem::frame_pair_step(h->fstate, pairable ? gem::kFramePairable : gem::kFrameSingle);
+        if (fp.hold) {
+            // nothing is enqueued: the next call, or whatever observes the map, bins it.  The first hold of a handle allocates the
+            // sets the pairs are going to rotate through (unless gem_reserve has): here, not one by one in the launches that follow
+            for (auto& other : h->pb) if (!other.bkt.p && (rc = ensure_tile_buffers(h, other, plan, h->stream, true))) { h->fstate.held = false; return rc; }
+            h->held = sw;
+            return pass_done(h, in.n);
+        }
+        const bool was_held = fp.launch[0].bin == 2;
+        h->fstate.deferred = fp.launch[0].fuse; h->fstate.held = false;   // (frame_launch fuses what IS deferred and makes what it bins the deferred)
+        gem_handle::FrameSweep* bins[2] = {was_held ? &h->held : &sw, &sw};
+        if ((rc = frame_launch(h, bins, fp.launch[0].bin))) { h->fstate = gem::FramePairState{}; return rc; }
+        h->main_reads_pb = true;
         return pass_done(h, in.n);
     }
     if (h->counting) GEM_HIP(h, hipMemsetAsync(h->d_counters, 0, 2 * sizeof(unsigned long long), h->stream));
@@ -572,7 +604,9 @@ int gem_reserve(gem_handle* h, long long max_points, int max_sweeps, int with_co
     for (int i = 0; i < n_plans; ++i) {
         const BoundPlan& p = plan[i];
         for (int k = 0; p.kind == 1 && k < env.sort_ring; ++k) if ((rc = ensure_sort_buffers(h, h->pb[k], p.sort))) return rc;
-        for (int k = 0; p.kind == 2 && k < 2; ++k) if ((rc = ensure_tile_buffers(h, h->pb[k], p.tile, h->stream, true))) return rc;
+        // (16x16 tiles: the two further sets a pair launch bins into, gem_frame_pair.hpp -- 13 MB a set at 600^2 cells)
+        const int tile_sets = (p.kind == 2 && p.tile.ts == 4 && h->frame_pair && h->defer && !h->track_lowest) ? 4 : 2;
+        for (int k = 0; p.kind == 2 && k < tile_sets; ++k) if ((rc = ensure_tile_buffers(h, h->pb[k], p.tile, h->stream, true))) return rc;
         if (sharded && p.kind == 1 && (rc = ensure_shard_tables(h, p.sort.blocks))) return rc;
     }
     if (sharded) {                                           // every strip's owner receives at most all of the step's points

@@ -104,7 +104,8 @@ typedef struct gem_stats {
     float     ms_bin, ms_fuse;     /* accumulated kernel time of the two pipeline kernels since reset          */
     int       launches_bin, launches_fuse;
     float     ms_frame;            /* ... and of k_frame (fuse of the previous sweep + bin of the new one)     */
-    int       launches_frame;
+    int       launches_frame;      /* SWEEPS that passed through a k_frame launch: a launch that carries two   */
+                                   /* adds 2, so ms_frame / launches_frame stays the device time per sweep     */
     float     ms_sort[6];          /* the sorted pipeline of big passes: count1, scan1, scatter1, count2, scan2, scatter2 */
     int       launches_sort;       /* passes through it                                                        */
     float     ms_walk;             /* ... and its k_fuse_walk                                                  */
@@ -152,7 +153,10 @@ int  gem_add(gem_handle* h, const gem_frame_params* p, int n, const float* xyzi,
  *      underneath, a stream of single colourless sweeps runs as ONE launch per frame (binning of the new cloud next
  *      to the fusion of the previous frame's records), the newest frame's fusion being launched by the next call
  *      that needs it; a cloud big enough for the sorted pipeline (a depth image) likewise leaves its last kernel, the walk
- *      over its sorted records, to the next call -- which can then launch it without a stream wait.           */
+ *      over its sorted records, to the next call -- which can then launch it without a stream wait.  A gem_add_device call
+ *      may enqueue NOTHING until the next call or the next observation of the map: where two sweeps share a launch (a stream
+ *      nobody reads in between; gem_hip_debug.h, "frame_pair") every other call is held.  The rule above -- the caller's buffer
+ *      stays untouched until gem_synchronize -- already covers it.                                                          */
 int  gem_add_device(gem_handle* h, const gem_frame_params* p, int n, const void* d_xyzi,
                     const void* d_rgb, const void* d_orig_index);
 

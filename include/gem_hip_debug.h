@@ -45,6 +45,11 @@ extern "C" {
  *       cannot; 2, the default = the host picks per launch: lean while no tile of the handle has reported the slow path and the pass
  *       to fuse was binned lean, generic from then on.  A frame that does not take the fast laser projection is binned by the generic
  *       form in every mode.  Setting it flushes the deferred pass),
+ *       "frame_pair" (0/1: 1 = a handle that has seen two pairable gem_add_device calls in a row holds every other call -- nothing is
+ *       enqueued -- and the call behind it launches ONE grid for both sweeps; whatever observes or modifies the map settles a held sweep
+ *       first.  Pairable: the lean form's conditions, no colours, no lowest tracking, the caller's own device buffer, the handle's own
+ *       stream, at least one point, no stamps, no counting.  0 = one launch per sweep.  The map is the same either way; DESIGN.md
+ *       section 4 has the measurement the default rests on.  Setting it flushes),
  *       "history_cull" (0/1, default 1: gem_costmap_mark_history hands the history's box table to its kernel, whose workgroups leave
  *       when their block of 4096 records lies off the costmap; 0 = every workgroup walks its records.  The grid and the bounds are the
  *       same either way),
@@ -70,7 +75,10 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            "walks_left" (walks of the sorted pipeline left to the next call) and "walks_unwaited" (those of them launched without a stream wait: their sort had completed),
  *            "frame_lean_launches", "frame_generic_launches" (launches of k_frame's lean / generic form so far: k_frame itself, the first
  *            frame's binning, the fuse-only launch at a synchronisation), "frame_form_seen" (the word of pinned host memory a tile's slow
- *            path sets: 1 = the host's choice is the generic form from now on),
+ *            path sets: 1 = the host's choice is the generic form from now on; a launch that carries two sweeps counts as the two
+ *            launches it stands for),
+ *            "frame_pair" (the knob), "frame_pairs" (launches so far that carried two sweeps in either half: the pair kernel's),
+ *            "frame_held_flushed" (held sweeps that were settled by a flush, not by the next pairable call),
  *            "nav_chunk" (the knob), "front_chunk" (the knob), "history_cull" (the knob), "obstacle_direct" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
  *            gem_costmap_mark_history) and "history_blocks_culled" (those of them the LAST gem_costmap_mark_history culled: a device word,
  *            downloaded by this call, which waits for the stream; 0 with "history_cull" 0),
