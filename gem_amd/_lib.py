@@ -299,6 +299,41 @@ TRAJGEN_SIGNATURES = {
     "gem_costmap_dwa_best": (c_int, _DWA_ARGS),
     "gem_costmap_dwa_best_device": (c_int, _DWA_ARGS),
 }
+# include/gem_hip_rollout.h (trajectory rollout: TrajectoryPlanner::createTrajectories on the costmap; gem_hip.h includes it)
+ROLLOUT_MAX_Y_VELS, ROLLOUT_MAX_LIST, ROLLOUT_MAX_STEPS = 8, 256, 4096
+ROLLOUT_ESCAPING, ROLLOUT_STUCK_LEFT, ROLLOUT_STUCK_RIGHT, ROLLOUT_STUCK_LEFT_STRAFE, ROLLOUT_STUCK_RIGHT_STRAFE = 1, 2, 4, 8, 16
+ROLLOUT_DOUBLES = ("sim_time", "sim_granularity", "angular_sim_granularity", "sim_period", "pdist_scale", "gdist_scale", "occdist_scale",
+                   "heading_lookahead", "max_vel_x", "min_vel_x", "max_vel_th", "min_vel_th", "min_in_place_vel_th", "backup_vel", "acc_lim_x",
+                   "acc_lim_y", "acc_lim_theta", "final_goal_x", "final_goal_y")
+ROLLOUT_INTS = ("vx_samples", "vtheta_samples", "dwa", "holonomic_robot", "final_goal_valid", "n_y_vels")
+
+
+class RolloutConfig(C.Structure):
+    _fields_ = [(n, c_double) for n in ROLLOUT_DOUBLES] + [(n, c_int) for n in ROLLOUT_INTS] + [("y_vels", c_double * ROLLOUT_MAX_Y_VELS)]
+
+
+class RolloutPlan(C.Structure):
+    """struct gem_rollout_plan"""
+    _fields_ = [("config", RolloutConfig)] + [(n, c_double) for n in ("max_x", "min_x", "max_th", "min_th", "dvx", "dvth")] + \
+               [(n, c_int) for n in ("n_vx", "n_vth", "state_flags", "max_steps", "off_b", "off_c", "off_d", "n_cand")] + \
+               [("lists", c_double * ROLLOUT_MAX_LIST)]
+
+
+class RolloutBest(C.Structure):
+    _fields_ = [("index", c_longlong), ("stage", c_int), ("reserved", c_int), ("cost", c_double), ("raw_cost", c_double), ("xv", c_double),
+                ("yv", c_double), ("thetav", c_double), ("reserved1", c_longlong)]
+
+
+_D3 = POINTER(c_double)
+_ROLLOUT_ARGS = [c_void_p, c_int, POINTER(RolloutPlan), _D3, _D3, c_int, POINTER(c_double), c_int, c_int, c_void_p, c_void_p, c_void_p]
+ROLLOUT_SIGNATURES = {
+    "gem_rollout_plan": (c_int, [POINTER(RolloutConfig), _D3, _D3, c_int, POINTER(RolloutPlan)]),
+    "gem_rollout_host": (c_int, [POINTER(RolloutPlan), _D3, _D3, POINTER(CostmapConfig), c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, POINTER(RolloutBest)]),
+    "gem_rollout_pick": (c_int, [POINTER(RolloutPlan), c_int, c_void_p, c_void_p, POINTER(RolloutBest)]),
+    "gem_costmap_rollout_best": (c_int, _ROLLOUT_ARGS),
+    "gem_costmap_rollout_best_device": (c_int, _ROLLOUT_ARGS),
+}
 # include/gem_hip_navplan.h (the global plan on the costmap: weighted potential and grid path; gem_hip.h includes it)
 NAV_OUTLINE, NAV_UNREACHED = 1, 0x7FFFFFFF
 
@@ -400,7 +435,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1566,6 +1566,32 @@ class Costmap:
         res = (int(best.index), float(best.cost), int(best.n_valid))
         return res + (tot,) if totals else res
 
+    # -- trajectory rollout (gem_hip_rollout.h) ------------------------------------------------------------------------------------------
+    def rollout_best(self, plan, pos, vel, state_flags: int, spec, flags: int = 0, costs: bool = False, device: bool = False):
+        """TrajectoryPlanner::createTrajectories on this costmap: every candidate of `plan` (rollout_plan, made for this pos = (x, y,
+        theta), vel = (vx, vy, vtheta) and state_flags) is rolled out against the bytes and the PATH and GOAL grids (prepare_map_grid
+        first), then the pick.  Host form: the answer as a dict (rollout_answer), or with costs (answer, float64 costs [n_cand],
+        int32 ahead [n_cand]); the call waits.  device=True: a uint8 device tensor [64] holding gem_rollout_best (rollout_answer reads
+        it once it is on the host), with costs (that, a float64 and an int32 device tensor); only enqueued."""
+        nc = int(plan.n_cand)
+        ks, ps, nv = self._spec(spec if spec is not None else [])
+        p3, v3 = _double3(pos), _double3(vel)
+        if device:
+            import torch
+            dev = torch.device("cuda")
+            best = torch.empty((64,), dtype=torch.uint8, device=dev)
+            cost = torch.empty((nc,), dtype=torch.float64, device=dev) if costs else None
+            ahead = torch.empty((nc,), dtype=torch.int32, device=dev) if costs else None
+            self.map._hold(best, cost, ahead)
+            self._call("gem_costmap_rollout_best_device", C.byref(plan), p3, v3, int(state_flags), ps, nv, int(flags),
+                       C.c_void_p(cost.data_ptr()) if costs else None, C.c_void_p(ahead.data_ptr()) if costs else None, C.c_void_p(best.data_ptr()))
+            return (best, cost, ahead) if costs else best
+        best = _lib.RolloutBest(-9, -9, -9, -9.0, -9.0, -9.0, -9.0, -9.0, -9)
+        cost = np.zeros(nc, np.float64) if costs else None
+        ahead = np.zeros(nc, np.int32) if costs else None
+        self._call("gem_costmap_rollout_best", C.byref(plan), p3, v3, int(state_flags), ps, nv, int(flags),
+                   cost.ctypes.data_as(C.c_void_p) if costs else None, ahead.ctypes.data_as(C.c_void_p) if costs else None, C.byref(best))
+        return (rollout_answer(best), cost, ahead) if costs else rollout_answer(best)
 
 
 def inflation_table(resolution: float, inflation_radius: float, inscribed_radius: float, cost_scaling_factor: float = 10.0):
@@ -1894,6 +1920,89 @@ def trajectory_velocity(plan, vel, index: int):
     if lib.gem_trajgen_velocity(C.byref(plan), _float3(vel), int(index), out) != _lib.GEM_OK:
         raise ValueError("trajectory_velocity: an index outside the plan's samples, or a plan trajgen_plan did not make")
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# ---- trajectory rollout (gem_hip_rollout.h) -------------------------------------------------------------------------------------------
+def _double3(v):
+    a = [float(x) for x in np.asarray(v, np.float64).reshape(-1)]
+    if len(a) != 3:
+        raise ValueError("expected 3 values")
+    return (C.c_double * 3)(*a)
+
+
+def rollout_config(config: dict) -> "_lib.RolloutConfig":
+    """gem_rollout_config from a dict: the doubles of _lib.ROLLOUT_DOUBLES, the ints of _lib.ROLLOUT_INTS but n_y_vels, and y_vels (a
+    sequence of at most eight).  final_goal = (x, y) sets final_goal_x / _y and final_goal_valid."""
+    c = _lib.RolloutConfig()
+    d = dict(config)
+    if d.get("final_goal") is not None:
+        d["final_goal_x"], d["final_goal_y"] = d["final_goal"]
+        d["final_goal_valid"] = 1
+    for k in _lib.ROLLOUT_DOUBLES:
+        setattr(c, k, float(d.get(k, 0.0)))
+    for k in _lib.ROLLOUT_INTS[:-1]:
+        setattr(c, k, int(d.get(k, 0)))
+    ys = [float(v) for v in d.get("y_vels", ())]
+    if len(ys) > _lib.ROLLOUT_MAX_Y_VELS:
+        raise ValueError("at most eight y_vels")
+    c.n_y_vels = int(d.get("n_y_vels", len(ys)))
+    for i, v in enumerate(ys):
+        c.y_vels[i] = v
+    return c
+
+
+def rollout_plan(config, pos, vel, state_flags: int = 0) -> "_lib.RolloutPlan":
+    """TrajectoryPlanner::createTrajectories' window and candidates for the state pos / vel and the caller's state flags
+    (gem_rollout_plan; host only, no device).  config: a dict (rollout_config) or a _lib.RolloutConfig.  n_cand, off_b / off_c /
+    off_d, max_steps, the window and the lists can be read from the plan."""
+    c = config if isinstance(config, _lib.RolloutConfig) else rollout_config(config)
+    plan = _lib.RolloutPlan()
+    if _lib.load().gem_rollout_plan(C.byref(c), _double3(pos), _double3(vel), int(state_flags), C.byref(plan)) != _lib.GEM_OK:
+        raise ValueError("rollout_plan: a parameter that is not finite, a time or granularity <= 0, fewer than two samples, more than 256 "
+                         "list values in sum, a negative scale, a zero y_vel, unknown state bits, more than 4096 steps, or |theta| beyond 64 pi")
+    return plan
+
+
+def rollout_answer(best) -> dict:
+    """gem_rollout_best as a dict: from the ctypes struct, or from the 64 bytes of the device form (a uint8 array or host tensor)"""
+    if not isinstance(best, _lib.RolloutBest):
+        best = _lib.RolloutBest.from_buffer_copy(np.ascontiguousarray(np.asarray(best), np.uint8).tobytes())
+    return {"index": int(best.index), "stage": int(best.stage), "cost": float(best.cost), "raw_cost": float(best.raw_cost),
+            "velocity": (float(best.xv), float(best.yv), float(best.thetav)), "bytes": bytes(best)}
+
+
+def rollout_host(plan, pos, vel, grid, resolution: float, origin, path, goal, spec, flags: int = 0, poses: bool = False, fill=None):
+    """The host twin of Costmap.rollout_best (gem_rollout_host; no device) over grid = uint8 [size_y, size_x] and the PATH and GOAL
+    distance grids int32 [size_y, size_x]; the state flags are the plan's.  Returns (answer, costs float64 [n_cand], ahead int32
+    [n_cand], steps int32 [n_cand]) and with poses also float64 [n_cand, max_steps, 4] whose slots past a candidate's steps keep
+    `fill` (None: zeros)."""
+    g = np.ascontiguousarray(grid, np.uint8)
+    pa, go = np.ascontiguousarray(path, np.int32), np.ascontiguousarray(goal, np.int32)
+    if g.ndim != 2 or pa.shape != g.shape or go.shape != g.shape:
+        raise ValueError("grid, path and goal must be [size_y, size_x]")
+    cfg = _lib.CostmapConfig(g.shape[1], g.shape[0], float(resolution), float(origin[0]), float(origin[1]), 0)
+    ks, ps, nv = Costmap._spec(spec if spec is not None else [])
+    nc, T = int(plan.n_cand), max(int(plan.max_steps), 1)
+    cost, ahead, steps = np.zeros(nc, np.float64), np.zeros(nc, np.int32), np.zeros(nc, np.int32)
+    out_poses = (np.zeros((nc, T, 4), np.float64) if fill is None else np.full((nc, T, 4), fill, np.float64)) if poses else None
+    best = _lib.RolloutBest()
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    if _lib.load().gem_rollout_host(C.byref(plan), _double3(pos), _double3(vel), C.byref(cfg), ptr(g), ptr(pa), ptr(go), ps, nv, int(flags), ptr(cost),
+                                    ptr(ahead), ptr(steps), ptr(out_poses) if poses else None, C.byref(best)) != _lib.GEM_OK:
+        raise ValueError("rollout_host: an argument the contract of gem_hip_rollout.h refuses")
+    res = (rollout_answer(best), cost, ahead, steps)
+    return res + (out_poses,) if poses else res
+
+
+def rollout_pick(plan, state_flags: int, costs, ahead) -> dict:
+    """The pick alone over costs float64 [n_cand] and ahead int32 [n_cand] (gem_rollout_pick; host only)"""
+    c, a = np.ascontiguousarray(costs, np.float64).reshape(-1), np.ascontiguousarray(ahead, np.int32).reshape(-1)
+    if c.size != int(plan.n_cand) or a.size != c.size:
+        raise ValueError("one cost and one ahead per candidate")
+    best = _lib.RolloutBest()
+    if _lib.load().gem_rollout_pick(C.byref(plan), int(state_flags), c.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.c_void_p), C.byref(best)) != _lib.GEM_OK:
+        raise ValueError("rollout_pick: a plan rollout_plan did not make, or state flags whose ESCAPING bit is not the plan's")
+    return rollout_answer(best)
 
 
 def contract_sincos(angles):

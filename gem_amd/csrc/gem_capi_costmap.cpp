@@ -147,7 +147,7 @@ void costmap_free(gem_handle* h)
     for (auto& m : c.map) free_map(m);
     for (Arena* a : {&c.small, &c.in, &c.win, &c.fp_pose, &c.fp_cost, &c.fp_traj, &c.infl_bits, &c.infl_flags, &c.mg_pose, &c.mg_traj,
                      &c.cr_cand, &c.cr_pose, &c.cr_len, &c.cr_ext, &c.cr_total, &c.cr_best,
-                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.nav_w, &c.fr_blocks, &c.ob_bits, &c.ob_rays, &c.ob_cnt, &c.vx_marks, &c.vx_touched, &c.vx_rays}) {
+                     &c.tg_pose, &c.tg_len, &c.tg_ext, &c.ro_cost, &c.ro_ahead, &c.ro_best, &c.nav_w, &c.fr_blocks, &c.ob_bits, &c.ob_rays, &c.ob_cnt, &c.vx_marks, &c.vx_touched, &c.vx_rays}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;
     }

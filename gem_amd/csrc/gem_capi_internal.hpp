@@ -8,7 +8,7 @@
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
 //   gem_costmap_host.hpp   the costmap family's shared host pieces (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
-//                          _navplan / _frontier / _obstacle / _voxlayer .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
+//                          _navplan / _frontier / _obstacle / _voxlayer / _rollout .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
 //   gem_rounds.hpp         the host loop of the tiled fixed-point kernels (plan, frontier labels): chunks of rounds up to the bound (pure C++)
 #pragma once
 
@@ -365,6 +365,7 @@ struct gem_handle {
         // columns, totals and the 32-byte result
         Arena cr_cand, cr_pose, cr_len, cr_ext, cr_total, cr_best;
         Arena tg_pose, tg_len, tg_ext;          // gem_costmap_dwa_best* (gem_capi_trajgen.cpp): the generated poses, lengths and the two external columns
+        Arena ro_cost, ro_ahead, ro_best;       // gem_costmap_rollout_best* (gem_capi_rollout.cpp): the candidates' costs and `ahead`, the 64-byte answer
         // gem_costmap_observe* (gem_capi_obstacle.cpp): the end-cell and mark bitmaps, all-zero between calls | the ray list | the
         // compaction's block counts and total
         Arena ob_bits, ob_rays, ob_cnt;

@@ -770,6 +770,62 @@ inline Trajectories generateTrajectories(const TrajectoryPlan& plan, const Traje
     return out;
 }
 
+// Trajectory rollout (gem_hip_rollout.h): base_local_planner's TrajectoryPlanner::createTrajectories, the planner move_base runs when
+// none is named -- the configuration, the plan (the window and the candidates' lists for a state and the caller's state flags), the
+// answer, the host twin and the pick alone.  The contract is restated there from memory, unverified against base_local_planner.
+struct RolloutConfig : gem_rollout_config {
+    RolloutConfig()                                          // TrajectoryPlannerROS's defaults (meter_scoring off)
+        : gem_rollout_config{1.0, 0.025, 0.025, 0.05, 0.6, 0.8, 0.01, 0.325, 0.5, 0.1, 1.0, -1.0, 0.4, -0.1, 2.5, 2.5, 3.2, 0.0, 0.0,
+                             3, 20, 1, 1, 0, 4, {-0.3, -0.1, 0.1, 0.3, 0.0, 0.0, 0.0, 0.0}} {}
+    void finalGoal(double x, double y) { final_goal_x = x; final_goal_y = y; final_goal_valid = 1; }
+};
+struct RolloutState { double pos[3], vel[3]; };              // (x, y, theta) and (vx, vy, vtheta)
+struct RolloutBest : gem_rollout_best {
+    RolloutBest() : gem_rollout_best{-1, 0, 0, -1.0, -1.0, 0.0, 0.0, 0.0, 0} {}
+};
+static_assert(sizeof(RolloutBest) == 64, "the answer is 64 bytes");
+typedef struct ::gem_rollout_plan RolloutPlanData;          // (the C call of the same name hides the bare struct name)
+struct RolloutPlan : RolloutPlanData {
+    RolloutPlan() : RolloutPlanData{} {}
+    RolloutPlan(const RolloutConfig& config, const RolloutState& s, int stateFlags = 0) : RolloutPlanData{}
+    {
+        if (::gem_rollout_plan(&config, s.pos, s.vel, stateFlags, this) != GEM_OK)
+            throw Error(GEM_ERR_INVALID, "RolloutPlan: a parameter that is not finite, a time or granularity <= 0, fewer than two samples, more than 256 list "
+                                         "values, a negative scale, a zero y_vel, unknown state bits, more than 4096 steps, or |theta| beyond 64 pi");
+    }
+    // the pick alone over the candidates' costs and `ahead` (host only); the ESCAPING bit of stateFlags must be the plan's
+    RolloutBest pick(int stateFlags, const std::vector<double>& cost, const std::vector<int>& ahead) const
+    {
+        RolloutBest b;
+        if (cost.size() != static_cast<size_t>(n_cand) || ahead.size() != cost.size() || gem_rollout_pick(this, stateFlags, cost.data(), ahead.data(), &b) != GEM_OK)
+            throw Error(GEM_ERR_INVALID, "RolloutPlan::pick: one cost and one ahead per candidate, the plan's ESCAPING bit");
+        return b;
+    }
+};
+static_assert(sizeof(RolloutPlan) == sizeof(RolloutPlanData), "a RolloutPlan is a gem_rollout_plan");
+struct Rollout {
+    RolloutBest best;
+    std::vector<double> cost;                                // [candidates]
+    std::vector<int> ahead, steps;                           // [candidates]: GOAL ahead of the end pose (-1: none) | poses recorded (host twin only)
+    std::vector<FootprintPose> poses;                        // [candidates * plan.max_steps] (host twin, on request)
+};
+// The host twin of Costmap::rolloutBest (gem_rollout_host) over the caller's bytes and PATH / GOAL grids, row-major [size_y * size_x]
+inline Rollout rolloutHost(const RolloutPlan& plan, const RolloutState& s, const gem_costmap_config& geometry, const std::vector<unsigned char>& bytes,
+                           const std::vector<int>& path, const std::vector<int>& goal, const std::vector<FootprintPoint>& spec, int flags = 0,
+                           bool wantPoses = false)
+{
+    const size_t cells = static_cast<size_t>(geometry.size_x) * geometry.size_y, n = static_cast<size_t>(plan.n_cand > 0 ? plan.n_cand : 0);
+    if (bytes.size() != cells || path.size() != cells || goal.size() != cells) throw Error(GEM_ERR_INVALID, "rolloutHost: one byte and two distances per cell");
+    Rollout out;
+    out.cost.assign(n, 0.0); out.ahead.assign(n, -1); out.steps.assign(n, 0);
+    if (wantPoses) out.poses.assign(n * static_cast<size_t>(plan.max_steps > 0 ? plan.max_steps : 1), FootprintPose{0.0, 0.0, 0.0, 0.0});
+    if (gem_rollout_host(&plan, s.pos, s.vel, &geometry, bytes.data(), path.data(), goal.data(), spec.empty() ? nullptr : &spec.front().x,
+                         static_cast<int>(spec.size()), flags, out.cost.data(), out.ahead.data(), out.steps.data(), wantPoses ? out.poses.data() : nullptr,
+                         &out.best) != GEM_OK)
+        throw Error(GEM_ERR_INVALID, "rolloutHost: an argument the contract of gem_hip_rollout.h refuses");
+    return out;
+}
+
 // A global plan (gem_hip_navplan.h): global_planner's makePlan in its order-free configuration -- Dijkstra, the non-quadratic
 // potential, the grid path -- restated from memory and unverified against the library.  The weight table is indexed by the cost
 // byte, 0 = impassable.
@@ -1125,6 +1181,20 @@ public:
                                         s.pos, s.vel, posesPerTrajectory, xy(spec), static_cast<int>(spec.size()),
                                         totals && n ? totals->data() : nullptr, &b),
                    "gem_costmap_dwa_best");
+        return b;
+    }
+    // createTrajectories on this costmap (gem_hip_rollout.h): every candidate of the plan rolled out against the bytes and the PATH and
+    // GOAL grids (prepareMapGrid first), then the pick.  One call, two launches, 64 bytes back.  Waits.
+    RolloutBest rolloutBest(const RolloutPlan& plan, const RolloutState& s, int stateFlags, const std::vector<FootprintPoint>& spec, int flags = 0,
+                            std::vector<double>* cost = nullptr, std::vector<int>* ahead = nullptr) const
+    {
+        const size_t n = static_cast<size_t>(plan.n_cand > 0 ? plan.n_cand : 0);
+        if (cost) cost->assign(n, 0.0);
+        if (ahead) ahead->assign(n, -1);
+        RolloutBest b;
+        map_.check(gem_costmap_rollout_best(map_.handle(), id_, &plan, s.pos, s.vel, stateFlags, xy(spec), static_cast<int>(spec.size()), flags,
+                                            cost ? cost->data() : nullptr, ahead ? ahead->data() : nullptr, &b),
+                   "gem_costmap_rollout_best");
         return b;
     }
 

@@ -752,6 +752,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- DWA's sampled trajectories: gem_trajgen_plan / _generate / _velocity / _generate_device, gem_costmap_dwa_best* -------------- */
 #include "gem_hip_trajgen.h"
 
+/* ---- trajectory rollout (TrajectoryPlanner::createTrajectories): gem_rollout_plan / _host / _pick, gem_costmap_rollout_best* ------ */
+#include "gem_hip_rollout.h"
+
 /* ---- the global plan: gem_navplan_weights, gem_navplan_host, gem_costmap_navplan / _status / _read -------------------------------- */
 #include "gem_hip_navplan.h"
 

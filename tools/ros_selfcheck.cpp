@@ -86,6 +86,22 @@
 //                    to contain the library's).  It settles the header's open points: the popcount <= threshold reading of
 //                    bitsBelowThreshold, no touch of the sensor, getSizeInMetersX for map_end, the 2 * resolution shortening, and
 //                    sqrt against hypot
+//   rollout gem_rollout_plan / gem_rollout_host / gem_rollout_pick restate base_local_planner::TrajectoryPlanner (trajectory_planner.cpp:
+//                    createTrajectories, generateTrajectory, computeNewXPosition / YPosition / ThetaPosition,
+//                    computeNewVelocity, footprintCost; trajectory_inc.h), from memory (include/gem_hip_rollout.h; tests/rollout_ref.py
+//                    restates the same contract in plain Python, literally and as evaluate-all-then-pick).  THIS ROW IS TEXT ONLY: no
+//                    code below drives it yet, and it cannot be compiled where the test suite runs.  What it has to do, in the
+//                    trajgen row's manner: a real TrajectoryPlanner over a CostmapModel and a Costmap2D filled from seeded noise
+//                    with a cleared block, heading_scoring, simple_attractor and meter_scoring off, dwa on and off, holonomic on
+//                    and off, updatePlan with a plan across the map and findBestPath for seeded states -- it prepares path_map_
+//                    and goal_map_ itself and calls createTrajectories -- against gem_costmap_mapgrid_prepare's grids read back
+//                    and gem_rollout_host over them: the winner's (xv, yv, thetav) and cost bit for bit, its points through
+//                    Trajectory::getPoint, and for the caller's flags a planner driven twice so that stuck_left_ / stuck_right_ and
+//                    the strafe flags are set by its own bookkeeping.  It settles the header's open points: the pairing of a
+//                    negative vtheta_samp with stuck_left, `<=` in the in-place and strafe phases against `<` in the forward one,
+//                    hypot against sqrt(x * x + y * y) in the window, and whether int(... + 0.5) of num_steps sees the double or a
+//                    float; and beside them whether escaping removes the forward phase only and the backward trajectory's cost
+//                    of -1.0 becomes 1.0
 //
 // None of these libraries exists in the build image, so oracle/gem_oracle_show.c and oracle/gem_oracle_color.c are pinned on hand-computed
 // scenes only.  This program is what a maintainer runs ONCE inside a ROS workspace that has the real grid_map_core and OpenCV (and an
