@@ -924,6 +924,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "dbg_sweep")          h->dbg_sweep = (int)value;
     else if (k == "dbg_frame")          h->dbg_frame = value != 0;
     else if (k == "frame_pair")         { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "frame_pair: 0 (one launch per sweep) or 1 (two, for a stream nobody reads in between)"); h->frame_pair = value != 0; }
+    else if (k == "frame_pair_overlap") { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "frame_pair_overlap: 0 (a launch of two runs two plain rounds per tile) or 1 (the overlapping kernel)"); h->frame_pair_overlap = value != 0; }
     else if (k == "frame_lean")         { if (value < 0 || value > 2) return fail(h, GEM_ERR_INVALID, "frame_lean: 0 (generic), 1 (lean) or 2 (the host picks)"); h->frame_lean = (int)value; }   // (settle above flushed the deferred pass)
     else if (k == "overlap")            h->overlap = value != 0;
     else if (k == "overlap_min_points") { if (value < 0) return fail(h, GEM_ERR_INVALID, "overlap_min_points: >= 0"); h->overlap_min_points = value; h->sort_overlap_min_points = value; }
@@ -995,6 +996,7 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "frame_pairs") *out = h->frame_pairs;
     else if (k == "frame_held_flushed") *out = h->frame_held_flushed;
     else if (k == "frame_pair") *out = h->frame_pair ? 1 : 0;
+    else if (k == "frame_pair_overlap") *out = h->frame_pair_overlap ? 1 : 0;
     else if (k == "frame_form_seen") *out = h->form_seen ? (long long)*static_cast<volatile const uint32_t*>(h->form_seen) : 0;
     else if (k == "walks_left") *out = h->walks_left;
     else if (k == "history_cull") *out = h->history_cull ? 1 : 0;

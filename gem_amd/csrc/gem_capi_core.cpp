@@ -445,7 +445,7 @@ int frame_launch(gem_handle* h, gem_handle::FrameSweep* const* bins, int nb)
         const gem::FuseArgs* fp[2] = {&h->deferred[0].fa, &h->deferred[1].fa};
         const gem::BinArgs* bp[2] = {nb > 0 ? &bins[0]->ba : nullptr, nb > 1 ? &bins[1]->ba : nullptr};
         Timed t(h, nb == 0 ? 1 : nf == 0 ? 0 : 10);
-        GEM_HIP(h, launch_frame_pair(h->stream, fp, nf, bp, nb, t.events()));
+        GEM_HIP(h, launch_frame_pair(h->stream, fp, nf, bp, nb, t.events(), h->frame_pair_overlap));
         ++h->frame_pairs;
     } else {
         // a tile reported the slow path between the hold and the launch (or the form is forced): the single generic launches instead

@@ -114,6 +114,7 @@ struct gem_handle {
     FrameSweep deferred[2], held;
     gem::FramePairState fstate;
     bool frame_pair = true;             // debug knob "frame_pair": 0 = one launch per sweep, as before
+    bool frame_pair_overlap = true;     // debug knob "frame_pair_overlap": 0 = a launch of two fuses with pair_k_frame (two plain rounds per tile), as before
     long long frame_pairs = 0, frame_held_flushed = 0;   // launches that carried two sweeps; held sweeps settled by a flush (gem_debug_get)
     // k_frame has two forms (gem_kernels.hip): the generic one, which switches a buffer set to the descriptor form on the device, and
     // a lean one that carries the bucket form only.  The HOST picks per launch: lean while the word `form_seen` -- pinned host memory

@@ -63,6 +63,17 @@ inline FramePairPlan frame_pair_step(FramePairState& s, FrameEvent e)
     return p;
 }
 
+// The overlapping pair kernel (pairov_k_frame, gem_frame_pair.hip) computes a tile workgroup's tile ONCE for both rounds, from the
+// first slot's words: the two fused sweeps must then describe the same map through the same tile map.  They do in every pair the
+// policy above forms (whatever moves or resizes the map flushes); launch_frame_pair checks it per launch and picks pair_k_frame
+// where it does not hold.
+inline bool frame_pair_same_map(const FuseArgs& x, const FuseArgs& y)
+{
+    return x.elevation == y.elevation && x.variance == y.variance && x.L == y.L && x.row0 == y.row0 && x.row1 == y.row1 &&
+           x.mahal == y.mahal && x.var_floor == y.var_floor &&
+           x.T == y.T && x.tiles_per_row == y.tiles_per_row && x.center_tr == y.center_tr && x.center_tc == y.center_tc;
+}
+
 // The pair kernel's arguments: a small head -- the block counts of the three block ranges -- and one lean argument block per sweep
 // slot.  Slot s of the tile half fuses the s-th deferred sweep (T == 0: none), slot s of the binning half bins the s-th new one
 // into its own set.  The tile map is each slot's own (FrameLeanTile: the two sweeps of a pair see the same map, the words are copies).

@@ -174,8 +174,10 @@ __device__ __forceinline__ void frame_tile_rest(FrameLeanTile& t)
     GEM_PIN(t.dense); GEM_PIN(t.mahal); GEM_PIN(t.var_floor);
 }
 
-template <int FLAGS, bool STAMPS, class A>
-__device__ __forceinline__ void frame_tile(const A& args, int block, unsigned char* lds_raw)
+// PRE (the pair kernel's overlapping form, gem_frame_pair.hip): the caller has loaded the count and issued this wave's first DMA
+// itself -- exactly the two requests below -- and hands the count in; every other instantiation is the code it was.
+template <int FLAGS, bool STAMPS, bool PRE = false, class A>
+__device__ __forceinline__ void frame_tile(const A& args, int block, unsigned char* lds_raw, [[maybe_unused]] uint32_t nrec_pre = 0u)
 {
     constexpr bool LOWEST = (FLAGS & 4) != 0;
     constexpr bool LEAN = std::is_same_v<A, FrameLeanTile>;
@@ -216,14 +218,15 @@ __device__ __forceinline__ void frame_tile(const A& args, int block, unsigned ch
     }
 
     // ---- one round trip: the count, the first kFrameSpec records of the bucket and the tile ------------------
-    const uint32_t nrec = a.bcount[tile];                                // block-uniform
+    uint32_t nrec;                                                       // block-uniform
+    if constexpr (PRE) nrec = nrec_pre; else nrec = a.bcount[tile];
     const uint32_t* const bkt = a.bkt + (size_t)tile * kFrameBucket * 3;
     auto dma = [&](uint32_t k0) {                                        // records [k0, k0 + 64) -> stage[k0 ..]: lane l's 12 bytes land at 16 l
         const auto* gsrc = (const __attribute__((address_space(1))) void*)(bkt + (size_t)(k0 + (uint32_t)lane) * 3);
         auto* ldst = (__attribute__((address_space(3))) void*)(stage + k0);
         __builtin_amdgcn_global_load_lds(gsrc, ldst, 12, 0, 0);
     };
-    dma((uint32_t)w * 64u);                                              // (inside the bucket whatever the count: kFrameSpec <= kFrameBucket)
+    if constexpr (!PRE) dma((uint32_t)w * 64u);                          // (inside the bucket whatever the count: kFrameSpec <= kFrameBucket)
 
     // ---- the lean form: every word beyond the head, requested where the wave started, is waited for here, one batch
     if constexpr (LEAN) { frame_tile_rest<FLAGS, STAMPS>(a); L = a.L; }

@@ -249,7 +249,7 @@ hipError_t launch_frame(hipStream_t st, const FuseArgs& fuse_prev, const BinArgs
                                        // lean: the bucket-only form (fuse_prev's pass was binned with BinArgs::lean; bin_this.lean is set by the caller)
 hipError_t launch_frame_lean(hipStream_t st, const FuseArgs& fuse_prev, const BinArgs& bin_this, int attr, unsigned blocks, LaunchEvents ev);   // launch_frame's lean
                                        // branch (gem_frame_lean.hip: the lean kernels' own translation unit); blocks: tile blocks + binning blocks
-hipError_t launch_frame_pair(hipStream_t st, const FuseArgs* const* fuse, int nfuse, const BinArgs* const* bin, int nbin, LaunchEvents ev);   // k_frame's pair form
+hipError_t launch_frame_pair(hipStream_t st, const FuseArgs* const* fuse, int nfuse, const BinArgs* const* bin, int nbin, LaunchEvents ev, bool overlap);   // k_frame's pair form
                                        // (gem_frame_pair.hip): fuses up to two lean-binned sweeps in order, bins up to two, each into its own set; lean, attr 0 only
 size_t     fuse_lds_bytes(int ts, int variant, int attr);
 hipError_t launch_init(hipStream_t st, const LayerPtrs& m, int cells, int clear_lowest);

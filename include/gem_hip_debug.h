@@ -50,6 +50,9 @@ extern "C" {
  *       first.  Pairable: the lean form's conditions, no colours, no lowest tracking, the caller's own device buffer, the handle's own
  *       stream, at least one point, no stamps, no counting.  0 = one launch per sweep.  The map is the same either way; DESIGN.md
  *       section 4 has the measurement the default rests on.  Setting it flushes),
+ *       "frame_pair_overlap" (0/1, default 1: a launch that fuses two sweeps into the same map runs the overlapping pair kernel -- both
+ *       sweeps' counts of a tile loaded in front of the first round, the second round's records requested right behind the barrier
+ *       between the rounds; 0 = pair_k_frame, two plain rounds per tile, as before.  Picked per launch.  The map is the same either way),
  *       "history_cull" (0/1, default 1: gem_costmap_mark_history hands the history's box table to its kernel, whose workgroups leave
  *       when their block of 4096 records lies off the costmap; 0 = every workgroup walks its records.  The grid and the bounds are the
  *       same either way),
@@ -77,7 +80,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            frame's binning, the fuse-only launch at a synchronisation), "frame_form_seen" (the word of pinned host memory a tile's slow
  *            path sets: 1 = the host's choice is the generic form from now on; a launch that carries two sweeps counts as the two
  *            launches it stands for),
- *            "frame_pair" (the knob), "frame_pairs" (launches so far that carried two sweeps in either half: the pair kernel's),
+ *            "frame_pair" (the knob), "frame_pair_overlap" (the knob), "frame_pairs" (launches so far that carried two sweeps in either half: the pair kernel's),
  *            "frame_held_flushed" (held sweeps that were settled by a flush, not by the next pairable call),
  *            "nav_chunk" (the knob), "front_chunk" (the knob), "history_cull" (the knob), "obstacle_direct" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
  *            gem_costmap_mark_history) and "history_blocks_culled" (those of them the LAST gem_costmap_mark_history culled: a device word,
