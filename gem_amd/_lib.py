@@ -237,12 +237,23 @@ INFLATE_SIGNATURES = {
 MAPGRID_PATH, MAPGRID_GOAL = 1, 2
 MAPGRID_STOP_ON_FAILURE, MAPGRID_SUM = 1, 2
 MAPGRID_MAX_POINTS, MAPGRID_MAX_WORDS = 1 << 20, 4096
+
+
+class MapGridTiledStatus(C.Structure):
+    _fields_ = [("started", c_int), ("goal_cell", c_int * 2), ("rounds", c_int), ("chunks", c_int)]
+
+
 MAPGRID_SIGNATURES = {
     "gem_mapgrid_adjust_plan": (c_int, [POINTER(c_double), c_longlong, c_double, POINTER(c_double), c_longlong, POINTER(c_longlong)]),
     "gem_costmap_mapgrid_prepare": (c_int, [c_void_p, c_int, POINTER(c_double), c_longlong, c_int]),
     "gem_costmap_mapgrid_read": (c_int, [c_void_p, c_int, c_int, c_void_p, POINTER(c_int), POINTER(c_int)]),
     "gem_costmap_mapgrid_score": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
     "gem_costmap_mapgrid_score_device": (c_int, [c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_double, c_int, c_void_p]),
+}
+# include/gem_hip_mapgrid_tiled.h (the same grids on a costmap of any size; gem_hip.h includes it)
+MAPGRID_TILED_SIGNATURES = {
+    "gem_costmap_mapgrid_prepare_tiled": (c_int, [c_void_p, c_int, POINTER(c_double), c_longlong, c_int, POINTER(MapGridTiledStatus)]),
+    "gem_costmap_mapgrid_prepare_front_tiled": (c_int, [c_void_p, c_int, POINTER(c_double), c_longlong, POINTER(MapGridTiledStatus)]),
 }
 # include/gem_hip_critics.h (the best trajectory: the critic list, the FRONT grid; gem_hip.h includes it)
 CRITIC_OBSTACLE, CRITIC_MAPGRID, CRITIC_EXTERNAL, CRITIC_MAX = 1, 2, 3, 8
@@ -434,7 +445,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
     except Exception:
         pass
     lib = C.CDLL(str(path))
-    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **CRITICS_SIGNATURES,
+    for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **MAPGRID_TILED_SIGNATURES, **CRITICS_SIGNATURES,
                                **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res

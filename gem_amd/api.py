@@ -1382,6 +1382,15 @@ class Costmap:
         v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
         self._call("gem_costmap_mapgrid_prepare", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]), int(which))
 
+    def prepare_map_grid_tiled(self, plan, which: int = _lib.MAPGRID_PATH | _lib.MAPGRID_GOAL) -> dict:
+        """prepare_map_grid on a costmap of any size (gem_costmap_mapgrid_prepare_tiled): the same grids in the same slots, relaxed tile
+        by tile in global memory.  The call waits.  dict(started, goal_cell, rounds, chunks): rounds depends on timing, the grids do not."""
+        v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
+        st = _lib.MapGridTiledStatus()
+        self._call("gem_costmap_mapgrid_prepare_tiled", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]), int(which),
+                   C.byref(st))
+        return _map_grid_tiled_status(st)
+
     def read_map_grid(self, which: int):
         """(distances int32 [size_y, size_x], started, (goal x, goal y)) of MAPGRID_PATH or MAPGRID_GOAL; the call waits."""
         out = np.zeros((self.size_y, self.size_x), np.int32)
@@ -1486,6 +1495,14 @@ class Costmap:
         moved forward) in a slot of its own; PATH and GOAL are not touched.  Only enqueued."""
         v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
         self._call("gem_costmap_mapgrid_prepare_front", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]))
+
+    def prepare_map_grid_front_tiled(self, plan) -> dict:
+        """prepare_map_grid_front on a costmap of any size (gem_costmap_mapgrid_prepare_front_tiled); the call waits.
+        dict(started, goal_cell, rounds, chunks)."""
+        v = np.ascontiguousarray(plan, np.float64).reshape(-1, 2)
+        st = _lib.MapGridTiledStatus()
+        self._call("gem_costmap_mapgrid_prepare_front_tiled", v.ctypes.data_as(C.POINTER(C.c_double)) if v.size else None, int(v.shape[0]), C.byref(st))
+        return _map_grid_tiled_status(st)
 
     def read_map_grid_front(self):
         """(distances int32 [size_y, size_x], started, (goal x, goal y)) of the FRONT grid; the call waits."""
@@ -1820,6 +1837,10 @@ def voxlayer_host(grid, columns, resolution: float, origin, voxels, observations
 def obstacle_critic(scale: float, flags: int = 0) -> _lib.Critic:
     """ObstacleCostFunction: flags of FOOTPRINT_INSCRIBED_LETHAL | FOOTPRINT_SUM | CRITIC_CENTRE_COST"""
     return _lib.Critic(_lib.CRITIC_OBSTACLE, 0, int(flags), 0, float(scale), 0.0)
+
+
+def _map_grid_tiled_status(st: _lib.MapGridTiledStatus) -> dict:
+    return {"started": int(st.started), "goal_cell": (int(st.goal_cell[0]), int(st.goal_cell[1])), "rounds": int(st.rounds), "chunks": int(st.chunks)}
 
 
 def map_grid_critic(scale: float, grid: int, xshift: float = 0.0, flags: int = 0) -> _lib.Critic:

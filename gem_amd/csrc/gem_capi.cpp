@@ -969,6 +969,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "history_cull")       { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "history_cull: 0 or 1"); h->history_cull = value != 0; }
     else if (k == "obstacle_direct")    { if (value < 0 || value > 1) return fail(h, GEM_ERR_INVALID, "obstacle_direct: 0 or 1"); h->obstacle_direct = value != 0; }
     else if (k == "nav_chunk")          { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "nav_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->nav_chunk = (int)value; }
+    else if (k == "mapgrid_chunk")      { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "mapgrid_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->mapgrid_chunk = (int)value; }
     else if (k == "front_chunk")        { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "front_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->front_chunk = (int)value; }
     else return fail(h, GEM_ERR_INVALID, "gem_debug_set: unknown key");
     return GEM_OK;
@@ -1003,6 +1004,7 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "obstacle_direct") *out = h->obstacle_direct ? 1 : 0;
     else if (k == "nav_chunk") *out = h->nav_chunk;
     else if (k == "front_chunk") *out = h->front_chunk;
+    else if (k == "mapgrid_chunk") *out = h->mapgrid_chunk;
     else if (k == "history_blocks") *out = h->history.enabled ? cost_mark_blocks(h->history.len) : 0;
     else if (k == "history_blocks_culled") { hipSetDevice(h->device); return history_blocks_culled(h, out); }
     else if (k == "step_pending") *out = h->step.valid ? 1 : 0;

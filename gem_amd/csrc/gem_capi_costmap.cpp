@@ -105,7 +105,7 @@ int update_origin(gem_handle* h, CostMap& m, double new_ox, double new_oy, const
 
 void free_map(CostMap& m)
 {
-    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status,
+    for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status, &m.mg_act,
                      &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status,
                      &m.fr_label, &m.fr_index, &m.fr_act, &m.fr_rec, &m.fr_out, &m.fr_words, &m.vox[0], &m.vox[1]}) {
         if (a->p) hipFree(a->p);
@@ -155,6 +155,8 @@ void costmap_free(gem_handle* h)
     c.nav_pin = nullptr;
     if (c.fr_pin) hipHostFree(c.fr_pin);
     c.fr_pin = nullptr;
+    if (c.mgt_pin) hipHostFree(c.mgt_pin);
+    c.mgt_pin = nullptr;
     for (int k = 0; k < 2; ++k) {
         if (c.mg_pin[k]) hipHostFree(c.mg_pin[k]);
         if (c.mg_ev[k]) hipEventDestroy(c.mg_ev[k]);

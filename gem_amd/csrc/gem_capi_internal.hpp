@@ -318,6 +318,7 @@ struct gem_handle {
             bool infl_valid = false;
             Arena mg_dist[3];           // gem_costmap_mapgrid_prepare's / _prepare_front's grids (gem_capi_mapgrid.cpp): path | goal | front, an int per cell
             Arena mg_status;            // per grid four ints: started, goal cell x, y, levels
+            Arena mg_act;               // gem_costmap_mapgrid_prepare_tiled: per requested grid (at most two) the tiles' two active maps
             unsigned long long gen = 0; // the costmap's generation: new at create, at every roll that moves it and at every gem_costmap_observe*
             unsigned long long mg_gen[3] = {0, 0, 0};   // the generation each grid was prepared in (0: never)
             // gem_costmap_navplan (gem_capi_navplan.cpp): the potential, an int per cell | the tiles' two active maps | the path, an int
@@ -353,6 +354,7 @@ struct gem_handle {
         unsigned mg_turn = 0;
         Arena mg_pose, mg_traj;
         std::vector<double> mg_plan;
+        void* mgt_pin = nullptr;        // gem_costmap_mapgrid_prepare_tiled: the pinned words its kernels answer through (the call waits: one block serves every costmap)
         // gem_costmap_navplan: the weight table on the device | pinned host memory, the table a call hands over and the status words its
         // kernels answer with (the call waits, so one block serves every costmap) | the path's cells on the host
         Arena nav_w;
@@ -387,6 +389,7 @@ struct gem_handle {
     } history;
     int  nav_chunk = 0;                 // debug knob "nav_chunk": rounds gem_costmap_navplan enqueues per host round trip (0 = tiles_x + tiles_y)
     int  front_chunk = 0;               // debug knob "front_chunk": label rounds gem_costmap_frontiers enqueues per host round trip (0 = tiles_x + tiles_y)
+    int  mapgrid_chunk = 0;             // debug knob "mapgrid_chunk": rounds gem_costmap_mapgrid_prepare_tiled enqueues per host round trip (0 = tiles_x + tiles_y)
     bool obstacle_direct = true;       // debug knob "obstacle_direct": gem_costmap_observe* walks a ray per accepted record (the default: measured faster) or one per distinct end cell
     bool history_cull = true;          // debug knob "history_cull": gem_costmap_mark_history hands the box table to its kernel
     // pointCloudtoOctomap's insertion loop and fullMapToMsg (gem_octree_*, gem_capi_octree.cpp; kernels in gem_octree.hip)

@@ -9,11 +9,16 @@
 // gem_debug_get("arena_allocations") counts them, and a second identical call allocates nothing.  A grid is valid while the
 // costmap's generation (new at create and at every roll that moves it) is the one it was prepared in.
 //
+// gem_costmap_mapgrid_prepare_tiled / _prepare_front_tiled fill the same slots on a costmap of any size with the tile rounds of
+// gem_mapgrid_tiled.hip; they wait (prepare_tiled below), and share everything up to the launches with the capped form (stage).
+//
 // A costmap has three grid slots: path, goal and front (the goal grid of DWA's front plan, include/gem_hip_critics.h).  prepare() and
 // read() below work on slots; the public `which` of the MapGrid calls still admits PATH | GOAL only, and the front slot is reached
 // through gem_costmap_mapgrid_prepare_front / _read_front and by gem_costmap_best_trajectory (gem_capi_critics.cpp).
 #include "gem_costmap_host.hpp"
 #include "gem_mapgrid.hpp"
+#include "gem_mapgrid_tiled.hpp"
+#include "gem_rounds.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -123,15 +128,24 @@ int score(gem_handle* h, int id, int which_one, const ScoreCall& c, double xshif
     return download_arrays(h, &down, 1, 0);
 }
 
-// gem_costmap_mapgrid_prepare and _prepare_front behind their own checks of `which`: `slots` is a mask of slots (bit 0 path | 1 goal |
-// 2 front), at most two of them: one launch
-int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots)
+// What the capped and the tiled prepare share up to their launches: the checks, the adjusted plan, the slots' grids and status words,
+// and this call's turn of the pinned cells, filled.  `slots` is a mask of slots (bit 0 path | 1 goal | 2 front), at most two of them.
+struct Staged {
+    CostMap* m = nullptr;
+    CostGeom g{};
+    size_t cells = 0;
+    int turn = 0;
+    int n_grids = 0;
+    MapGridArgs a{};                    // grid, cells, n, the sizes, and per requested grid dist / status / goal
+};
+
+int stage(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots, bool capped, Staged& s)
 {
     int rc;
     CostMap* m;
     if ((rc = costmap_find(h, id, what, &m))) return rc;
     if (n < 0 || (n > 0 && !plan_xy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": a negative count, or a NULL plan with a non-zero count").c_str());
-    if (!fits(*m)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS").c_str());
+    if (capped && !fits(*m)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": ceil(size_x / 64) * size_y above GEM_MAPGRID_MAX_WORDS").c_str());
     auto& cm = h->costmap;
     const CostGeom g = geom_of(*m);
     const long long count = adjust_plan(plan_xy, n, g.res, nullptr, 0, GEM_MAPGRID_MAX_POINTS);
@@ -141,8 +155,8 @@ int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long
 
     // the grids and status words; then this call's turn of the pinned cells
     const size_t cells = (size_t)g.sx * g.sy;
-    for (int s = 0; s < kSlots; ++s)
-        if ((slots & (1 << s)) && (rc = ensure(h, m->mg_dist[s], cells * sizeof(int)))) return rc;
+    for (int k = 0; k < kSlots; ++k)
+        if ((slots & (1 << k)) && (rc = ensure(h, m->mg_dist[k], cells * sizeof(int)))) return rc;
     if ((rc = ensure(h, m->mg_status, kSlots * kMapGridStatusWords * sizeof(int)))) return rc;
     const int turn = (int)(cm.mg_turn & 1u);
     if (!cm.mg_ev[turn]) GEM_HIP(h, hipEventCreateWithFlags(&cm.mg_ev[turn], hipEventDisableTiming));
@@ -162,22 +176,93 @@ int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long
     }
     ++cm.mg_turn;
 
-    MapGridArgs a{};
+    s.m = m; s.g = g; s.cells = cells; s.turn = turn;
+    MapGridArgs& a = s.a;
+    a = MapGridArgs{};
     a.grid = grid_of(*m); a.cells = pin; a.n = (int)count;
     a.sx = g.sx; a.sy = g.sy; a.nw = mapgrid_row_words(g.sx);
     int ng = 0;
-    for (int s = 0; s < kSlots; ++s) {
-        if (!(slots & (1 << s))) continue;
-        a.dist[ng] = static_cast<int*>(m->mg_dist[s].p);
-        a.status[ng] = static_cast<int*>(m->mg_status.p) + s * kMapGridStatusWords;
-        a.goal[ng] = s != 0;                                             // the front grid is a goal grid of its own plan
+    for (int k = 0; k < kSlots; ++k) {
+        if (!(slots & (1 << k))) continue;
+        a.dist[ng] = static_cast<int*>(m->mg_dist[k].p);
+        a.status[ng] = static_cast<int*>(m->mg_status.p) + k * kMapGridStatusWords;
+        a.goal[ng] = k != 0;                                             // the front grid is a goal grid of its own plan
         ++ng;
     }
-    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], ng == 2 ? a.dist[1] : nullptr, (uint32_t)cells, (int)cells + 1));
-    GEM_HIP(h, launch_mapgrid_distance(h->stream, a, ng));
-    GEM_HIP(h, hipEventRecord(cm.mg_ev[turn], h->stream));
-    cm.mg_ev_pending[turn] = true;
-    for (int s = 0; s < kSlots; ++s) if (slots & (1 << s)) m->mg_gen[s] = m->gen;
+    s.n_grids = ng;
+    return GEM_OK;
+}
+
+// gem_costmap_mapgrid_prepare and _prepare_front behind their own checks of `which`: one launch of the LDS search, only enqueued
+int prepare(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots)
+{
+    Staged s;
+    if (const int rc = stage(h, id, what, plan_xy, n, slots, true, s)) return rc;
+    auto& cm = h->costmap;
+    const MapGridArgs& a = s.a;
+    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], s.n_grids == 2 ? a.dist[1] : nullptr, (uint32_t)s.cells, (int)s.cells + 1));
+    GEM_HIP(h, launch_mapgrid_distance(h->stream, a, s.n_grids));
+    GEM_HIP(h, hipEventRecord(cm.mg_ev[s.turn], h->stream));
+    cm.mg_ev_pending[s.turn] = true;
+    for (int k = 0; k < kSlots; ++k) if (slots & (1 << k)) s.m->mg_gen[k] = s.m->gen;
+    return GEM_OK;
+}
+
+// gem_costmap_mapgrid_prepare_tiled and _prepare_front_tiled: the same grids in the same slots by the tile rounds of
+// gem_mapgrid_tiled.hip, on a costmap of any size.  The call WAITS: fill, seed, then CHUNKS of rounds, each closed by k_mgt_close, which
+// answers through pinned words; the host loop and its bound are run_tile_rounds' (gem_rounds.hpp), a chunk is tiles_x + tiles_y rounds
+// (gem_debug_set "mapgrid_chunk" sets another length), exactly as gem_costmap_navplan drives its potential.  The rim pass follows the
+// converged close.  The slots' generations are 0 from before the first launch until then: a failure in between leaves "never
+// prepared", not a half-relaxed grid.  The first close has waited for the seed kernel, so the pinned cells need no event.
+int prepare_tiled(gem_handle* h, int id, const char* what, const double* plan_xy, long long n, int slots, gem_mapgrid_tiled_status* st)
+{
+    int rc;
+    Staged s;
+    if ((rc = stage(h, id, what, plan_xy, n, slots, false, s))) return rc;
+    auto& cm = h->costmap;
+    CostMap* m = s.m;
+    MapGridTiledArgs a{};
+    a.grid = s.a.grid; a.cells = s.a.cells; a.n = s.a.n;
+    a.sx = (int)s.g.sx; a.sy = (int)s.g.sy; a.ntx = nav_tiles(a.sx); a.nty = nav_tiles(a.sy);
+    a.n_grids = s.n_grids;
+    for (int k = 0; k < 2; ++k) { a.dist[k] = s.a.dist[k]; a.status[k] = s.a.status[k]; a.goal[k] = s.a.goal[k]; }
+    const size_t nt = (size_t)a.ntx * a.nty;
+    if ((rc = ensure(h, m->mg_act, 2 * 2 * nt * sizeof(int)))) return rc;
+    if (!cm.mgt_pin) GEM_HIP(h, hipHostMalloc(&cm.mgt_pin, kMgtPinWords * sizeof(int), hipHostMallocDefault));
+    a.act = static_cast<int*>(m->mg_act.p);
+    a.pin = static_cast<int*>(cm.mgt_pin);
+    volatile int* pin = a.pin;
+    for (int i = 0; i < kMgtPinWords; ++i) pin[i] = 0;
+
+    for (int k = 0; k < kSlots; ++k) if (slots & (1 << k)) m->mg_gen[k] = 0;     // (a failure below leaves no grid to read)
+    GEM_HIP(h, launch_mapgrid_fill(h->stream, a.dist[0], a.n_grids == 2 ? a.dist[1] : nullptr, (uint32_t)s.cells, (int)s.cells + 1));
+    GEM_HIP(h, launch_mgt_seed(h->stream, a));
+    RoundsResult rr;
+    rc = run_tile_rounds(
+        (long long)s.cells, h->mapgrid_chunk > 0 ? h->mapgrid_chunk : (long long)a.ntx + a.nty,
+        [&](int round) -> int {
+            a.round = round;
+            GEM_HIP(h, launch_mgt_round(h->stream, a));
+            return GEM_OK;
+        },
+        [&](int round, bool& converged) -> int {
+            a.round = round;
+            GEM_HIP(h, launch_mgt_close(h->stream, a));
+            GEM_HIP(h, hipStreamSynchronize(h->stream));
+            converged = pin[kMgtConverged] != 0;
+            return GEM_OK;
+        },
+        rr);
+    if (rc) return rc;
+    if (!rr.converged) return fail(h, GEM_ERR_HIP, (std::string(what) + ": the distances did not converge within their bound").c_str());
+    GEM_HIP(h, launch_mgt_rim(h->stream, a));
+    for (int k = 0; k < kSlots; ++k) if (slots & (1 << k)) m->mg_gen[k] = m->gen;
+    if (st) {
+        st->started = pin[kMgtStarted];
+        st->goal_cell[0] = pin[kMgtGoalX]; st->goal_cell[1] = pin[kMgtGoalY];
+        st->rounds = pin[kMgtRounds];
+        st->chunks = rr.chunks;
+    }
     return GEM_OK;
 }
 
@@ -223,6 +308,22 @@ int gem_costmap_mapgrid_prepare_front(gem_handle* h, int id, const double* plan_
 {
     GEM_ENTRY("gem_costmap_mapgrid_prepare_front");
     return prepare(h, id, "gem_costmap_mapgrid_prepare_front", plan_xy, n, 1 << kFrontSlot);
+}
+
+int gem_costmap_mapgrid_prepare_tiled(gem_handle* h, int id, const double* plan_xy, long long n, int which, gem_mapgrid_tiled_status* st)
+{
+    GEM_ENTRY("gem_costmap_mapgrid_prepare_tiled");
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, "gem_costmap_mapgrid_prepare_tiled", &m))) return rc;
+    if (!(which & kBoth) || (which & ~kBoth)) return fail(h, GEM_ERR_INVALID, "gem_costmap_mapgrid_prepare_tiled: which is a mask of GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL");
+    return prepare_tiled(h, id, "gem_costmap_mapgrid_prepare_tiled", plan_xy, n, which, st);
+}
+
+int gem_costmap_mapgrid_prepare_front_tiled(gem_handle* h, int id, const double* plan_xy, long long n, gem_mapgrid_tiled_status* st)
+{
+    GEM_ENTRY("gem_costmap_mapgrid_prepare_front_tiled");
+    return prepare_tiled(h, id, "gem_costmap_mapgrid_prepare_front_tiled", plan_xy, n, 1 << kFrontSlot, st);
 }
 
 int gem_costmap_mapgrid_read(gem_handle* h, int id, int which_one, int* out, int* out_started, int out_goal_cell[2])

@@ -17,7 +17,8 @@ constexpr int kMapGridScoreThreads = 256;
 constexpr unsigned char kMapGridBlocked = 253;                     // a byte from here on is blocked: 253, 254, 255
 constexpr int kMapGridPlanes = 3;                                  // LDS planes: open (prologue) | two frontiers
 
-// status words of a grid on the device
+// status words of a grid on the device.  kMapGridLevels: the levels k_mapgrid_distance walked; of a grid made by the tiled form
+// (gem_mapgrid_tiled.hip) the protocol's round counter, the last round that found an active tile plus one
 enum { kMapGridStarted = 0, kMapGridGoalX = 1, kMapGridGoalY = 2, kMapGridLevels = 3, kMapGridStatusWords = 4 };
 
 struct MapGridArgs {

@@ -843,6 +843,19 @@ struct NavPlan {
     }
 };
 
+// What Costmap::prepareMapGridTiled / prepareMapGridFrontTiled answer (gem_hip_mapgrid.h): rounds depends on timing, the grids do not.
+struct MapGridTiledStatus {
+    bool started = false;                                    // a point of the plan was accepted
+    int goalX = -1, goalY = -1;                              // the local goal's cell
+    int rounds = 0, chunks = 0;                              // launches that found an active tile | host round trips
+    static MapGridTiledStatus from(const gem_mapgrid_tiled_status& s)
+    {
+        MapGridTiledStatus r;
+        r.started = s.started != 0; r.goalX = s.goal_cell[0]; r.goalY = s.goal_cell[1]; r.rounds = s.rounds; r.chunks = s.chunks;
+        return r;
+    }
+};
+
 // A frontier (gem_hip_frontier.h): an 8-connected component of the unknown cells that have a known 4-neighbour the last plan reached;
 // in the manner of explore_lite's FrontierSearch, restated from memory and unverified against the library.
 struct Frontier {
@@ -1034,6 +1047,14 @@ public:
     }
     void prepareMapGrid(const std::vector<FootprintPoint>& plan, int which = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL)
     { map_.check(gem_costmap_mapgrid_prepare(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size()), which), "gem_costmap_mapgrid_prepare"); }
+    // The same grids on a costmap of any size (gem_costmap_mapgrid_prepare_tiled): relaxed tile by tile in global memory.  Waits.
+    MapGridTiledStatus prepareMapGridTiled(const std::vector<FootprintPoint>& plan, int which = GEM_MAPGRID_PATH | GEM_MAPGRID_GOAL)
+    {
+        gem_mapgrid_tiled_status st{};
+        map_.check(gem_costmap_mapgrid_prepare_tiled(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size()), which, &st),
+                   "gem_costmap_mapgrid_prepare_tiled");
+        return MapGridTiledStatus::from(st);
+    }
     // waits
     MapGrid mapGrid(MapGridWhich which) const
     {
@@ -1065,6 +1086,14 @@ public:
     // its own, for DWA's goal_front critic; PATH and GOAL are not touched.  Only enqueued; mapGridFront waits.
     void prepareMapGridFront(const std::vector<FootprintPoint>& plan)
     { map_.check(gem_costmap_mapgrid_prepare_front(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size())), "gem_costmap_mapgrid_prepare_front"); }
+    // ... on a costmap of any size (gem_costmap_mapgrid_prepare_front_tiled).  Waits.
+    MapGridTiledStatus prepareMapGridFrontTiled(const std::vector<FootprintPoint>& plan)
+    {
+        gem_mapgrid_tiled_status st{};
+        map_.check(gem_costmap_mapgrid_prepare_front_tiled(map_.handle(), id_, xy(plan), static_cast<long long>(plan.size()), &st),
+                   "gem_costmap_mapgrid_prepare_front_tiled");
+        return MapGridTiledStatus::from(st);
+    }
     MapGrid mapGridFront() const
     {
         const gem_costmap_config c = geometry();

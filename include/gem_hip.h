@@ -749,6 +749,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- the best trajectory: gem_costmap_mapgrid_prepare_front / _read_front, gem_costmap_best_trajectory*, gem_critics_select ----- */
 #include "gem_hip_critics.h"
 
+/* ---- the distance grids on a costmap of any size: gem_costmap_mapgrid_prepare_tiled / _prepare_front_tiled ------------------------ */
+#include "gem_hip_mapgrid_tiled.h"
+
 /* ---- DWA's sampled trajectories: gem_trajgen_plan / _generate / _velocity / _generate_device, gem_costmap_dwa_best* -------------- */
 #include "gem_hip_trajgen.h"
 

@@ -19,6 +19,8 @@
  *                point (x += forward_point_distance * cos(atan2(dy, dx)), y likewise) stays with the caller: it needs atan2 and is
  *                three lines of host code.  gem_costmap_mapgrid_read_front waits, as gem_costmap_mapgrid_read does.  The existing
  *                calls still know two grids: their which / which_one = 4 stays GEM_ERR_INVALID.
+ *                gem_costmap_mapgrid_prepare_front_tiled (gem_hip_mapgrid_tiled.h) is to it what gem_costmap_mapgrid_prepare_tiled is to
+ *                gem_costmap_mapgrid_prepare: the same grid in the same slot on a costmap of any size, and the call WAITS.
  *   a critic     {kind, grid, flags, column, scale, xshift}.  Its score for trajectory t is an exact integer converted to double,
  *                or the caller's double:
  *       GEM_CRITIC_OBSTACLE   the trajectory cost of gem_costmap_score_trajectories with the same spec and the flags

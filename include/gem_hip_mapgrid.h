@@ -6,7 +6,9 @@
  * Every device entry takes the handle's lock and runs on the handle's stream: marks, merges and inflation enqueued before a
  * prepare are visible to it without a host wait, and a scoring call behind it sees its grids.  A cycle is
  *     reset_window(master) -> mark -> clear_footprint -> merge -> inflate -> mapgrid_prepare -> score_trajectories + mapgrid_score,
- * and the first host wait is the one for the scores.
+ * and the first host wait is the one for the scores.  With gem_costmap_mapgrid_prepare_tiled in the prepare's place (a map above
+ * GEM_MAPGRID_MAX_WORDS, a large local map) the first host wait of a cycle is the PREPARE, not the scores: that call waits, its round
+ * count depends on the data.
  *
  * The contract is RESTATED from ROS noetic base_local_planner: src/map_grid.cpp (computeTargetDistance, updatePathCell,
  * adjustPlanResolution, setTargetCells, setLocalGoal), include/base_local_planner/map_cell.h and src/map_grid_cost_function.cpp
@@ -54,14 +56,28 @@
  *   gem_costmap_mapgrid_score   n_traj trajectories of poses_per_traj poses each (host arrays; the call waits) -> out_traj[n_traj].
  *                _device: poses and results in device memory; the call only enqueues and the buffers are untouched until
  *                gem_synchronize, as for gem_costmap_score_trajectories_device.  A non-finite pose simply answers -4.
- * A MapGrid belongs to a LOCAL costmap: the whole search lives in one workgroup's LDS, so ceil(size_x / 64) * size_y must not exceed
- * GEM_MAPGRID_MAX_WORDS (e.g. 512 x 512).  A global-memory form for larger maps, with many workgroups and a frontier exchange between
- * tiles, is not provided.
+ * gem_costmap_mapgrid_prepare keeps the whole search in one workgroup's LDS, so ceil(size_x / 64) * size_y must not exceed
+ * GEM_MAPGRID_MAX_WORDS (e.g. 512 x 512) there.
+ *   gem_costmap_mapgrid_prepare_tiled   the same grids on a costmap of ANY size: the sections `constants`, `the run` and
+ *                `computeTargetDistance` above apply unchanged, to the byte.  The distances live in global memory and are relaxed tile
+ *                by tile of 64 x 64 cells, one launch per round over every tile, a tile that no neighbour changed leaving at once
+ *                (the protocol of gem_costmap_navplan's potential; computeTargetDistance is its unit-weight, multi-source case).
+ *                The grids land in the same slots with the same status words and generation, so gem_costmap_mapgrid_read, _score,
+ *                _score_device, gem_costmap_best_trajectory, _dwa_best and _rollout_best work behind it without a change.  The call
+ *                WAITS: the round count depends on the data, as in gem_costmap_navplan; rounds are enqueued in chunks of tiles_x +
+ *                tiles_y, each closed by a read of a converged word in pinned host memory.  The requested grids count as never
+ *                prepared from before the first launch until convergence: a failure in between leaves no half-relaxed grid to read.
+ *                Not converged within size_x * size_y + 2 rounds (it cannot happen): GEM_ERR_HIP.  *st (may be NULL): started and
+ *                goal_cell as gem_costmap_mapgrid_read answers them; rounds = launches that found an active tile (it depends on
+ *                timing, the grids do not); chunks = host round trips.  A second identical call allocates nothing.  Its error cases
+ *                are gem_costmap_mapgrid_prepare's without the cap.  (gem_costmap_mapgrid_prepare_front_tiled is
+ *                the same for the FRONT grid; both are declared in gem_hip_mapgrid_tiled.h.)  gem_costmap_mapgrid_prepare itself still only enqueues and still refuses a map above
+ *                the cap: nothing dispatches from it to the tiled form.
  *
  * GEM_ERR_INVALID, nothing enqueued and nothing changed: a bad id; a handle with a communicator; a NULL array with a non-zero
  * count; n < 0, n_traj < 0, n_traj * poses_per_traj above 2^31 - 2, poses_per_traj outside [1, 2^20]; a non-finite plan coordinate
  * or xshift; a resolution not finite and positive (gem_mapgrid_adjust_plan); an adjusted plan above GEM_MAPGRID_MAX_POINTS; `which`
- * empty or with unknown bits, which_one not exactly one grid, unknown flag bits; a map above GEM_MAPGRID_MAX_WORDS; scoring or reading
+ * empty or with unknown bits, which_one not exactly one grid, unknown flag bits; a map above GEM_MAPGRID_MAX_WORDS (the capped prepare alone); scoring or reading
  * a grid that was never prepared, or was prepared before the costmap last rolled (gem_costmap_update_origin / _roll_to moved it) or
  * was created anew: the host keeps a generation number per costmap (the library recomputes the grids every cycle for the same
  * reason). */
