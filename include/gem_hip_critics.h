@@ -72,7 +72,7 @@
  * array with a non-zero count; n_traj < 0, n_traj * poses_per_traj above 2^31 - 2, poses_per_traj outside [1, 2^20]; n_critics outside
  * [1, GEM_CRITIC_MAX]; an unknown kind; a scale negative or not finite; unknown flag bits for the kind; more than one OBSTACLE critic;
  * with an OBSTACLE critic n_vertices out of range or a non-finite spec coordinate; a MAPGRID critic whose grid is not exactly one of
- * the three, whose xshift is not finite, or whose grid was never prepared or was prepared before the costmap last rolled (a critic with
+ * the three, whose xshift is not finite, or whose grid was never prepared or was prepared before the costmap last rolled or was observed (a critic with
  * scale 0 is checked like any other); n_ext_columns < 0 or an EXTERNAL column outside [0, n_ext_columns); in the host form a length
  * outside [1, poses_per_traj].  For the FRONT entries: the cases of gem_costmap_mapgrid_prepare / _read. */
 #define GEM_CRITIC_OBSTACLE 1   /* flags: GEM_FOOTPRINT_INSCRIBED_LETHAL | GEM_FOOTPRINT_SUM | GEM_CRITIC_CENTRE_COST */

@@ -18,7 +18,7 @@
  *
  *   inputs       the costmap's bytes as they are when the call runs on the stream (size_y rows of size_x), and the potential `pot` of
  *                the costmap's last plan.  Keeping the two consistent -- no mark, merge or inflation between the plan and the search --
- *                is the CALLER'S business: nothing checks it.  A costmap without a plan, or whose plan predates its last roll, is
+ *                is the CALLER'S business: nothing checks it.  A costmap without a plan, or whose plan predates its last roll or observe call, is
  *                refused by the generation test of gem_costmap_navplan_read.
  *   known(n)     byte[n] != 255.          reached(n)   pot[n] != GEM_NAV_UNREACHED.
  *   doors of c   its 4-neighbours on the map that are known and reached.  The plan's start cell has potential 0 whatever its byte: it
@@ -45,7 +45,7 @@
  *                grow: a second identical call allocates nothing.  status.rounds is the number of launches that found an active tile
  *                (it depends on timing, nothing else does), status.chunks the number of host round trips.
  *   gem_costmap_frontiers_read   waits.  The last search's kept list (out, may be NULL, cap records; cap below n_kept:
- *                GEM_ERR_INVALID) and label grid (out_labels, may be NULL).  Refused before any search, after a roll, and after a new
+ *                GEM_ERR_INVALID) and label grid (out_labels, may be NULL).  Refused before any search, after a roll or an observe call, and after a new
  *                gem_costmap_navplan: a search carries the plan it was made from.  gem_costmap_navplan_goal leaves the potential
  *                alone and so keeps the search.
  *   gem_costmap_navplan_goal   the grid path from the last plan's start to ANOTHER goal on the last plan's potential, which it does not

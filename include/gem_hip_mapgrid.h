@@ -57,7 +57,7 @@
  *                _device: poses and results in device memory; the call only enqueues and the buffers are untouched until
  *                gem_synchronize, as for gem_costmap_score_trajectories_device.  A non-finite pose simply answers -4.
  * gem_costmap_mapgrid_prepare keeps the whole search in one workgroup's LDS, so ceil(size_x / 64) * size_y must not exceed
- * GEM_MAPGRID_MAX_WORDS (e.g. 512 x 512) there.
+ * GEM_MAPGRID_MAX_WORDS there (512 x 512 is the largest square; 513 x 66 and 70 x 520 fit, 1 x 4100 does not).
  *   gem_costmap_mapgrid_prepare_tiled   the same grids on a costmap of ANY size: the sections `constants`, `the run` and
  *                `computeTargetDistance` above apply unchanged, to the byte.  The distances live in global memory and are relaxed tile
  *                by tile of 64 x 64 cells, one launch per round over every tile, a tile that no neighbour changed leaving at once
@@ -78,9 +78,10 @@
  * count; n < 0, n_traj < 0, n_traj * poses_per_traj above 2^31 - 2, poses_per_traj outside [1, 2^20]; a non-finite plan coordinate
  * or xshift; a resolution not finite and positive (gem_mapgrid_adjust_plan); an adjusted plan above GEM_MAPGRID_MAX_POINTS; `which`
  * empty or with unknown bits, which_one not exactly one grid, unknown flag bits; a map above GEM_MAPGRID_MAX_WORDS (the capped prepare alone); scoring or reading
- * a grid that was never prepared, or was prepared before the costmap last rolled (gem_costmap_update_origin / _roll_to moved it) or
+ * a grid that was never prepared, or was prepared before the costmap last rolled (gem_costmap_update_origin / _roll_to moved it), was
+ * observed (gem_costmap_observe* or gem_costmap_voxel_observe* with at least one observation: gem_hip_obstacle.h, gem_hip_voxlayer.h) or
  * was created anew: the host keeps a generation number per costmap (the library recomputes the grids every cycle for the same
- * reason). */
+ * reason).  A refusal of the capped prepare leaves grids that gem_costmap_mapgrid_prepare_tiled made readable as they were. */
 #define GEM_MAPGRID_PATH 1
 #define GEM_MAPGRID_GOAL 2
 #define GEM_MAPGRID_STOP_ON_FAILURE 1   /* d == OB answers -3, d == UN answers -2 */

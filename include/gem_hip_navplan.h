@@ -60,7 +60,8 @@
  *
  * GEM_ERR_INVALID, nothing enqueued and nothing changed: a bad id; a handle with a communicator; a NULL w, start, goal or status, a
  * negative weight; non-finite coordinates; unknown flag bits; the overflow condition; sizes below 1 (host twin); a read or a status
- * before any plan, or after the costmap rolled (gem_costmap_update_origin / _roll_to moved it) or was created anew: the generation number of
+ * before any plan, or after the costmap rolled (gem_costmap_update_origin / _roll_to moved it), was observed (gem_costmap_observe* or
+ * gem_costmap_voxel_observe* with at least one observation) or was created anew: the generation number of
  * gem_hip_mapgrid.h. */
 #define GEM_NAV_OUTLINE   1
 #define GEM_NAV_UNREACHED 0x7fffffff

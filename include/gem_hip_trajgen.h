@@ -66,7 +66,9 @@
  *   gem_costmap_dwa_best / _device   generation into arenas of the handle that only grow, then the critics and the pick of
  *                gem_costmap_best_trajectory_device on them: one call, three launches, 32 bytes back.  An EXTERNAL critic's column
  *                0 / 1 is the generated oscillation / twirling column.  out_total [n_traj] (may be NULL) and out_best are host memory
- *                and the call waits; _device: device memory, only enqueued.  A second identical call allocates nothing.
+ *                and the call waits; _device: device memory, only enqueued.  A second identical call allocates nothing.  A
+ *                MAPGRID critic's grid passes gem_costmap_best_trajectory's test (gem_hip_critics.h): never prepared, or prepared
+ *                before the costmap last rolled or was observed, is refused.
  *
  * GEM_ERR_INVALID, nothing enqueued and nothing written: a NULL argument other than those that may be; a parameter, pos, vel or goal
  * that is not finite; sim_time, sim_period, sim_granularity or (without discretize_by_time) angular_sim_granularity <= 0; unknown
