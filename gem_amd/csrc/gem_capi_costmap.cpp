@@ -10,7 +10,10 @@
 // A mark is its mark launches followed by one resolve launch on the handle's stream; the inputs that already live on the device
 // (the capture, the submap stack) are read where they are, a capture's record count from its device word.  Every device buffer comes
 // from ensure(), so gem_debug_get("arena_allocations") counts it.
-#include "gem_costmap_host.hpp"
+// Also here: what the layers share on the host -- read_bounds and read_window / write_window under the four read and write entry
+// points of the bytes and the columns (gem_costmap_host.hpp), and stage_observations, obs_params_common and touch of ObstacleLayer
+// and VoxelLayer (gem_observe_host.hpp).
+#include "gem_observe_host.hpp"
 #include "gem_voxlayer.hpp"
 
 #include <algorithm>
@@ -19,7 +22,6 @@ namespace {
 
 constexpr size_t kRec = sizeof(LocalRecord);
 constexpr long long kMaxInputs = 2147483646ll;                      // 2^31 - 2: the stamp 2 * (i + 1) + 1 fits 32 bits
-constexpr long long kMaxCells = 1ll << 30;
 
 unsigned long long* acc_words(gem_handle* h) { return static_cast<unsigned long long*>(h->costmap.small.p); }
 CostAccum accum_of(gem_handle* h, CostMap& m) { return CostAccum{static_cast<uint32_t*>(m.stamps.p), acc_words(h)}; }
@@ -27,29 +29,12 @@ CostAccum accum_of(gem_handle* h, CostMap& m) { return CostAccum{static_cast<uin
 int invalid(gem_handle* h, const char* what, const char* reason) { return fail(h, GEM_ERR_INVALID, (std::string(what) + ": " + reason).c_str()); }
 int usable(gem_handle* h, const char* what) { return h->tp_x ? invalid(h, what, "not on a handle with a communicator") : GEM_OK; }
 
-bool window_ok(const CostMap& m, int min_i, int min_j, int max_i, int max_j)
-{
-    return min_i >= 0 && min_j >= 0 && min_i <= max_i && min_j <= max_j && (long long)max_i <= (long long)m.cfg.size_x &&
-           (long long)max_j <= (long long)m.cfg.size_y;
-}
-
-// the resolve pass behind a mark's launches, then the caller's bounds merged with the touched ones: touch() of costmap_layer.cpp,
-// *min = std::min(p, *min) and *max = std::max(p, *max) over the accepted inputs
+// the resolve pass behind a mark's launches, then the caller's bounds merged with the touched ones
 int finish_mark(gem_handle* h, CostMap& m, double bounds[4])
 {
     unsigned long long* acc = acc_words(h);
     GEM_HIP(h, launch_cost_resolve(h->stream, cells_of(m), static_cast<uint32_t*>(m.stamps.p), grid_of(m), acc, acc + 4));
-    if (!bounds) return GEM_OK;
-    unsigned long long w[4];
-    HostXfer d{w, acc + 4, sizeof(w)};
-    int rc;
-    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
-    double v;
-    for (int k = 0; k < 2; ++k) {
-        if (cost_key_decode(w[k], false, &v)) bounds[k] = bounds[k] < v ? bounds[k] : v;
-        if (cost_key_decode(w[2 + k], true, &v)) bounds[2 + k] = v < bounds[2 + k] ? bounds[2 + k] : v;
-    }
-    return GEM_OK;
+    return read_bounds(h, bounds);
 }
 
 int mark_records(gem_handle* h, CostMap& m, const LocalRecord* d_rec, long long n, double thresh, double bounds[4])
@@ -91,11 +76,10 @@ int update_origin(gem_handle* h, CostMap& m, double new_ox, double new_oy, const
     if (cell_ox == 0 && cell_oy == 0) return GEM_OK;
     const double ox = m.cfg.origin_x + cell_ox * m.cfg.resolution, oy = m.cfg.origin_y + cell_oy * m.cfg.resolution;
     if (!std::isfinite(ox) || !std::isfinite(oy)) return fail(h, GEM_ERR_INVALID, (std::string(what) + ": origin not finite").c_str());
-    GEM_HIP(h, launch_cost_roll(h->stream, grid_of(m), static_cast<unsigned char*>(m.grid[1 - m.act].p), m.cfg.size_x, m.cfg.size_y,
-                                cell_ox, cell_oy, m.cfg.default_value));
+    GEM_HIP(h, launch_cost_roll(h->stream, grid_of(m), m.grid[1 - m.act].p, 1, m.cfg.size_x, m.cfg.size_y, cell_ox, cell_oy, m.cfg.default_value));
     m.act = 1 - m.act;
     if (m.has_vox) {                                                    // VoxelLayer::updateOrigin: the columns move with the bytes
-        GEM_HIP(h, launch_vox_roll(h->stream, columns_of(m), static_cast<uint32_t*>(m.vox[1 - m.vox_act].p), m.cfg.size_x, m.cfg.size_y, cell_ox, cell_oy));
+        GEM_HIP(h, launch_cost_roll(h->stream, columns_of(m), m.vox[1 - m.vox_act].p, 4, m.cfg.size_x, m.cfg.size_y, cell_ox, cell_oy, kVoxUnknown));
         m.vox_act = 1 - m.vox_act;
     }
     m.cfg.origin_x = ox; m.cfg.origin_y = oy;
@@ -137,6 +121,121 @@ int costmap_search_fresh(gem_handle* h, const CostMap& m, const char* what)
 {
     if (!m.fr_gen) return invalid(h, what, "no search was made, or a plan was made since");
     if (m.fr_gen != m.gen) return invalid(h, what, "the search was made before the costmap last rolled or was observed");
+    return GEM_OK;
+}
+
+bool geometry_ok(const gem_costmap_config* c)
+{
+    return c && c->size_x != 0 && c->size_y != 0 && (long long)c->size_x * c->size_y <= kMaxCells && std::isfinite(c->resolution) &&
+           c->resolution > 0.0 && std::isfinite(c->origin_x) && std::isfinite(c->origin_y);
+}
+
+bool window_ok(const CostMap& m, int min_i, int min_j, int max_i, int max_j)
+{
+    return min_i >= 0 && min_j >= 0 && min_i <= max_i && min_j <= max_j && (long long)max_i <= (long long)m.cfg.size_x &&
+           (long long)max_j <= (long long)m.cfg.size_y;
+}
+
+int read_window(gem_handle* h, CostMap& m, const char* what, void* grid, size_t elem, CostWindow win, void* out, size_t row_stride)
+{
+    if (!window_ok(m, win.min_i, win.min_j, win.max_i, win.max_j)) return invalid(h, what, "window outside the map");
+    const size_t w = (size_t)(win.max_i - win.min_i), rows = (size_t)(win.max_j - win.min_j), bytes = w * rows * elem;
+    if (!w || !rows) return GEM_OK;
+    if (!out || row_stride < w) return invalid(h, what, "null output or a row stride below the window's width");
+    int rc;
+    void* src = grid;
+    if (!(w == m.cfg.size_x && rows == m.cfg.size_y)) {                 // a partial window is packed on the device first
+        if ((rc = ensure(h, h->costmap.win, bytes))) return rc;
+        GEM_HIP(h, launch_cost_window(h->stream, grid, elem, m.cfg.size_x, win, h->costmap.win.p, true));
+        src = h->costmap.win.p;
+    }
+    if (row_stride == w) {
+        HostXfer d{out, src, bytes};
+        return download_arrays(h, &d, 1, 0);
+    }
+    std::vector<unsigned char>& tmp = h->costmap.host_rows;             // packed rows, then out at the caller's stride
+    tmp.resize(bytes);
+    HostXfer d{tmp.data(), src, bytes};
+    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
+    for (size_t r = 0; r < rows; ++r) memcpy(static_cast<unsigned char*>(out) + r * row_stride * elem, tmp.data() + r * w * elem, w * elem);
+    return GEM_OK;
+}
+
+int write_window(gem_handle* h, CostMap& m, const char* what, void* grid, size_t elem, CostWindow win, const void* in, size_t row_stride)
+{
+    if (!window_ok(m, win.min_i, win.min_j, win.max_i, win.max_j)) return invalid(h, what, "window outside the map");
+    const size_t w = (size_t)(win.max_i - win.min_i), rows = (size_t)(win.max_j - win.min_j), bytes = w * rows * elem;
+    if (!w || !rows) return GEM_OK;
+    if (!in || row_stride < w) return invalid(h, what, "null input or a row stride below the window's width");
+    int rc;
+    if ((rc = ensure(h, h->costmap.win, bytes))) return rc;
+    if (row_stride != w) {                                              // the caller's rows, packed
+        std::vector<unsigned char>& tmp = h->costmap.host_rows;
+        tmp.resize(bytes);
+        for (size_t r = 0; r < rows; ++r) memcpy(tmp.data() + r * w * elem, static_cast<const unsigned char*>(in) + r * row_stride * elem, w * elem);
+        in = tmp.data();
+    }
+    HostXfer x{const_cast<void*>(in), h->costmap.win.p, bytes};
+    if ((rc = upload_arrays(h, &x, 1))) return rc;
+    GEM_HIP(h, launch_cost_window(h->stream, grid, elem, m.cfg.size_x, win, h->costmap.win.p, false));
+    return GEM_OK;
+}
+
+int stage_observations(gem_handle* h, const ObserveCall& c, const void* points[GEM_OBS_MAX])
+{
+    auto& in = h->costmap.in;
+    size_t host_bytes = 0, at[GEM_OBS_MAX];
+    for (int k = 0; k < c.n_obs; ++k) {
+        at[k] = host_bytes;
+        host_bytes += ((size_t)c.obs[k].n * c.obs[k].point_step + 255) / 256 * 256;
+    }
+    int rc;
+    if (!c.on_device && host_bytes && (rc = ensure(h, in, host_bytes))) return rc;
+    HostXfer up[GEM_OBS_MAX];
+    int n_up = 0;
+    for (int k = 0; k < c.n_obs; ++k) {
+        points[k] = c.on_device ? c.obs[k].points : static_cast<const unsigned char*>(in.p) + at[k];
+        if (!c.on_device && c.obs[k].n > 0)
+            up[n_up++] = HostXfer{const_cast<void*>(c.obs[k].points), const_cast<void*>(points[k]), (size_t)c.obs[k].n * c.obs[k].point_step};
+    }
+    return n_up ? upload_arrays(h, up, n_up) : GEM_OK;
+}
+
+ObsParams obs_params_common(const CostGeom& g, const gem_observation& o, const void* points, double layer_max_h)
+{
+    ObsParams p{};
+    p.points = static_cast<const unsigned char*>(points);
+    p.n = (uint32_t)o.n; p.step = o.point_step;
+    p.ox = o.origin[0]; p.oy = o.origin[1]; p.oz = o.origin[2];
+    p.sq_obstacle_range = o.obstacle_range * o.obstacle_range;
+    p.raytrace_range = o.raytrace_range;
+    p.min_h = o.min_obstacle_height; p.max_h = o.max_obstacle_height; p.layer_max_h = layer_max_h;
+    p.cell_range = obs_cell_distance(o.raytrace_range, g.res);
+    p.marking = (o.flags & GEM_OBS_MARKING) ? 1 : 0;
+    return p;
+}
+
+void touch(double bounds[4], double x, double y)
+{
+    if (!bounds) return;
+    bounds[0] = obs_std_min(x, bounds[0]); bounds[1] = obs_std_min(y, bounds[1]);
+    bounds[2] = obs_std_max(x, bounds[2]); bounds[3] = obs_std_max(y, bounds[3]);
+}
+
+// A mark used to merge with `bounds[k] < v ? bounds[k] : v` and `v < bounds[2 + k] ? bounds[2 + k] : v`; obs_std_min(v, bounds[k]) and
+// obs_std_max(v, bounds[2 + k]), which the observes used, expand to these very expressions, so the two agree for every input, NaN
+// and signed zeros included: a NaN in bounds is replaced (both comparisons are false), and of two zeros the decoded one stays.
+int read_bounds(gem_handle* h, double bounds[4])
+{
+    if (!bounds) return GEM_OK;
+    unsigned long long w[4];
+    HostXfer d{w, acc_words(h) + 4, sizeof(w)};
+    if (const int rc = download_arrays(h, &d, 1, 0)) return rc;
+    double v;
+    for (int k = 0; k < 2; ++k) {
+        if (cost_key_decode(w[k], false, &v)) bounds[k] = obs_std_min(v, bounds[k]);
+        if (cost_key_decode(w[2 + k], true, &v)) bounds[2 + k] = obs_std_max(v, bounds[2 + k]);
+    }
     return GEM_OK;
 }
 
@@ -195,7 +294,7 @@ int gem_costmap_create(gem_handle* h, const gem_costmap_config* cfg, int* out_id
     m.cfg = *cfg; m.act = 0;
     m.gen = ++c.generation;
     GEM_HIP(h, hipMemsetAsync(m.stamps.p, 0, stamp_bytes, h->stream));
-    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(m), (uint32_t)cells, m.cfg.default_value));
+    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(m), 1, (uint32_t)cells, m.cfg.default_value));
     m.used = true;
     *out_id = id;
     return GEM_OK;
@@ -229,8 +328,8 @@ int gem_costmap_reset(gem_handle* h, int id)
     int rc;
     CostMap* m;
     if ((rc = costmap_find(h, id, "gem_costmap_reset", &m))) return rc;
-    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(*m), cells_of(*m), m->cfg.default_value));
-    if (m->has_vox) GEM_HIP(h, launch_vox_fill(h->stream, columns_of(*m), cells_of(*m)));      // VoxelLayer::resetMaps
+    GEM_HIP(h, launch_cost_fill(h->stream, grid_of(*m), 1, cells_of(*m), m->cfg.default_value));
+    if (m->has_vox) GEM_HIP(h, launch_cost_fill(h->stream, columns_of(*m), 4, cells_of(*m), kVoxUnknown));      // VoxelLayer::resetMaps
     return GEM_OK;
 }
 
@@ -371,56 +470,17 @@ int gem_costmap_merge(gem_handle* h, int id, int master_id, int min_i, int min_j
 int gem_costmap_read(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, unsigned char* out, size_t row_stride)
 {
     GEM_ENTRY("gem_costmap_read");
-    int rc;
     CostMap* m;
-    if ((rc = costmap_find(h, id, "gem_costmap_read", &m))) return rc;
-    if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_read: window outside the map");
-    const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
-    if (!w || !rows) return GEM_OK;
-    if (!out || row_stride < w) return fail(h, GEM_ERR_INVALID, "gem_costmap_read: null output or a row stride below the window's width");
-    const bool whole = w == m->cfg.size_x && rows == m->cfg.size_y;
-    const unsigned char* src = grid_of(*m);
-    if (!whole) {                                                        // a partial window is packed on the device first
-        if ((rc = ensure(h, h->costmap.win, w * rows))) return rc;
-        GEM_HIP(h, launch_cost_window(h->stream, grid_of(*m), m->cfg.size_x, CostWindow{min_i, min_j, max_i, max_j},
-                                      static_cast<unsigned char*>(h->costmap.win.p)));
-        src = static_cast<const unsigned char*>(h->costmap.win.p);
-    }
-    if (row_stride == w) {
-        HostXfer d{out, const_cast<unsigned char*>(src), w * rows};
-        return download_arrays(h, &d, 1, 0);
-    }
-    std::vector<unsigned char>& tmp = h->costmap.host_rows;             // packed rows, then out at the caller's stride
-    tmp.resize(w * rows);
-    HostXfer d{tmp.data(), const_cast<unsigned char*>(src), w * rows};
-    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
-    for (size_t r = 0; r < rows; ++r) memcpy(out + r * row_stride, tmp.data() + r * w, w);
-    return GEM_OK;
+    if (const int rc = costmap_find(h, id, "gem_costmap_read", &m)) return rc;
+    return read_window(h, *m, "gem_costmap_read", grid_of(*m), 1, CostWindow{min_i, min_j, max_i, max_j}, out, row_stride);
 }
 
 int gem_costmap_write(gem_handle* h, int id, int min_i, int min_j, int max_i, int max_j, const unsigned char* in, size_t row_stride)
 {
     GEM_ENTRY("gem_costmap_write");
-    int rc;
     CostMap* m;
-    if ((rc = costmap_find(h, id, "gem_costmap_write", &m))) return rc;
-    if (!window_ok(*m, min_i, min_j, max_i, max_j)) return fail(h, GEM_ERR_INVALID, "gem_costmap_write: window outside the map");
-    const size_t w = (size_t)(max_i - min_i), rows = (size_t)(max_j - min_j);
-    if (!w || !rows) return GEM_OK;
-    if (!in || row_stride < w) return fail(h, GEM_ERR_INVALID, "gem_costmap_write: null input or a row stride below the window's width");
-    if ((rc = ensure(h, h->costmap.win, w * rows))) return rc;
-    const unsigned char* src = in;
-    if (row_stride != w) {
-        std::vector<unsigned char>& tmp = h->costmap.host_rows;
-        tmp.resize(w * rows);
-        for (size_t r = 0; r < rows; ++r) memcpy(tmp.data() + r * w, in + r * row_stride, w);
-        src = tmp.data();
-    }
-    HostXfer x{const_cast<unsigned char*>(src), h->costmap.win.p, w * rows};
-    if ((rc = upload_arrays(h, &x, 1))) return rc;
-    GEM_HIP(h, launch_cost_unpack(h->stream, static_cast<const unsigned char*>(h->costmap.win.p), m->cfg.size_x,
-                                  CostWindow{min_i, min_j, max_i, max_j}, grid_of(*m)));
-    return GEM_OK;
+    if (const int rc = costmap_find(h, id, "gem_costmap_write", &m)) return rc;
+    return write_window(h, *m, "gem_costmap_write", grid_of(*m), 1, CostWindow{min_i, min_j, max_i, max_j}, in, row_stride);
 }
 
 } // extern "C"

@@ -17,11 +17,6 @@ namespace {
 
 static_assert(kInflateMaxCells == GEM_INFLATE_MAX_CELLS, "the kernels' radius limit is the header's");
 
-bool window_ok(const CostMap& m, int x0, int y0, int xn, int yn)
-{
-    return x0 >= 0 && y0 >= 0 && x0 <= xn && y0 <= yn && (long long)xn <= (long long)m.cfg.size_x && (long long)yn <= (long long)m.cfg.size_y;
-}
-
 // cell_inflation_radius_ = cellDistance(inflation_radius_); false: the parameters or the resolution are not usable, or R is too large
 bool inflation_cells(const gem_inflation_params* p, double res, unsigned* out_R)
 {

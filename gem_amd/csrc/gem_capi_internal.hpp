@@ -8,7 +8,9 @@
 //   gem_capi.cpp           the extern "C" entry points of include/gem_hip.h (single-device part) and include/gem_hip_debug.h
 //   gem_capi_comm.cpp      communicators, the all-gather of the layers, the sharded step (gem_add_sharded_device and its halves)
 //   gem_costmap_host.hpp   the costmap family's shared host pieces (gem_capi_costmap / _inflate / _footprint / _mapgrid / _critics /
-//                          _navplan / _frontier / _obstacle / _voxlayer / _rollout .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search
+//                          _navplan / _frontier / _obstacle / _voxlayer / _rollout .cpp): the lookup by id, geometry and grid, the staleness checks of a plan and a search,
+//                          the bounds read-back, a window read or written
+//   gem_observe_host.hpp   what gem_capi_obstacle.cpp and gem_capi_voxlayer.cpp share: the staged observations, the common ObsParams, touch
 //   gem_rounds.hpp         the host loop of the tiled fixed-point kernels (plan, frontier labels): chunks of rounds up to the bound (pure C++)
 #pragma once
 

@@ -4,10 +4,10 @@
 //
 // State (gem_handle::Costmaps): ob_bits, the end-cell and mark bitmaps, all-zero between calls (the kernels clear what they consume);
 // ob_rays, the ray list; ob_cnt, the compaction's block counts and total; `in`, the host clouds of gem_costmap_observe behind each
-// other.  All come from ensure(), so gem_debug_get("arena_allocations") counts them.  Per observation the call enqueues its pass, then
+// other (stage_observations of gem_observe_host.hpp).  All come from ensure(), so gem_debug_get("arena_allocations") counts them.  Per observation the call enqueues its pass, then
 // (clearing) the compaction and the walk -- or with "obstacle_direct" the walk per record --; behind the last observation one launch
 // applies the marks.  Clears and marks commute with nothing in between them, so the stream's order is all the ordering there is.
-#include "gem_costmap_host.hpp"
+#include "gem_observe_host.hpp"
 #include "gem_compact.hpp"
 #include "gem_obstacle.hpp"
 
@@ -16,7 +16,6 @@
 namespace {
 
 constexpr long long kMaxRecords = 2147483646ll;                     // 2^31 - 2
-constexpr long long kMaxCells = 1ll << 30;
 static_assert(sizeof(gem_observation) == 80, "gem_observation is 80 bytes");
 static_assert(kObsMax == GEM_OBS_MAX && kObsMarking == GEM_OBS_MARKING && kObsClearing == GEM_OBS_CLEARING, "the kernels' constants are the header's");
 
@@ -46,34 +45,11 @@ namespace {
 // the host's part of an observation: the origin's cell, the map's far edges, the cell range
 ObsParams params_of(const CostGeom& g, const gem_observation& o, const void* points, double layer_max_h)
 {
-    ObsParams p{};
-    p.points = static_cast<const unsigned char*>(points);
-    p.n = (uint32_t)o.n; p.step = o.point_step;
-    p.ox = o.origin[0]; p.oy = o.origin[1]; p.oz = o.origin[2];
-    p.sq_obstacle_range = o.obstacle_range * o.obstacle_range;
-    p.raytrace_range = o.raytrace_range;
-    p.min_h = o.min_obstacle_height; p.max_h = o.max_obstacle_height; p.layer_max_h = layer_max_h;
+    ObsParams p = obs_params_common(g, o, points, layer_max_h);
     p.end_x = g.ox + g.sx * g.res; p.end_y = g.oy + g.sy * g.res;
-    p.cell_range = obs_cell_distance(o.raytrace_range, g.res);
-    p.marking = (o.flags & GEM_OBS_MARKING) ? 1 : 0;
     p.clearing = ((o.flags & GEM_OBS_CLEARING) && cost_cell_xy(g, p.ox, p.oy, p.x0, p.y0)) ? 1 : 0;
     return p;
 }
-
-void touch(double bounds[4], double x, double y)
-{
-    if (!bounds) return;
-    bounds[0] = obs_std_min(x, bounds[0]); bounds[1] = obs_std_min(y, bounds[1]);
-    bounds[2] = obs_std_max(x, bounds[2]); bounds[3] = obs_std_max(y, bounds[3]);
-}
-
-struct ObserveCall {
-    const char* what;
-    const gem_observation* obs;
-    int n_obs;
-    double layer_max_h;
-    bool on_device;
-};
 
 int observe(gem_handle* h, int id, const ObserveCall& c, double bounds[4])
 {
@@ -86,25 +62,13 @@ int observe(gem_handle* h, int id, const ObserveCall& c, double bounds[4])
     const CostGeom g = geom_of(*m);
     const uint32_t cells = cells_of(*m), words = obs_words(cells);
     auto& cm = h->costmap;
-    size_t max_n = 0, host_bytes = 0, at[GEM_OBS_MAX];
-    for (int k = 0; k < c.n_obs; ++k) {
-        max_n = std::max(max_n, (size_t)c.obs[k].n);
-        at[k] = host_bytes;
-        host_bytes += ((size_t)c.obs[k].n * c.obs[k].point_step + 255) / 256 * 256;
-    }
+    const void* points[GEM_OBS_MAX];
+    const size_t max_n = longest_observation(c);
     const size_t nb = (size_t)compact_blocks((long long)cells);
     if ((rc = ensure_zeroed(h, cm.ob_bits, 2 * (size_t)words * sizeof(uint32_t))) || (rc = ensure(h, cm.ob_rays, std::max<size_t>(max_n, 1) * sizeof(uint32_t))) ||
         (rc = ensure(h, cm.ob_cnt, (nb + 1) * sizeof(uint32_t))))
         return rc;
-    if (!c.on_device && host_bytes) {
-        if ((rc = ensure(h, cm.in, host_bytes))) return rc;
-        HostXfer up[GEM_OBS_MAX];
-        int n_up = 0;
-        for (int k = 0; k < c.n_obs; ++k)
-            if (c.obs[k].n > 0)
-                up[n_up++] = HostXfer{const_cast<void*>(c.obs[k].points), static_cast<unsigned char*>(cm.in.p) + at[k], (size_t)c.obs[k].n * c.obs[k].point_step};
-        if (n_up && (rc = upload_arrays(h, up, n_up))) return rc;
-    }
+    if ((rc = stage_observations(h, c, points))) return rc;
 
     unsigned long long* acc = static_cast<unsigned long long*>(cm.small.p);
     ObsScratch s{};
@@ -114,9 +78,7 @@ int observe(gem_handle* h, int id, const ObserveCall& c, double bounds[4])
     s.acc = acc;
     m->gen = ++cm.generation;                                           // the grid changes: plans, searches and distance grids made before are stale
     for (int k = 0; k < c.n_obs; ++k) {
-        const gem_observation& o = c.obs[k];
-        const void* points = c.on_device ? o.points : static_cast<const unsigned char*>(cm.in.p) + at[k];
-        const ObsParams p = params_of(g, o, points, c.layer_max_h);
+        const ObsParams p = params_of(g, c.obs[k], points[k], c.layer_max_h);
         if (p.clearing) touch(bounds, p.ox, p.oy);
         if (p.n == 0u || !(p.clearing || p.marking)) continue;
         GEM_HIP(h, launch_obs_pass(h->stream, g, p, s, h->obstacle_direct));
@@ -125,16 +87,7 @@ int observe(gem_handle* h, int id, const ObserveCall& c, double bounds[4])
         else GEM_HIP(h, launch_obs_walk_cells(h->stream, g, p, s, grid_of(*m)));
     }
     GEM_HIP(h, launch_obs_apply(h->stream, cells, s.mark_bits, grid_of(*m), acc, acc + 4));
-    if (!bounds) return GEM_OK;
-    unsigned long long w[4];
-    HostXfer d{w, acc + 4, sizeof(w)};
-    if ((rc = download_arrays(h, &d, 1, 0))) return rc;
-    double v;
-    for (int k = 0; k < 2; ++k) {
-        if (cost_key_decode(w[k], false, &v)) bounds[k] = obs_std_min(v, bounds[k]);
-        if (cost_key_decode(w[2 + k], true, &v)) bounds[2 + k] = obs_std_max(v, bounds[2 + k]);
-    }
-    return GEM_OK;
+    return read_bounds(h, bounds);
 }
 
 } // namespace
@@ -157,9 +110,7 @@ int gem_costmap_observe_device(gem_handle* h, int id, const gem_observation* obs
 int gem_obstacle_host(unsigned char* grid, const gem_costmap_config* geom, const gem_observation* obs, int n_obs, double layer_max_obstacle_height,
                       double bounds[4])
 {
-    if (!grid || !geom || geom->size_x == 0 || geom->size_y == 0 || (long long)geom->size_x * geom->size_y > kMaxCells ||
-        !std::isfinite(geom->resolution) || !(geom->resolution > 0.0) || !std::isfinite(geom->origin_x) || !std::isfinite(geom->origin_y))
-        return GEM_ERR_INVALID;
+    if (!grid || !geometry_ok(geom)) return GEM_ERR_INVALID;
     if (check_observations(obs, n_obs, layer_max_obstacle_height)) return GEM_ERR_INVALID;
     const CostGeom g{geom->origin_x, geom->origin_y, geom->resolution, geom->size_x, geom->size_y};
     for (int pass = 0; pass < 2; ++pass)                                // 0: clearing, 1: marking

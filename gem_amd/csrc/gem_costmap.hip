@@ -13,8 +13,9 @@
 //                     consecutive inputs touch few cells, and each non-zero entry leaves with one global atomic max
 //   larger costmaps   the wave-reduced stamps go to global memory directly
 // The touched bounds (min / max of px, py over the accepted inputs) go wave -> workgroup (LDS) -> four global words as
-// order-preserving 64-bit keys under integer min.  Only vector stores and atomics write memory.
-#include "gem_costmap.hpp"
+// order-preserving 64-bit keys under integer min.  The reduction and the publication of the bounds are gem_cost_pass.hpp's, shared with
+// ObstacleLayer and VoxelLayer; the element-wise kernels here (fill, roll, window) serve a grid of bytes or of voxel columns.  Only vector stores and atomics write memory.
+#include "gem_cost_pass.hpp"
 
 namespace gem {
 
@@ -105,23 +106,12 @@ __device__ __forceinline__ void cost_mark_block(const Src& src, const CostGeom& 
         }
     }
 
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo_x = fmin(lo_x, __shfl_xor(lo_x, off)); hi_x = fmax(hi_x, __shfl_xor(hi_x, off));
-        lo_y = fmin(lo_y, __shfl_xor(lo_y, off)); hi_y = fmax(hi_y, __shfl_xor(hi_y, off));
-    }
-    if (lane_id() == 0 && lo_x <= hi_x) {                               // the wave accepted an input
-        atomicMin(&s_acc[0], cost_key(lo_x)); atomicMin(&s_acc[1], cost_key(lo_y));
-        atomicMin(&s_acc[2], ~cost_key(hi_x)); atomicMin(&s_acc[3], ~cost_key(hi_y));
-    }
-    __syncthreads();
+    cost_bounds_out(lo_x, lo_y, hi_x, hi_y, s_acc, out.acc);
     if (LDS)
         for (uint32_t c = threadIdx.x; c < cells; c += kCostThreads) {
             const uint32_t s = s_stamp[c];
             if (s) __hip_atomic_fetch_max(out.stamps + c, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    if (threadIdx.x < 4 && s_acc[threadIdx.x] != ~0ull)
-        __hip_atomic_fetch_min(out.acc + threadIdx.x, s_acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <class Src, bool LDS>
@@ -167,10 +157,7 @@ __global__ __launch_bounds__(kCostThreads) void k_cost_mark_history(CostPointsSr
 __global__ __launch_bounds__(256) void k_cost_resolve(uint32_t cells, uint32_t* __restrict__ stamps, unsigned char* __restrict__ grid,
                                                       unsigned long long* __restrict__ acc, unsigned long long* __restrict__ published)
 {
-    if (blockIdx.x == 0 && threadIdx.x < 4) {
-        published[threadIdx.x] = acc[threadIdx.x];
-        acc[threadIdx.x] = ~0ull;
-    }
+    if (blockIdx.x == 0) cost_publish(acc, published);
     const uint32_t c0 = (blockIdx.x * 256u + threadIdx.x) * 4u;         // the stamp array is padded to a multiple of four words
     if (c0 >= cells) return;
     const uint4 s = *reinterpret_cast<const uint4*>(stamps + c0);
@@ -182,14 +169,17 @@ __global__ __launch_bounds__(256) void k_cost_resolve(uint32_t cells, uint32_t* 
     *reinterpret_cast<uint4*>(stamps + c0) = make_uint4(0u, 0u, 0u, 0u);
 }
 
-__global__ __launch_bounds__(256) void k_cost_fill(unsigned char* __restrict__ grid, uint32_t cells, unsigned char value)
+// The element-wise kernels of a grid, T a byte of the costmap or a 32-bit voxel column (gem_voxlayer.hpp)
+template <class T>
+__global__ __launch_bounds__(256) void k_cost_fill(T* __restrict__ grid, uint32_t cells, T value)
 {
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;
     if (c < cells) grid[c] = value;
 }
 
-__global__ __launch_bounds__(256) void k_cost_roll(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst, uint32_t sx,
-                                                   uint32_t sy, long long cell_ox, long long cell_oy, unsigned char value)
+template <class T>
+__global__ __launch_bounds__(256) void k_cost_roll(const T* __restrict__ src, T* __restrict__ dst, uint32_t sx, uint32_t sy, long long cell_ox,
+                                                   long long cell_oy, T value)
 {
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;
     if (c >= sx * sy) return;
@@ -198,12 +188,22 @@ __global__ __launch_bounds__(256) void k_cost_roll(const unsigned char* __restri
     dst[c] = in ? src[(size_t)y * sx + (size_t)x] : value;
 }
 
+// thread t of a launch over a window: false behind the window's last cell, else the cell's index in the grid
+__device__ __forceinline__ bool cost_window_cell(uint32_t sx, const CostWindow& w, uint32_t& t, size_t& c)
+{
+    const uint32_t ww = (uint32_t)(w.max_i - w.min_i);
+    t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return false;
+    c = (size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww));
+    return true;
+}
+
 __global__ __launch_bounds__(256) void k_cost_merge(const unsigned char* __restrict__ layer, unsigned char* __restrict__ master,
                                                     uint32_t sx, CostWindow w, int mode)
 {
-    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
-    const size_t c = (size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww));
+    uint32_t t;
+    size_t c;
+    if (!cost_window_cell(sx, w, t, c)) return;
     const unsigned char v = layer[c];
     if (v == kCostNoInfo) return;
     if (mode == 0) { master[c] = v; return; }                           // updateWithOverwrite
@@ -211,20 +211,15 @@ __global__ __launch_bounds__(256) void k_cost_merge(const unsigned char* __restr
     if (old == kCostNoInfo || old < v) master[c] = v;                   // updateWithMax
 }
 
-__global__ __launch_bounds__(256) void k_cost_window(const unsigned char* __restrict__ grid, uint32_t sx, CostWindow w,
-                                                     unsigned char* __restrict__ packed)
+// PACK: the window's elements into `packed`; else the reverse
+template <class T, bool PACK>
+__global__ __launch_bounds__(256) void k_cost_window(T* __restrict__ grid, uint32_t sx, CostWindow w, T* __restrict__ packed)
 {
-    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
-    packed[t] = grid[(size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww))];
-}
-
-__global__ __launch_bounds__(256) void k_cost_unpack(const unsigned char* __restrict__ packed, uint32_t sx, CostWindow w,
-                                                     unsigned char* __restrict__ grid)
-{
-    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
-    grid[(size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww))] = packed[t];
+    uint32_t t;
+    size_t c;
+    if (!cost_window_cell(sx, w, t, c)) return;
+    if (PACK) packed[t] = grid[c];
+    else grid[c] = packed[t];
 }
 
 template <class Src>
@@ -267,50 +262,61 @@ hipError_t launch_cost_mark_visual(hipStream_t st, const CostGeom& g, const Cost
     return launch_mark(st, CostVisualSrc{a}, 2ll * a.g.L * a.g.L, g, out);
 }
 
-static unsigned blocks_of(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
-
 hipError_t launch_cost_resolve(hipStream_t st, uint32_t cells, uint32_t* stamps, unsigned char* grid, unsigned long long* acc,
                                unsigned long long* published)
 {
-    hipLaunchKernelGGL(k_cost_resolve, dim3(blocks_of(((uint64_t)cells + 3) / 4)), dim3(256), 0, st, cells, stamps, grid, acc, published);
+    hipLaunchKernelGGL(k_cost_resolve, dim3(cost_blocks(((uint64_t)cells + 3) / 4)), dim3(256), 0, st, cells, stamps, grid, acc, published);
     return hipGetLastError();
 }
 
-hipError_t launch_cost_fill(hipStream_t st, unsigned char* grid, uint32_t cells, unsigned char value)
+// The launchers below take elem = 1 (a byte of the costmap) or 4 (a voxel column) and nothing else; the callers pass constants.
+template <class T>
+static hipError_t fill_of(hipStream_t st, void* grid, uint32_t cells, uint32_t value)
 {
-    hipLaunchKernelGGL(k_cost_fill, dim3(blocks_of(cells)), dim3(256), 0, st, grid, cells, value);
+    hipLaunchKernelGGL(k_cost_fill<T>, dim3(cost_blocks(cells)), dim3(256), 0, st, static_cast<T*>(grid), cells, (T)value);
     return hipGetLastError();
 }
 
-hipError_t launch_cost_roll(hipStream_t st, const unsigned char* src, unsigned char* dst, uint32_t sx, uint32_t sy, long long cell_ox,
-                            long long cell_oy, unsigned char value)
+hipError_t launch_cost_fill(hipStream_t st, void* grid, size_t elem, uint32_t cells, uint32_t value)
 {
-    hipLaunchKernelGGL(k_cost_roll, dim3(blocks_of((uint64_t)sx * sy)), dim3(256), 0, st, src, dst, sx, sy, cell_ox, cell_oy, value);
+    return elem == 4 ? fill_of<uint32_t>(st, grid, cells, value) : fill_of<unsigned char>(st, grid, cells, value);
+}
+
+template <class T>
+static hipError_t roll_of(hipStream_t st, const void* src, void* dst, uint32_t sx, uint32_t sy, long long cell_ox, long long cell_oy, uint32_t value)
+{
+    hipLaunchKernelGGL(k_cost_roll<T>, dim3(cost_blocks((uint64_t)sx * sy)), dim3(256), 0, st, static_cast<const T*>(src), static_cast<T*>(dst), sx, sy,
+                       cell_ox, cell_oy, (T)value);
     return hipGetLastError();
+}
+
+hipError_t launch_cost_roll(hipStream_t st, const void* src, void* dst, size_t elem, uint32_t sx, uint32_t sy, long long cell_ox,
+                            long long cell_oy, uint32_t value)
+{
+    return elem == 4 ? roll_of<uint32_t>(st, src, dst, sx, sy, cell_ox, cell_oy, value) : roll_of<unsigned char>(st, src, dst, sx, sy, cell_ox, cell_oy, value);
 }
 
 hipError_t launch_cost_merge(hipStream_t st, const unsigned char* layer, unsigned char* master, uint32_t sx, CostWindow w, int mode)
 {
-    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
+    const uint64_t t = cost_window_cells(w);
     if (!t) return hipSuccess;
-    hipLaunchKernelGGL(k_cost_merge, dim3(blocks_of(t)), dim3(256), 0, st, layer, master, sx, w, mode);
+    hipLaunchKernelGGL(k_cost_merge, dim3(cost_blocks(t)), dim3(256), 0, st, layer, master, sx, w, mode);
     return hipGetLastError();
 }
 
-hipError_t launch_cost_window(hipStream_t st, const unsigned char* grid, uint32_t sx, CostWindow w, unsigned char* packed)
+template <class T>
+static hipError_t window_of(hipStream_t st, void* grid, uint32_t sx, CostWindow w, void* packed, bool pack)
 {
-    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
-    if (!t) return hipSuccess;
-    hipLaunchKernelGGL(k_cost_window, dim3(blocks_of(t)), dim3(256), 0, st, grid, sx, w, packed);
+    const dim3 blocks(cost_blocks(cost_window_cells(w)));
+    if (pack) hipLaunchKernelGGL((k_cost_window<T, true>), blocks, dim3(256), 0, st, static_cast<T*>(grid), sx, w, static_cast<T*>(packed));
+    else hipLaunchKernelGGL((k_cost_window<T, false>), blocks, dim3(256), 0, st, static_cast<T*>(grid), sx, w, static_cast<T*>(packed));
     return hipGetLastError();
 }
 
-hipError_t launch_cost_unpack(hipStream_t st, const unsigned char* packed, uint32_t sx, CostWindow w, unsigned char* grid)
+hipError_t launch_cost_window(hipStream_t st, void* grid, size_t elem, uint32_t sx, CostWindow w, void* packed, bool pack)
 {
-    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
-    if (!t) return hipSuccess;
-    hipLaunchKernelGGL(k_cost_unpack, dim3(blocks_of(t)), dim3(256), 0, st, packed, sx, w, grid);
-    return hipGetLastError();
+    if (!cost_window_cells(w)) return hipSuccess;
+    return elem == 4 ? window_of<uint32_t>(st, grid, sx, w, packed, pack) : window_of<unsigned char>(st, grid, sx, w, packed, pack);
 }
 
 } // namespace gem

@@ -2,9 +2,9 @@
 //   mark     the updateBounds bodies of PointMapLayer (layers/src/pointMap_layer.cpp:55-81) and ElevationMapLayer
 //            (layers/src/elevationMap_layer.cpp:58-81): every input's costmap cell in double, its verdict carried by a stamp
 //   resolve  the stamps into the byte grid (FREE_SPACE / LETHAL_OBSTACLE), the stamps cleared, the touched bounds published
-//   roll     Costmap2D::updateOrigin through a second byte grid
-//   merge    updateWithOverwrite / updateWithMax over a window;  window / unpack: a window's bytes, packed, for the read-back and
-//            the write
+//   fill / roll / window   element-wise over the bytes or the voxel columns: a reset, Costmap2D::updateOrigin through a second grid,
+//            a window packed for the read-back and unpacked for the write
+//   merge    updateWithOverwrite / updateWithMax over a window
 #pragma once
 
 #include "gem_local.hpp"
@@ -105,13 +105,17 @@ hipError_t launch_cost_mark_history(hipStream_t st, const CostGeom& g, const Cos
 // stamps -> grid; acc -> published[4] (the words as they are), acc reset to all-ones
 hipError_t launch_cost_resolve(hipStream_t st, uint32_t cells, uint32_t* stamps, unsigned char* grid, unsigned long long* acc,
                                unsigned long long* published);
-hipError_t launch_cost_fill(hipStream_t st, unsigned char* grid, uint32_t cells, unsigned char value);
-// dst(x, y) = src(x + cell_ox, y + cell_oy) where that lies in the map, `value` elsewhere
-hipError_t launch_cost_roll(hipStream_t st, const unsigned char* src, unsigned char* dst, uint32_t sx, uint32_t sy, long long cell_ox,
-                            long long cell_oy, unsigned char value);
 struct CostWindow { int min_i, min_j, max_i, max_j; };
+inline uint64_t cost_window_cells(CostWindow w) { return (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j); }
+inline unsigned cost_blocks(uint64_t threads) { return (unsigned)((threads + 255) / 256); }        // workgroups of 256 threads
 hipError_t launch_cost_merge(hipStream_t st, const unsigned char* layer, unsigned char* master, uint32_t sx, CostWindow w, int mode);
-hipError_t launch_cost_window(hipStream_t st, const unsigned char* grid, uint32_t sx, CostWindow w, unsigned char* packed);
-hipError_t launch_cost_unpack(hipStream_t st, const unsigned char* packed, uint32_t sx, CostWindow w, unsigned char* grid);
+// The element-wise kernels of a grid of `elem`-byte elements: 1, the costmap's bytes, or 4, its voxel columns (gem_voxlayer.hpp).
+//   fill    every element `value`
+//   roll    dst(x, y) = src(x + cell_ox, y + cell_oy) where that lies in the map, `value` elsewhere
+//   window  pack: the window's elements into `packed`, row after row; else the reverse.  An empty window launches nothing.
+hipError_t launch_cost_fill(hipStream_t st, void* grid, size_t elem, uint32_t cells, uint32_t value);
+hipError_t launch_cost_roll(hipStream_t st, const void* src, void* dst, size_t elem, uint32_t sx, uint32_t sy, long long cell_ox,
+                            long long cell_oy, uint32_t value);
+hipError_t launch_cost_window(hipStream_t st, void* grid, size_t elem, uint32_t sx, CostWindow w, void* packed, bool pack);
 
 } // namespace gem

@@ -26,9 +26,11 @@
 // (or none) to a list of n words and the same walk takes a group per record.  Measured (tools/bench_obstacle.py, profiles/
 // obstacle_c2.txt) it is the faster one on every workload tried -- the end-cell form halves the walk but pays three launches of
 // compaction and an end bitmap whose rim words every workgroup hits -- so it is the DEFAULT, and the end-cell form is the second path.
+// The reduction of the bounds, their publication and the choice of the walk's group width, line arithmetic and grid are
+// gem_cost_pass.hpp's, shared with the mark kernels and VoxelLayer.
 // Integer and double arithmetic only (division and square root IEEE); only vector stores and atomics write memory.
 #include "gem_compact.hpp"
-#include "gem_obstacle.hpp"
+#include "gem_cost_pass.hpp"
 
 namespace gem {
 
@@ -104,23 +106,12 @@ __global__ __launch_bounds__(kCostThreads) void k_obs_pass(CostGeom g, ObsParams
         }
     }
 
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo_x = fmin(lo_x, __shfl_xor(lo_x, off)); hi_x = fmax(hi_x, __shfl_xor(hi_x, off));
-        lo_y = fmin(lo_y, __shfl_xor(lo_y, off)); hi_y = fmax(hi_y, __shfl_xor(hi_y, off));
-    }
-    if (lane_id() == 0 && lo_x <= hi_x) {                               // the wave touched a point
-        atomicMin(&s_acc[0], cost_key(lo_x)); atomicMin(&s_acc[1], cost_key(lo_y));
-        atomicMin(&s_acc[2], ~cost_key(hi_x)); atomicMin(&s_acc[3], ~cost_key(hi_y));
-    }
-    __syncthreads();
+    cost_bounds_out(lo_x, lo_y, hi_x, hi_y, s_acc, s.acc);
     if (LDS)
         for (uint32_t w = threadIdx.x; w < 2u * words; w += kCostThreads) {
             const uint32_t b = s_bits[w];
             if (b) __hip_atomic_fetch_or((w < words ? s.end_bits + w : s.mark_bits + (w - words)), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    if (threadIdx.x < 4 && s_acc[threadIdx.x] != ~0ull)
-        __hip_atomic_fetch_min(s.acc + threadIdx.x, s_acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the ray from (x0, y0) to `cell` by the G lanes of a group: lane l stores the cells l, l + G, ... of 0 .. end
@@ -176,10 +167,7 @@ struct ObsEndSrc : CompactSrc {
 __global__ __launch_bounds__(256) void k_obs_apply(uint32_t cells, uint32_t* __restrict__ mark_bits, unsigned char* __restrict__ grid,
                                                    unsigned long long* __restrict__ acc, unsigned long long* __restrict__ published)
 {
-    if (blockIdx.x == 0 && threadIdx.x < 4) {
-        published[threadIdx.x] = acc[threadIdx.x];
-        acc[threadIdx.x] = ~0ull;
-    }
+    if (blockIdx.x == 0) cost_publish(acc, published);
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     if (w >= (cells + 31u) / 32u) return;
     uint32_t b = mark_bits[w];
@@ -190,14 +178,6 @@ __global__ __launch_bounds__(256) void k_obs_apply(uint32_t cells, uint32_t* __r
         b &= b - 1u;
         if (c < cells) grid[c] = kCostLethal;
     }
-}
-
-int obs_group_width(const CostGeom& g, uint32_t cell_range)
-{
-    const uint32_t side = g.sx > g.sy ? g.sx : g.sy, longest = cell_range < side ? cell_range : side;
-    int w = 8;
-    while (w < 64 && (uint32_t)w < (longest + 1u) / 2u) w *= 2;
-    return w;
 }
 
 hipError_t launch_obs_pass(hipStream_t st, const CostGeom& g, const ObsParams& p, const ObsScratch& s, bool direct)
@@ -218,32 +198,20 @@ hipError_t launch_obs_pass(hipStream_t st, const CostGeom& g, const ObsParams& p
     return hipGetLastError();
 }
 
-template <int G>
-static hipError_t launch_walk(hipStream_t st, const CostGeom& g, const ObsParams& p, const uint32_t* rays, const uint32_t* total, uint32_t bound,
-                              unsigned char* grid)
-{
-    constexpr uint32_t kGroups = kObsWalkThreads / G;
-    uint32_t nb = (bound + kGroups - 1) / kGroups;
-    if (nb > 8192u) nb = 8192u;                                         // the groups stride over the rest
-    if (nb == 0u) return hipSuccess;
-    if (g.sx <= kObsNarrow && g.sy <= kObsNarrow)
-        hipLaunchKernelGGL((k_obs_walk<G, uint32_t>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, (int)p.x0, (int)p.y0, p.cell_range, rays, total, bound, grid);
-    else
-        hipLaunchKernelGGL((k_obs_walk<G, unsigned long long>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, (int)p.x0, (int)p.y0, p.cell_range, rays, total,
-                           bound, grid);
-    return hipGetLastError();
-}
-
-static hipError_t launch_walk_by_width(hipStream_t st, const CostGeom& g, const ObsParams& p, const uint32_t* rays, const uint32_t* total, uint32_t bound,
-                                       unsigned char* grid)
-{
-    switch (obs_group_width(g, p.cell_range)) {
-    case 8: return launch_walk<8>(st, g, p, rays, total, bound, grid);
-    case 16: return launch_walk<16>(st, g, p, rays, total, bound, grid);
-    case 32: return launch_walk<32>(st, g, p, rays, total, bound, grid);
-    default: return launch_walk<64>(st, g, p, rays, total, bound, grid);
+// k_obs_walk over rays[0 .. bound) for launch_walk_groups
+struct ObsWalk {
+    hipStream_t st;
+    const CostGeom& g;
+    const ObsParams& p;
+    const uint32_t *rays, *total;
+    uint32_t bound;
+    unsigned char* grid;
+    template <int G, class Wide>
+    void launch(uint32_t nb) const
+    {
+        hipLaunchKernelGGL((k_obs_walk<G, Wide>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, (int)p.x0, (int)p.y0, p.cell_range, rays, total, bound, grid);
     }
-}
+};
 
 hipError_t launch_obs_walk_cells(hipStream_t st, const CostGeom& g, const ObsParams& p, const ObsScratch& s, unsigned char* grid)
 {
@@ -252,18 +220,18 @@ hipError_t launch_obs_walk_cells(hipStream_t st, const CostGeom& g, const ObsPar
     src.bits = s.end_bits; src.rays = s.rays; src.cells = cells; src.cap = bound;
     const hipError_t e = compact(st, src, (long long)cells, s.block_cnt, s.total);
     if (e != hipSuccess) return e;
-    return launch_walk_by_width(st, g, p, s.rays, s.total, bound, grid);
+    return launch_walk_groups(g, p.cell_range, bound, ObsWalk{st, g, p, s.rays, s.total, bound, grid});
 }
 
 hipError_t launch_obs_walk_records(hipStream_t st, const CostGeom& g, const ObsParams& p, const ObsScratch& s, unsigned char* grid)
 {
-    return launch_walk_by_width(st, g, p, s.rays, nullptr, p.n, grid);
+    return launch_walk_groups(g, p.cell_range, p.n, ObsWalk{st, g, p, s.rays, nullptr, p.n, grid});
 }
 
 hipError_t launch_obs_apply(hipStream_t st, uint32_t cells, uint32_t* mark_bits, unsigned char* grid, unsigned long long* acc,
                             unsigned long long* published)
 {
-    hipLaunchKernelGGL(k_obs_apply, dim3((obs_words(cells) + 255u) / 256u), dim3(256), 0, st, cells, mark_bits, grid, acc, published);
+    hipLaunchKernelGGL(k_obs_apply, dim3(cost_blocks(obs_words(cells))), dim3(256), 0, st, cells, mark_bits, grid, acc, published);
     return hipGetLastError();
 }
 

@@ -108,9 +108,6 @@ struct ObsScratch {
 
 inline uint32_t obs_words(uint32_t cells) { return (cells + 31u) / 32u; }
 
-// the lane-group width of the walk: a power of two in 8 .. 64 near half the longest ray's cell count (a ray is a pass or two)
-int obs_group_width(const CostGeom& g, uint32_t cell_range);
-
 // the pass over one observation's cloud; direct: every record's end cell goes to s.rays[record] instead of the end bitmap
 hipError_t launch_obs_pass(hipStream_t st, const CostGeom& g, const ObsParams& p, const ObsScratch& s, bool direct);
 // end-cell form: the set bits of s.end_bits compacted into s.rays (the bits cleared), then one walk per ray

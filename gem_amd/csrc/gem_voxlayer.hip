@@ -21,29 +21,13 @@
 //        new-marks word and the touched byte zeroed, the bounds keys published and reset as k_cost_resolve does.
 // With mark_threshold above 0 only the accepted records of a cell that ended LETHAL touch the bounds, which is known behind the apply:
 // k_vox_mark_bounds then reads the marking clouds once more (only when the caller asked for bounds) and k_vox_publish ends the call.
+// The reduction of the bounds, their publication and the walk's dispatch are gem_cost_pass.hpp's; the columns are filled,
+// rolled and read through the element-wise kernels of gem_costmap.hip (launch_cost_fill / _roll / _window with 4-byte elements).
 // Integer and double arithmetic only (division and square root IEEE); only vector stores and atomics write memory.
+#include "gem_cost_pass.hpp"
 #include "gem_voxlayer.hpp"
-#include "gem_wave.hpp"
 
 namespace gem {
-
-// the wave's bounds into the workgroup's four keys, the workgroup's into the call's
-__device__ __forceinline__ void vox_bounds_out(double lo_x, double lo_y, double hi_x, double hi_y, unsigned long long* s_acc,
-                                               unsigned long long* acc)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        lo_x = fmin(lo_x, __shfl_xor(lo_x, off)); hi_x = fmax(hi_x, __shfl_xor(hi_x, off));
-        lo_y = fmin(lo_y, __shfl_xor(lo_y, off)); hi_y = fmax(hi_y, __shfl_xor(hi_y, off));
-    }
-    if (lane_id() == 0 && lo_x <= hi_x) {                               // the wave touched a point
-        atomicMin(&s_acc[0], cost_key(lo_x)); atomicMin(&s_acc[1], cost_key(lo_y));
-        atomicMin(&s_acc[2], ~cost_key(hi_x)); atomicMin(&s_acc[3], ~cost_key(hi_y));
-    }
-    __syncthreads();
-    if (threadIdx.x < 4 && s_acc[threadIdx.x] != ~0ull)
-        __hip_atomic_fetch_min(acc + threadIdx.x, s_acc[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // BOUNDS_ONLY: the second reading of a marking cloud behind the apply (mark_threshold above 0)
 template <bool BOUNDS_ONLY>
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(kCostThreads) void k_vox_pass(CostGeom g, VoxGeom v
             }
         }
     }
-    vox_bounds_out(lo_x, lo_y, hi_x, hi_y, s_acc, s.acc);
+    cost_bounds_out(lo_x, lo_y, hi_x, hi_y, s_acc, s.acc);
 }
 
 // a group of G lanes takes a ray of rays[0 .. n): lane l clears the voxels l, l + G, ... of 0 .. end and touches their cells
@@ -136,10 +120,7 @@ __global__ __launch_bounds__(256) void k_vox_apply(uint32_t cells, VoxGeom v, ui
                                                    unsigned char* __restrict__ touched, unsigned char* __restrict__ grid, int publish,
                                                    unsigned long long* __restrict__ acc, unsigned long long* __restrict__ published)
 {
-    if (publish && blockIdx.x == 0 && threadIdx.x < 4) {
-        published[threadIdx.x] = acc[threadIdx.x];
-        acc[threadIdx.x] = ~0ull;
-    }
+    if (publish && blockIdx.x == 0) cost_publish(acc, published);
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;
     if (c >= cells) return;
     const uint32_t nm = marks[c];
@@ -158,40 +139,8 @@ __global__ __launch_bounds__(256) void k_vox_apply(uint32_t cells, VoxGeom v, ui
 
 __global__ __launch_bounds__(64) void k_vox_publish(unsigned long long* __restrict__ acc, unsigned long long* __restrict__ published)
 {
-    if (threadIdx.x < 4) {
-        published[threadIdx.x] = acc[threadIdx.x];
-        acc[threadIdx.x] = ~0ull;
-    }
+    cost_publish(acc, published);
 }
-
-__global__ __launch_bounds__(256) void k_vox_fill(uint32_t* __restrict__ columns, uint32_t cells)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c < cells) columns[c] = kVoxUnknown;
-}
-
-__global__ __launch_bounds__(256) void k_vox_roll(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, uint32_t sx, uint32_t sy,
-                                                  long long cell_ox, long long cell_oy)
-{
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= sx * sy) return;
-    const long long x = (long long)(c % sx) + cell_ox, y = (long long)(c / sx) + cell_oy;
-    const bool in = x >= 0 && x < (long long)sx && y >= 0 && y < (long long)sy;
-    dst[c] = in ? src[(size_t)y * sx + (size_t)x] : kVoxUnknown;
-}
-
-// PACK: the window's columns into `packed`; else the reverse
-template <bool PACK>
-__global__ __launch_bounds__(256) void k_vox_window(uint32_t* __restrict__ columns, uint32_t sx, CostWindow w, uint32_t* __restrict__ packed)
-{
-    const uint32_t ww = (uint32_t)(w.max_i - w.min_i), t = blockIdx.x * 256u + threadIdx.x;
-    if (t >= ww * (uint32_t)(w.max_j - w.min_j)) return;
-    const size_t c = (size_t)(w.min_j + (int)(t / ww)) * sx + (size_t)(w.min_i + (int)(t % ww));
-    if (PACK) packed[t] = columns[c];
-    else columns[c] = packed[t];
-}
-
-static unsigned vox_blocks(uint64_t threads) { return (unsigned)((threads + 255) / 256); }
 
 hipError_t launch_vox_pass(hipStream_t st, const CostGeom& g, const VoxGeom& v, const VoxParams& p, const VoxScratch& s)
 {
@@ -211,37 +160,31 @@ hipError_t launch_vox_mark_bounds(hipStream_t st, const CostGeom& g, const VoxGe
     return hipGetLastError();
 }
 
-template <int G>
-static hipError_t launch_walk(hipStream_t st, const CostGeom& g, const VoxGeom& v, const VoxParams& p, const VoxScratch& s)
-{
-    constexpr uint32_t kGroups = kObsWalkThreads / G;
-    uint32_t nb = (p.o.n + kGroups - 1) / kGroups;
-    if (nb > 8192u) nb = 8192u;                                         // the groups stride over the rest
-    if (nb == 0u) return hipSuccess;
-    const int x0 = (int)p.fx0, y0 = (int)p.fy0, z0 = (int)p.fz0;
-    if (g.sx <= kObsNarrow && g.sy <= kObsNarrow)
-        hipLaunchKernelGGL((k_vox_walk<G, uint32_t>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, v.sz, x0, y0, z0, s.rays, p.o.n, s.columns, s.touched);
-    else
-        hipLaunchKernelGGL((k_vox_walk<G, unsigned long long>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, v.sz, x0, y0, z0, s.rays, p.o.n, s.columns,
-                           s.touched);
-    return hipGetLastError();
-}
+// k_vox_walk over the rays of an observation for launch_walk_groups
+struct VoxWalk {
+    hipStream_t st;
+    const CostGeom& g;
+    const VoxGeom& v;
+    const VoxParams& p;
+    const VoxScratch& s;
+    template <int G, class Wide>
+    void launch(uint32_t nb) const
+    {
+        hipLaunchKernelGGL((k_vox_walk<G, Wide>), dim3(nb), dim3(kObsWalkThreads), 0, st, g, v.sz, (int)p.fx0, (int)p.fy0, (int)p.fz0, s.rays, p.o.n,
+                           s.columns, s.touched);
+    }
+};
 
 hipError_t launch_vox_walk(hipStream_t st, const CostGeom& g, const VoxGeom& v, const VoxParams& p, const VoxScratch& s)
 {
-    switch (obs_group_width(g, p.o.cell_range)) {                       // the dominant axis is x or y for every ray longer than 16 voxels
-    case 8: return launch_walk<8>(st, g, v, p, s);
-    case 16: return launch_walk<16>(st, g, v, p, s);
-    case 32: return launch_walk<32>(st, g, v, p, s);
-    default: return launch_walk<64>(st, g, v, p, s);
-    }
+    return launch_walk_groups(g, p.o.cell_range, p.o.n, VoxWalk{st, g, v, p, s});   // the dominant axis is x or y for every ray longer than 16 voxels
 }
 
 hipError_t launch_vox_apply(hipStream_t st, const CostGeom& g, const VoxGeom& v, const VoxScratch& s, unsigned char* grid, bool publish,
                             unsigned long long* published)
 {
     const uint32_t cells = g.sx * g.sy;
-    hipLaunchKernelGGL(k_vox_apply, dim3(vox_blocks(cells)), dim3(256), 0, st, cells, v, s.columns, s.marks, s.touched, grid, publish ? 1 : 0, s.acc,
+    hipLaunchKernelGGL(k_vox_apply, dim3(cost_blocks(cells)), dim3(256), 0, st, cells, v, s.columns, s.marks, s.touched, grid, publish ? 1 : 0, s.acc,
                        published);
     return hipGetLastError();
 }
@@ -249,34 +192,6 @@ hipError_t launch_vox_apply(hipStream_t st, const CostGeom& g, const VoxGeom& v,
 hipError_t launch_vox_publish(hipStream_t st, unsigned long long* acc, unsigned long long* published)
 {
     hipLaunchKernelGGL(k_vox_publish, dim3(1), dim3(64), 0, st, acc, published);
-    return hipGetLastError();
-}
-
-hipError_t launch_vox_fill(hipStream_t st, uint32_t* columns, uint32_t cells)
-{
-    hipLaunchKernelGGL(k_vox_fill, dim3(vox_blocks(cells)), dim3(256), 0, st, columns, cells);
-    return hipGetLastError();
-}
-
-hipError_t launch_vox_roll(hipStream_t st, const uint32_t* src, uint32_t* dst, uint32_t sx, uint32_t sy, long long cell_ox, long long cell_oy)
-{
-    hipLaunchKernelGGL(k_vox_roll, dim3(vox_blocks((uint64_t)sx * sy)), dim3(256), 0, st, src, dst, sx, sy, cell_ox, cell_oy);
-    return hipGetLastError();
-}
-
-hipError_t launch_vox_window(hipStream_t st, const uint32_t* columns, uint32_t sx, CostWindow w, uint32_t* packed)
-{
-    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
-    if (!t) return hipSuccess;
-    hipLaunchKernelGGL((k_vox_window<true>), dim3(vox_blocks(t)), dim3(256), 0, st, const_cast<uint32_t*>(columns), sx, w, packed);
-    return hipGetLastError();
-}
-
-hipError_t launch_vox_unpack(hipStream_t st, const uint32_t* packed, uint32_t sx, CostWindow w, uint32_t* columns)
-{
-    const uint64_t t = (uint64_t)(w.max_i - w.min_i) * (uint64_t)(w.max_j - w.min_j);
-    if (!t) return hipSuccess;
-    hipLaunchKernelGGL((k_vox_window<false>), dim3(vox_blocks(t)), dim3(256), 0, st, columns, sx, w, const_cast<uint32_t*>(packed));
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 //           none) per clearing record, the touched bounds
 //   walk    one group of lanes per ray: both bits of the voxels 0 .. end of the closed-form 3-D line cleared, their cells touched
 //   apply   behind every walk: the byte rule per cell from the cleared column, the touched byte and the new marks; the scratch zeroed
+// The columns themselves are reset, rolled and windowed by gem_costmap.hpp's element-wise launchers.
 #pragma once
 
 #include "gem_obstacle.hpp"
@@ -188,11 +189,5 @@ hipError_t launch_vox_apply(hipStream_t st, const CostGeom& g, const VoxGeom& v,
 hipError_t launch_vox_mark_bounds(hipStream_t st, const CostGeom& g, const VoxGeom& v, const VoxParams& p, const VoxScratch& s);
 // acc -> published[4], acc reset to all-ones
 hipError_t launch_vox_publish(hipStream_t st, unsigned long long* acc, unsigned long long* published);
-// every column unknown; dst(x, y) = src(x + cell_ox, y + cell_oy) where that lies in the map, unknown elsewhere; a window's columns
-// packed and unpacked as launch_cost_window / _unpack do for the bytes
-hipError_t launch_vox_fill(hipStream_t st, uint32_t* columns, uint32_t cells);
-hipError_t launch_vox_roll(hipStream_t st, const uint32_t* src, uint32_t* dst, uint32_t sx, uint32_t sy, long long cell_ox, long long cell_oy);
-hipError_t launch_vox_window(hipStream_t st, const uint32_t* columns, uint32_t sx, CostWindow w, uint32_t* packed);
-hipError_t launch_vox_unpack(hipStream_t st, const uint32_t* packed, uint32_t sx, CostWindow w, uint32_t* columns);
 
 } // namespace gem
