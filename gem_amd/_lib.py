@@ -387,6 +387,21 @@ FRONTIER_SIGNATURES = {
     "gem_costmap_frontiers_read": (c_int, [c_void_p, c_int, c_void_p, c_longlong, c_void_p]),
     "gem_costmap_navplan_goal": (c_int, [c_void_p, c_int, POINTER(c_double), c_void_p, c_longlong, POINTER(NavplanStatus)]),
 }
+# include/gem_hip_navpath.h (paths on the last plan's potential, grid or gradient, a batch of goals; gem_hip.h includes it)
+NAVPATH_GRID, NAVPATH_GRADIENT = 0, 1
+NAVPATH_FOUND, NAVPATH_OFF_MAP, NAVPATH_UNREACHED, NAVPATH_HIGH, NAVPATH_ZERO_GRADIENT, NAVPATH_CAP = 1, 2, 3, 4, 5, 6
+
+
+class NavpathResult(C.Structure):
+    _fields_ = [("status", c_int), ("n_points", c_int), ("goal_cell", c_int * 2), ("goal_potential", c_int), ("reserved", c_int * 3)]
+
+
+_NAVPATHS_ARGS = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+NAVPATH_SIGNATURES = {
+    "gem_navpath_host": (c_int, [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), c_int, c_int, c_void_p, POINTER(NavpathResult)]),
+    "gem_costmap_navplan_paths": (c_int, _NAVPATHS_ARGS),
+    "gem_costmap_navplan_paths_device": (c_int, _NAVPATHS_ARGS),
+}
 # include/gem_hip_obstacle.h (ObstacleLayer on the costmap: ray-traced clearing and marking; gem_hip.h includes it)
 OBS_MARKING, OBS_CLEARING, OBS_MAX = 1, 2, 8
 
@@ -446,7 +461,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **MAPGRID_TILED_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **NAVPATH_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

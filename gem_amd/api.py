@@ -1489,6 +1489,42 @@ class Costmap:
                          geo["origin_y"] + ((cells // self.size_x).astype(np.float64) + 0.5) * geo["resolution"]], axis=1).reshape(-1, 2)
         return path, _nav_status(st)
 
+    # -- paths on the last plan's potential (gem_hip_navpath.h) ------------------------------------------------------------------------
+    def nav_paths(self, goals, form: int = _lib.NAVPATH_GRADIENT, max_points: int = 4096, points: bool = True, raw: bool = False):
+        """Paths from the last plan's start to up to 1024 goals (world points [n, 2]) on the last plan's potential, in one launch, one wave
+        per goal (gem_costmap_navplan_paths): form NAVPATH_GRADIENT, global_planner's default path of sub-cell points half a cell apart,
+        or NAVPATH_GRID, the grid path of nav_plan_to.  The potential, the last path and status and the frontier search stay as they
+        are.  The call waits.  Returns (paths, results): paths a list of float64 [n_i, 2] world points from start to goal (cell
+        coordinates p become origin + (p + 0.5) * resolution, in double; None with points=False), results a list of dicts (status,
+        n_points, goal_cell, goal_potential).  raw=True: (float32 [n, max_points, 2] in walk order, goal first, cell coordinates,
+        rows beyond n_points untouched zeros; int32 [n, 8] result words)."""
+        g = np.ascontiguousarray(goals, np.float64).reshape(-1, 2)
+        n = int(g.shape[0])
+        pts = np.zeros((n, int(max_points), 2), np.float32) if points and n and 0 < int(max_points) <= (1 << 24) // max(n, 1) else None
+        res = np.zeros((max(n, 1), 8), np.int32)
+        self._call("gem_costmap_navplan_paths", g.ctypes.data_as(C.c_void_p) if n else None, n, int(form), int(max_points),
+                   pts.ctypes.data_as(C.c_void_p) if pts is not None else None, res.ctypes.data_as(C.c_void_p))
+        if raw:
+            return pts, res
+        return (_nav_world_paths(pts, res, self.geometry()) if pts is not None else None), [_navpath_result(r) for r in res]
+
+    def nav_paths_device(self, goals, form: int = _lib.NAVPATH_GRADIENT, max_points: int = 4096, device=None):
+        """nav_paths with its outputs left on the device (gem_costmap_navplan_paths_device): the goal cells are handed over and the walk
+        is enqueued on the handle's stream; the call does not wait for it.  Returns (float32 [n, max_points, 2] device tensor in walk
+        order, goal first, cell coordinates; int32 [n, 8] device tensor of result words)."""
+        import torch
+        g = np.ascontiguousarray(goals, np.float64).reshape(-1, 2)
+        n = int(g.shape[0])
+        if not (1 <= n <= 1024 and 2 <= int(max_points) <= (1 << 24) // n):
+            raise ValueError("nav_paths_device: n_goals outside 1 .. 1024, max_points below 2, or n_goals * max_points above 2^24")
+        dev = torch.device("cuda") if device is None else device
+        pts = torch.empty((n, int(max_points), 2), dtype=torch.float32, device=dev)     # (rows beyond a goal's n_points are not written)
+        res = torch.empty((n, 8), dtype=torch.int32, device=dev)
+        self.map._hold(pts, res)
+        self._call("gem_costmap_navplan_paths_device", g.ctypes.data_as(C.c_void_p), n, int(form), int(max_points), C.c_void_p(pts.data_ptr()),
+                   C.c_void_p(res.data_ptr()))
+        return pts, res
+
     # -- the best trajectory (gem_hip_critics.h) ----------------------------------------------------------------------------------------
     def prepare_map_grid_front(self, plan) -> None:
         """The FRONT grid, which DWA's goal_front critic reads: the goal grid of `plan` (the caller's front plan, its last point already
@@ -1724,6 +1760,38 @@ def nav_plan_host(grid, start_cell, goal_cell, weights=None, outline: bool = Tru
                                     s, e, pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), int(cells.size), C.byref(st)) != _lib.GEM_OK:
         raise ValueError("nav_plan_host: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1")
     return pot, cells[:st.n_path].copy(), _nav_status(st)
+
+
+def _navpath_result(r) -> dict:
+    return {"status": int(r[0]), "n_points": int(r[1]), "goal_cell": (int(r[2]), int(r[3])), "goal_potential": int(r[4])}
+
+
+def _nav_world_paths(pts, res, geo) -> list:
+    """the walks' points reversed (start first) as world points: origin + ((double)p + 0.5) * resolution"""
+    o, r = np.array([geo["origin_x"], geo["origin_y"]], np.float64), float(geo["resolution"])
+    return [o + (pts[i, :int(res[i, 1])][::-1].astype(np.float64) + 0.5) * r for i in range(pts.shape[0])]
+
+
+def nav_paths_host(pot, start_cell, goal_cells, form: int = _lib.NAVPATH_GRADIENT, max_points: int = 4096, points: bool = True):
+    """The host twin of Costmap.nav_paths, goal by goal (gem_navpath_host; no device): pot = int32 [size_y, size_x], start_cell (x, y),
+    goal_cells [n, 2] of (x, y), on the map or not.  Returns (float32 [n, max_points, 2] in walk order, goal first, cell coordinates,
+    or None with points=False; int32 [n, 8] result words: status, n_points, goal_cell, goal_potential, three zeros)."""
+    p = np.ascontiguousarray(pot, np.int32)
+    if p.ndim != 2 or not p.size:
+        raise ValueError("pot must be int32 [size_y, size_x]")
+    goals = np.ascontiguousarray(goal_cells, np.int32).reshape(-1, 2)
+    n = int(goals.shape[0])
+    sy, sx = p.shape
+    s = (C.c_int * 2)(*[int(v) for v in start_cell])
+    pts = np.zeros((n, int(max_points), 2), np.float32) if points and int(max_points) > 0 else None
+    res = np.zeros((n, 8), np.int32)
+    fn = _lib.load().gem_navpath_host
+    for i in range(n):
+        e = (C.c_int * 2)(int(goals[i, 0]), int(goals[i, 1]))
+        if fn(p.ctypes.data_as(C.c_void_p), sx, sy, s, e, int(form), int(max_points), pts[i].ctypes.data_as(C.c_void_p) if pts is not None else None,
+              C.cast(res[i].ctypes.data_as(C.c_void_p), C.POINTER(_lib.NavpathResult))) != _lib.GEM_OK:
+            raise ValueError("nav_paths_host: a size of 2^24 or more, max_points outside 2 .. 2^20, or an unknown form")
+    return pts, res
 
 
 def _frontier(f, geo) -> dict:

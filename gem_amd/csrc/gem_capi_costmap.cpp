@@ -90,7 +90,7 @@ int update_origin(gem_handle* h, CostMap& m, double new_ox, double new_oy, const
 void free_map(CostMap& m)
 {
     for (Arena* a : {&m.grid[0], &m.grid[1], &m.stamps, &m.infl_table, &m.mg_dist[0], &m.mg_dist[1], &m.mg_dist[2], &m.mg_status, &m.mg_act,
-                     &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status,
+                     &m.nav_pot, &m.nav_act, &m.nav_path, &m.nav_status, &m.np_goal, &m.np_res, &m.np_pts,
                      &m.fr_label, &m.fr_index, &m.fr_act, &m.fr_rec, &m.fr_out, &m.fr_words, &m.vox[0], &m.vox[1]}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr; a->cap = 0;

@@ -329,6 +329,8 @@ struct gem_handle {
             unsigned long long nav_gen = 0;             // the generation the last plan ran in (0: never)
             int nav_n_path = 0;                         // its path's cells
             gem_navplan_status nav_last{};              // ... and its status (gem_costmap_navplan_status)
+            // gem_costmap_navplan_paths (gem_capi_navpath.cpp): the goals' cells, two ints per goal | the waiting form's results and points
+            Arena np_goal, np_res, np_pts;
             // gem_costmap_frontiers (gem_capi_frontier.cpp): the labels, an int per cell | each root's list index at the root's cell,
             // an int per cell, never cleared | the tiles' two active maps | the records, field by field, one per possible component |
             // the kept list (gem_frontier) | the device words
@@ -362,6 +364,7 @@ struct gem_handle {
         Arena nav_w;
         void* nav_pin = nullptr;
         std::vector<int> nav_cells;
+        std::vector<int> np_cells;      // gem_costmap_navplan_paths: the goals' cells on the host
         // gem_costmap_frontiers: the compaction's block counts and total | pinned host memory its kernels answer through (the call
         // waits, so one block serves every costmap)
         Arena fr_blocks;

@@ -843,6 +843,14 @@ struct NavPlan {
     }
 };
 
+// Paths on the last plan's potential for a batch of goals (gem_hip_navpath.h): the grid path, or global_planner's default, the gradient
+// path -- sub-cell points half a cell apart, restated from memory and unverified against the library.  One entry per goal, in order.
+struct NavPaths {
+    std::vector<gem_navpath_result> results;                 // status (GEM_NAVPATH_FOUND ...), n_points, the goal's cell and potential
+    std::vector<std::vector<FootprintPoint>> paths;          // world points from the start to the goal; what was walked, when not found
+    bool found(size_t i) const { return results[i].status == GEM_NAVPATH_FOUND; }
+};
+
 // What Costmap::prepareMapGridTiled / prepareMapGridFrontTiled answer (gem_hip_mapgrid.h): rounds depends on timing, the grids do not.
 struct MapGridTiledStatus {
     bool started = false;                                    // a point of the plan was accepted
@@ -1148,6 +1156,29 @@ public:
             p.path.push_back(FootprintPoint{c.origin_x + (static_cast<double>(cell % static_cast<int>(c.size_x)) + 0.5) * c.resolution,
                                             c.origin_y + (static_cast<double>(cell / static_cast<int>(c.size_x)) + 0.5) * c.resolution});
         return p;
+    }
+    // Paths from the last plan's start to up to 1024 goals on the last plan's potential, in one launch, one wave per goal
+    // (gem_hip_navpath.h); form GEM_NAVPATH_GRADIENT or GEM_NAVPATH_GRID.  The potential, the last path and status and the frontier
+    // search stay as they are.  Waits.  The walks' cell coordinates p are reversed and become origin + (p + 0.5) * resolution, in double.
+    NavPaths navPaths(const std::vector<FootprintPoint>& goals, int form = GEM_NAVPATH_GRADIENT, int maxPoints = 4096)
+    {
+        // the library's limits, before anything is sized by them: 1 .. 1024 goals, 2 .. 2^20 points, at most 2^24 points in all
+        if (goals.empty() || goals.size() > 1024 || maxPoints < 2 || maxPoints > (1 << 20) || goals.size() * static_cast<size_t>(maxPoints) > (size_t(1) << 24))
+            throw Error(GEM_ERR_INVALID, "Costmap::navPaths: goals outside 1 .. 1024, maxPoints outside 2 .. 2^20, or more than 2^24 points in all");
+        NavPaths r;
+        r.results.resize(goals.size());
+        std::vector<float> pts(goals.size() * static_cast<size_t>(maxPoints) * 2);
+        map_.check(gem_costmap_navplan_paths(map_.handle(), id_, &goals[0].x, static_cast<int>(goals.size()), form, maxPoints, pts.data(), r.results.data()),
+                   "gem_costmap_navplan_paths");
+        const gem_costmap_config c = geometry();
+        r.paths.resize(goals.size());
+        for (size_t g = 0; g < goals.size(); ++g) {
+            const float* p = pts.data() + g * static_cast<size_t>(maxPoints) * 2;
+            for (int i = r.results[g].n_points - 1; i >= 0; --i)
+                r.paths[g].push_back(FootprintPoint{c.origin_x + (static_cast<double>(p[2 * i]) + 0.5) * c.resolution,
+                                                    c.origin_y + (static_cast<double>(p[2 * i + 1]) + 0.5) * c.resolution});
+        }
+        return r;
     }
     // Frontier search over the costmap's bytes and the potential of its last plan (gem_hip_frontier.h).  Waits.  readFrontiers() reads
     // the last search's kept frontiers back in ascending root order and, with labels, the label grid (a cell's root, -1 for a cell

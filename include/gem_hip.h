@@ -770,6 +770,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- VoxelLayer: gem_costmap_voxels_*, gem_costmap_voxel_observe / _observe_device, gem_voxlayer_host ------------------------------ */
 #include "gem_hip_voxlayer.h"
 
+/* ---- paths on the last plan's potential, grid or gradient, a batch of goals: gem_navpath_host, gem_costmap_navplan_paths / _device -- */
+#include "gem_hip_navpath.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@
  *     buffers, and the quadratic update jumps from 1.0046 * hf to hf at dc = hf, so it is not even monotone.  No parallel form can be
  *     bit-equal to it.
  *   - the gradient path, A*, default_tolerance, the orientation filter, publishing the potential.
+ *     (The gradient path is a pure function of the potential and is stated on its own, for a batch of goals: gem_hip_navpath.h.)
  *   - the library's early exit at the goal: the potential here is the converged one EVERYWHERE.
  *   - convert_offset_: the library's half-cell shift of start and goal is not modelled; both are world points mapped by the
  *     worldToMap of gem_hip.h (its refusal of non-finite input is turned into GEM_ERR_INVALID here).
