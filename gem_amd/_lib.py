@@ -402,6 +402,12 @@ NAVPATH_SIGNATURES = {
     "gem_costmap_navplan_paths": (c_int, _NAVPATHS_ARGS),
     "gem_costmap_navplan_paths_device": (c_int, _NAVPATHS_ARGS),
 }
+# include/gem_hip_navquad.h (the quadratic potential on the costmap, order-free and exact; gem_hip.h includes it)
+NAVQUAD_MAX_WEIGHT = 462
+NAVQUAD_SIGNATURES = {
+    "gem_navquad_host": NAVPLAN_SIGNATURES["gem_navplan_host"],
+    "gem_costmap_navplan_quadratic": NAVPLAN_SIGNATURES["gem_costmap_navplan"],
+}
 # include/gem_hip_obstacle.h (ObstacleLayer on the costmap: ray-traced clearing and marking; gem_hip.h includes it)
 OBS_MARKING, OBS_CLEARING, OBS_MAX = 1, 2, 8
 
@@ -461,7 +467,7 @@ def load(rebuild_if_stale: bool = True) -> C.CDLL:
         pass
     lib = C.CDLL(str(path))
     for name, (res, args) in {**SIGNATURES, **HISTORY_SIGNATURES, **FOOTPRINT_SIGNATURES, **INFLATE_SIGNATURES, **MAPGRID_SIGNATURES, **MAPGRID_TILED_SIGNATURES, **CRITICS_SIGNATURES,
-                               **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **NAVPATH_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
+                               **TRAJGEN_SIGNATURES, **ROLLOUT_SIGNATURES, **NAVPLAN_SIGNATURES, **FRONTIER_SIGNATURES, **NAVPATH_SIGNATURES, **NAVQUAD_SIGNATURES, **OBSTACLE_SIGNATURES, **VOXLAYER_SIGNATURES, **DEBUG_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

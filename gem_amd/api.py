@@ -1437,6 +1437,24 @@ class Costmap:
                          geo["origin_y"] + ((cells // self.size_x).astype(np.float64) + 0.5) * geo["resolution"]], axis=1).reshape(-1, 2)
         return path, _nav_status(st)
 
+    def nav_plan_quadratic(self, start, goal, weights=None, outline: bool = True):
+        """nav_plan on the QUADRATIC potential of gem_hip_navquad.h (gem_costmap_navplan_quadratic): the two-axis update stated in exact
+        integers, order-free, nowhere above the linear potential; weights at most 462.  The plan takes the linear plan's place: nav_status,
+        read_potential, nav_plan_to, nav_paths and frontiers work on it.  Returns what nav_plan returns."""
+        w = np.ascontiguousarray(nav_weights() if weights is None else weights, np.int32)
+        if w.shape != (256,):
+            raise ValueError("weights must be int32 [256]")
+        s, g = (C.c_double * 2)(*[float(v) for v in start]), (C.c_double * 2)(*[float(v) for v in goal])
+        st = _lib.NavplanStatus()
+        self._call("gem_costmap_navplan_quadratic", s, g, w.ctypes.data_as(C.POINTER(C.c_int)), _lib.NAV_OUTLINE if outline else 0, None, 0, C.byref(st))
+        cells = np.zeros(int(st.n_path), np.int32)
+        if cells.size:
+            self._call("gem_costmap_navplan_read", None, cells.ctypes.data_as(C.c_void_p), int(cells.size))
+        geo = self.geometry()                                           # cell centres, in double, as the C entry computes them
+        path = np.stack([geo["origin_x"] + ((cells % self.size_x).astype(np.float64) + 0.5) * geo["resolution"],
+                         geo["origin_y"] + ((cells // self.size_x).astype(np.float64) + 0.5) * geo["resolution"]], axis=1).reshape(-1, 2)
+        return path, _nav_status(st)
+
     def nav_status(self) -> dict:
         """The status of the costmap's last plan (gem_costmap_navplan_status), whoever made it; nothing is enqueued."""
         st = _lib.NavplanStatus()
@@ -1759,6 +1777,26 @@ def nav_plan_host(grid, start_cell, goal_cell, weights=None, outline: bool = Tru
     if _lib.load().gem_navplan_host(g.ctypes.data_as(C.c_void_p), sx, sy, w.ctypes.data_as(C.POINTER(C.c_int)), _lib.NAV_OUTLINE if outline else 0,
                                     s, e, pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), int(cells.size), C.byref(st)) != _lib.GEM_OK:
         raise ValueError("nav_plan_host: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1")
+    return pot, cells[:st.n_path].copy(), _nav_status(st)
+
+
+def nav_quad_host(grid, start_cell, goal_cell, weights=None, outline: bool = True):
+    """The host twin of Costmap.nav_plan_quadratic (gem_navquad_host; no device): arguments and results of nav_plan_host, weights at
+    most 462."""
+    g = np.ascontiguousarray(grid, np.uint8)
+    if g.ndim != 2 or not g.size:
+        raise ValueError("grid must be uint8 [size_y, size_x]")
+    w = np.ascontiguousarray(nav_weights() if weights is None else weights, np.int32)
+    if w.shape != (256,):
+        raise ValueError("weights must be int32 [256]")
+    sy, sx = g.shape
+    pot = np.zeros((sy, sx), np.int32)
+    cells = np.empty(sx * sy, np.int32)
+    st = _lib.NavplanStatus()
+    s, e = (C.c_int * 2)(*[int(v) for v in start_cell]), (C.c_int * 2)(*[int(v) for v in goal_cell])
+    if _lib.load().gem_navquad_host(g.ctypes.data_as(C.c_void_p), sx, sy, w.ctypes.data_as(C.POINTER(C.c_int)), _lib.NAV_OUTLINE if outline else 0,
+                                    s, e, pot.ctypes.data_as(C.c_void_p), cells.ctypes.data_as(C.c_void_p), int(cells.size), C.byref(st)) != _lib.GEM_OK:
+        raise ValueError("nav_quad_host: a negative weight, one above 462, or size_x * size_y * max(w) not below 2^31 - 1")
     return pot, cells[:st.n_path].copy(), _nav_status(st)
 
 

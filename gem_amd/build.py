@@ -24,11 +24,11 @@ SOURCES = [CSRC / "gem_kernels.hip", CSRC / "gem_frame_lean.hip", CSRC / "gem_fr
            CSRC / "gem_history.hip", CSRC / "gem_capi_history.cpp",
            CSRC / "gem_footprint.hip", CSRC / "gem_capi_footprint.cpp", CSRC / "gem_inflate.hip", CSRC / "gem_capi_inflate.cpp",
            CSRC / "gem_mapgrid.hip", CSRC / "gem_mapgrid_tiled.hip", CSRC / "gem_capi_mapgrid.cpp", CSRC / "gem_critics.hip", CSRC / "gem_capi_critics.cpp",
-           CSRC / "gem_trajgen.hip", CSRC / "gem_capi_trajgen.cpp", CSRC / "gem_navplan.hip", CSRC / "gem_capi_navplan.cpp", CSRC / "gem_navgrad.hip", CSRC / "gem_capi_navpath.cpp",
+           CSRC / "gem_trajgen.hip", CSRC / "gem_capi_trajgen.cpp", CSRC / "gem_navplan.hip", CSRC / "gem_capi_navplan.cpp", CSRC / "gem_navgrad.hip", CSRC / "gem_capi_navpath.cpp", CSRC / "gem_navquad.hip",
            CSRC / "gem_frontier.hip", CSRC / "gem_capi_frontier.cpp", CSRC / "gem_obstacle.hip", CSRC / "gem_capi_obstacle.cpp",
            CSRC / "gem_voxlayer.hip", CSRC / "gem_capi_voxlayer.cpp", CSRC / "gem_rollout.hip", CSRC / "gem_capi_rollout.cpp"]
 HEADERS = [CSRC / "gem_device.hpp", CSRC / "gem_kernels.hpp", CSRC / "gem_frame_lean.hpp", CSRC / "gem_frame_pair.hpp", CSRC / "gem_frame_tile.hpp", CSRC / "gem_frame_sort.hpp", CSRC / "gem_wave.hpp", CSRC / "gem_compact.hpp", CSRC / "gem_transport.hpp", CSRC / "gem_hostcopy.hpp", CSRC / "gem_capi_internal.hpp", CSRC / "gem_plan.hpp", CSRC / "gem_clean.hpp", CSRC / "gem_local.hpp", CSRC / "gem_voxel.hpp", CSRC / "gem_global.hpp", CSRC / "gem_compose.hpp", CSRC / "gem_costmap.hpp", CSRC / "gem_lsd.hpp", CSRC / "gem_octree.hpp", CSRC / "gem_depth.hpp", CSRC / "gem_history.hpp", CSRC / "gem_footprint.hpp", CSRC / "gem_inflate.hpp", CSRC / "gem_mapgrid.hpp", CSRC / "gem_mapgrid_tiled.hpp", CSRC / "gem_score_device.hpp", CSRC / "gem_critics.hpp", CSRC / "gem_trajgen.hpp", CSRC / "gem_sincos.hpp",
-           CSRC / "gem_navplan.hpp", CSRC / "gem_navpath.hpp", CSRC / "gem_navgrad.hpp", ROOT.parent / "include" / "gem_hip_navpath.h", CSRC / "gem_frontier.hpp", CSRC / "gem_costmap_host.hpp", CSRC / "gem_cost_pass.hpp", CSRC / "gem_observe_host.hpp", CSRC / "gem_rounds.hpp", CSRC / "gem_tile_round.hpp", CSRC / "gem_obstacle.hpp", CSRC / "gem_voxlayer.hpp", CSRC / "gem_rollout.hpp", ROOT.parent / "include" / "gem_hip_rollout.h", ROOT.parent / "include" / "gem_hip_voxlayer.h", ROOT.parent / "include" / "gem_hip_frontier.h", ROOT.parent / "include" / "gem_hip_obstacle.h",
+           CSRC / "gem_navplan.hpp", CSRC / "gem_navpath.hpp", CSRC / "gem_navgrad.hpp", CSRC / "gem_navquad.hpp", ROOT.parent / "include" / "gem_hip_navpath.h", ROOT.parent / "include" / "gem_hip_navquad.h", CSRC / "gem_frontier.hpp", CSRC / "gem_costmap_host.hpp", CSRC / "gem_cost_pass.hpp", CSRC / "gem_observe_host.hpp", CSRC / "gem_rounds.hpp", CSRC / "gem_tile_round.hpp", CSRC / "gem_obstacle.hpp", CSRC / "gem_voxlayer.hpp", CSRC / "gem_rollout.hpp", ROOT.parent / "include" / "gem_hip_rollout.h", ROOT.parent / "include" / "gem_hip_voxlayer.h", ROOT.parent / "include" / "gem_hip_frontier.h", ROOT.parent / "include" / "gem_hip_obstacle.h",
            ROOT.parent / "include" / "gem_hip_debug.h", ROOT.parent / "include" / "gem_hip.h", ROOT.parent / "include" / "gem_hip_history.h",
            ROOT.parent / "include" / "gem_hip_footprint.h", ROOT.parent / "include" / "gem_hip_inflate.h", ROOT.parent / "include" / "gem_hip_mapgrid.h", ROOT.parent / "include" / "gem_hip_mapgrid_tiled.h",
            ROOT.parent / "include" / "gem_hip_critics.h", ROOT.parent / "include" / "gem_hip_trajgen.h", ROOT.parent / "include" / "gem_hip_navplan.h"]

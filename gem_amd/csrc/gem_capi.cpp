@@ -971,6 +971,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value)
     else if (k == "nav_chunk")          { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "nav_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->nav_chunk = (int)value; }
     else if (k == "mapgrid_chunk")      { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "mapgrid_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->mapgrid_chunk = (int)value; }
     else if (k == "front_chunk")        { if (value < 0 || value > (1 << 20)) return fail(h, GEM_ERR_INVALID, "front_chunk: 0 (tiles_x + tiles_y) or 1 .. 2^20 rounds"); h->front_chunk = (int)value; }
+    else if (k == "navquad_passes")     { if (value < 0 || value > 64) return fail(h, GEM_ERR_INVALID, "navquad_passes: 0 (the default) or 1 .. 64 passes"); h->navquad_passes = (int)value; }
     else return fail(h, GEM_ERR_INVALID, "gem_debug_set: unknown key");
     return GEM_OK;
 }
@@ -1004,6 +1005,7 @@ int gem_debug_get(gem_handle* h, const char* key, long long* out)
     else if (k == "obstacle_direct") *out = h->obstacle_direct ? 1 : 0;
     else if (k == "nav_chunk") *out = h->nav_chunk;
     else if (k == "front_chunk") *out = h->front_chunk;
+    else if (k == "navquad_passes") *out = h->navquad_passes;
     else if (k == "mapgrid_chunk") *out = h->mapgrid_chunk;
     else if (k == "history_blocks") *out = h->history.enabled ? cost_mark_blocks(h->history.len) : 0;
     else if (k == "history_blocks_culled") { hipSetDevice(h->device); return history_blocks_culled(h, out); }

@@ -393,6 +393,7 @@ struct gem_handle {
         Arena small;                    // device words: workgroups the last gem_costmap_mark_history culled
     } history;
     int  nav_chunk = 0;                 // debug knob "nav_chunk": rounds gem_costmap_navplan enqueues per host round trip (0 = tiles_x + tiles_y)
+    int  navquad_passes = 0;            // debug knob "navquad_passes": in-tile passes a round of gem_costmap_navplan_quadratic allows a tile (0 = kNavQuadPasses)
     int  front_chunk = 0;               // debug knob "front_chunk": label rounds gem_costmap_frontiers enqueues per host round trip (0 = tiles_x + tiles_y)
     int  mapgrid_chunk = 0;             // debug knob "mapgrid_chunk": rounds gem_costmap_mapgrid_prepare_tiled enqueues per host round trip (0 = tiles_x + tiles_y)
     bool obstacle_direct = true;       // debug knob "obstacle_direct": gem_costmap_observe* walks a ray per accepted record (the default: measured faster) or one per distinct end cell

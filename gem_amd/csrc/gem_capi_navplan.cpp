@@ -1,5 +1,7 @@
 // gem_capi_navplan.cpp -- the global-plan entry points of include/gem_hip_navplan.h: the weight table and the host twin (host only),
-// gem_costmap_navplan and its read-back.  The kernels are in gem_navplan.hip, the path routine in gem_navpath.hpp.
+// gem_costmap_navplan and its read-back; and those of include/gem_hip_navquad.h, the quadratic potential: gem_navquad_host and
+// gem_costmap_navplan_quadratic, which share everything here with the linear plan but the potential itself.  The kernels are in
+// gem_navplan.hip and gem_navquad.hip, the path routine in gem_navpath.hpp, the quadratic cell update in gem_navquad.hpp.
 //
 // gem_costmap_navplan maps start and goal with worldToMap on the host (it knows the geometry after rolling), hands the weight table
 // over in pinned host memory and enqueues: init, then CHUNKS of rounds, each chunk closed by k_nav_finish, which answers through the
@@ -9,6 +11,7 @@
 // with the handle's costmaps; all come from ensure() and only grow, so a second identical call allocates nothing.
 #include "gem_costmap_host.hpp"
 #include "gem_navplan.hpp"
+#include "gem_navquad.hpp"
 #include "gem_rounds.hpp"
 
 #include <algorithm>
@@ -117,6 +120,101 @@ int finish_plan(gem_handle* h, CostMap& m, const NavArgs& a, unsigned long long 
     return cap < n ? fail(h, GEM_ERR_INVALID, (std::string(what) + ": the path has more points than out_xy holds").c_str()) : GEM_OK;
 }
 
+// gem_costmap_navplan and gem_costmap_navplan_quadratic behind their preludes: the same checks, arenas, rounds and finish.  The
+// quadratic plan differs in one more check (the weight limit), in its round launcher and in what the kernel makes of the table.
+int plan_on_costmap(gem_handle* h, int id, const char* what, bool quadratic, const double start_xy[2], const double goal_xy[2], const int* w,
+                    int flags, double* out_xy, long long cap, gem_navplan_status* st)
+{
+    const std::string name(what);
+    int rc;
+    CostMap* m;
+    if ((rc = costmap_find(h, id, what, &m))) return rc;
+    if (!start_xy || !goal_xy || !w || !st) return fail(h, GEM_ERR_INVALID, (name + ": a NULL start, goal, weight table or status").c_str());
+    if (flags & ~GEM_NAV_OUTLINE) return fail(h, GEM_ERR_INVALID, (name + ": unknown flag bits").c_str());
+    if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, (name + ": a negative capacity").c_str());
+    for (int k = 0; k < 2; ++k)
+        if (!std::isfinite(start_xy[k]) || !std::isfinite(goal_xy[k])) return fail(h, GEM_ERR_INVALID, (name + ": a coordinate not finite").c_str());
+    const CostGeom g = geom_of(*m);
+    const long long cells = (long long)g.sx * g.sy;
+    if (!weights_ok(w, cells)) return fail(h, GEM_ERR_INVALID, (name + ": a negative weight, or size_x * size_y * max(w) not below 2^31 - 1").c_str());
+    if (quadratic && *std::max_element(w, w + 256) > kNavQuadMaxWeight) return fail(h, GEM_ERR_INVALID, (name + ": a weight above 462").c_str());
+
+    auto& cm = h->costmap;
+    const size_t nt = (size_t)nav_tiles((int)g.sx) * nav_tiles((int)g.sy);
+    if ((rc = ensure(h, m->nav_pot, (size_t)cells * sizeof(int))) || (rc = ensure(h, m->nav_path, (size_t)cells * sizeof(int))) ||
+        (rc = ensure(h, m->nav_act, 2 * nt * sizeof(int))) || (rc = ensure(h, m->nav_status, kNavStatusWords * sizeof(int))) ||
+        (rc = ensure(h, cm.nav_w, 256 * sizeof(int)))) return rc;
+    if (!cm.nav_pin) GEM_HIP(h, hipHostMalloc(&cm.nav_pin, kNavPinBytes, hipHostMallocDefault));
+    NavArgs a = bind_args(h, *m);
+    std::copy(w, w + 256, a.pin);
+
+    empty_status(st);
+    uint32_t cell = 0u;
+    a.start = cost_cell(g, start_xy[0], start_xy[1], cell) ? (int)cell : -1;
+    a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
+    if (a.start >= 0) { st->start_cell[0] = a.start % a.sx; st->start_cell[1] = a.start / a.sx; }
+    if (a.goal >= 0) { st->goal_cell[0] = a.goal % a.sx; st->goal_cell[1] = a.goal / a.sx; }
+    a.outline = (flags & GEM_NAV_OUTLINE) ? 1 : 0;
+    a.passes = h->navquad_passes > 0 ? h->navquad_passes : kNavQuadPasses;
+
+    m->nav_gen = 0;                                                     // (a failure below leaves no plan to read)
+    m->nav_n_path = 0;
+    m->fr_gen = 0;                                                      // (a frontier search carries the plan it was made from)
+    GEM_HIP(h, launch_nav_init(h->stream, a));
+    const volatile int* pin_status = a.pin + 256;
+    RoundsResult rr;
+    rc = run_tile_rounds(
+        cells, h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty,
+        [&](int round) -> int {
+            a.round = round;
+            GEM_HIP(h, quadratic ? launch_navquad_round(h->stream, a) : launch_nav_round(h->stream, a));
+            return GEM_OK;
+        },
+        [&](int round, bool& converged) -> int {
+            a.round = round;
+            GEM_HIP(h, launch_nav_finish(h->stream, a));
+            GEM_HIP(h, hipStreamSynchronize(h->stream));
+            converged = pin_status[kNavConverged] != 0;
+            return GEM_OK;
+        },
+        rr);
+    if (rc) return rc;
+    if (!rr.converged) return fail(h, GEM_ERR_HIP, (name + ": the potential did not converge within its bound").c_str());
+    st->rounds = pin_status[kNavRounds];
+    st->chunks = rr.chunks;
+    return finish_plan(h, *m, a, m->gen, what, st, out_xy, cap);
+}
+
+// gem_navplan_host and gem_navquad_host: the same checks, status and path; the potential is the caller's
+int plan_on_host(bool quadratic, const unsigned char* grid, int size_x, int size_y, const int* w, int flags, const int start_cell[2],
+                 const int goal_cell[2], int* pot, int* path_cells, long long cap, gem_navplan_status* status)
+{
+    if (!grid || !w || !start_cell || !goal_cell || !status || size_x < 1 || size_y < 1 || (flags & ~GEM_NAV_OUTLINE) || (path_cells && cap < 0))
+        return GEM_ERR_INVALID;
+    const long long cells = (long long)size_x * size_y;
+    if (!weights_ok(w, cells)) return GEM_ERR_INVALID;
+    if (quadratic && *std::max_element(w, w + 256) > kNavQuadMaxWeight) return GEM_ERR_INVALID;
+    auto cell_of = [&](const int c[2]) { return c[0] >= 0 && c[1] >= 0 && c[0] < size_x && c[1] < size_y ? c[1] * size_x + c[0] : -1; };
+    const int start = cell_of(start_cell), goal = cell_of(goal_cell);
+    empty_status(status);
+    if (start >= 0) { status->start_cell[0] = start_cell[0]; status->start_cell[1] = start_cell[1]; }
+    if (goal >= 0) { status->goal_cell[0] = goal_cell[0]; status->goal_cell[1] = goal_cell[1]; }
+    std::vector<int> own;
+    if (!pot) { own.resize((size_t)cells); pot = own.data(); }
+    if (quadratic) navquad_potential_host(grid, size_x, size_y, w, (flags & GEM_NAV_OUTLINE) != 0, start, pot);
+    else host_potential(grid, size_x, size_y, w, (flags & GEM_NAV_OUTLINE) != 0, start, pot);
+    if (goal >= 0) status->goal_potential = pot[goal];
+    if (start < 0 || goal < 0 || pot[goal] == GEM_NAV_UNREACHED) return GEM_OK;
+    const long long n = nav_grid_path(pot, size_x, size_y, start, goal, nullptr, 0);
+    status->found = 1;
+    status->n_path = (int)n;
+    if (!path_cells) return GEM_OK;
+    if (cap < n) return GEM_ERR_INVALID;
+    nav_grid_path(pot, size_x, size_y, start, goal, path_cells, n);
+    std::reverse(path_cells, path_cells + n);
+    return GEM_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -146,90 +244,27 @@ int gem_navplan_weights(int neutral_cost, double cost_factor, int lethal_cost, i
 int gem_navplan_host(const unsigned char* grid, int size_x, int size_y, const int* w, int flags, const int start_cell[2], const int goal_cell[2],
                      int* pot, int* path_cells, long long cap, gem_navplan_status* status)
 {
-    if (!grid || !w || !start_cell || !goal_cell || !status || size_x < 1 || size_y < 1 || (flags & ~GEM_NAV_OUTLINE) || (path_cells && cap < 0))
-        return GEM_ERR_INVALID;
-    const long long cells = (long long)size_x * size_y;
-    if (!weights_ok(w, cells)) return GEM_ERR_INVALID;
-    auto cell_of = [&](const int c[2]) { return c[0] >= 0 && c[1] >= 0 && c[0] < size_x && c[1] < size_y ? c[1] * size_x + c[0] : -1; };
-    const int start = cell_of(start_cell), goal = cell_of(goal_cell);
-    empty_status(status);
-    if (start >= 0) { status->start_cell[0] = start_cell[0]; status->start_cell[1] = start_cell[1]; }
-    if (goal >= 0) { status->goal_cell[0] = goal_cell[0]; status->goal_cell[1] = goal_cell[1]; }
-    std::vector<int> own;
-    if (!pot) { own.resize((size_t)cells); pot = own.data(); }
-    host_potential(grid, size_x, size_y, w, (flags & GEM_NAV_OUTLINE) != 0, start, pot);
-    if (goal >= 0) status->goal_potential = pot[goal];
-    if (start < 0 || goal < 0 || pot[goal] == GEM_NAV_UNREACHED) return GEM_OK;
-    const long long n = nav_grid_path(pot, size_x, size_y, start, goal, nullptr, 0);
-    status->found = 1;
-    status->n_path = (int)n;
-    if (!path_cells) return GEM_OK;
-    if (cap < n) return GEM_ERR_INVALID;
-    nav_grid_path(pot, size_x, size_y, start, goal, path_cells, n);
-    std::reverse(path_cells, path_cells + n);
-    return GEM_OK;
+    return plan_on_host(false, grid, size_x, size_y, w, flags, start_cell, goal_cell, pot, path_cells, cap, status);
+}
+
+int gem_navquad_host(const unsigned char* grid, int size_x, int size_y, const int* w, int flags, const int start_cell[2], const int goal_cell[2],
+                     int* pot, int* path_cells, long long cap, gem_navplan_status* status)
+{
+    return plan_on_host(true, grid, size_x, size_y, w, flags, start_cell, goal_cell, pot, path_cells, cap, status);
 }
 
 int gem_costmap_navplan(gem_handle* h, int id, const double start_xy[2], const double goal_xy[2], const int* w, int flags, double* out_xy,
                         long long cap, gem_navplan_status* st)
 {
     GEM_ENTRY("gem_costmap_navplan");
-    const char* what = "gem_costmap_navplan";
-    int rc;
-    CostMap* m;
-    if ((rc = costmap_find(h, id, what, &m))) return rc;
-    if (!start_xy || !goal_xy || !w || !st) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a NULL start, goal, weight table or status");
-    if (flags & ~GEM_NAV_OUTLINE) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: unknown flag bits");
-    if (out_xy && cap < 0) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative capacity");
-    for (int k = 0; k < 2; ++k)
-        if (!std::isfinite(start_xy[k]) || !std::isfinite(goal_xy[k])) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a coordinate not finite");
-    const CostGeom g = geom_of(*m);
-    const long long cells = (long long)g.sx * g.sy;
-    if (!weights_ok(w, cells)) return fail(h, GEM_ERR_INVALID, "gem_costmap_navplan: a negative weight, or size_x * size_y * max(w) not below 2^31 - 1");
+    return plan_on_costmap(h, id, "gem_costmap_navplan", false, start_xy, goal_xy, w, flags, out_xy, cap, st);
+}
 
-    auto& cm = h->costmap;
-    const size_t nt = (size_t)nav_tiles((int)g.sx) * nav_tiles((int)g.sy);
-    if ((rc = ensure(h, m->nav_pot, (size_t)cells * sizeof(int))) || (rc = ensure(h, m->nav_path, (size_t)cells * sizeof(int))) ||
-        (rc = ensure(h, m->nav_act, 2 * nt * sizeof(int))) || (rc = ensure(h, m->nav_status, kNavStatusWords * sizeof(int))) ||
-        (rc = ensure(h, cm.nav_w, 256 * sizeof(int)))) return rc;
-    if (!cm.nav_pin) GEM_HIP(h, hipHostMalloc(&cm.nav_pin, kNavPinBytes, hipHostMallocDefault));
-    NavArgs a = bind_args(h, *m);
-    std::copy(w, w + 256, a.pin);
-
-    empty_status(st);
-    uint32_t cell = 0u;
-    a.start = cost_cell(g, start_xy[0], start_xy[1], cell) ? (int)cell : -1;
-    a.goal = cost_cell(g, goal_xy[0], goal_xy[1], cell) ? (int)cell : -1;
-    if (a.start >= 0) { st->start_cell[0] = a.start % a.sx; st->start_cell[1] = a.start / a.sx; }
-    if (a.goal >= 0) { st->goal_cell[0] = a.goal % a.sx; st->goal_cell[1] = a.goal / a.sx; }
-    a.outline = (flags & GEM_NAV_OUTLINE) ? 1 : 0;
-
-    m->nav_gen = 0;                                                     // (a failure below leaves no plan to read)
-    m->nav_n_path = 0;
-    m->fr_gen = 0;                                                      // (a frontier search carries the plan it was made from)
-    GEM_HIP(h, launch_nav_init(h->stream, a));
-    const volatile int* pin_status = a.pin + 256;
-    RoundsResult rr;
-    rc = run_tile_rounds(
-        cells, h->nav_chunk > 0 ? h->nav_chunk : (long long)a.ntx + a.nty,
-        [&](int round) -> int {
-            a.round = round;
-            GEM_HIP(h, launch_nav_round(h->stream, a));
-            return GEM_OK;
-        },
-        [&](int round, bool& converged) -> int {
-            a.round = round;
-            GEM_HIP(h, launch_nav_finish(h->stream, a));
-            GEM_HIP(h, hipStreamSynchronize(h->stream));
-            converged = pin_status[kNavConverged] != 0;
-            return GEM_OK;
-        },
-        rr);
-    if (rc) return rc;
-    if (!rr.converged) return fail(h, GEM_ERR_HIP, "gem_costmap_navplan: the potential did not converge within its bound");
-    st->rounds = pin_status[kNavRounds];
-    st->chunks = rr.chunks;
-    return finish_plan(h, *m, a, m->gen, what, st, out_xy, cap);
+int gem_costmap_navplan_quadratic(gem_handle* h, int id, const double start_xy[2], const double goal_xy[2], const int* w, int flags, double* out_xy,
+                                  long long cap, gem_navplan_status* st)
+{
+    GEM_ENTRY("gem_costmap_navplan_quadratic");
+    return plan_on_costmap(h, id, "gem_costmap_navplan_quadratic", true, start_xy, goal_xy, w, flags, out_xy, cap, st);
 }
 
 // Another goal on the last plan's potential (include/gem_hip_frontier.h): one launch of k_nav_finish.  After convergence both active

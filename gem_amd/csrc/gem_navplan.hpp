@@ -35,6 +35,7 @@ struct NavArgs {
     int start, goal;                    // linear cells, -1 off the map
     int outline;
     int round;                          // the round of this launch (finish: the next one)
+    int passes;                         // k_navquad_round alone: in-tile passes a tile is allowed in one round
 };
 
 hipError_t launch_nav_init(hipStream_t st, const NavArgs& a);

@@ -1133,6 +1133,28 @@ public:
                                             c.origin_y + (static_cast<double>(cell / static_cast<int>(c.size_x)) + 0.5) * c.resolution});
         return p;
     }
+    // navPlan on the QUADRATIC potential (gem_hip_navquad.h): the two-axis update in exact integers, order-free, nowhere above the
+    // linear potential; weights at most 462.  The plan takes the linear plan's place: potential(), navPlanTo, navPaths and the frontier
+    // search work on it.  Waits.
+    NavPlan navPlanQuadratic(const FootprintPoint& start, const FootprintPoint& goal, const std::vector<int>& weights = {}, bool outline = true)
+    {
+        const std::vector<int> w = weights.empty() ? NavPlan::weights() : weights;
+        if (w.size() != 256) throw Error(GEM_ERR_INVALID, "Costmap::navPlanQuadratic: the weight table has 256 entries");
+        NavPlan p;
+        const int flags = outline ? GEM_NAV_OUTLINE : 0;
+        map_.check(gem_costmap_navplan_quadratic(map_.handle(), id_, &start.x, &goal.x, w.data(), flags, nullptr, 0, &p.status),
+                   "gem_costmap_navplan_quadratic");
+        p.found = p.status.found != 0;
+        std::vector<int> cells(static_cast<size_t>(p.status.n_path));
+        map_.check(gem_costmap_navplan_read(map_.handle(), id_, nullptr, cells.empty() ? nullptr : cells.data(), static_cast<long long>(cells.size())),
+                   "gem_costmap_navplan_read");
+        const gem_costmap_config c = geometry();
+        p.path.reserve(cells.size());
+        for (int cell : cells)                                // cell centres, in double, as the C entry computes them
+            p.path.push_back(FootprintPoint{c.origin_x + (static_cast<double>(cell % static_cast<int>(c.size_x)) + 0.5) * c.resolution,
+                                            c.origin_y + (static_cast<double>(cell / static_cast<int>(c.size_x)) + 0.5) * c.resolution});
+        return p;
+    }
     std::vector<int> potential() const
     {
         const gem_costmap_config c = geometry();

@@ -773,6 +773,9 @@ int  gem_octree_read(gem_handle* h, int slot, void* data, size_t capacity, size_
 /* ---- paths on the last plan's potential, grid or gradient, a batch of goals: gem_navpath_host, gem_costmap_navplan_paths / _device -- */
 #include "gem_hip_navpath.h"
 
+/* ---- the quadratic potential, order-free and exact: gem_navquad_host, gem_costmap_navplan_quadratic -------------------------------- */
+#include "gem_hip_navquad.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,8 @@ extern "C" {
  *       default = tiles_x + tiles_y, or 1 .. 2^20; a small value makes a test take the second chunk.  The plan is the same either way),
  *       "mapgrid_chunk" (the same for the distance rounds of gem_costmap_mapgrid_prepare_tiled / _prepare_front_tiled: 0, the default =
  *       tiles_x + tiles_y, or 1 .. 2^20.  The grids are the same either way),
+ *       "navquad_passes" (in-tile passes a round of gem_costmap_navplan_quadratic allows a tile before the tile marks itself and goes on
+ *       a round later: 0, the default = 3, or 1 .. 64; tools/bench_navquad.py measures the choice.  The plan is the same either way),
  *       "front_chunk" (the same for the label rounds of gem_costmap_frontiers: 0, the default = tiles_x + tiles_y, or 1 .. 2^20.  The
  *       search is the same either way),
  *       "obstacle_direct" (0/1, default 1: gem_costmap_observe* walks one ray per accepted record, the direct form; 0 = one ray per
@@ -84,7 +86,7 @@ int gem_debug_set(gem_handle* h, const char* key, long long value);
  *            launches it stands for),
  *            "frame_pair" (the knob), "frame_pair_overlap" (the knob), "frame_pairs" (launches so far that carried two sweeps in either half: the pair kernel's),
  *            "frame_held_flushed" (held sweeps that were settled by a flush, not by the next pairable call),
- *            "nav_chunk" (the knob), "mapgrid_chunk" (the knob), "front_chunk" (the knob), "history_cull" (the knob), "obstacle_direct" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
+ *            "nav_chunk" (the knob), "mapgrid_chunk" (the knob), "front_chunk" (the knob), "navquad_passes" (the knob), "history_cull" (the knob), "obstacle_direct" (the knob), "history_blocks" (blocks of 4096 records the history cloud holds, the workgroups of a
  *            gem_costmap_mark_history) and "history_blocks_culled" (those of them the LAST gem_costmap_mark_history culled: a device word,
  *            downloaded by this call, which waits for the stream; 0 with "history_cull" 0),
  *            "step_pending" (1: the second half of a gem_add_sharded_device step is still to come),

@@ -12,9 +12,10 @@
  * plain Python, twice.  Only ONE configuration is restated, the one whose answer does not depend on the order cells are visited in:
  *     use_dijkstra = true, use_quadratic = false (PotentialCalculator: min of the four neighbours + cost), use_grid_path = true.
  * Deliberately NOT restated:
- *   - navfn and the quadratic calculator: their potential is a float whose value depends on the visiting order of the priority
- *     buffers, and the quadratic update jumps from 1.0046 * hf to hf at dc = hf, so it is not even monotone.  No parallel form can be
- *     bit-equal to it.
+ *   - navfn and the quadratic calculator AS THE LIBRARY COMPUTES THEM: their potential is a float whose value depends on the visiting
+ *     order of the priority buffers, and the quadratic update jumps from 1.0046 * hf to hf at dc = hf, so it is not even monotone.
+ *     No parallel form can be bit-equal to it.  The quadratic update stated in exact integers and clamped at hf IS monotone and
+ *     order-free: that contract, the project's own, is gem_hip_navquad.h (gem_costmap_navplan_quadratic), beside this one.
  *   - the gradient path, A*, default_tolerance, the orientation filter, publishing the potential.
  *     (The gradient path is a pure function of the potential and is stated on its own, for a batch of goals: gem_hip_navpath.h.)
  *   - the library's early exit at the goal: the potential here is the converged one EVERYWHERE.

@@ -62,6 +62,13 @@
 //                    potential of every cell the library settled below the goal's (the library leaves at the goal, the device
 //                    converges everywhere) and the path cell by cell.  convert_offset_ is makePlan's and is not driven.  It
 //                    cannot be run where the test suite runs and has not been through a compiler
+//   navquad gem_costmap_navplan_quadratic's increment (include/gem_hip_navquad.h) takes its three coefficients from
+//                    global_planner::QuadraticCalculator::calculatePotential (the same as navfn's updateCell), RECALLED FROM MEMORY.
+//                    The contract is the project's own -- integers, a floor, the clamp to 1 .. hf -- so the row does not ask for
+//                    equality: over every hf in 1 .. 252 and every dc in 0 .. hf it feeds the library's calculator a 3 x 3 potential
+//                    with ta and tc as two neighbours and compares its result with ta + inc(hf, dc) within the departures the
+//                    header names (under one unit for the floor, 0.46 % of hf for the clamp, one unit where max(1, .) acts).  A
+//                    wrong coefficient shows at once.  It has not been through a compiler either
 //   obs  gem_costmap_observe restates costmap_2d::ObstacleLayer::updateBounds (obstacle_layer.cpp: raytraceFreespace with its four
 //                    clips, updateRaytraceBounds, the marking loop), Costmap2D::raytraceLine / bresenham2D / cellDistance
 //                    (costmap_2d.h) and the height window of ObservationBuffer::bufferCloud (include/gem_hip_obstacle.h;
@@ -119,8 +126,8 @@
 // (add -loctomap -loctomath to the link line), the foot row (add -lbase_local_planner), the mapgrid row, the critics row and the trajgen
 // row (the same library; the critics row also needs base_local_planner/simple_scored_sampling_planner.h among the includes, the
 // trajgen row base_local_planner/simple_trajectory_generator.h and base_local_planner/local_planner_limits.h).  The navplan row has not
-// been through a compiler either; it is the one row of another package, global_planner: add -lglobal_planner to the link line (its
-// three headers are among the includes below).  The obs row has not been through a compiler either (costmap_2d's obstacle_layer.h
+// been through a compiler either, nor has the navquad row; they are the rows of another package, global_planner: add -lglobal_planner
+// to the link line (its headers are among the includes below).  The obs row has not been through a compiler either (costmap_2d's obstacle_layer.h
 // pulls in tf2_ros, message_filters and laser_geometry: add -llaser_geometry -lmessage_filters to the link line).
 //
 // It is NOT part of the product and is not built by gem_amd/build.py; nothing here is needed on the GPU box of the test suite.
@@ -166,6 +173,7 @@
 #include <global_planner/dijkstra.h>
 #include <global_planner/grid_path.h>
 #include <global_planner/potential_calculator.h>
+#include <global_planner/quadratic_calculator.h>
 #include <geometry_msgs/PoseStamped.h>
 #include <geometry_msgs/Point.h>
 #include <octomap/ColorOcTree.h>
@@ -1131,6 +1139,27 @@ int check_navplan(uint32_t seed)
     return 0;
 }
 
+// ---- navquad -------------------------------------------------------------------------------------------------------------------
+// The library's quadratic update against the increment of include/gem_hip_navquad.h, through gem_navquad_host on a 3 x 3 map whose
+// centre has the two neighbours ta and tc: not equality (the contract is the project's own), the departures the header names.
+int check_navquad()
+{
+    global_planner::QuadraticCalculator calc(3, 3);
+    for (int hf = 1; hf <= 252; ++hf)
+        for (int dc = 0; dc <= hf; ++dc) {
+            const float ta = 1000.0f, tc = ta + (float)dc;
+            const float high = 1.0e10f;                                       // the package's POT_HIGH
+            float pot[9] = {high, high, high, ta, high, high, high, tc, high};   // left = ta, down = tc
+            const float lib = calc.calculatePotential(pot, (unsigned char)hf, 4, -1.0f);
+            // the contract's increment, in the integers the header states
+            const long long num = -2301ll * dc * dc + 5307ll * dc * hf + 7040ll * hf * hf, den = 10000ll * hf;
+            const long long inc = dc >= hf ? hf : std::max(1ll, std::min<long long>(hf, num / den));
+            const double slack = 1.0 + 0.0046 * hf + 1e-3 * hf;              // floor, clamp, float rounding of the library's polynomial
+            if (std::fabs((double)lib - (1000.0 + (double)inc)) > slack) report("navquad: the library's update is not within the named departures", hf * 1000 + dc, 1000.0 + (double)inc, lib);
+        }
+    return 0;
+}
+
 // ---- octo ----------------------------------------------------------------------------------------------------------------------
 // fullMapToMsg (octomap_msgs/conversions.h): msg.data = the bytes tree.writeData(stream) writes.  An empty tree writes nothing there
 // only if the library agrees with the deliberate difference of gem_hip.h; the row reports it.
@@ -1216,9 +1245,10 @@ int main(int argc, char** argv)
     if (rc == 0) rc = check_critics(seed + 9u);
     if (rc == 0) rc = check_trajgen(seed + 10u);
     if (rc == 0) rc = check_navplan(seed + 11u);
+    if (rc == 0) rc = check_navquad();
     if (rc == 0) rc = check_obs(seed + 12u);
     if (rc) return rc;
     if (g_failures) { std::fprintf(stderr, "%d difference(s): the restatement of grid_map / cv::circle / pcl::VoxelGrid / transformPointCloud / KdTreeFLANN / StatisticalOutlierRemoval / costmap_2d / base_local_planner / global_planner / octomap does NOT match this installation\n", g_failures); return 1; }
-    std::printf("all twelve rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner, global_planner and octomap (seed %u)\n", seed);
+    std::printf("all thirteen rows pinned on the installed grid_map_core, OpenCV, PCL, costmap_2d, base_local_planner, global_planner and octomap (seed %u)\n", seed);
     return 0;
 }
